@@ -22,10 +22,15 @@ metric: path rays/s = trace calls issued by the bounce loop (primary + secondary
 TRT.c:1024) per second.  The per-frame ray count is deterministic; it is taken once from the
 kernel's counting variant in an UNTIMED pass (the timed kernel carries no counters).
 
-The frame that is timed is CHECKED: after the timed loop rank 0 hashes the last frame (FNV-1a-64 of the
-double framebuffer, untimed) and compares it with the hash the GENUINE reference produced for the same
-scene and camera (tests/golden/golden_full.json, made by tests/golden/make_golden_full.py); a wrong
-pixel anywhere fails the run (exit code 3, "verified": false in the line).
+A plain run sets up, warms up, times the steps and prints the line.  --dump-outputs DIR writes the frame
+the last timed step produced (DIR/frame.npy, float64) so that two builds can be compared output for output.
+
+--full adds everything else, untimed: the render kernel strictly one frame at a time and the roofline, the
+moving-camera loop, BASELINE configs 2, 4 and 5, the CPU baseline, and the CHECK of the timed frame: rank 0
+hashes the last frame (FNV-1a-64 of the double framebuffer) and compares it with the hash the GENUINE
+reference produced for the same scene and camera (tests/golden/golden_full.json, made by
+tests/golden/make_golden_full.py); a wrong pixel anywhere fails the run (exit code 3, "verified": false in
+the line).
 """
 import argparse
 import ctypes as C
@@ -119,7 +124,7 @@ def cpu_baseline(scene, width, height, bounces, full_frame):
     from terminalraytracer_amd import layout as L
     from terminalraytracer_amd import scenes as S
     w, h = (width, height) if full_frame else (480, 270)
-    threads = min(os.cpu_count() or 1, 64)
+    threads = min(os.cpu_count() or 1, 64, int(os.environ.get("OMP_NUM_THREADS") or 64))  # a shared host's share of its cores
     t0 = time.perf_counter()
     _, st = T.oracle_render(scene, w, h, bounces, SPP, threads=threads)  # also yields the ray count of the sample
     dt_all = time.perf_counter() - t0
@@ -311,10 +316,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--animation", type=int, default=0, metavar="F",
                     help="config 5: 256 spheres, 12 bounces, orbit cameras t = f/60 for f < F, a new camera every step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip BASELINE configs 2, 4 and 5 (rendered and verified after the headline on one GPU)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the check of the timed frame against the reference's hash")
-    ap.add_argument("--no-moving-camera", action="store_true", help="skip the headline's second loop (the reference's orbiting camera)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: the render kernel one frame at a time and the "
+                    "roofline, the check of the timed frame against the reference's hash, the moving-camera loop, BASELINE configs 2, 4 "
+                    "and 5, the CPU baseline.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the frame the last step produced (rank 0's "
+                    "assembled float64 framebuffer, H x W x 3) as DIR/frame.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip BASELINE configs 2, 4 and 5 (rendered and verified after the headline on one GPU)")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the check of the timed frame against the reference's hash")
+    ap.add_argument("--no-moving-camera", action="store_true", help="with --full: skip the headline's second loop (the reference's orbiting camera)")
     ap.add_argument("--kernel", type=int, default=0, help="0 production, 1 reference-order (debug)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL; gloo only for rehearsals)")
     ap.add_argument("--rccl-stand-in", action="store_true", help="TEST HOOK: bind the library TRT_RCCL_LIB names in RCCL's place "
@@ -481,15 +491,16 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # untimed: strictly one frame at a time on ONE context, every launch bracketed by HIP events on its stream; the render
+    # untimed (--full): strictly one frame at a time on ONE context, every launch bracketed by HIP events on its stream; the render
     # kernel's own duration (the roofline's denominator) and the ordered-mean kernel's behind it
     d1 = min(args.steps, 20)
-    for i in range(2 + d1):
-        ctx0.render_device(camera_of(i), rowset, bounces, SPP, scratch.data_ptr(), scratch.numel() * 8)
-        ctx0.synchronize()
-    render_ms, reduce_ms = ctx0.render_kernel_times(d1)
-    render_ms_avg, reduce_ms_avg = float(np.mean(render_ms)), float(np.mean(reduce_ms))
-    barrier()
+    if args.full:
+        for i in range(2 + d1):
+            ctx0.render_device(camera_of(i), rowset, bounces, SPP, scratch.data_ptr(), scratch.numel() * 8)
+            ctx0.synchronize()
+        render_ms, reduce_ms = ctx0.render_kernel_times(d1)
+        render_ms_avg, reduce_ms_avg = float(np.mean(render_ms)), float(np.mean(reduce_ms))
+        barrier()
 
     if args.check:  # the sharded, gathered frame must equal the frame of one renderer, bit for bit
         frame = render(scene.camera)
@@ -536,9 +547,15 @@ def main():
             every = [mine]
         per_rank = [{"rank": i, "render_ms": round(float(t[0]), 4), "gather_ms": round(float(t[1]), 4)} for i, t in enumerate(every)]
 
-    # untimed: the frame the timed loop produced last (and, for the animation, frame 59) against the GENUINE reference's hash
+    # untimed: what the last timed step handed its caller, the assembled frame on rank 0, before anything else is rendered
+    if args.dump_outputs and rank == 0:
+        torch.cuda.synchronize()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "frame.npy"), np.ascontiguousarray(fetch(last), dtype=np.float64))
+
+    # untimed (--full): the frame the timed loop produced last (and, for the animation, frame 59) against the GENUINE reference's hash
     verified, checks = None, []
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         probes = [((args.steps - 1) % len(cameras), False)]
         if args.animation > 59 and (args.steps - 1) % len(cameras) != 59:
             probes.append((59, True))
@@ -561,7 +578,7 @@ def main():
     # orbit cameras, the last frame checked against the genuine reference's hash of that very frame.  (The orbit sees other
     # frames than the still, so the ray counts are those of its own cameras.)
     moving = None
-    if world == 1 and workload == "c3" and args.animation == 0 and args.kernel == 0 and args.sky_dim == SKY_DIM and not args.no_moving_camera:
+    if args.full and world == 1 and workload == "c3" and args.animation == 0 and args.kernel == 0 and args.sky_dim == SKY_DIM and not args.no_moving_camera:
         orbit = animation_cameras(width, height, 60)
         ctx0.enable_counters(True)
         orbit_path = []
@@ -597,10 +614,7 @@ def main():
         ms_step = seconds / args.steps * 1e3
         rows = local_rows
         nd, npt = scene.dir_lights.shape[0], scene.point_lights.shape[0]
-        alg = algorithmic_bytes(width, rows, wl["spheres"], args.sky_dim, nd, npt)
-        achieved = alg / (render_ms_avg * 1e-3) / 1e9
         path_mean = float(np.mean(path_cam))
-        prof = committed_profile() if (world == 1 and workload == "c3") else None
         variant = ctx0.render_variant()  # the shading decoupled from the owning lane or the plain rounds
         variant_name = "render_rounds_kernel<false, false, %s%s>" % ("true" if variant["decoupled"] else "false",
                                                                     ", true" if ctx0.path_patches()[0] else "")
@@ -609,7 +623,7 @@ def main():
                       "path rays/s (primary+secondary) at 1920x1080, 256 spheres, 12 bounces, orbiting camera",
             "value": path_timed / seconds,
             "unit": "rays/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step, "full": args.full,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": wl["text"] if args.sky_dim == SKY_DIM else wl["text"].replace("256^2", f"{args.sky_dim}^2"), "sharding": f"{world} x interleaved {args.tile_rows}-row tiles, 1 gather/frame",
@@ -625,9 +639,6 @@ def main():
                        "camera": "static: the eye's two candidate tables are built once, before the timed region (an orbit rebuilds them every "
                                  "frame, ~0.06 ms: see configs.c5)" if args.animation == 0 else "a new camera every frame (the eye's tables are rebuilt per frame, inside the timed region)"},
             "frames_per_s": args.steps / seconds,
-            # the same loop under the reference's real usage: a new camera every frame (its own ray counts; see `moving_camera`)
-            "value_moving_camera": moving["value"] if moving else None,
-            "moving_camera": moving,
             "scene_setup_s": made.get("setup_s") if not rehearsal else None,
             "scene_tables": ctx0.scene_info(),
             "per_rank": per_rank,
@@ -638,44 +649,9 @@ def main():
             "all_rays_per_s": (path_timed + shadow_timed) / seconds,
             "frames_in_flight": args.depth,
             "verified": verified, "verification": checks,
-            # one frame at a time (no overlap between consecutive frames): render kernel + ordered mean, HIP events per launch
-            "one_frame_at_a_time": {"render_kernel_ms": render_ms_avg, "reduce_kernel_ms": reduce_ms_avg, "launches": d1,
-                                    "path_rays_per_s": path_mean / ((render_ms_avg + reduce_ms_avg) * 1e-3)},
             # the timed loop by the device's own clock (HIP events, first launch's start to last launch's end): frames overlap, so this is
             # what a frame costs the GPU in the pipelined loop; it must not exceed ms_per_step (which adds the host's part of the loop)
             "device_ms_per_step": device_span_ms / args.steps if device_span_ms is not None else None,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         # what actually bounds the kernel: the issue of vector instructions, most of them per-ray FP64
-                         # geometry.  COMMITTED counters of this kernel (profiles/traffic.json), not measured in this run.
-                         "bound_actual": "valu_issue",
-                         "valu_busy": ((prof or {}).get("valu") or {}).get("valu_busy_measured"),
-                         "fp64_share": ((prof or {}).get("compute_executed") or {}).get("fp64_share_of_valu_instructions"),
-                         "issue_frac": (compute_executed((prof or {}).get("compute_executed"), render_ms_avg) or {}).get("issue_frac"),
-                         "traffic": (prof or {}).get("hbm_bytes_per_launch"),
-                         "traffic_source": (prof or {}).get("source"),
-                         "profile": profile_identity(prof),
-                         "algorithmic_bytes": alg, "kernel": variant_name, "kernel_ms": render_ms_avg,
-                         "achieved_by_step": alg / (ms_step * 1e-3) / 1e9,
-                         "traffic_over_algorithmic": ((prof or {}).get("hbm_bytes_per_launch") or 0) / alg if prof else None,
-                         "compute_executed": compute_executed((prof or {}).get("compute_executed"), render_ms_avg),
-                         "note": "achieved = algorithmic bytes of a frame (SURVEY 8d) / the render kernel's own average duration, HIP events "
-                                 "on its stream, frames launched strictly one at a time (one_frame_at_a_time); the timed region keeps "
-                                 "frames_in_flight frames in flight, so consecutive launches overlap there.  The path is VALU-issue-bound: "
-                                 "~1 algorithmic byte per ray, frac << 1 by nature (SURVEY 0, DESIGN.md 5); `traffic` and `valu` are "
-                                 "COMMITTED rocprofv3 PMC results (profiles/traffic.json), not measured in this run"},
-            # SURVEY 8d, compute basis: what the REFERENCE's algorithm spends on these rays (every trace_ray call tests all N spheres
-            # and the ground: 25 N + 17 FP64 flops), over the render kernel's own duration.  The candidate tables skip most of those
-            # tests, so this is work avoided as much as work done and may exceed the FP64 vector peak; what the hardware executed is
-            # in `valu` (instructions, measured VALU busy).
-            "compute": {"basis": "reference-equivalent FP64 flops = trace_ray calls x (25 N + 17)",
-                        "flops_per_frame": (path_mean + float(np.mean(shadow_cam))) * (25 * wl["spheres"] + 17),
-                        # NOT a rate of executed work and not to be set against a peak: the reference's flops for these rays over the
-                        # kernel's duration.  The tables avoid most of them (roofline.compute_executed is what the hardware did).
-                        "reference_equivalent_tflops": (path_mean + float(np.mean(shadow_cam))) * (25 * wl["spheres"] + 17) / (render_ms_avg * 1e-3) / 1e12,
-                        "unit": "TFLOP/s of the REFERENCE's algorithm, mostly avoided rather than executed",
-                        "fp64_vector_peak_for_orientation": FP64_PEAK_TFLOPS,
-                        "peak_source": "MI355X FP64 vector: half the 157.3 TFLOP/s FP32 vector figure of MI355X_MICROARCH.md; -ffp-contract=off halves it again"},
-            "valu": (prof or {}).get("valu"),
             "kernel_info": ctx0.kernel_info(),
             # one round = one path ray per lane (+ one shadow ray per light for the lanes that hit something)
             "diagnostics": dict(diag, path_lane_utilisation=path_per_cam[0] / max(1, 64 * diag["wave_loop_trips"]),
@@ -683,14 +659,58 @@ def main():
                                 exact_test_rounds_per_trace=diag["phase2_rounds"] / max(1, path_per_cam[0] + shadow_per_cam[0]) * 64)
             if args.kernel == 0 else diag,
         }
-        if world == 1 and workload == "c3" and not args.no_configs and args.kernel == 0 and args.sky_dim == SKY_DIM:
+        if args.full:
+            alg = algorithmic_bytes(width, rows, wl["spheres"], args.sky_dim, nd, npt)
+            achieved = alg / (render_ms_avg * 1e-3) / 1e9
+            prof = committed_profile() if (world == 1 and workload == "c3") else None
+            out.update({
+                # the same loop under the reference's real usage: a new camera every frame (its own ray counts; see `moving_camera`)
+                "value_moving_camera": moving["value"] if moving else None,
+                "moving_camera": moving,
+                # one frame at a time (no overlap between consecutive frames): render kernel + ordered mean, HIP events per launch
+                "one_frame_at_a_time": {"render_kernel_ms": render_ms_avg, "reduce_kernel_ms": reduce_ms_avg, "launches": d1,
+                                        "path_rays_per_s": path_mean / ((render_ms_avg + reduce_ms_avg) * 1e-3)},
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                             # what actually bounds the kernel: the issue of vector instructions, most of them per-ray FP64
+                             # geometry.  COMMITTED counters of this kernel (profiles/traffic.json), not measured in this run.
+                             "bound_actual": "valu_issue",
+                             "valu_busy": ((prof or {}).get("valu") or {}).get("valu_busy_measured"),
+                             "fp64_share": ((prof or {}).get("compute_executed") or {}).get("fp64_share_of_valu_instructions"),
+                             "issue_frac": (compute_executed((prof or {}).get("compute_executed"), render_ms_avg) or {}).get("issue_frac"),
+                             "traffic": (prof or {}).get("hbm_bytes_per_launch"),
+                             "traffic_source": (prof or {}).get("source"),
+                             "profile": profile_identity(prof),
+                             "algorithmic_bytes": alg, "kernel": variant_name, "kernel_ms": render_ms_avg,
+                             "achieved_by_step": alg / (ms_step * 1e-3) / 1e9,
+                             "traffic_over_algorithmic": ((prof or {}).get("hbm_bytes_per_launch") or 0) / alg if prof else None,
+                             "compute_executed": compute_executed((prof or {}).get("compute_executed"), render_ms_avg),
+                             "note": "achieved = algorithmic bytes of a frame (SURVEY 8d) / the render kernel's own average duration, HIP events "
+                                     "on its stream, frames launched strictly one at a time (one_frame_at_a_time); the timed region keeps "
+                                     "frames_in_flight frames in flight, so consecutive launches overlap there.  The path is VALU-issue-bound: "
+                                     "~1 algorithmic byte per ray, frac << 1 by nature (SURVEY 0, DESIGN.md 5); `traffic` and `valu` are "
+                                     "COMMITTED rocprofv3 PMC results (profiles/traffic.json), not measured in this run"},
+                # SURVEY 8d, compute basis: what the REFERENCE's algorithm spends on these rays (every trace_ray call tests all N spheres
+                # and the ground: 25 N + 17 FP64 flops), over the render kernel's own duration.  The candidate tables skip most of those
+                # tests, so this is work avoided as much as work done and may exceed the FP64 vector peak; what the hardware executed is
+                # in `valu` (instructions, measured VALU busy).
+                "compute": {"basis": "reference-equivalent FP64 flops = trace_ray calls x (25 N + 17)",
+                            "flops_per_frame": (path_mean + float(np.mean(shadow_cam))) * (25 * wl["spheres"] + 17),
+                            # NOT a rate of executed work and not to be set against a peak: the reference's flops for these rays over the
+                            # kernel's duration.  The tables avoid most of them (roofline.compute_executed is what the hardware did).
+                            "reference_equivalent_tflops": (path_mean + float(np.mean(shadow_cam))) * (25 * wl["spheres"] + 17) / (render_ms_avg * 1e-3) / 1e12,
+                            "unit": "TFLOP/s of the REFERENCE's algorithm, mostly avoided rather than executed",
+                            "fp64_vector_peak_for_orientation": FP64_PEAK_TFLOPS,
+                            "peak_source": "MI355X FP64 vector: half the 157.3 TFLOP/s FP32 vector figure of the MI355X specifications; -ffp-contract=off halves it again"},
+                "valu": (prof or {}).get("valu"),
+            })
+        if args.full and world == 1 and workload == "c3" and not args.no_configs and args.kernel == 0 and args.sky_dim == SKY_DIM:
             r.close()  # the headline's buffers make room
             r = None
             try:
                 out["configs"] = other_configs(hip, host, torch, local, 0 if auto_depth else args.depth, args.tile_rows)
             except Exception as e:  # never lose the headline over the rest
                 out["configs"] = {"error": f"{type(e).__name__}: {e}"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(scene, width, height, bounces, full_frame=(workload == "c3"))
             except Exception as e:  # the checker libraries are built by __graft_entry__.build(); never lose the GPU line over them

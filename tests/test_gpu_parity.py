@@ -579,7 +579,7 @@ def test_bench_two_ranks_through_the_c_abi_on_one_gpu():
     env = dict(os.environ, TRT_RCCL_LIB=stub, TRT_RCCL_STUB_DEADLINE="120")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(T.ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--rccl-stand-in", "--check",
-                          "--steps", "5", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=T.ROOT)
+                          "--steps", "5", "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=T.ROOT)
     assert out.returncode == 0, out.stderr[-1500:]
     assert "CHECK sharded(2) == single: True" in out.stderr
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

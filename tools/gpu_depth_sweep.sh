@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/depth; mkdir -p $O
 [ -n "$1" ] && export TRT_HIP_LIB=$PWD/$1
-B="python3 bench.py --no-cpu-baseline --no-verify --no-configs --no-moving-camera"
+B="python3 bench.py --full --no-cpu-baseline --no-verify --no-configs --no-moving-camera"
 for c in 0 1; do
   for depth in 1 2 3 4 6; do
     TRT_COMPACTION=$c timeout -k 10 200 $B --depth $depth 2> $O/err.log | python3 -c "

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/noreduce; mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --no-verify --no-configs --no-moving-camera"
+B="python3 bench.py --full --no-cpu-baseline --no-verify --no-configs --no-moving-camera"
 for r in 1 2; do
 for lib in "$@"; do
   for c in 0 1; do

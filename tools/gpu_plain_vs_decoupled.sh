@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/pvd; mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --no-verify --no-configs --no-moving-camera"
+B="python3 bench.py --full --no-cpu-baseline --no-verify --no-configs --no-moving-camera"
 S="--depth 1 --steps 4 --warmup 1"
 for c in 0 1; do
   export TRT_COMPACTION=$c

@@ -13,7 +13,7 @@ if [ "$sel" != none ]; then
 fi
 for lib in terminalraytracer_amd/libtrt_hip.so "$@"; do
   for mode in "" "--animation 60"; do
-    TRT_HIP_LIB=$PWD/$lib timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-configs $mode 2> $out/err.log | python3 -c "
+    TRT_HIP_LIB=$PWD/$lib timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-configs $mode 2> $out/err.log | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); g=d['diagnostics']
 print('$lib $mode', 'ms/step %.3f  d1 kernel %.3f ms  %.2f G path rays/s  verified %s  vgprs %d  iters %s  activity %s  fallbacks %s swept %d'%(d['ms_per_step'], d['one_frame_at_a_time']['render_kernel_ms'], d['value']/1e9, d['verified'], d['kernel_info']['vgprs'], {k: round(v/max(1,g['wave_loop_trips']),2) for k,v in g.get('exact_loop_iterations',{}).items()}, g.get('exact_loop_lane_activity'), g.get('point_light_closest_hit_fallbacks'), g['swept_traces']))" || { tail -5 $out/err.log; exit 1; }

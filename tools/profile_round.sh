@@ -8,9 +8,9 @@ R=$GRAFT_REPO_ROOT
 cd $R
 O=gpurun_out/$tag
 mkdir -p $O
-timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err
-timeout -k 10 300 python3 bench.py --animation 60 --no-cpu-baseline > $O/bench_anim.json 2> $O/bench_anim.err
-B="python3 bench.py --no-cpu-baseline --no-verify --no-configs --no-moving-camera"
+timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 python3 bench.py --full --animation 60 --no-cpu-baseline > $O/bench_anim.json 2> $O/bench_anim.err
+B="python3 bench.py --full --no-cpu-baseline --no-verify --no-configs --no-moving-camera"
 timeout -k 10 200 rocprofv3 --output-format csv --kernel-trace --stats -d $O/stats_d1 -o p -- $B --depth 1 > $O/bench_d1_prof.json
 timeout -k 10 200 rocprofv3 --output-format csv --kernel-trace --stats -d $O/stats_d2 -o p -- $B > $O/bench_d2_prof.json
 S="--depth 1 --steps 4 --warmup 1"
