@@ -7,7 +7,7 @@ LIB   ?= terminalraytracer_amd/libtrt_hip.so
 BUILD := build
 # -ffp-contract=off: results must be bit-identical to the reference's non-FMA x86-64 build.
 # -fno-slp-vectorize: packed FP32 (v_pk_fma_f32) buys nothing on gfx950 and costs registers.
-# extra -D switches for kernel-tuning A/B builds, e.g. make lib LIB=build/w4.so TUNE=-DTRT_PERSISTENT_WAVES=4
+# extra -D switches for kernel-tuning A/B builds, e.g. make lib LIB=build/r128.so TUNE=-DTRT_REDUCE_BLOCK=128
 TUNE ?=
 empty :=
 space := $(empty) $(empty)

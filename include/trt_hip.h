@@ -226,8 +226,8 @@ int trt_render_variant(trt_context *ctx, int *decoupled, int *workgroup_threads)
  * extension off (the default) a different kernel instantiation runs and nothing of this is on the path. */
 int trt_set_refraction(trt_context *ctx, const double *ior, int count);
 
-/* Resource usage of the render kernel the next frame runs (hipFuncGetAttributes / occupancy query; max_blocks_per_cu counts
- * workgroups of trt_render_variant's size). */
+/* Resource usage of the render kernel trt_render_variant describes (hipFuncGetAttributes / occupancy query; max_blocks_per_cu
+ * counts workgroups of trt_render_variant's size, and for 256-thread workgroups is the plain rounds' figure, which sizes them). */
 int trt_kernel_info(trt_context *ctx, int *vgprs, int *sgprs, int *static_lds_bytes, int *max_blocks_per_cu,
                     int *compute_units);
 

@@ -473,19 +473,6 @@ extern "C" int trt_set_refraction(trt_context *ctx, const double *ior, int count
     return TRT_OK;
 }
 
-extern "C" int trt_render_variant(trt_context *ctx, int *decoupled, int *workgroup_threads)
-{
-    if (!ctx)
-        return fail(TRT_ERR_ARGUMENT, "ctx is NULL");
-    // the variant the most recent launch ran; before the first launch, what a whole large frame would run
-    const bool d = ctx->have_scene && (ctx->last_units > 0 ? ctx->last_compact : renders_decoupled(ctx, kCompactionMinUnits));
-    if (decoupled)
-        *decoupled = d ? 1 : 0;
-    if (workgroup_threads)
-        *workgroup_threads = ctx->kernel == 1 ? 256 : (d ? trt::kCompactBlock : (ctx->last_units > 0 ? ctx->last_big : renders_big(ctx)) ? trt::kBigBlock : trt::kPersistentBlock);
-    return TRT_OK;
-}
-
 extern "C" int trt_set_kernel(trt_context *ctx, int which)
 {
     if (!ctx || which < 0 || which > 1)

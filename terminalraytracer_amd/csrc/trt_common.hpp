@@ -1,5 +1,5 @@
 // trt_common.hpp -- what the kernels of the frame producer share: launch shape of the persistent grid, work-queue
-// constants, the LDS image size, the culling-table view, the diagnostic stamp macros and the two small streaming
+// constants, the LDS image size, the culling-table view, the ISA profile's stage marks and the two small streaming
 // kernels either side of the render kernel (ordered mean over a pixel's samples, RGB8 quantisation).
 #pragma once
 
@@ -15,67 +15,19 @@ namespace trt
 #endif
 constexpr int kPersistentBlock = TRT_BLOCK;
 
-// TRT_STAMP=1: diagnostic build with s_memtime stamps between the stages of the main loop; per-stage wave-cycle
-// sums go to counters[4..] (read SHARES from it, never its run time: the stamps fence the schedule).
-#ifndef TRT_STAMP
-#define TRT_STAMP 0
-#endif
-#if TRT_STAMP == 2
-// -DTRT_STAMP=2: the "clock" is s101, which tools/archive/count_isa.py makes a count of executed instructions (it inserts an add at the
-// head of every basic block of the compiler's assembly: tools/archive/build_isa_count.sh); the per-stage sums are then instruction counts
-#define TRT_STAMP_AT(slot)                                                  \
-    do                                                                      \
-    {                                                                       \
-        unsigned now_;                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                  \
-        asm volatile("s_mov_b32 %0, s101" : "=s"(now_)::"memory");          \
-        __builtin_amdgcn_sched_barrier(0);                                  \
-        stamp_sum[slot] += (unsigned)(now_ - (unsigned)stamp_prev);         \
-        stamp_prev = now_;                                                  \
-    } while (0)
-#elif TRT_STAMP
-#define TRT_STAMP_AT(slot)                                                                   \
-    do                                                                                       \
-    {                                                                                        \
-        unsigned long long now_;                                                             \
-        __builtin_amdgcn_sched_barrier(0);                                                   \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory");          \
-        __builtin_amdgcn_sched_barrier(0);                                                   \
-        stamp_sum[slot] += now_ - stamp_prev;                                                \
-        stamp_prev = now_;                                                                   \
-    } while (0)
-#elif defined(TRT_MARKS) && TRT_MARKS == 2
+#if defined(TRT_MARKS) && TRT_MARKS == 2
 // -DTRT_MARKS=2: the ISA PROFILE of the shipping kernels (tools/isa_profile.py, tools/build_isa_profile.sh).  A stage boundary
 // writes its number to m0 -- which these kernels do not use otherwise; the post-pass checks that -- and the post-pass adds, at
 // the head of every basic block, the block's instructions of every kind to lane m0 of one reserved VGPR per kind
 // (v_readlane / s_add / v_writelane; s100, s101 and v240... are outside what the kernels allocate).  No stamp sums in
 // SGPRs, no counting instantiation: the code profiled is the shipping instantiation's own, up to the scheduling barriers.
-#define TRT_STAMP_AT(slot)                                       \
+#define TRT_MARK_AT(slot)                                        \
     do                                                           \
     {                                                            \
         __builtin_amdgcn_sched_barrier(0);                       \
         asm volatile("s_mov_b32 m0, %0 ; MARK" ::"n"(slot));     \
         __builtin_amdgcn_sched_barrier(0);                       \
     } while (0)
-#elif defined(TRT_MARKS)
-// -DTRT_MARKS=1: the stage boundaries as comments in the compiler's assembly (tools/archive/isa_stage_counts.py counts the
-// instructions between them); a scheduling barrier keeps each stage's instructions on its own side
-#define TRT_STAMP_AT(slot)                      \
-    do                                          \
-    {                                           \
-        __builtin_amdgcn_sched_barrier(0);      \
-        asm volatile("; MARK " #slot);          \
-        __builtin_amdgcn_sched_barrier(0);      \
-    } while (0)
-#else
-#define TRT_STAMP_AT(slot) \
-    do                     \
-    {                      \
-    } while (0)
-#endif
-// boundaries that only the ISA profile knows (the stamp builds keep their 24 slots)
-#if defined(TRT_MARKS) && TRT_MARKS == 2
-#define TRT_MARK_AT(slot) TRT_STAMP_AT(slot)
 #else
 #define TRT_MARK_AT(slot) \
     do                    \
@@ -110,18 +62,6 @@ static_assert(kQueueChunkSmall >= 64, "see kQueueChunkSamples");
 #define TRT_CULL_GROUP 8
 #endif
 constexpr int kCullGroup = TRT_CULL_GROUP; // the culling table is padded to a multiple of this many entries
-
-struct PersistentLaunch
-{
-    unsigned grid, block;
-};
-
-inline PersistentLaunch persistent_launch_shape(int compute_units, int blocks_per_cu, long units)
-{
-    long want = (units + kPersistentBlock - 1) / kPersistentBlock;
-    long cap = (long)compute_units * (blocks_per_cu > 0 ? blocks_per_cu : 1);
-    return PersistentLaunch{(unsigned)(want < cap ? (want > 0 ? want : 1) : cap), (unsigned)kPersistentBlock};
-}
 
 // FP32 culling table of trt_filter.h on the device
 struct CullView

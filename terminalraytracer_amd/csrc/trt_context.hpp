@@ -4,7 +4,7 @@
 //
 //   trt_capi.hip    contexts, scene upload, settings                  (product API, section 2 of trt_hip.h)
 //   trt_tables.hip  the candidate tables: marking and packing kernels, builders
-//   trt_render.hip  render dispatch: the instantiations of the production kernel, occupancy, copy-out, kernel times
+//   trt_render.hip  render dispatch: which kernel a frame runs and its launch, occupancy, copy-out, kernel times
 //   trt_diag.hip    counters read-out, table read-backs, self-tests, single-ray probes        (trt_hip_diag.h)
 //   trt_dropin.hip  project_scene / render_frame and the default context                     (section 1 of trt_hip.h)
 //   trt_dist.hip    one frame over the GPUs of a node                                        (section 3 of trt_hip.h)
@@ -93,7 +93,7 @@ constexpr int kCounterSlots = trt::kProfileAt + 64 * trt::kProfileKinds; // + th
 #else
 constexpr int kCounterSlots = 40;
 #endif
-// [path, shadow, rounds, phase-2 rounds, 24 stage stamps of the diagnostic build, swept, passes, loop diagnostics 30..36]
+// [path, shadow, rounds, phase-2 rounds, 4..27 reserved, swept, passes, loop diagnostics 30..36]
 constexpr int kEventRing = 256;
 constexpr double kPi = 3.14159265358979323846; // TRT.c:43
 
@@ -231,9 +231,7 @@ struct trt_context
     int rounds_blocks_per_cu = 0;
     int compact_blocks_per_cu = 0; // the same for the kernel with shading rings in LDS
     int big_blocks_per_cu = 0;     // ... and for the plain rounds in 1024-thread workgroups (render_rounds_kernel<.., BIG>; 0: not available)
-    long last_units = 0;           // samples of the most recent launch (trt_render_variant / trt_kernel_info describe that launch's kernel)
-    bool last_compact = false;     // the most recent launch ran the kernel with the shading decoupled
-    bool last_big = false;         // ... the plain rounds in 1024-thread workgroups
+    int last_variant = -1;         // the kernel the most recent launch ran (trt_render.hip: Variant); -1: none yet
     // what the queue of each lane set was last left ready for (workgroups, waves per workgroup, words' shift; 0 workgroups: nothing):
     // the ordered-mean pass of a frame starts the queue for the next one, which then needs no kernel of its own in front of it
     unsigned queue_ready[2][3] = {{0, 0, 0}, {0, 0, 0}};
@@ -260,8 +258,6 @@ struct trt_context
 namespace trt_impl
 {
 
-constexpr int kCompactionMinLights = 2; // trt_set_compaction(-1): decouple the shading from two lights up (with one it is a wash)
-
 // LDS image of the production kernel for the context's scene and tables
 inline size_t image_lds_bytes(const trt_context *ctx, int spp)
 {
@@ -279,28 +275,6 @@ inline size_t compact_lds_bytes(const trt_context *ctx, int spp)
     return sizeof(double) * (compact_ring_at(ctx, spp) + (size_t)(trt::kCompactBlock / 64) * trt::kRingDoubles);
 }
 
-// Does a frame of `units` samples on this context run the kernel with the shading decoupled from the owning lane (COMPACT,
-// trt_rounds.hpp)?  Measured (profiles/r02/n_compaction.md): 6 % faster with the two lights of the BASELINE scenes, 10 / 12 /
-// 15 / 17 % with 3 / 4 / 6 / 8; the ring costs about what one light's idle lanes cost.  Its 1024-thread workgroups hold a
-// whole CU until their last wave retires, which pipelined frames feel on SMALL launches (profiles/r02/t_shards.txt: a 1/8
-// shard of the 1080p frame, three in flight, 0.249 ms decoupled against 0.218 plain; half a frame 0.884 against 0.871; the
-// whole frame 1.630 against 1.685): by default only launches of 16 M samples or more are decoupled.
-constexpr long kCompactionMinUnits = 16L << 20;
-
-inline bool renders_decoupled(const trt_context *ctx, long units)
-{
-    if (ctx->kernel != 0 || ctx->ior_count || ctx->compact_blocks_per_cu <= 0 || ctx->compaction == 0)
-        return false;
-    if (ctx->grids.path_enabled && ctx->grids.patch_m) // scenes whose spheres have patches (dense ones) run the plain rounds
-        return false;
-    // ... and only scenes whose path rays are served by tables: with the few spheres of a scene that sweeps (BASELINE configs[1]:
-    // 8 spheres, most rays end on the ground or the sky) the ring costs more than the idle lanes (round 4, final kernel,
-    // profiles/r04/i_all_configs_one_gpu.md: 43.3 G path rays/s plain against 40.8 decoupled; config 3 equal, config 4 +4 % decoupled)
-    const bool pays = ctx->scene.num_dir + ctx->scene.num_point >= kCompactionMinLights && units >= kCompactionMinUnits && ctx->grids.path_enabled &&
-                      ctx->compact_blocks_per_cu * trt::kCompactBlock >= ctx->rounds_blocks_per_cu * trt::kPersistentBlock;
-    return ctx->compaction > 0 || pays;
-}
-
 inline size_t scene_lds_bytes(const trt::SceneView &s)
 {
     return sizeof(double) * ((size_t)s.num_spheres * trt::kSphereDoubles + (size_t)s.num_dir * trt::kDirLightDoubles +
@@ -315,14 +289,6 @@ inline bool print_host_times()
 {
     static const bool on = getenv("TRT_PRINT_HOST_TIMES") != nullptr;
     return on;
-}
-
-// Does a frame run the plain rounds in 1024-thread workgroups (render_rounds_kernel<.., BIG>)?  When the scene has patches, no
-// counters are asked for, and sixteen waves around ONE image are more than the 256-thread workgroups that fit the CU's LDS hold.
-inline bool renders_big(const trt_context *ctx)
-{
-    return ctx->kernel == 0 && !ctx->ior_count && !ctx->counters_enabled && ctx->grids.path_enabled && ctx->grids.patch_m > 0 &&
-           ctx->big_blocks_per_cu * trt::kBigBlock > ctx->rounds_blocks_per_cu * trt::kPersistentBlock;
 }
 
 inline bool rowset_valid(const trt_rowset *r)

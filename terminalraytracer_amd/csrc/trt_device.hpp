@@ -35,36 +35,19 @@ TRT_DEV d3 scale(d3 a, double s) { return d3{a.x * s, a.y * s, a.z * s}; }
 // operand and VCC = 0 (so v_div_fmas is a plain FMA), v_div_fixup passes a finite quotient through, the sqrt scaling is off.
 // The functions below run the SAME arithmetic steps without the wrappers when EVERY active lane of the wave is inside
 // that window, and the compiler's full sequence otherwise (one wave-uniform branch), so the results are those of
-// `/` and __builtin_sqrt bit for bit; trt_selftest_unit compares them on the device.  TRT_LEAN_MATH=0 turns this off.
-#ifndef TRT_LEAN_MATH
-#define TRT_LEAN_MATH 1
-#endif
+// `/` and __builtin_sqrt bit for bit; trt_selftest_unit compares them on the device (unit_reference below).
 
 // the short ways below are the ones taken: say so, so that they are laid out as the fall-through (two taken branches fewer each)
-#ifndef TRT_OPT_LIKELY
-#define TRT_OPT_LIKELY 1
-#endif
-#if TRT_OPT_LIKELY
 #define TRT_LIKELY(c) __builtin_expect(!!(c), 1)
-#else
-#define TRT_LIKELY(c) (c)
-#endif
 
 TRT_DEV unsigned hi32(double x) { return (unsigned)(__builtin_bit_cast(unsigned long long, x) >> 32); }
-TRT_DEV unsigned lo32(double x) { return (unsigned)__builtin_bit_cast(unsigned long long, x); }
 
 // positive, finite, biased exponent in [723, 1323): 2^-300 <= x < 2^300
 TRT_DEV bool mid_range(double x) { return hi32(x) - (723u << 20) < (600u << 20); }
 
-#ifndef TRT_LEAN_SQRT
-#define TRT_LEAN_SQRT 1
-#endif
-#ifndef TRT_OPT_SQRT_FIXUP
-#define TRT_OPT_SQRT_FIXUP 1 // the short way first, the compiler's sequence as a rare fix-up behind ONE forward branch (no diamond)
-#endif
+// the short way first, the compiler's sequence as a rare fix-up behind ONE forward branch (no diamond)
 TRT_DEV double sqrt_exact(double x) // == __builtin_sqrt(x)
 {
-#if TRT_LEAN_MATH && TRT_LEAN_SQRT && TRT_OPT_SQRT_FIXUP
     // the steps of the compiler's expansion between its scaling and its 0/inf select, for every lane; a lane outside the window gets
     // garbage from them and, in the rare wave that has such a lane, the compiler's full sequence instead
     const double y = __builtin_amdgcn_rsq(x);
@@ -83,33 +66,12 @@ TRT_DEV double sqrt_exact(double x) // == __builtin_sqrt(x)
         root = outside ? full : root;
     }
     return root;
-#elif TRT_LEAN_MATH && TRT_LEAN_SQRT
-    if (TRT_LIKELY(!__any(!mid_range(x))))
-    { // the steps of the compiler's expansion between its scaling and its 0/inf select
-        const double y = __builtin_amdgcn_rsq(x);
-        double g = x * y, h = y * 0.5;
-        const double r = __builtin_fma(-h, g, 0.5);
-        g = __builtin_fma(g, r, g);
-        h = __builtin_fma(h, r, h);
-        double d = __builtin_fma(-g, g, x);
-        g = __builtin_fma(d, h, g);
-        d = __builtin_fma(-g, g, x);
-        return __builtin_fma(d, h, g);
-    }
-    return __builtin_sqrt(x);
-#else
-    return __builtin_sqrt(x);
-#endif
 }
 
 // TRT.c:439-450: sqrt of the squared length, then THREE divisions, only when length > 1e-4
-#ifndef TRT_LEAN_UNIT
-#define TRT_LEAN_UNIT 2
-#endif
 TRT_DEV d3 unit(d3 a)
 {
     const double len = sqrt_exact(a.x * a.x + a.y * a.y + a.z * a.z);
-#if TRT_LEAN_MATH && TRT_LEAN_UNIT == 2
     // Round 4: no branch on the length and no copies.  A vector that is left alone (len <= 1e-4 or NaN) is "divided" by 1.0 --
     // x 1.0, a zero residual, + 0: the operand's own bits for every finite x -- so the three quotients are formed for every lane.
     // The short way is taken by the WAVE when, in every active lane, len < 2^300 (false for NaN / inf: then some component is
@@ -148,42 +110,6 @@ TRT_DEV d3 unit(d3 a)
         a.z /= len;
     }
     return a;
-#else
-    if (len > 0.0001)
-    {
-#if TRT_LEAN_MATH
-        // a numerator takes the short way if it is zero (the quotient is that zero, sign included) or mid-range in
-        // magnitude; with len mid-range too, no quotient is near overflow or underflow
-        const unsigned ax = hi32(a.x) & 0x7fffffffu, ay = hi32(a.y) & 0x7fffffffu, az = hi32(a.z) & 0x7fffffffu;
-        const bool ok = mid_range(len) && (ax - (723u << 20) < (600u << 20) || (ax | lo32(a.x)) == 0) &&
-                        (ay - (723u << 20) < (600u << 20) || (ay | lo32(a.y)) == 0) && (az - (723u << 20) < (600u << 20) || (az | lo32(a.z)) == 0);
-        if (!__any(!ok))
-        {
-            // one reciprocal refinement for the three quotients (what the three expansions would each repeat)
-            double r = __builtin_amdgcn_rcp(len);
-            double e = __builtin_fma(-len, r, 1.0);
-            r = __builtin_fma(r, e, r);
-            e = __builtin_fma(-len, r, 1.0);
-            r = __builtin_fma(r, e, r);
-            double q[3] = {a.x, a.y, a.z};
-#pragma unroll
-            for (int k = 0; k < 3; k++)
-            {
-                const double num = q[k];
-                const double q0 = num * r;
-                const double err = __builtin_fma(-len, q0, num);
-                const double quo = __builtin_fma(err, r, q0);
-                q[k] = __builtin_copysign(quo, num); // v_div_fixup gives the quotient the sign of num/len; matters for +-0 only
-            }
-            return d3{q[0], q[1], q[2]};
-        }
-#endif
-        a.x /= len;
-        a.y /= len;
-        a.z /= len;
-    }
-    return a;
-#endif
 }
 
 // the compiler's own expansions, for trt_selftest_unit
@@ -497,14 +423,10 @@ TRT_DEV long sky_index_estimate(int dim, float dim_f, d3 dir, bool &ambiguous)
     return ((long)face * dim + (long)(int)V) * dim + (long)(int)U;
 }
 
-#ifndef TRT_SKY_ESTIMATE
-#define TRT_SKY_ESTIMATE 1 // 0: always the FP64 form (A/B)
-#endif
 // the reference's index for the lanes with `active`: the estimate, and the FP64 form for a wave in which some lane's is ambiguous
 TRT_DEV long sky_index_unit(int dim, d3 dir, double dim_f);
 TRT_DEV uint32_t sky_texel_wave(const uint32_t *sky, int dim, d3 dir, double dim_f, bool active)
 {
-#if TRT_SKY_ESTIMATE
     bool ambiguous;
     long idx = sky_index_estimate(dim, (float)dim_f, dir, ambiguous);
     if (__any(active && ambiguous))
@@ -513,9 +435,6 @@ TRT_DEV uint32_t sky_texel_wave(const uint32_t *sky, int dim, d3 dir, double dim
         idx = ambiguous ? exact : idx;
     }
     return active ? sky[idx] : 0u;
-#else
-    return active ? sky[sky_index_unit(dim, dir, dim_f)] : 0u;
-#endif
 }
 
 TRT_DEV d3 texel_color(uint32_t t) // TRT.c:866: byte / 255.0

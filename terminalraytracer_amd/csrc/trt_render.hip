@@ -1,11 +1,8 @@
-// trt_render.hip -- render dispatch: the instantiations of the production kernel (csrc/trt_rounds.hpp), occupancy, the copy-out to
-// the host, kernel times and resource usage.
+// trt_render.hip -- render dispatch: which instantiation of the production kernel (csrc/trt_rounds.hpp) a frame runs and its launch,
+// occupancy, the copy-out to the host, kernel times and resource usage.
 // Compiled for gfx950 only, with -ffp-contract=off (see trt_device.hpp).
 #define TRT_UNIT_RENDER 1 // this unit is the home of the kernels that are not templates (trt_common.hpp, trt_simple.hpp)
 #include "trt_context.hpp"
-#ifndef TRT_QUEUE_PER_XCD
-#define TRT_QUEUE_PER_XCD 1
-#endif
 #ifndef TRT_REDUCE_BLOCK
 #define TRT_REDUCE_BLOCK 64 // one wave: fits beside the render kernels of the frames in flight wherever a wave retires (+0.8 % decoupled)
 #endif
@@ -15,6 +12,121 @@ using namespace trt_impl;
 
 namespace trt_impl
 {
+
+// ---- which kernel a frame runs ----
+// The production kernel's instantiations (render_rounds_kernel<COUNT, REFRACT, COMPACT, PATCHES, BIG>), each with its counting
+// form where it has one (the rays trt_read_counters reports), and the reference-order kernel (trt_set_kernel(1)).
+enum Variant : int
+{
+    kPlain, kPlainCount,
+    kPatches, kPatchesCount,     // a family per patch of a sphere (trt_raygrid.h)
+    kPatchesBig,                 // ... in 1024-thread workgroups: one LDS image for sixteen waves
+    kDecoupled, kDecoupledCount, // the shading decoupled from the owning lane (COMPACT, trt_rounds.hpp): rings in LDS
+    kRefract, kRefractCount, kRefractPatches, kRefractPatchesCount, // the refraction extension (parity unpinned)
+    kReference,                  // render_simple_kernel: one thread per pixel; not in kRounds
+};
+
+using RoundsKernel = void (*)(trt::SceneView, trt::CullView, trt::FrameView, trt::GridView);
+struct RoundsVariant
+{
+    RoundsKernel fn;
+    int block;  // threads per workgroup
+    bool rings; // LDS: the image, then a shading ring per wave (compact_lds_bytes); otherwise the image alone
+};
+static const RoundsVariant kRounds[kReference] = {
+    {trt::render_rounds_kernel<false>, trt::kPersistentBlock, false},
+    {trt::render_rounds_kernel<true>, trt::kPersistentBlock, false},
+    {trt::render_rounds_kernel<false, false, false, true>, trt::kPersistentBlock, false},
+    {trt::render_rounds_kernel<true, false, false, true>, trt::kPersistentBlock, false},
+    {trt::render_rounds_kernel<false, false, false, true, true>, trt::kBigBlock, false},
+    {trt::render_rounds_kernel<false, false, true>, trt::kCompactBlock, true},
+    {trt::render_rounds_kernel<true, false, true>, trt::kCompactBlock, true},
+    {trt::render_rounds_kernel<false, true>, trt::kPersistentBlock, false},
+    {trt::render_rounds_kernel<true, true>, trt::kPersistentBlock, false},
+    {trt::render_rounds_kernel<false, true, false, true>, trt::kPersistentBlock, false},
+    {trt::render_rounds_kernel<true, true, false, true>, trt::kPersistentBlock, false},
+};
+
+constexpr int kCompactionMinLights = 2; // trt_set_compaction(-1): decouple the shading from two lights up (with one it is a wash)
+
+// Is a frame of `units` samples on this context decoupled?  Measured (profiles/r02/n_compaction.md): 6 % faster with the two lights
+// of the BASELINE scenes, 10 / 12 / 15 / 17 % with 3 / 4 / 6 / 8; the ring costs about what one light's idle lanes cost.  Its
+// 1024-thread workgroups hold a whole CU until their last wave retires, which pipelined frames feel on SMALL launches
+// (profiles/r02/t_shards.txt: a 1/8 shard of the 1080p frame, three in flight, 0.249 ms decoupled against 0.218 plain; half a
+// frame 0.884 against 0.871; the whole frame 1.630 against 1.685): by default only launches of 16 M samples or more are decoupled.
+constexpr long kCompactionMinUnits = 16L << 20;
+
+static bool renders_decoupled(const trt_context *ctx, long units)
+{
+    if (!ctx->have_scene || ctx->compact_blocks_per_cu <= 0 || ctx->compaction == 0)
+        return false;
+    // ... and only scenes whose path rays are served by tables: with the few spheres of a scene that sweeps (BASELINE configs[1]:
+    // 8 spheres, most rays end on the ground or the sky) the ring costs more than the idle lanes (round 4, final kernel,
+    // profiles/r04/i_all_configs_one_gpu.md: 43.3 G path rays/s plain against 40.8 decoupled; config 3 equal, config 4 +4 % decoupled)
+    const bool pays = ctx->scene.num_dir + ctx->scene.num_point >= kCompactionMinLights && units >= kCompactionMinUnits && ctx->grids.path_enabled &&
+                      ctx->compact_blocks_per_cu * trt::kCompactBlock >= ctx->rounds_blocks_per_cu * trt::kPersistentBlock;
+    return ctx->compaction > 0 || pays;
+}
+
+static Variant choose_variant(const trt_context *ctx, long units, int spp)
+{
+    if (ctx->kernel == 1)
+        return kReference;
+    const bool count = ctx->counters_enabled;
+    const bool patches = ctx->grids.path_enabled && ctx->grids.patch_m > 0;
+    if (ctx->ior_count)
+        return patches ? (count ? kRefractPatchesCount : kRefractPatches) : (count ? kRefractCount : kRefract);
+    // scenes whose spheres have patches (dense ones) run the plain rounds; the rings must fit beside the image (the occupancy
+    // figures were taken for 64 rays per pixel: with more, the jitter table may push the rings out of LDS)
+    if (!patches && renders_decoupled(ctx, units) && compact_lds_bytes(ctx, spp) <= (size_t)ctx->lds_limit)
+        return count ? kDecoupledCount : kDecoupled;
+    if (!patches)
+        return count ? kPlainCount : kPlain;
+    // sixteen waves around ONE image when they are more than the 256-thread workgroups that fit the CU's LDS hold
+    const bool big = ctx->big_blocks_per_cu * trt::kBigBlock > ctx->rounds_blocks_per_cu * trt::kPersistentBlock;
+    return count ? kPatchesCount : big ? kPatchesBig : kPatches;
+}
+
+// the variant trt_render_variant / trt_kernel_info describe: the most recent launch's; before the first, a whole large frame's
+static Variant described_variant(const trt_context *ctx)
+{
+    return ctx->last_variant >= 0 ? (Variant)ctx->last_variant : choose_variant(ctx, kCompactionMinUnits, 64);
+}
+
+struct RenderPlan
+{
+    Variant variant;
+    unsigned grid, block;
+    size_t lds;       // dynamic LDS bytes
+    unsigned ring_at; // kDecoupled*: FrameView::ring_at
+};
+
+// The launch of a frame of `units` samples: the production kernel's workgroups fill the context's CUs as far as the units need
+// them; every 256-thread variant is sized by the plain instantiation's occupancy.
+static RenderPlan plan_render(const trt_context *ctx, long units, int spp)
+{
+    const Variant v = choose_variant(ctx, units, spp);
+    if (v == kReference)
+        return RenderPlan{v, (unsigned)((units / spp + 255) / 256), 256u, scene_lds_bytes(ctx->scene), 0u};
+    const RoundsVariant &k = kRounds[v];
+    const int per_cu = k.rings ? ctx->compact_blocks_per_cu : k.block == trt::kBigBlock ? ctx->big_blocks_per_cu : ctx->rounds_blocks_per_cu;
+    const long cap = (long)(ctx->compute_units - (ctx->stream == ctx->own_stream ? ctx->reserved_cus : 0)) * std::max(per_cu, 1);
+    const long want = (units + k.block - 1) / k.block;
+    RenderPlan p{v, (unsigned)std::max(1L, std::min(want, cap)), (unsigned)k.block, image_lds_bytes(ctx, spp), 0u};
+    if (k.rings)
+    {
+        p.lds = compact_lds_bytes(ctx, spp);
+        p.ring_at = (unsigned)compact_ring_at(ctx, spp);
+    }
+    return p;
+}
+
+// workgroups of a variant that fit one CU at the LDS of a frame of 64 rays per pixel
+static hipError_t occupancy(const trt_context *ctx, Variant v, int *blocks)
+{
+    const RoundsVariant &k = kRounds[v];
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, k.fn, k.block, k.rings ? compact_lds_bytes(ctx, 64) : image_lds_bytes(ctx, 64));
+}
 
 // The production kernel's occupancy depends on the scene and its tables only through the size of the LDS image: queried once
 // per size, not once per frame.
@@ -27,23 +139,15 @@ int refresh_occupancy(trt_context *ctx)
     if (ctx->occupancy_for_lds != image_lds_bytes(ctx, 64))
     {
         int blocks = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, trt::render_rounds_kernel<false>, trt::kPersistentBlock, image_lds_bytes(ctx, 64)));
+        HIP_TRY(occupancy(ctx, kPlain, &blocks));
         ctx->rounds_blocks_per_cu = std::max(blocks, 1);
         ctx->occupancy_for_lds = image_lds_bytes(ctx, 64);
         ctx->compact_blocks_per_cu = 0;
         if (compact_lds_bytes(ctx, 64) <= (size_t)ctx->lds_limit)
-        {
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, trt::render_rounds_kernel<false, false, true>, trt::kCompactBlock,
-                                                                 compact_lds_bytes(ctx, 64)));
-            ctx->compact_blocks_per_cu = blocks;
-        }
+            HIP_TRY(occupancy(ctx, kDecoupled, &ctx->compact_blocks_per_cu));
         ctx->big_blocks_per_cu = 0;
         if (ctx->rounds_blocks_per_cu < 4) // the image no longer fits four times: one image for sixteen waves instead
-        {
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, trt::render_rounds_kernel<false, false, false, true, true>, trt::kBigBlock,
-                                                                 image_lds_bytes(ctx, 64)));
-            ctx->big_blocks_per_cu = blocks;
-        }
+            HIP_TRY(occupancy(ctx, kPatchesBig, &ctx->big_blocks_per_cu));
     }
     return TRT_OK;
 }
@@ -94,17 +198,8 @@ int prepare_axes(trt_context *ctx, const Camera *cam, int width, int height)
 void allow_large_lds_render(const trt_context *ctx)
 {
     (void)hipFuncSetAttribute((const void *)trt::render_simple_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
-    (void)hipFuncSetAttribute((const void *)trt::render_rounds_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
-    (void)hipFuncSetAttribute((const void *)trt::render_rounds_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
-    (void)hipFuncSetAttribute((const void *)trt::render_rounds_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
-    (void)hipFuncSetAttribute((const void *)trt::render_rounds_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
-    (void)hipFuncSetAttribute((const void *)trt::render_rounds_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
-    (void)hipFuncSetAttribute((const void *)trt::render_rounds_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
-    (void)hipFuncSetAttribute((const void *)trt::render_rounds_kernel<false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
-    (void)hipFuncSetAttribute((const void *)trt::render_rounds_kernel<false, false, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
-    (void)hipFuncSetAttribute((const void *)trt::render_rounds_kernel<true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
-    (void)hipFuncSetAttribute((const void *)trt::render_rounds_kernel<false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
-    (void)hipFuncSetAttribute((const void *)trt::render_rounds_kernel<true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
+    for (const RoundsVariant &k : kRounds)
+        (void)hipFuncSetAttribute((const void *)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
 }
 
 } // namespace trt_impl
@@ -131,19 +226,6 @@ extern "C" int trt_read_counters(trt_context *ctx, unsigned long long *path_rays
     ctx->last_passes = c[29];
     for (int k = 0; k < 7; k++)
         ctx->last_loops[k] = c[30 + k];
-    if (getenv("TRT_PRINT_STAMPS"))
-    { // diagnostic builds only (-DTRT_STAMP=1): per-stage wave-cycle sums
-        static const char *const names[24] = {"units+primary", "unit(next_dir)", "P set-up", "P sweep", "P exact tests", "P plane",
-                                              "P post: hit", "P post: sky", "Sd look-up", "Sd set-up/load", "Sd sweep", "Sd exact tests",
-                                              "Sd plane", "Sd tail", "Sp unit/look-up", "Sp set-up/load", "Sp sweep", "Sp exact tests",
-                                              "Sp plane", "Sp tail", "lit accumulate", "END", "loop edge", "-"};
-        const int slots = 24;
-        unsigned long long total = 0;
-        for (int i = 0; i < slots; i++)
-            total += c[4 + i];
-        for (int i = 0; i < slots && total; i++)
-            fprintf(stderr, "stamp %-16s %6.2f %%  %llu\n", names[i], 100.0 * c[4 + i] / total, c[4 + i]);
-    }
 #if defined(TRT_MARKS) && TRT_MARKS == 2
     if (getenv("TRT_PRINT_PROFILE"))
         for (int k = 0; k < trt::kProfileKinds; k++)
@@ -226,23 +308,23 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
     if (rc)
         return rc;
     const long pixels = (long)local_rows * rows->width;
-    const size_t lds = scene_lds_bytes(ctx->scene);
+    const long units = pixels * rays_per_pixel; // samples
     if (ctx->counters_enabled)
         HIP_TRY(hipMemsetAsync(ctx->d_counters.ptr, 0, kCounterSlots * sizeof(unsigned long long), stream));
     const int slot = (int)(ctx->launches % kEventRing);
-    if (ctx->kernel == 1)
+    const RenderPlan plan = plan_render(ctx, units, rays_per_pixel);
+    const dim3 grid(plan.grid), block(plan.block);
+    unsigned *const ready = ctx->queue_ready[lane_set];
+    if (plan.variant == kReference)
     {
-        const int block = 256;
-        const unsigned grid = (unsigned)((pixels + block - 1) / block);
         HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
-        hipLaunchKernelGGL(trt::render_simple_kernel, dim3(grid), dim3(block), lds, stream, ctx->scene, f);
+        hipLaunchKernelGGL(trt::render_simple_kernel, grid, block, plan.lds, stream, ctx->scene, f);
         HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
         HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
     }
     else
     {
         // production (kernel 0): persistent waves, synchronous rounds over SAMPLE units, then the ordered mean per pixel
-        const long units = pixels * rays_per_pixel;
         if ((unsigned long long)units >= 0x7fffffffull)
             return fail(TRT_ERR_ARGUMENT, "%ld work units exceed the 2^31 index range", units);
         if (scratch.capacity < (size_t)units * 3)
@@ -250,90 +332,42 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
         HIP_TRY(scratch.reserve((size_t)units * 3));
         f.samples = scratch.ptr;
         f.spp_magic = (unsigned)std::min<unsigned long long>((0x100000000ull + (unsigned)rays_per_pixel - 1) / (unsigned)rays_per_pixel, 0xffffffffull);
-        // shading decoupled from the owning lane (COMPACT, trt_rounds.hpp) when the rings fit in LDS: by default only if they
-        // cost no resident wave and the scene has lights enough to pay for them.
-        // (the occupancy figures were taken for 64 rays per pixel: with more, the jitter table may push the rings out of LDS)
-        const bool compact = renders_decoupled(ctx, units) && compact_lds_bytes(ctx, rays_per_pixel) <= (size_t)ctx->lds_limit;
-        ctx->last_units = units;
         if (image_lds_bytes(ctx, rays_per_pixel) > (size_t)ctx->lds_limit)
             return fail(TRT_ERR_CAPACITY, "scene and %d rays per pixel need %zu B of LDS staging, device offers %d", rays_per_pixel,
                         image_lds_bytes(ctx, rays_per_pixel), ctx->lds_limit);
-        trt::PersistentLaunch pl = trt::persistent_launch_shape(ctx->compute_units - (ctx->stream == ctx->own_stream ? ctx->reserved_cus : 0),
-                                                                ctx->rounds_blocks_per_cu, units);
-        if (compact)
-        {
-            const long cap = (long)(ctx->compute_units - (ctx->stream == ctx->own_stream ? ctx->reserved_cus : 0)) * ctx->compact_blocks_per_cu;
-            const long want = (units + trt::kCompactBlock - 1) / trt::kCompactBlock;
-            pl = trt::PersistentLaunch{(unsigned)std::max(1L, std::min(want, cap)), (unsigned)trt::kCompactBlock};
-        }
-        const bool big = !compact && renders_big(ctx);
-        if (big)
-        {
-            const long cap = (long)(ctx->compute_units - (ctx->stream == ctx->own_stream ? ctx->reserved_cus : 0)) * ctx->big_blocks_per_cu;
-            const long want = (units + trt::kBigBlock - 1) / trt::kBigBlock;
-            pl = trt::PersistentLaunch{(unsigned)std::max(1L, std::min(want, cap)), (unsigned)trt::kBigBlock};
-        }
-        ctx->last_big = big;
-        const size_t plds = image_lds_bytes(ctx, rays_per_pixel);
-        const dim3 grid(pl.grid), block(pl.block);
         if (ctx->ior_count && ctx->ior_count != ctx->scene.num_spheres) // before the first event of the launch is recorded
             return fail(TRT_ERR_ARGUMENT, "trt_set_refraction was given %d indices, the scene has %d spheres", ctx->ior_count, ctx->scene.num_spheres);
-        ctx->last_compact = compact;
+        if (ctx->ior_count)
+            f.ior = ctx->d_ior.ptr;
+        f.ring_at = plan.ring_at;
         // The queue (trt_common.hpp, kQueueStride): a word per XCD and chunks of half the size for scenes whose tables are small enough
         // that a wave may change its place in the image twice as often (no patches), when every word has workgroups; otherwise one
         // word.  Every wave owns its first chunk without asking.
-        const bool per_xcd = TRT_QUEUE_PER_XCD && !(ctx->grids.path_enabled && ctx->grids.patch_m > 0) && pl.grid >= (1u << trt::kQueueXcdShift);
+        const bool per_xcd = !(ctx->grids.path_enabled && ctx->grids.patch_m > 0) && plan.grid >= (1u << trt::kQueueXcdShift);
         f.queue_shift = per_xcd ? (unsigned)trt::kQueueXcdShift : 0u;
         f.chunk = per_xcd ? trt::kQueueChunkSmall : trt::kQueueChunkSamples;
-        unsigned *const ready = ctx->queue_ready[lane_set];
-        if (ready[0] != pl.grid || ready[1] != pl.block / 64 || ready[2] != f.queue_shift) // else the frame before left it ready (reduce_samples_kernel)
-            hipLaunchKernelGGL(trt::start_queue_kernel, dim3(1), dim3(64), 0, stream, f.queue, pl.grid, pl.block / 64, f.queue_shift);
-        ready[0] = 0; // the render kernel uses it up
+        const bool left_ready = ready[0] == plan.grid && ready[1] == plan.block / 64 && ready[2] == f.queue_shift; // by the frame before
+        ready[0] = 0; // the render kernel uses it up; ready again once this frame's launches have gone in
+        if (!left_ready)
+            hipLaunchKernelGGL(trt::start_queue_kernel, dim3(1), dim3(64), 0, stream, f.queue, plan.grid, plan.block / 64, f.queue_shift);
         HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
-        const bool patches = ctx->grids.path_enabled && ctx->grids.patch_m > 0; // a family per patch of a sphere: its own instantiations
-        if (ctx->ior_count)
-        { // the refraction extension (parity unpinned): its own instantiation, the reference's path is not touched
-            f.ior = ctx->d_ior.ptr;
-            if (patches && ctx->counters_enabled)
-                hipLaunchKernelGGL((trt::render_rounds_kernel<true, true, false, true>), grid, block, plds, stream, ctx->scene, ctx->cull, f, ctx->grids);
-            else if (patches)
-                hipLaunchKernelGGL((trt::render_rounds_kernel<false, true, false, true>), grid, block, plds, stream, ctx->scene, ctx->cull, f, ctx->grids);
-            else if (ctx->counters_enabled)
-                hipLaunchKernelGGL((trt::render_rounds_kernel<true, true>), grid, block, plds, stream, ctx->scene, ctx->cull, f, ctx->grids);
-            else
-                hipLaunchKernelGGL((trt::render_rounds_kernel<false, true>), grid, block, plds, stream, ctx->scene, ctx->cull, f, ctx->grids);
-        }
-        else if (compact)
-        {
-            f.ring_at = (unsigned)compact_ring_at(ctx, rays_per_pixel);
-            const size_t clds = compact_lds_bytes(ctx, rays_per_pixel);
-            if (ctx->counters_enabled)
-                hipLaunchKernelGGL((trt::render_rounds_kernel<true, false, true>), grid, block, clds, stream, ctx->scene, ctx->cull, f, ctx->grids);
-            else
-                hipLaunchKernelGGL((trt::render_rounds_kernel<false, false, true>), grid, block, clds, stream, ctx->scene, ctx->cull, f, ctx->grids);
-        }
-        else if (patches && ctx->counters_enabled)
-            hipLaunchKernelGGL((trt::render_rounds_kernel<true, false, false, true>), grid, block, plds, stream, ctx->scene, ctx->cull, f, ctx->grids);
-        else if (patches && big)
-            hipLaunchKernelGGL((trt::render_rounds_kernel<false, false, false, true, true>), grid, block, plds, stream, ctx->scene, ctx->cull, f, ctx->grids);
-        else if (patches)
-            hipLaunchKernelGGL((trt::render_rounds_kernel<false, false, false, true>), grid, block, plds, stream, ctx->scene, ctx->cull, f, ctx->grids);
-        else if (ctx->counters_enabled)
-            hipLaunchKernelGGL((trt::render_rounds_kernel<true>), grid, block, plds, stream, ctx->scene, ctx->cull, f, ctx->grids);
-        else
-            hipLaunchKernelGGL((trt::render_rounds_kernel<false>), grid, block, plds, stream, ctx->scene, ctx->cull, f, ctx->grids);
+        hipLaunchKernelGGL(kRounds[plan.variant].fn, grid, block, plan.lds, stream, ctx->scene, ctx->cull, f, ctx->grids);
         HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
 #if !TRT_AB_SKIP_REDUCE // diagnostic build (profiles/r03: what the ordered mean's streaming pass costs in the pipelined loop)
-        { // TRT.c:1063-1065: the mean over each pixel's samples, in sample order
+        { // TRT.c:1063-1065: the mean over each pixel's samples, in sample order; it starts the queue for the next frame of this shape
             const long values = pixels * 3;
             hipLaunchKernelGGL(trt::reduce_samples_kernel, dim3((unsigned)((values + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK)), dim3(TRT_REDUCE_BLOCK), 0, stream,
-                               (const double *)scratch.ptr, (double *)d_pixels, values, rays_per_pixel, f.inv_spp, f.queue, pl.grid, pl.block / 64, f.queue_shift);
-            ready[0] = pl.grid, ready[1] = pl.block / 64, ready[2] = f.queue_shift;
+                               (const double *)scratch.ptr, (double *)d_pixels, values, rays_per_pixel, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
         }
 #endif
         HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
     }
     HIP_TRY(hipGetLastError());
+#if !TRT_AB_SKIP_REDUCE
+    if (plan.variant != kReference)
+        ready[0] = plan.grid, ready[1] = plan.block / 64, ready[2] = f.queue_shift;
+#endif
+    ctx->last_variant = plan.variant;
     ctx->launches++;
     return TRT_OK;
 }
@@ -540,22 +574,27 @@ extern "C" int trt_launch_span_ms(trt_context *first, long first_launch, trt_con
     return TRT_OK;
 }
 
+extern "C" int trt_render_variant(trt_context *ctx, int *decoupled, int *workgroup_threads)
+{
+    if (!ctx)
+        return fail(TRT_ERR_ARGUMENT, "ctx is NULL");
+    const Variant v = described_variant(ctx);
+    if (decoupled)
+        *decoupled = v != kReference && kRounds[v].rings ? 1 : 0;
+    if (workgroup_threads)
+        *workgroup_threads = v == kReference ? 256 : kRounds[v].block;
+    return TRT_OK;
+}
+
 extern "C" int trt_kernel_info(trt_context *ctx, int *vgprs, int *sgprs, int *static_lds_bytes, int *max_blocks_per_cu,
                                int *compute_units)
 {
     if (!ctx)
         return fail(TRT_ERR_ARGUMENT, "ctx is NULL");
     HIP_TRY(hipSetDevice(ctx->device));
-    const bool decoupled = ctx->have_scene && (ctx->last_units > 0 ? ctx->last_compact : renders_decoupled(ctx, kCompactionMinUnits));
-    const bool patches = ctx->have_scene && ctx->grids.path_enabled && ctx->grids.patch_m > 0;
-    const bool big = !decoupled && renders_big(ctx);
-    const void *fn = ctx->kernel == 1 ? (const void *)trt::render_simple_kernel
-                     : decoupled      ? (const void *)trt::render_rounds_kernel<false, false, true>
-                     : big            ? (const void *)trt::render_rounds_kernel<false, false, false, true, true>
-                     : patches        ? (const void *)trt::render_rounds_kernel<false, false, false, true>
-                                      : (const void *)trt::render_rounds_kernel<false>;
+    const Variant v = described_variant(ctx);
     hipFuncAttributes attr;
-    HIP_TRY(hipFuncGetAttributes(&attr, fn));
+    HIP_TRY(hipFuncGetAttributes(&attr, v == kReference ? (const void *)trt::render_simple_kernel : (const void *)kRounds[v].fn));
     if (vgprs)
         *vgprs = attr.numRegs;
     if (sgprs)
@@ -563,17 +602,16 @@ extern "C" int trt_kernel_info(trt_context *ctx, int *vgprs, int *sgprs, int *st
     if (static_lds_bytes)
         *static_lds_bytes = (int)attr.sharedSizeBytes;
     if (max_blocks_per_cu)
-    {
+    { // what the launch is sized by: the 256-thread variants by the plain instantiation's occupancy
         int blocks = 0;
-        const size_t lds = ctx->have_scene ? (ctx->kernel == 1 ? scene_lds_bytes(ctx->scene) : image_lds_bytes(ctx, 64)) : 0;
-        if (ctx->kernel == 1)
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, trt::render_simple_kernel, 256, lds));
-        else if (decoupled)
-            blocks = ctx->compact_blocks_per_cu; // workgroups of kCompactBlock threads
-        else if (big)
-            blocks = ctx->big_blocks_per_cu; // likewise
+        if (v == kReference)
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, trt::render_simple_kernel, 256, ctx->have_scene ? scene_lds_bytes(ctx->scene) : 0));
+        else if (kRounds[v].rings)
+            blocks = ctx->compact_blocks_per_cu;
+        else if (kRounds[v].block == trt::kBigBlock)
+            blocks = ctx->big_blocks_per_cu;
         else
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, trt::render_rounds_kernel<false>, trt::kPersistentBlock, lds));
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kRounds[kPlain].fn, trt::kPersistentBlock, ctx->have_scene ? image_lds_bytes(ctx, 64) : 0));
         *max_blocks_per_cu = blocks;
     }
     if (compute_units)

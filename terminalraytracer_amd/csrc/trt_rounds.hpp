@@ -38,26 +38,9 @@
 #include "trt_raygrid.h"
 #include "trt_common.hpp"
 
-// A/B switches of round 5's instruction-level changes (profiles/r05/f_ab_log.txt); 1 = as shipped unless noted
-#ifndef TRT_OPT_DIRCONST
-#define TRT_OPT_DIRCONST 1
-#endif
-#ifndef TRT_OPT_POOLCHECK
-#define TRT_OPT_POOLCHECK 1 // the exact loops ask the lanes for a pool word only in the iterations that can need one
-#endif
-#ifndef TRT_OPT_EXPECT
-#define TRT_OPT_EXPECT 1 // the whole-wave sweep and the closest-hit search of a point light are the rare ways: laid out as such
-#endif
-#if TRT_OPT_EXPECT
+// the whole-wave sweep and the closest-hit search of a point light are the rare ways: laid out as such (profiles/r05/f_ab_log.txt)
 #define TRT_EXPECT_LIST(c) __builtin_expect(!!(c), 1)
 #define TRT_EXPECT_RARE(c) __builtin_expect(!!(c), 0)
-#else
-#define TRT_EXPECT_LIST(c) (c)
-#define TRT_EXPECT_RARE(c) (c)
-#endif
-#ifndef TRT_OPT_BZSZ
-#define TRT_OPT_BZSZ 1
-#endif
 
 namespace trt
 {
@@ -299,44 +282,22 @@ TRT_DEV bool exact_step(const LdsImage &L, d3 o, d3 d, double a, int i, bool val
 // indices ascending, up to seven inline, longer lists in `pool`).  Otherwise the wave sweeps the FP32 culling table
 // (trt_filter.h) -- `fixed` != nullptr: all rays share the direction that culling table was built for -- and each lane
 // pops its candidate bits.
-// TRT_LIST_PREFILTER: lists longer than this many entries in some lane of the wave are first thinned by the FP32 filter
-// (0 = never).
-#ifndef TRT_LIST_PREFILTER
-#define TRT_LIST_PREFILTER 12
-#endif
+// Lists longer than kListPrefilter entries in some lane of the wave are first thinned by the FP32 filter.
+constexpr int kListPrefilter = 12;
 
 
 template <bool ANY_HIT, bool REFRACT = false, int MARK_BASE = 0>
 TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bool active, d3 gp, d3 gn, unsigned &phase2_rounds, unsigned &lane_tests,
                   const float4 *fixed, bool use_list, unsigned long long cell, const unsigned long long *pool, int list_bits, int inside = -1,
-                  const double *shared_ad = nullptr // every lane's ray has the SAME direction (a directional light's shadow rays): {d.d, d.gn} from the LDS image
-#if TRT_STAMP
-                  ,
-                  unsigned long long *stamp_sum = nullptr, unsigned long long *stamp_prev_p = nullptr, int stamp_base = 0
-#endif
-)
+                  const double *shared_ad = nullptr) // every lane's ray has the SAME direction (a directional light's shadow rays): {d.d, d.gn} from the LDS image
 {
-#if TRT_STAMP
-    unsigned long long &stamp_prev = *stamp_prev_p;
-#define TRT_TRACE_STAMP(k) TRT_STAMP_AT(stamp_base + (k))
-#elif defined(TRT_MARKS) && TRT_MARKS == 2
-#define TRT_TRACE_STAMP(k) TRT_STAMP_AT(MARK_BASE + (k)) // MARK_BASE: the call site's slots (a template parameter: an immediate)
-#elif defined(TRT_MARKS)
-#define TRT_TRACE_STAMP(k) TRT_STAMP_AT(trace_##k)
-#else
-#define TRT_TRACE_STAMP(k) \
-    do                     \
-    {                      \
-    } while (0)
-#endif
+#define TRT_TRACE_MARK(k) TRT_MARK_AT(MARK_BASE + (k)) // MARK_BASE: the call site's slots (a template parameter: an immediate)
     (void)fixed;
     Hit best;
     best.d2 = __builtin_inf();
     best.p = o;
     best.i = -1;
     best.t = 0.0;
-    if (!TRT_OPT_DIRCONST)
-        shared_ad = nullptr;
     const double a = shared_ad ? shared_ad[0] : dot(d, d);
     if (TRT_EXPECT_LIST(use_list))
     {
@@ -348,15 +309,11 @@ TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bo
         const int per_shift = list_bits == 8 ? 3 : 2, per_mask = (1 << per_shift) - 1; // 8 or 4 entries per pool word
         unsigned long long cur = cell;
         int k = 0;
-#if TRT_STAMP == 1
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-        TRT_TRACE_STAMP(0); // table load
-#if TRT_LIST_PREFILTER
+        TRT_TRACE_MARK(0); // table load
         // Long lists (dense scenes): the FP32 filter of trt_filter.h first goes over the list -- 9 FP32 operations per entry
         // instead of ~19 FP64 -- and only the entries it cannot reject go to the exact test.  Like the sweep it never decides
         // a hit.  Up to eight survivors (four of 16 bits) fit one 64-bit word; if some lane has more, the wave tests its lists directly.
-        if (__any(count > TRT_LIST_PREFILTER))
+        if (__any(count > kListPrefilter))
         {
             trt_ray_filter flt;
             trt_filter_setup(&flt, o.x, o.y, o.z, d.x, d.y, d.z, a, cull.c0x, cull.c0y, cull.c0z, cull.cn, cull.rm);
@@ -366,12 +323,10 @@ TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bo
             for (int j = 0; __any(j < count); j++)
             {
                 const bool valid = j < count;
-#if TRT_OPT_POOLCHECK
-                if ((j & per_mask) == 0)
-#endif
-                if (__any(valid && pooled && (j & per_mask) == 0))
-                    if (valid && pooled && (j & per_mask) == 0)
-                        word = pool[at + ((unsigned)j >> per_shift)];
+                if ((j & per_mask) == 0) // the lanes are asked for a pool word only in the iterations that can need one
+                    if (__any(valid && pooled && (j & per_mask) == 0))
+                        if (valid && pooled && (j & per_mask) == 0)
+                            word = pool[at + ((unsigned)j >> per_shift)];
                 const unsigned i = valid ? (unsigned)word & entry_mask : 0u;
                 word >>= list_bits;
                 unsigned sign;
@@ -399,19 +354,16 @@ TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bo
                 pooled = false;
             }
         }
-#endif
-        TRT_TRACE_STAMP(1);
+        TRT_TRACE_MARK(1);
         while (__any(k < count))
         {
             phase2_rounds++;
             const bool valid = k < count;
             lane_tests += valid;
-#if TRT_OPT_POOLCHECK
             if ((k & per_mask) == 0) // k is the wave's: seven iterations of eight ask nothing of the lanes
-#endif
-            if (__any(valid && pooled && (k & per_mask) == 0))
-                if (valid && pooled && (k & per_mask) == 0)
-                    cur = pool[at + ((unsigned)k >> per_shift)];
+                if (__any(valid && pooled && (k & per_mask) == 0))
+                    if (valid && pooled && (k & per_mask) == 0)
+                        cur = pool[at + ((unsigned)k >> per_shift)];
             const int i = valid ? (int)((unsigned)cur & entry_mask) : 0;
             cur >>= list_bits;
             k++;
@@ -423,7 +375,7 @@ TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bo
     {
         trt_ray_filter flt;
         trt_filter_setup(&flt, o.x, o.y, o.z, d.x, d.y, d.z, a, cull.c0x, cull.c0y, cull.c0z, cull.cn, cull.rm);
-        TRT_TRACE_STAMP(0);
+        TRT_TRACE_MARK(0);
         for (int base = 0; base < cull.padded; base += 64)
         {
             // phase 1: wave-uniform sweep; each verdict is a sign bit shifted into a per-lane word by v_alignbit,
@@ -459,7 +411,7 @@ TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bo
                 cand = chunk == 64 ? ~0ull : ~((1ull << (64 - chunk)) - 1ull); // degenerate ray: every sphere of the chunk
             if (!active)
                 cand = 0;
-            TRT_TRACE_STAMP(1); // sweep
+            TRT_TRACE_MARK(1); // sweep
             // phase 2: exact FP64 tests of this lane's candidates, ascending index (first index wins ties, TRT.c:816)
             while (__any(cand != 0))
             {
@@ -476,7 +428,7 @@ TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bo
     }
     if (!ANY_HIT && best.i >= 0)
         best.p = d3{o.x + best.t * d.x, o.y + best.t * d.y, o.z + best.t * d.z}; // the winner's hit point: the expression of TRT.c:664-666 again
-    TRT_TRACE_STAMP(2); // exact tests
+    TRT_TRACE_MARK(2); // exact tests
     // ground plane (TRT.c:831-853; ray_intersects_plane TRT.c:677-695).  One wave-level decision, then straight-line code with
     // selects: a ray can only hit if |d.n| > 1e-5 and numerator and denominator of t have the same sign (opposite signs: t <= 0,
     // whatever the quotient's digits are), so a wave whose rays all head away from the plane skips the division.
@@ -503,8 +455,8 @@ TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bo
             }
         }
     }
-    TRT_TRACE_STAMP(3); // plane
-#undef TRT_TRACE_STAMP
+    TRT_TRACE_MARK(3); // plane
+#undef TRT_TRACE_MARK
     return best;
 }
 
@@ -534,12 +486,10 @@ TRT_DEV void point_light_search(const LdsImage &L, int n, d3 o, d3 d, bool activ
         rounds++;
         const bool valid = k < count;
         lane_tests += valid;
-#if TRT_OPT_POOLCHECK
         if ((k & per_mask) == 0)
-#endif
-        if (__any(valid && pooled && (k & per_mask) == 0))
-            if (valid && pooled && (k & per_mask) == 0)
-                cur = pool[at + ((unsigned)k >> per_shift)];
+            if (__any(valid && pooled && (k & per_mask) == 0))
+                if (valid && pooled && (k & per_mask) == 0)
+                    cur = pool[at + ((unsigned)k >> per_shift)];
         const int i = valid ? (int)((unsigned)cur & entry_mask) : 0;
         cur >>= list_bits;
         k++;
@@ -676,24 +626,14 @@ TRT_DEV unsigned lanes_below(unsigned long long mask)
     return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
 
-// Per-lane counters of the counting kernel variant and the stamps of the diagnostic build, handed through the stages.
+// Per-lane counters of the counting kernel variant, handed through the stages.
 struct Tally
 {
     unsigned path = 0, shadow = 0, rounds = 0, swept = 0, passes = 0;
     unsigned iters[3] = {0, 0, 0}; // wave-level iterations of the exact-test loops: path rays, directional-light shadow rays, point-light ones
     unsigned tests[3] = {0, 0, 0}; // exact tests of THIS lane in those loops (tests / (64 iters) = the loops' lane activity)
     unsigned full = 0;             // point-light shadow searches that fell back from the any-hit form to the closest-hit one
-#if TRT_STAMP
-    unsigned long long stamp_sum[24] = {0}, stamp_prev = 0;
-#endif
 };
-#if TRT_STAMP
-#define TRT_STAGE_STAMPS(t)                       \
-    unsigned long long *const stamp_sum = (t).stamp_sum; \
-    unsigned long long &stamp_prev = (t).stamp_prev
-#else
-#define TRT_STAGE_STAMPS(t) (void)(t)
-#endif
 
 // What the path ray of a round found (TRT.c:793-889).
 struct PathHit
@@ -715,7 +655,6 @@ template <bool COUNT, bool REFRACT = false, bool PATCHES = false>
 TRT_DEV PathHit path_stage(const LdsImage &L, const CullView &cull, const GridView &grids, int n, d3 o, d3 d, int &fam, bool alive, d3 gp, d3 gn,
                            Tally &tally, int inside = -1)
 {
-    TRT_STAGE_STAMPS(tally);
     bool p_list = false;
     unsigned long long p_cell = 0;
     if (grids.path_enabled)
@@ -730,12 +669,7 @@ TRT_DEV PathHit path_stage(const LdsImage &L, const CullView &cull, const GridVi
     if (COUNT && !p_list)
         tally.swept++;
     PathHit r;
-#if TRT_STAMP
-    r.ph = trace<false, REFRACT>(L, cull, n, o, d, alive, gp, gn, tally.iters[0], tally.tests[0], nullptr, p_list, p_cell, grids.pool, grids.list_bits, inside, nullptr, stamp_sum,
-                                 &stamp_prev, 2);
-#else
     r.ph = trace<false, REFRACT, 2>(L, cull, n, o, d, alive, gp, gn, tally.iters[0], tally.tests[0], nullptr, p_list, p_cell, grids.pool, grids.list_bits, inside);
-#endif
     r.hit = alive && r.ph.i >= 0;
     r.sky = alive && r.ph.i < 0;
     if (r.hit)
@@ -755,7 +689,7 @@ TRT_DEV PathHit path_stage(const LdsImage &L, const CullView &cull, const GridVi
         }
         r.normal = unit(raw); // TRT.c:878
     }
-    TRT_STAMP_AT(6); // P post: nudge direction, normal
+    TRT_MARK_AT(6); // P post: nudge direction, normal
     return r;
 }
 
@@ -766,7 +700,6 @@ template <bool COUNT>
 TRT_DEV d3 shadow_stage(const LdsImage &L, const CullView &cull, const GridView &grids, int n, int nd, int nl, d3 o, d3 normal, int mat,
                         bool lit_lanes, d3 gp, d3 gn, Tally &tally)
 {
-    TRT_STAGE_STAMPS(tally);
     d3 lit = d3{0.0, 0.0, 0.0};
     if (!__any(lit_lanes))
         return lit;
@@ -795,17 +728,12 @@ TRT_DEV d3 shadow_stage(const LdsImage &L, const CullView &cull, const GridView 
             }
             if (COUNT && !use_list)
                 tally.swept++;
-            TRT_STAMP_AT(8); // look-up
-#if TRT_STAMP
-            const Hit sh = trace<true>(L, cull, n, o, sd, lit_lanes, gp, gn, tally.iters[1], tally.tests[1], L.cull_dir + li * cull.padded, use_list, cell, grids.pool,
-                                       grids.list_bits, -1, L.dir + li * kDirRecord + 6, stamp_sum, &stamp_prev, 9);
-#else
+            TRT_MARK_AT(8); // look-up
             const Hit sh = trace<true, false, 9>(L, cull, n, o, sd, lit_lanes, gp, gn, tally.iters[1], tally.tests[1], L.cull_dir + li * cull.padded, use_list, cell, grids.pool, grids.list_bits,
                                                  -1, L.dir + li * kDirRecord + 6);
-#endif
             is_lit = sh.i < 0;
             factor = min1(dot(normal, sd));
-            TRT_STAMP_AT(13); // directional shadow tail
+            TRT_MARK_AT(13); // directional shadow tail
         }
         else
         { // point light, TRT.c:926-957
@@ -830,7 +758,7 @@ TRT_DEV d3 shadow_stage(const LdsImage &L, const CullView &cull, const GridView 
             }
             if (COUNT && !use_list)
                 tally.swept++;
-            TRT_STAMP_AT(14); // unit(to_light), strength, look-up
+            TRT_MARK_AT(14); // unit(to_light), strength, look-up
             // ANY-HIT search (trt_lightgrid.h (4)): a candidate that is provably hit nearer than the light proves "dark", whichever
             // hit is the closest; no hit at all is "lit"; anything else (a blocker about as far as the light) leaves the lane
             // unsure and sends its wave through the closest-hit search of TRT.c:937-942 below.
@@ -845,17 +773,13 @@ TRT_DEV d3 shadow_stage(const LdsImage &L, const CullView &cull, const GridView 
                 point_light_search(L, n, o, sd, lit_lanes, gp, gn, tally.iters[2], tally.tests[2], cell, grids.pool, grids.list_bits, lo, hi, dark, unsure);
                 is_lit = !dark;
                 full = __any(lit_lanes && unsure);
-                TRT_STAMP_AT(17); // any-hit search
+                TRT_MARK_AT(17); // any-hit search
             }
             if (TRT_EXPECT_RARE(full))
             {
                 if (COUNT)
                     tally.full++;
-#if TRT_STAMP
-                const Hit sh = trace<false>(L, cull, n, o, sd, lit_lanes, gp, gn, tally.iters[2], tally.tests[2], nullptr, use_list, cell, grids.pool, grids.list_bits, -1, nullptr, stamp_sum, &stamp_prev, 15);
-#else
                 const Hit sh = trace<false, false, 26>(L, cull, n, o, sd, lit_lanes, gp, gn, tally.iters[2], tally.tests[2], nullptr, use_list, cell, grids.pool, grids.list_bits);
-#endif
                 is_lit = sh.i < 0;
                 // A blocker: is it farther than the light?  The reference compares light_d2 with the squared distance to the
                 // blocker point NUDGED 1e-6 back along the ray (TRT.c:871-874, :939-942): (D - 1e-6)^2 up to ~1e-14 relative
@@ -875,7 +799,7 @@ TRT_DEV d3 shadow_stage(const LdsImage &L, const CullView &cull, const GridView 
                 }
             }
             factor = strength * min1(dot(normal, sd));
-            TRT_STAMP_AT(19); // point shadow tail
+            TRT_MARK_AT(19); // point shadow tail
         }
         if (lit_lanes && is_lit)
             lit = add(lit, mulc(scale(lcolor, factor), load3(L.mat + mat * 5)));
@@ -1040,16 +964,9 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
     unsigned my_task = 0, old_slot = 0;         // this round's task of the lane (its number), the previous round's (its place in the ring)
     bool my_open = false, old_open = false;     // ... whose colour has not arrived yet
     bool waiting = false;                       // the sample ended on a hit whose colour arrives in the next round: the lane sits that round out
-
-    TRT_STAGE_STAMPS(tally);
-#if TRT_STAMP == 2
-    stamp_prev = 0; // the instruction count starts at 0 at the kernel's entry (tools/archive/count_isa.py); the prologue goes to the first slot
-#elif TRT_STAMP
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_prev)::"memory");
-#endif
     for (;;)
     {
-        TRT_STAMP_AT(22); // loop edge
+        TRT_MARK_AT(22); // loop edge
         // =============== hand out work units; primary rays of new samples (TRT.c:981-1016) ===============
         {
             TRT_FRESH_ARGS;
@@ -1104,11 +1021,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
                         d3 dir = d3{0.0, 0.0, 0.0};
                         dir = add(dir, scale(load3(L.cam + 0), sx));
                         dir = add(dir, scale(load3(L.cam + 3), sy));
-#if TRT_OPT_BZSZ
                         dir = add(dir, load3(L.cam + 13)); // scale(basis z, sz), formed once per workgroup (stage_lds_image)
-#else
-                        dir = add(dir, scale(load3(L.cam + 6), L.cam[12]));
-#endif
                         next_dir = sub(dir, load3(L.cam + 9)); // sic, TRT.c:1005
                         o = load3(L.cam + 9);
                         fam = 0;
@@ -1126,13 +1039,13 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
             break;
         if (COUNT)
             tally.rounds++;
-        TRT_STAMP_AT(0); // units + primary rays
+        TRT_MARK_AT(0); // units + primary rays
         d = unit(next_dir); // TRT.c:1008 for a primary ray, TRT.c:1055 for a reflected one
 
         // ======================================= P: the path ray =======================================
         if (COUNT && alive)
             tally.path++;
-        TRT_STAMP_AT(1); // unit(next_dir)
+        TRT_MARK_AT(1); // unit(next_dir)
         PathHit hit;
         {
             TRT_FRESH_ARGS;
@@ -1174,7 +1087,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
             if (alive)
                 weight_sum += weight_before; // TRT.c:1034 (a sample that ends is normalised by this sum, one that goes on carries it)
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); // the ring is written by some lanes and read by others
-            TRT_STAMP_AT(7); // P post: sky texel, reflection, nudge, enqueue
+            TRT_MARK_AT(7); // P post: sky texel, reflection, nudge, enqueue
             // ---- S over tasks: ONE pass of up to 64 tasks from the head of the ring, if a task of the previous round waits (they
             // are at the head, fewer than 64) or 64 wait.  At most 63 stay behind, so 63 + 64 is the most the ring ever holds. ----
             if (q_head != q_tail && ((int)(q_old - q_head) > 0 || q_tail - q_head >= 64u))
@@ -1199,7 +1112,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
             }
             q_old = q_tail;
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            TRT_STAMP_AT(20); // lit accumulate
+            TRT_MARK_AT(20); // lit accumulate
             // ---- colours that have arrived, in bounce order (TRT.c:1040): last round's task is shaded by now, this round's may be ----
             if (old_open)
             {
@@ -1240,9 +1153,6 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
                 {
                     TRT_FRESH_ARGS;
                     unsigned slot = slot_id;
-#if TRT_AB_DUMMY_STORES // diagnostic build (profiles/r03: what the sample scratch costs): every store lands in 48 KB
-                    slot &= 2047u;
-#endif
                     asm volatile("" : "+v"(slot)); // the address is formed here, not kept as 64 bits for the life of the sample
                     double *out = f.samples + (size_t)slot * 3;
                     out[0] = sample.x * q;
@@ -1278,7 +1188,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
                 next_dir = reflect(d, h_normal);              // TRT.c:1054, normalised at the top of the next round
                 o = add(hit.ph.p, scale(hit.back, 0.000001)); // TRT.c:873-874; origin of the shadow rays and of the next path ray
             }
-            TRT_STAMP_AT(7); // P post: sky texel, reflection, nudge
+            TRT_MARK_AT(7); // P post: sky texel, reflection, nudge
             // ===================================== S(i): shadow rays =====================================
             if (COUNT && __any(path_hit))
                 tally.passes++;
@@ -1326,7 +1236,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
             lit = shadow_stage<COUNT>(L, cull, grids, n, nd, nl, shade_at, h_normal, h_mat, path_hit, gp, gn, tally);
         }
 
-        TRT_STAMP_AT(20); // lit accumulate
+        TRT_MARK_AT(20); // lit accumulate
         // ======================================= END of the bounce =======================================
         if (path_hit)
         { // TRT.c:960-962 then :1034-1048
@@ -1359,11 +1269,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
             if (end_sample)
             {
                 TRT_FRESH_ARGS;
-#if TRT_AB_DUMMY_STORES
-                double *out = f.samples + (size_t)(slot_id & 2047u) * 3;
-#else
                 double *out = f.samples + (size_t)slot_id * 3;
-#endif
                 out[0] = sample.x * q; // plain stores: non-temporal ones (keeping the 498 MB stream out of L2) measured no different
                 out[1] = sample.y * q;
                 out[2] = sample.z * q;
@@ -1371,7 +1277,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
             }
         }
         }
-        TRT_STAMP_AT(21); // END of the bounce
+        TRT_MARK_AT(21); // END of the bounce
     }
 
 #if defined(TRT_MARKS) && TRT_MARKS == 2
@@ -1405,10 +1311,6 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
             for (int k = 0; k < 3; k++)
                 atomicAdd(&f.counters[30 + k], (unsigned long long)tally.iters[k]); // wave-level iterations of the three exact-test loops
             atomicAdd(&f.counters[36], (unsigned long long)tally.full);            // point-light searches that fell back to the closest hit
-#if TRT_STAMP
-            for (int i = 0; i < 24; i++)
-                atomicAdd(&f.counters[4 + i], stamp_sum[i]);
-#endif
         }
     }
 }

@@ -1253,6 +1253,41 @@ def test_render_kernels_keep_four_waves_per_simd(ctx):
         assert info["vgprs"] <= 128 and info["max_blocks_per_cu"] == blocks, (kernel, info)
 
 
+def test_a_queue_left_ready_serves_only_the_next_frame_of_its_shape(ctx):
+    """The ordered mean of a frame starts the work queue for the next launch of the same shape (workgroups, waves per workgroup,
+    words' shift), which then runs no start_queue_kernel in front of its render kernel; a launch of another shape starts the
+    queue itself.  One context through frames whose shapes differ and recur -- one queue word and a word per XCD, 256- and
+    1024-thread workgroups, patches, the reference-order kernel in between -- each frame bit for bit the oracle's."""
+    scene = S.synth_scene(64, T.sky("synth"), T.bench_camera(64, 36))
+    b = 4
+    # (width, height, compaction, patches m, kernel) at one ray per pixel; the queue's (workgroups, waves, shift) on the right
+    wide = (64, 36, 0, 0, hip.Context.PRODUCTION)  # (9, 4, 3): a word per XCD
+    tiny = (8, 4, 0, 0, hip.Context.PRODUCTION)  # (1, 4, 0)
+    decoupled = (64, 36, 1, 0, hip.Context.PRODUCTION)  # (3, 16, 0)
+    patches = (64, 36, 0, 1, hip.Context.PRODUCTION)  # (9, 4, 0): scenes with patches keep one word
+    reference = (64, 36, 0, 0, hip.Context.REFERENCE_ORDER)  # no queue: the one left ready stays ready
+    frames = [wide, wide, tiny, wide, decoupled, decoupled, reference, wide, wide, reference, wide, patches, patches, wide, tiny, tiny]
+    want = {(w, h): T.oracle_render(scene, w, h, b, 1)[0] for w, h in {(f[0], f[1]) for f in frames}}
+    m_now = None
+    try:
+        ctx.set_scene(scene)
+        for i, (w, h, compaction, m, kernel) in enumerate(frames):
+            if m != m_now:
+                ctx.set_path_patches(m)
+                m_now = m
+            ctx.set_kernel(kernel)
+            ctx.set_compaction(compaction)
+            got = ctx.render_host(scene.camera, hip.RowSet.whole(w, h), b, 1)
+            assert np.array_equal(bits(got), bits(want[(w, h)])), (i, frames[i])
+            threads = 1024 if compaction else 256
+            assert ctx.render_variant() == {"decoupled": compaction == 1 and kernel == hip.Context.PRODUCTION, "workgroup_threads": threads}, i
+            assert ctx.path_patches()[0] == m, i
+    finally:
+        ctx.set_kernel(hip.Context.PRODUCTION)
+        ctx.set_compaction(-1)
+        ctx.set_path_patches(-1)
+
+
 # ---- one copy of the scene's tables per device (trt_share_scene), the pool of long lists ----
 
 def test_contexts_share_one_copy_of_the_scene_tables(ctx):

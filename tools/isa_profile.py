@@ -6,7 +6,7 @@ import os, re, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 KINDS = ["valu", "fp64", "trans", "cmp", "cndmask", "mov", "salu", "wait", "lds", "vmem", "visits"]
-# an interval STARTS at its boundary (csrc/trt_rounds.hpp: TRT_STAMP_AT / TRT_MARK_AT) and runs to the next one passed
+# an interval STARTS at its boundary (csrc/trt_rounds.hpp: TRT_MARK_AT) and runs to the next one passed
 NAMES = {63: "prologue (image, first hand-out)", 22: "units+primary", 0: "unit(next_dir)", 1: "P set-up (family, member, cell)",
          2: "P sweep / list thinning", 3: "P exact tests", 4: "P plane", 5: "P post: hit (back, normal)", 6: "P post: sky texel, reflect",
          7: "S entry", 24: "Sd look-up", 8: "Sd trace set-up", 9: "Sd sweep / thinning", 10: "Sd exact tests", 11: "Sd plane", 12: "Sd tail",

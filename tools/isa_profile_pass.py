@@ -1,6 +1,6 @@
 """Post-pass over the compiler's gfx950 assembly of a -DTRT_MARKS=2 build: the ISA PROFILE of the shipping render kernels.
 
-The stage boundaries of a -DTRT_MARKS=2 build are `s_mov_b32 m0, <slot> ; MARK` (TRT_STAMP_AT / TRT_MARK_AT in
+The stage boundaries of a -DTRT_MARKS=2 build are `s_mov_b32 m0, <slot> ; MARK` (TRT_MARK_AT in
 csrc/trt_common.hpp); nothing else in these kernels touches m0 (checked here).  At the head of every basic block of the
 NON-counting instantiations (`render_rounds_kernel<false, ...>`: the ones that ship) this pass inserts, for every KIND of
 instruction the block holds,
