@@ -43,7 +43,7 @@ $(BUILD)/%$(TAG).o: $(CSRC)/%.hip $(HIP_HEADERS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-$(BUILD)/trt_dist.o: $(CSRC)/trt_dist.hip include/trt.h include/trt_hip.h include/trt_hip_diag.h
+$(BUILD)/trt_dist.o: $(CSRC)/trt_dist.hip $(CSRC)/trt_handles.hpp include/trt.h include/trt_hip.h include/trt_hip_diag.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $(CSRC)/trt_dist.hip
 

@@ -190,15 +190,12 @@ extern "C" int trt_create(int device, trt_context **out)
     if (device < 0 || device >= count)
         return fail(TRT_ERR_ARGUMENT, "device %d out of range (%d visible)", device, count);
     HIP_TRY(hipSetDevice(device));
-    trt_context *ctx = new trt_context();
+    std::unique_ptr<trt_context> ctx(new trt_context());
     ctx->device = device;
-    const int rc = init_context(ctx);
-    if (rc)
-    { // hand nothing half-built to the caller, keep nothing behind
-        (void)trt_destroy(ctx);
+    const int rc = init_context(ctx.get());
+    if (rc) // hand nothing half-built to the caller, keep nothing behind
         return rc;
-    }
-    *out = ctx;
+    *out = ctx.release();
     return TRT_OK;
 }
 
@@ -230,19 +227,19 @@ static int init_context(trt_context *ctx)
         if (sscanf(e, "%d", &mode) == 1 && mode >= -1 && mode <= 1)
             ctx->compaction = mode;
     }
-    HIP_TRY(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
+    HIP_TRY(ctx->own_stream.create());
     ctx->stream = ctx->own_stream;
     for (int i = 0; i < kEventRing; i++)
     {
-        HIP_TRY(hipEventCreate(&ctx->ev_start[i]));
-        HIP_TRY(hipEventCreate(&ctx->ev_mid[i]));
-        HIP_TRY(hipEventCreate(&ctx->ev_stop[i]));
+        HIP_TRY(ctx->ev_start[i].create());
+        HIP_TRY(ctx->ev_mid[i].create());
+        HIP_TRY(ctx->ev_stop[i].create());
     }
-    for (int i = 0; i < 16; i++)
-        HIP_TRY(hipEventCreateWithFlags(&ctx->ev_chunk[i], hipEventDisableTiming));
-    for (int i = 0; i < 8; i++)
-        HIP_TRY(hipEventCreateWithFlags(&ctx->ev_band[i], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+    for (Event &e : ctx->ev_chunk)
+        HIP_TRY(e.create(hipEventDisableTiming));
+    for (Event &e : ctx->ev_band)
+        HIP_TRY(e.create(hipEventDisableTiming));
+    HIP_TRY(ctx->ev_fork.create(hipEventDisableTiming));
     HIP_TRY(ctx->d_counters.reserve(kCounterSlots));
     HIP_TRY(ctx->d_queue.reserve(trt::kQueueWords));
     HIP_TRY(hipMemset(ctx->d_counters.ptr, 0, kCounterSlots * sizeof(unsigned long long)));
@@ -257,48 +254,8 @@ extern "C" int trt_destroy(trt_context *ctx)
 {
     if (!ctx)
         return TRT_OK;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream)
-        (void)hipStreamSynchronize(ctx->stream);
-    for (int i = 0; i < kEventRing; i++)
-    {
-        if (ctx->ev_start[i])
-            (void)hipEventDestroy(ctx->ev_start[i]);
-        if (ctx->ev_mid[i])
-            (void)hipEventDestroy(ctx->ev_mid[i]);
-        if (ctx->ev_stop[i])
-            (void)hipEventDestroy(ctx->ev_stop[i]);
-    }
-    for (int i = 0; i < 16; i++)
-        if (ctx->ev_chunk[i])
-            (void)hipEventDestroy(ctx->ev_chunk[i]);
-    for (int i = 0; i < 8; i++)
-        if (ctx->ev_band[i])
-            (void)hipEventDestroy(ctx->ev_band[i]);
-    (void)hipGetLastError();
-    if (ctx->copy_stream)
-        (void)hipStreamDestroy(ctx->copy_stream);
-    if (ctx->alt_stream)
-        (void)hipStreamDestroy(ctx->alt_stream);
-    if (ctx->ev_fork)
-        (void)hipEventDestroy(ctx->ev_fork);
-    if (ctx->T)
-        ctx->T->eye_slots_taken &= ~(1u << ctx->eye_slot);
-    ctx->T.reset(); // the tables go with their last context
-    ctx->d_jitter.release();
-    ctx->d_axes.release();
-    ctx->d_samples.release();
-    ctx->d_samples_alt.release();
-    ctx->d_fb.release();
-    ctx->d_rgb8.release();
-    ctx->d_ior.release();
-    ctx->d_counters.release();
-    ctx->d_queue.release();
-    if (ctx->h_staging)
-        (void)hipHostFree(ctx->h_staging);
-    if (ctx->own_stream)
-        (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
+    (void)hipGetLastError(); // a failed free or destroy is not the error of the caller's next launch
     return TRT_OK;
 }
 
@@ -321,21 +278,19 @@ extern "C" int trt_reserve_cus(trt_context *ctx, int reserved)
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     const bool was_own = ctx->stream == ctx->own_stream;
-    hipStream_t fresh = nullptr;
+    Stream fresh;
     if (reserved == 0)
-        HIP_TRY(hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking));
+        HIP_TRY(fresh.create());
     else
     { // one bit per CU; the driver deals consecutive bits round the XCDs, so dropping the top bits thins every XCD alike
         std::vector<uint32_t> mask((size_t)(ctx->compute_units + 31) / 32, 0u);
         for (int cu = 0; cu < ctx->compute_units - reserved; cu++)
             mask[(size_t)cu / 32] |= 1u << (cu % 32);
-        HIP_TRY(hipExtStreamCreateWithCUMask(&fresh, (uint32_t)mask.size(), mask.data()));
+        HIP_TRY(fresh.create((uint32_t)mask.size(), mask.data()));
     }
-    if (ctx->own_stream)
-        (void)hipStreamDestroy(ctx->own_stream);
-    ctx->own_stream = fresh;
+    ctx->own_stream = std::move(fresh);
     if (was_own)
-        ctx->stream = fresh;
+        ctx->stream = ctx->own_stream;
     ctx->reserved_cus = reserved;
     return TRT_OK;
 }

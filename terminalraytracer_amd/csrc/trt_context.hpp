@@ -68,6 +68,7 @@
 #endif
 
 #include "trt_common.hpp"
+#include "trt_handles.hpp"
 #include "trt_rounds.hpp"
 
 namespace trt_impl
@@ -105,36 +106,12 @@ inline double triangle_wave(double t)
     return (m < kPi) ? (m / kPi) : (2 - (m / kPi));
 }
 
-template <typename T>
-struct DeviceBuffer
-{
-    T *ptr = nullptr;
-    size_t capacity = 0; // elements
-    hipError_t reserve(size_t n)
-    {
-        if (n <= capacity && ptr)
-            return hipSuccess;
-        if (ptr)
-            (void)hipFree(ptr);
-        ptr = nullptr;
-        capacity = 0;
-        hipError_t e = hipMalloc((void **)&ptr, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess)
-            capacity = std::max<size_t>(n, 1);
-        return e;
-    }
-    void release()
-    {
-        if (ptr)
-            (void)hipFree(ptr);
-        ptr = nullptr;
-        capacity = 0;
-    }
-};
-
 } // namespace trt_impl
 
 using trt_impl::DeviceBuffer;
+using trt_impl::Event;
+using trt_impl::PinnedBuffer;
+using trt_impl::Stream;
 using trt_impl::kEventRing;
 
 // Everything on the device that depends on the SCENE only (primitives, cubemap, every candidate table but the eye's two): built by
@@ -173,21 +150,14 @@ struct SceneTables
     unsigned eye_slots_taken = 0;                  // bit s: a context renders with the eye tables of slot s
     bool built_for_moving_scene = false;           // the cheap tables of a scene that changes from call to call
     double build_seconds = 0.0;                    // host time of the last table build (trt_scene_info)
-    ~SceneTables()
-    {
-        (void)hipSetDevice(device);
-        d_spheres.release(), d_dir.release(), d_point.release(), d_cull.release(), d_dir_masks.release(), d_point_masks.release();
-        d_dirgrids.release(), d_pointgrids.release(), d_discs.release(), d_cones.release(), d_dir_lists.release(), d_point_lists.release();
-        d_path_lists.release(), d_pool.release(), d_pool_used.release(), d_families.release(), d_sphere_fam.release(), d_patch_rec.release();
-        d_sky.release();
-    }
+    ~SceneTables() { (void)hipSetDevice(device); } // before the buffers are freed
 };
 
 struct trt_context
 {
     int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
+    Stream own_stream;
+    hipStream_t stream = nullptr; // own_stream, or the caller's (trt_set_stream)
     int compute_units = 0;
     int reserved_cus = 0; // CUs the context's own stream may not use (trt_reserve_cus)
     int lds_limit = 0;
@@ -218,8 +188,7 @@ struct trt_context
     int ior_count = 0;          // 0 = off (the reference's path)
     DeviceBuffer<unsigned long long> d_counters;
     DeviceBuffer<unsigned int> d_queue;
-    double *h_staging = nullptr; // pinned
-    size_t h_staging_bytes = 0;
+    PinnedBuffer h_staging; // trt_render_host, trt_render_host_rgb8
 
     // cache keys of the per-frame tables (jitter; per-column / per-row screen coordinates)
     int jit_spp = -1;
@@ -237,22 +206,33 @@ struct trt_context
     unsigned queue_ready[2][3] = {{0, 0, 0}, {0, 0, 0}};
     int compaction = -1;           // trt_set_compaction: -1 when it costs no occupancy, 0 never, 1 whenever the rings fit
     size_t occupancy_for_lds = (size_t)-1;
-    hipEvent_t ev_chunk[16]; // hand-over of framebuffer chunks to the host copy threads (trt_render_host)
-    hipEvent_t ev_band[8];   // a band of rows is rendered: its copy-out may start (trt_render_host)
-    hipStream_t copy_stream = nullptr;
-    hipStream_t alt_stream = nullptr; // second render stream of trt_render_host: odd bands (their tails overlap the next band)
-    hipEvent_t ev_fork = nullptr;
+    Event ev_chunk[16]; // hand-over of framebuffer chunks to the host copy threads (trt_render_host)
+    Event ev_band[8];   // a band of rows is rendered: its copy-out may start (trt_render_host)
+    Stream copy_stream;
+    Stream alt_stream; // second render stream of trt_render_host: odd bands (their tails overlap the next band)
+    Event ev_fork;
     bool counters_enabled = false;
     unsigned long long last_trips = 0, last_phase2 = 0, last_swept = 0, last_passes = 0; // diagnostics of the counting kernel variant
     unsigned long long last_loops[8] = {0, 0, 0, 0, 0, 0, 0, 0};                        // trt_read_loop_diagnostics
 
-    hipEvent_t ev_start[kEventRing], ev_mid[kEventRing], ev_stop[kEventRing]; // launch begins | render kernel done | reduction done
+    Event ev_start[kEventRing], ev_mid[kEventRing], ev_stop[kEventRing]; // launch begins | render kernel done | reduction done
     long launches = 0;
 
     // skybox cache key of the default context
     const void *sky_faces[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int sky_dim = -1;
     unsigned long long sky_stamp = 0; // content stamp of the faces (sampled texels): a free-and-reload at the same addresses is noticed
+
+    // After this body the members are destroyed in reverse order of declaration: the events and the two extra streams of
+    // trt_render_host, then the buffers they copy, the scene tables (if this was their last context), own_stream last.
+    ~trt_context()
+    {
+        (void)hipSetDevice(device);
+        if (stream)
+            (void)hipStreamSynchronize(stream);
+        if (T)
+            T->eye_slots_taken &= ~(1u << eye_slot);
+    }
 };
 
 namespace trt_impl

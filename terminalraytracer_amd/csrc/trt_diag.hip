@@ -156,7 +156,6 @@ extern "C" int trt_selftest_div_sqrt(trt_context *ctx, const double *a, const do
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipMemcpy(quot, dq, n * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(root, dr, n * sizeof(double), hipMemcpyDeviceToHost));
-    buf.release();
     return TRT_OK;
 }
 
@@ -176,7 +175,6 @@ extern "C" int trt_selftest_unit(trt_context *ctx, const double *xyzw, size_t n,
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipMemcpy(fast, df, 4 * n * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(reference, dr, 4 * n * sizeof(double), hipMemcpyDeviceToHost));
-    buf.release();
     return TRT_OK;
 }
 
@@ -232,7 +230,6 @@ extern "C" int trt_selftest_sky(trt_context *ctx, const double *dirs, size_t n, 
     HIP_TRY(hipMemcpy(exact, out.ptr, n * sizeof(long), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(estimate, out.ptr + n, n * sizeof(long), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(ambiguous, flags.ptr, n * sizeof(int), hipMemcpyDeviceToHost));
-    in.release(), out.release(), flags.release();
     return TRT_OK;
 }
 
@@ -250,7 +247,6 @@ extern "C" int trt_selftest_cube(trt_context *ctx, const float *xyz, size_t n, f
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipMemcpy(device_out, buf.ptr + 3 * n, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
-    buf.release();
     for (size_t i = 0; i < n; i++)
     { // the same header compiled for the host: the C restatement of the four instructions
         int face;
@@ -286,8 +282,6 @@ extern "C" int trt_probe_rays(trt_context *ctx, const Ray *rays, size_t n, int *
     HIP_TRY(hipMemcpy(normal, dn, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(material, dm, 5 * n * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(lit, dl, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
-    buf.release();
-    dobj.release();
     return TRT_OK;
 }
 
@@ -346,8 +340,6 @@ extern "C" int trt_probe_rays_production(trt_context *ctx, const Camera *camera,
     HIP_TRY(hipMemcpy(normal, dn, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(material, dm, 5 * n * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(lit, dl, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
-    buf.release();
-    dobj.release();
     return TRT_OK;
 }
 

@@ -15,6 +15,7 @@
 // using that one), so libtrt_hip.so itself does not depend on it and single-GPU hosts never load it.
 #include "trt_hip.h"
 #include "trt_hip_diag.h"
+#include "trt_handles.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -26,8 +27,11 @@
 
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <vector>
+
+using namespace trt_impl; // the owners of trt_handles.hpp
 
 namespace
 {
@@ -49,6 +53,14 @@ int dist_fail(int code, const char *fmt, ...)
         hipError_t e_ = (expr);                                                                                    \
         if (e_ != hipSuccess)                                                                                      \
             return dist_fail(TRT_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+#define DIST_TRT(expr)                                                \
+    do                                                                \
+    {                                                                 \
+        const int rc_ = (expr);                                       \
+        if (rc_ != TRT_OK)                                            \
+            return dist_fail(rc_, "%s: %s", #expr, trt_last_error()); \
     } while (0)
 
 // the nine RCCL entry points used, bound by name
@@ -160,15 +172,16 @@ __global__ void assemble_rows_kernel(const T *gathered, const int *source_row, T
 
 struct Slot
 {
-    trt_context *ctx = nullptr;
-    hipStream_t stream = nullptr; // the context's own
-    double *shard = nullptr;      // this rank's rows (padded to the largest shard); on the root a view into `gathered`
-    double *gathered = nullptr;   // root: world x max_rows rows, rank-major
-    double *frame = nullptr;      // root: height rows in frame order
-    // the same three for the frame as the emitter's bytes, 3 per pixel (trt_dist_enable_rgb8)
-    unsigned char *shard8 = nullptr, *gathered8 = nullptr, *frame8 = nullptr;
-    hipEvent_t rendered = nullptr, consumed = nullptr;
-    hipEvent_t gather_begin = nullptr; // on the communicator's stream once the shard is rendered; `consumed` ends the gather (both with timing)
+    std::unique_ptr<trt_context, int (*)(trt_context *)> ctx{nullptr, trt_destroy};
+    hipStream_t stream = nullptr;     // the context's own
+    DeviceBuffer<double> buffer;      // this rank's rows, padded to the largest shard; on the root: world x those, rank-major (the gather buffer)
+    double *shard = nullptr;          // this rank's rows in `buffer`
+    DeviceBuffer<double> frame;       // root: height rows in frame order
+    // the same for the frame as the emitter's bytes, 3 per pixel (trt_dist_enable_rgb8)
+    DeviceBuffer<unsigned char> buffer8, frame8;
+    unsigned char *shard8 = nullptr;
+    Event rendered, consumed;
+    Event gather_begin; // on the communicator's stream once the shard is rendered; `consumed` ends the gather (both with timing)
     bool used = false, gathered_once = false;
 };
 
@@ -182,14 +195,28 @@ struct trt_dist
     int local_rows = 0, max_rows = 0;
     std::vector<int> rows_of_rank; // rows owned by every rank
     std::vector<Slot> slots;
-    hipStream_t comm_stream = nullptr;
+    Stream comm_stream;
     ncclComm_t comm = nullptr;
-    int *d_source_row = nullptr; // root: frame row -> row of the gather buffer
+    DeviceBuffer<int> d_source_row; // root: frame row -> row of the gather buffer
     bool through_comm = false;   // world > 1, or world == 1 with an id given: the gather path is taken (with no peers to receive from)
     bool rgb8 = false;           // byte buffers allocated (trt_dist_enable_rgb8)
     int comm_ranks = 0;          // what ncclCommCount says of the communicator that was created (0: none, the gather path is not taken)
     bool poisoned = false;       // a collective failed on this rank: its peers may have gone on without it, nothing can be trusted any more
     long calls = 0;
+
+    bool gathers() const { return rank == root && through_comm; } // receives the shards into each slot's `buffer`, assembles the frame
+    ~trt_dist() // the members are freed after this body: after the communicator
+    {
+        (void)hipSetDevice(device);
+        for (Slot &s : slots)
+            if (s.ctx)
+                (void)trt_synchronize(s.ctx.get());
+        if (comm_stream)
+            (void)hipStreamSynchronize(comm_stream);
+        if (comm)
+            if (Rccl *R = rccl())
+                (void)R->CommDestroy(comm);
+    }
 };
 
 extern "C" const char *trt_dist_last_error(void) { return g_dist_error; }
@@ -259,45 +286,64 @@ extern "C" int trt_dist_comm_ranks(trt_dist *d)
 
 extern "C" int trt_dist_destroy(trt_dist *d)
 {
-    if (!d)
-        return TRT_OK;
-    (void)hipSetDevice(d->device);
-    for (Slot &s : d->slots)
-        if (s.ctx)
-            (void)trt_synchronize(s.ctx);
-    if (d->comm_stream)
-        (void)hipStreamSynchronize(d->comm_stream);
-    if (d->comm)
-        if (Rccl *R = rccl())
-            (void)R->CommDestroy(d->comm);
+    delete d;
+    return TRT_OK;
+}
+
+// the slots, their buffers and the communicator of a new trt_dist whose shape is set
+static int init_dist(trt_dist *d, const Scene *scene, const void *id, int frames_in_flight, int reserved_cus)
+{
+    DIST_HIP(hipSetDevice(d->device));
+    const size_t row_doubles = (size_t)d->width * 3;
+    d->slots.resize((size_t)frames_in_flight);
     for (Slot &s : d->slots)
     {
-        if (s.rendered)
-            (void)hipEventDestroy(s.rendered);
-        if (s.consumed)
-            (void)hipEventDestroy(s.consumed);
-        if (s.gather_begin)
-            (void)hipEventDestroy(s.gather_begin);
-        if (s.gathered)
-            (void)hipFree(s.gathered);
-        else if (s.shard)
-            (void)hipFree(s.shard);
-        if (s.frame)
-            (void)hipFree(s.frame);
-        if (s.gathered8)
-            (void)hipFree(s.gathered8);
-        else if (s.shard8)
-            (void)hipFree(s.shard8);
-        if (s.frame8)
-            (void)hipFree(s.frame8);
-        if (s.ctx)
-            (void)trt_destroy(s.ctx);
+        trt_context *ctx = nullptr;
+        DIST_TRT(trt_create(d->device, &ctx));
+        s.ctx.reset(ctx);
+        // ONE copy of the scene and of its candidate tables per device: the first slot builds them, the others render from them
+        // (trt_share_scene); only the eye's tables, the scratch and the frame buffers are a slot's own
+        if (&s == &d->slots[0])
+            DIST_TRT(trt_set_scene(ctx, scene));
+        else
+            DIST_TRT(trt_share_scene(ctx, d->slots[0].ctx.get()));
+        if (reserved_cus > 0)
+            DIST_TRT(trt_reserve_cus(ctx, reserved_cus));
+        void *stream = nullptr;
+        DIST_TRT(trt_get_stream(ctx, &stream));
+        s.stream = (hipStream_t)stream;
+        DIST_HIP(s.buffer.reserve((size_t)(d->gathers() ? d->world : 1) * d->max_rows * row_doubles));
+        s.shard = s.buffer.ptr + (d->gathers() ? (size_t)d->rank * d->max_rows * row_doubles : 0); // the root renders straight into the gather buffer
+        if (d->gathers())
+            DIST_HIP(s.frame.reserve((size_t)d->height * row_doubles));
+        DIST_HIP(s.rendered.create(hipEventDisableTiming));
+        DIST_HIP(s.consumed.create()); // with timing: trt_dist_frame_times
+        DIST_HIP(s.gather_begin.create());
     }
-    if (d->d_source_row)
-        (void)hipFree(d->d_source_row);
-    if (d->comm_stream)
-        (void)hipStreamDestroy(d->comm_stream);
-    delete d;
+    if (d->through_comm)
+    {
+        Rccl *R = rccl();
+        if (!R)
+            return dist_fail(TRT_ERR_NOT_INITIALISED, "%s", rccl_why());
+        DIST_HIP(d->comm_stream.create());
+        ncclUniqueId uid;
+        memcpy(&uid, id, sizeof uid);
+        const ncclResult_t r = R->CommInitRank(&d->comm, d->world, uid, d->rank);
+        if (r != ncclSuccess)
+            return dist_fail(TRT_ERR_HIP, "ncclCommInitRank(rank %d of %d): %s", d->rank, d->world, R->GetErrorString(r));
+        // what the library itself says of the communicator: a record of "RCCL saw N ranks" for the caller (trt_dist_comm_ranks)
+        const ncclResult_t rc = R->CommCount(d->comm, &d->comm_ranks);
+        if (rc != ncclSuccess || d->comm_ranks != d->world)
+            return dist_fail(TRT_ERR_HIP, "the communicator has %d ranks, %d were asked for (%s)", d->comm_ranks, d->world, R->GetErrorString(rc));
+        if (d->rank == d->root)
+        { // frame row -> row of the rank-major gather buffer (the tile map of trt_rowset_frame_row)
+            std::vector<int> source((size_t)d->height, -1);
+            if (trt_dist_source_rows(d->width, d->height, d->tile_rows, d->world, source.data()) != d->max_rows)
+                return dist_fail(TRT_ERR_ARGUMENT, "the row tiles do not cover the frame");
+            DIST_HIP(d->d_source_row.reserve(source.size()));
+            DIST_HIP(hipMemcpy(d->d_source_row.ptr, source.data(), source.size() * sizeof(int), hipMemcpyHostToDevice));
+        }
+    }
     return TRT_OK;
 }
 
@@ -311,7 +357,7 @@ extern "C" int trt_dist_create(int device, const Scene *scene, const void *id, i
         frames_in_flight > 8 || reserved_cus < 0 || (world > 1 && !id))
         return dist_fail(TRT_ERR_ARGUMENT, "bad argument (rank %d of %d, %d x %d, tiles of %d rows, %d frames in flight)", rank, world, width,
                          height, tile_rows, frames_in_flight);
-    trt_dist *d = new trt_dist();
+    std::unique_ptr<trt_dist> d(new trt_dist());
     d->device = device, d->rank = rank, d->world = world;
     d->through_comm = world > 1 || id != nullptr;
     d->width = width, d->height = height, d->tile_rows = tile_rows;
@@ -323,93 +369,17 @@ extern "C" int trt_dist_create(int device, const Scene *scene, const void *id, i
         d->rows_of_rank.push_back(trt_rowset_rows(&rs));
         d->max_rows = std::max(d->max_rows, d->rows_of_rank.back());
     }
-    auto bail = [&](int rc) {
+    const int rc = init_dist(d.get(), scene, id, frames_in_flight, reserved_cus);
+    if (rc)
+    { // nothing half-built is kept; trt_dist_last_error() still reports the first failure, not what the teardown may say
         char keep[sizeof g_dist_error];
         memcpy(keep, g_dist_error, sizeof keep);
-        (void)trt_dist_destroy(d);
+        d.reset();
         memcpy(g_dist_error, keep, sizeof keep);
         return rc;
-    };
-#define DIST_TRY(expr)                \
-    do                                \
-    {                                 \
-        const int rc_ = (expr);       \
-        if (rc_ != TRT_OK)            \
-            return bail(rc_);         \
-    } while (0)
-#define DIST_TRT(expr)                                                                     \
-    do                                                                                     \
-    {                                                                                      \
-        const int rc_ = (expr);                                                            \
-        if (rc_ != TRT_OK)                                                                 \
-            return bail(dist_fail(rc_, "%s: %s", #expr, trt_last_error()));                \
-    } while (0)
-#define DIST_HIP_B(expr)                                                                                         \
-    do                                                                                                           \
-    {                                                                                                            \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess)                                                                                    \
-            return bail(dist_fail(TRT_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__)); \
-    } while (0)
-
-    DIST_HIP_B(hipSetDevice(device));
-    const size_t row_doubles = (size_t)width * 3;
-    d->slots.resize((size_t)frames_in_flight);
-    for (Slot &s : d->slots)
-    {
-        DIST_TRT(trt_create(device, &s.ctx));
-        // ONE copy of the scene and of its candidate tables per device: the first slot builds them, the others render from them
-        // (trt_share_scene); only the eye's tables, the scratch and the frame buffers are a slot's own
-        if (&s == &d->slots[0])
-            DIST_TRT(trt_set_scene(s.ctx, scene));
-        else
-            DIST_TRT(trt_share_scene(s.ctx, d->slots[0].ctx));
-        if (reserved_cus > 0)
-            DIST_TRT(trt_reserve_cus(s.ctx, reserved_cus));
-        void *stream = nullptr;
-        DIST_TRT(trt_get_stream(s.ctx, &stream));
-        s.stream = (hipStream_t)stream;
-        if (rank == d->root && d->through_comm)
-        { // the root renders straight into its part of the gather buffer
-            DIST_HIP_B(hipMalloc((void **)&s.gathered, (size_t)world * d->max_rows * row_doubles * sizeof(double)));
-            s.shard = s.gathered + (size_t)rank * d->max_rows * row_doubles;
-            DIST_HIP_B(hipMalloc((void **)&s.frame, (size_t)height * row_doubles * sizeof(double)));
-        }
-        else
-            DIST_HIP_B(hipMalloc((void **)&s.shard, (size_t)std::max(d->max_rows, 1) * row_doubles * sizeof(double)));
-        DIST_HIP_B(hipEventCreateWithFlags(&s.rendered, hipEventDisableTiming));
-        DIST_HIP_B(hipEventCreate(&s.consumed));     // with timing: trt_dist_frame_times
-        DIST_HIP_B(hipEventCreate(&s.gather_begin));
     }
-    if (d->through_comm)
-    {
-        Rccl *R = rccl();
-        if (!R)
-            return bail(dist_fail(TRT_ERR_NOT_INITIALISED, "%s", rccl_why()));
-        DIST_HIP_B(hipStreamCreateWithFlags(&d->comm_stream, hipStreamNonBlocking));
-        ncclUniqueId uid;
-        memcpy(&uid, id, sizeof uid);
-        const ncclResult_t r = R->CommInitRank(&d->comm, world, uid, rank);
-        if (r != ncclSuccess)
-            return bail(dist_fail(TRT_ERR_HIP, "ncclCommInitRank(rank %d of %d): %s", rank, world, R->GetErrorString(r)));
-        // what the library itself says of the communicator: a record of "RCCL saw N ranks" for the caller (trt_dist_comm_ranks)
-        const ncclResult_t rc = R->CommCount(d->comm, &d->comm_ranks);
-        if (rc != ncclSuccess || d->comm_ranks != world)
-            return bail(dist_fail(TRT_ERR_HIP, "the communicator has %d ranks, %d were asked for (%s)", d->comm_ranks, world, R->GetErrorString(rc)));
-        if (rank == d->root)
-        { // frame row -> row of the rank-major gather buffer (the tile map of trt_rowset_frame_row)
-            std::vector<int> source((size_t)height, -1);
-            if (trt_dist_source_rows(width, height, tile_rows, world, source.data()) != d->max_rows)
-                return bail(dist_fail(TRT_ERR_ARGUMENT, "the row tiles do not cover the frame"));
-            DIST_HIP_B(hipMalloc((void **)&d->d_source_row, source.size() * sizeof(int)));
-            DIST_HIP_B(hipMemcpy(d->d_source_row, source.data(), source.size() * sizeof(int), hipMemcpyHostToDevice));
-        }
-    }
-    *out = d;
+    *out = d.release();
     return TRT_OK;
-#undef DIST_TRY
-#undef DIST_TRT
-#undef DIST_HIP_B
 }
 
 extern "C" int trt_dist_set_scene(trt_dist *d, const Scene *scene)
@@ -417,11 +387,11 @@ extern "C" int trt_dist_set_scene(trt_dist *d, const Scene *scene)
     if (!d || !scene)
         return dist_fail(TRT_ERR_ARGUMENT, "NULL argument");
     for (Slot &s : d->slots) // every slot's frames in flight still read the old tables
-        if (trt_synchronize(s.ctx))
+        if (trt_synchronize(s.ctx.get()))
             return dist_fail(TRT_ERR_HIP, "trt_synchronize: %s", trt_last_error());
     for (Slot &s : d->slots)
     { // the first slot builds the new scene's tables (its old ones stay alive until the last sharer has let go), the others share them
-        const int rc = &s == &d->slots[0] ? trt_set_scene(s.ctx, scene) : trt_share_scene(s.ctx, d->slots[0].ctx);
+        const int rc = &s == &d->slots[0] ? trt_set_scene(s.ctx.get(), scene) : trt_share_scene(s.ctx.get(), d->slots[0].ctx.get());
         if (rc)
         { // some slots may hold the new scene and others the old one: frames would alternate between the two without an error.
           // Nothing of this trt_dist can be trusted any more -- the same state a failed collective leaves (trt_hip.h).
@@ -443,16 +413,10 @@ extern "C" int trt_dist_enable_rgb8(trt_dist *d)
     const size_t row_bytes = (size_t)d->width * 3;
     for (Slot &s : d->slots)
     { // a call that failed half-way may be repeated: what exists is kept
-        if (d->rank == d->root && d->through_comm)
-        {
-            if (!s.gathered8)
-                DIST_HIP(hipMalloc((void **)&s.gathered8, (size_t)d->world * d->max_rows * row_bytes));
-            s.shard8 = s.gathered8 + (size_t)d->rank * d->max_rows * row_bytes;
-            if (!s.frame8)
-                DIST_HIP(hipMalloc((void **)&s.frame8, (size_t)d->height * row_bytes));
-        }
-        else if (!s.shard8)
-            DIST_HIP(hipMalloc((void **)&s.shard8, (size_t)std::max(d->max_rows, 1) * row_bytes));
+        DIST_HIP(s.buffer8.reserve((size_t)(d->gathers() ? d->world : 1) * d->max_rows * row_bytes));
+        s.shard8 = s.buffer8.ptr + (d->gathers() ? (size_t)d->rank * d->max_rows * row_bytes : 0);
+        if (d->gathers())
+            DIST_HIP(s.frame8.reserve((size_t)d->height * row_bytes));
     }
     d->rgb8 = true;
     return TRT_OK;
@@ -486,10 +450,10 @@ static int render_and_gather(trt_dist *d, const Camera *camera, int bounce_limit
     s.used = true;
     if (d->local_rows > 0)
     {
-        int rc = trt_render_device(s.ctx, camera, &d->rows, bounce_limit, rays_per_pixel, s.shard,
+        int rc = trt_render_device(s.ctx.get(), camera, &d->rows, bounce_limit, rays_per_pixel, s.shard,
                                    (size_t)std::max(d->max_rows, 1) * row_doubles * sizeof(double));
         if (!rc && bytes)
-            rc = trt_quantize_device(s.ctx, s.shard, (size_t)d->local_rows * d->width, s.shard8);
+            rc = trt_quantize_device(s.ctx.get(), s.shard, (size_t)d->local_rows * d->width, s.shard8);
         if (rc)
             return poison(dist_fail(rc, "trt_render_device: %s", trt_last_error()));
     }
@@ -514,7 +478,7 @@ static int render_and_gather(trt_dist *d, const Camera *camera, int bounce_limit
             if (r != d->root && d->rows_of_rank[(size_t)r] > 0)
             {
                 const size_t at = (size_t)r * d->max_rows * row_elements, count = (size_t)d->rows_of_rank[(size_t)r] * row_elements;
-                first = R->Recv(bytes ? (void *)(s.gathered8 + at) : (void *)(s.gathered + at), count, type, r, d->comm, d->comm_stream);
+                first = R->Recv(bytes ? (void *)(s.buffer8.ptr + at) : (void *)(s.buffer.ptr + at), count, type, r, d->comm, d->comm_stream);
             }
     }
     else if (opened && d->local_rows > 0)
@@ -532,17 +496,17 @@ static int render_and_gather(trt_dist *d, const Camera *camera, int bounce_limit
         const long total = (long)d->height * (long)row_elements;
         if (bytes)
             hipLaunchKernelGGL(assemble_rows_kernel<unsigned char>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, d->comm_stream,
-                               (const unsigned char *)s.gathered8, (const int *)d->d_source_row, s.frame8, (long)row_elements, total);
+                               (const unsigned char *)s.buffer8.ptr, (const int *)d->d_source_row.ptr, s.frame8.ptr, (long)row_elements, total);
         else
             hipLaunchKernelGGL(assemble_rows_kernel<double>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, d->comm_stream,
-                               (const double *)s.gathered, (const int *)d->d_source_row, s.frame, (long)row_elements, total);
+                               (const double *)s.buffer.ptr, (const int *)d->d_source_row.ptr, s.frame.ptr, (long)row_elements, total);
         if (hipGetLastError() != hipSuccess)
             return poison(dist_fail(TRT_ERR_HIP, "the assembly kernel could not be launched"));
     }
     if (hipEventRecord(s.consumed, d->comm_stream) != hipSuccess)
         return poison(dist_fail(TRT_ERR_HIP, "hipEventRecord failed"));
     if (d_frame)
-        *d_frame = d->rank == d->root ? (bytes ? (void *)s.frame8 : (void *)s.frame) : nullptr;
+        *d_frame = d->rank == d->root ? (bytes ? (void *)s.frame8.ptr : (void *)s.frame.ptr) : nullptr;
     return TRT_OK;
 }
 
@@ -586,7 +550,7 @@ extern "C" int trt_dist_frame_times(trt_dist *d, float *render_ms, float *gather
     for (Slot &s : d->slots)
     {
         float r = 0.0f, m = 0.0f;
-        if (s.used && d->local_rows > 0 && trt_render_kernel_times(s.ctx, &r, &m, 1) == 1)
+        if (s.used && d->local_rows > 0 && trt_render_kernel_times(s.ctx.get(), &r, &m, 1) == 1)
             render += r + m, renders++;
         float g = 0.0f;
         if (s.gathered_once && hipEventElapsedTime(&g, s.gather_begin, s.consumed) == hipSuccess)
@@ -643,5 +607,5 @@ extern "C" trt_context *trt_dist_context(trt_dist *d, int slot)
 {
     if (!d || slot < 0 || slot >= (int)d->slots.size())
         return nullptr;
-    return d->slots[(size_t)slot].ctx;
+    return d->slots[(size_t)slot].ctx.get();
 }

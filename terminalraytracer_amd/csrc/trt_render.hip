@@ -406,15 +406,7 @@ extern "C" int trt_render_host(trt_context *ctx, const Camera *camera, const trt
     const size_t count = (size_t)trt_rowset_rows(rows) * rows->width;
     const size_t bytes = count * sizeof(Vector);
     HIP_TRY(ctx->d_fb.reserve(count * 3));
-    if (ctx->h_staging_bytes < bytes)
-    {
-        if (ctx->h_staging)
-            (void)hipHostFree(ctx->h_staging);
-        ctx->h_staging = nullptr;
-        ctx->h_staging_bytes = 0;
-        HIP_TRY(hipHostMalloc((void **)&ctx->h_staging, std::max<size_t>(bytes, 1), hipHostMallocDefault));
-        ctx->h_staging_bytes = std::max<size_t>(bytes, 1);
-    }
+    HIP_TRY(ctx->h_staging.reserve(bytes));
     const double t_begin = host_now_ms();
     // A whole frame is rendered in up to four bands of rows: while band b+1 is being rendered, band b crosses PCIe on the
     // copy stream into pinned staging, chunk by chunk (an event per chunk), and a few host threads copy landed chunks
@@ -435,8 +427,8 @@ extern "C" int trt_render_host(trt_context *ctx, const Camera *camera, const trt
     if (bands > 1 && !ctx->copy_stream)
     { // created on first use: every stream of a process competes for a handful of hardware queues, and two streams that
       // land on one queue run one after the other (a renderer that never comes here keeps its streams to itself)
-        HIP_TRY(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&ctx->alt_stream, hipStreamNonBlocking));
+        HIP_TRY(ctx->copy_stream.create());
+        HIP_TRY(ctx->alt_stream.create());
     }
     const hipStream_t copy_stream = bands > 1 ? ctx->copy_stream : ctx->stream;
     if (ctx->have_scene && camera)
@@ -472,7 +464,7 @@ extern "C" int trt_render_host(trt_context *ctx, const Camera *camera, const trt
             chunk_at[chunks] = at + (size_t)i * per;
             chunk_len[chunks] = (size_t)i * per < len ? std::min(per, len - (size_t)i * per) : 0;
             if (chunk_len[chunks])
-                HIP_TRY(hipMemcpyAsync((char *)ctx->h_staging + chunk_at[chunks], (const char *)ctx->d_fb.ptr + chunk_at[chunks], chunk_len[chunks],
+                HIP_TRY(hipMemcpyAsync((char *)ctx->h_staging.ptr + chunk_at[chunks], (const char *)ctx->d_fb.ptr + chunk_at[chunks], chunk_len[chunks],
                                        hipMemcpyDeviceToHost, copy_stream));
             HIP_TRY(hipEventRecord(ctx->ev_chunk[chunks], copy_stream));
         }
@@ -490,7 +482,7 @@ extern "C" int trt_render_host(trt_context *ctx, const Camera *camera, const trt
                 worker_error[w] = e;
                 return;
             }
-            memcpy((char *)pixels + chunk_at[i], (const char *)ctx->h_staging + chunk_at[i], chunk_len[i]);
+            memcpy((char *)pixels + chunk_at[i], (const char *)ctx->h_staging.ptr + chunk_at[i], chunk_len[i]);
         }
     };
     if (workers == 1)
@@ -632,15 +624,7 @@ extern "C" int trt_render_host_rgb8(trt_context *ctx, const Camera *camera, cons
         return TRT_OK;
     HIP_TRY(ctx->d_fb.reserve(count * 3));
     HIP_TRY(ctx->d_rgb8.reserve(count * 3));
-    if (ctx->h_staging_bytes < count * 3)
-    {
-        if (ctx->h_staging)
-            (void)hipHostFree(ctx->h_staging);
-        ctx->h_staging = nullptr;
-        ctx->h_staging_bytes = 0;
-        HIP_TRY(hipHostMalloc((void **)&ctx->h_staging, count * 3, hipHostMallocDefault));
-        ctx->h_staging_bytes = count * 3;
-    }
+    HIP_TRY(ctx->h_staging.reserve(count * 3));
     const double t_begin = host_now_ms();
     int rc = trt_render_device(ctx, camera, rows, bounce_limit, rays_per_pixel, ctx->d_fb.ptr, count * sizeof(Vector));
     if (rc)
@@ -648,9 +632,9 @@ extern "C" int trt_render_host_rgb8(trt_context *ctx, const Camera *camera, cons
     rc = trt_quantize_device(ctx, ctx->d_fb.ptr, count, ctx->d_rgb8.ptr); // (int)(c*255), TRT.c:1157-1163, on the device
     if (rc)
         return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->h_staging, ctx->d_rgb8.ptr, count * 3, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_rgb8.ptr, count * 3, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    memcpy(rgb, ctx->h_staging, count * 3);
+    memcpy(rgb, ctx->h_staging.ptr, count * 3);
     if (print_host_times())
         fprintf(stderr, "trt_render_host_rgb8: %.3f ms for %zu pixels\n", host_now_ms() - t_begin, count);
     return TRT_OK;
