@@ -36,7 +36,7 @@ enum
     TRT_ERR_HIP = -1,         /* a HIP runtime call failed */
     TRT_ERR_ARGUMENT = -2,    /* NULL / out-of-range argument */
     TRT_ERR_NO_SCENE = -3,    /* render before trt_set_scene */
-    TRT_ERR_CAPACITY = -4,    /* output buffer too small, or scene too large for LDS staging */
+    TRT_ERR_CAPACITY = -4,    /* output buffer too small; a scene too large for LDS with trt_set_scene_image(ctx, 0) or the refraction extension */
     TRT_ERR_NOT_INITIALISED = -5
 };
 
@@ -45,7 +45,8 @@ enum
 /* Replaces `void project_scene(Scene *scene, Screen *screen)` (TRT.c:966; caller TRT.c:1339).
  * Same semantics at the reference's compile-time constants BOUNCE_LIMIT=10, RAYS_PER_PIXEL=10:
  * reads *scene (host pointers inside), overwrites screen->pixels[0 .. width*height).
- * Lazily creates a default context on device 0.  void like the original: a HIP failure prints
+ * Lazily creates a default context on device 0.  Any number of spheres and lights, as the reference: a scene whose image
+ * does not fit LDS is read from device memory.  void like the original: a HIP failure prints
  * the error and aborts (the reference cannot fail here either). */
 void project_scene(Scene *scene, Screen *screen);
 

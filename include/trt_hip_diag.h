@@ -7,6 +7,7 @@
  *   read-backs    the candidate tables the device built, for comparison with the host reference builders
  *   self-tests    device division / square root / normalisation / cube instructions / skybox estimate against their references
  *   probes        single rays through the reference-order kernel and through the production kernel's stages
+ *   scene image   where the kernels read the scene from: LDS or device memory
  *   test hooks    the pool cap of the long candidate lists; a stand-in for RCCL so that several ranks can share one GPU
  */
 #ifndef TRT_HIP_DIAG_H
@@ -113,6 +114,19 @@ int trt_probe_rays_production(trt_context *ctx, const Camera *camera, const Ray 
  * beside the host-clocked ms_per_step. */
 long trt_launch_count(trt_context *ctx);
 int trt_launch_span_ms(trt_context *first, long first_launch, trt_context *last, long last_launch, float *ms);
+
+/* Where the production kernel and the reference-order kernel (trt_set_kernel(1)) read the scene from.  Every workgroup stages
+ * an image of the scene (spheres, materials, lights, culling tables, table headers, camera, jitter) into LDS while it fits the
+ * device's LDS; a scene whose image does not fit is read from an image in device memory instead, written per launch in the same
+ * layout by one workgroup in front of the render kernel.  mode -1 (the default): device memory only when the LDS image of the
+ * frame does not fit; 0: LDS only -- a scene that does not fit fails with TRT_ERR_CAPACITY, in trt_set_scene or, when only the
+ * rays per pixel push it over, at render time; 1: device memory always (the same frames: for tests and A/B measurements).
+ * The refraction extension has no device-memory form: such a scene fails at render time whatever the mode. */
+int trt_set_scene_image(trt_context *ctx, int mode);
+
+/* The scene image of the kernel trt_render_variant describes: in_device_memory 1 when it reads the image from device memory,
+ * image_bytes its size (the production kernel's image for that launch's rays per pixel, or the reference-order kernel's records). */
+int trt_render_image(trt_context *ctx, int *in_device_memory, unsigned long long *image_bytes);
 
 /* TEST HOOK: allow (1) or forbid (0, the default) the environment variable TRT_RCCL_LIB to name the library that trt_dist_* binds in
  * RCCL's place (tests/rccl_stub.cpp: send / recv through shared memory, so that several ranks can share the one GPU of a test

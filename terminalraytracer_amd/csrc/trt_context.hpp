@@ -168,6 +168,7 @@ struct trt_context
     trt::SceneView scene{};
     trt::CullView cull{};
     DeviceBuffer<double> d_jitter, d_fb, d_axes, d_samples, d_samples_alt;
+    DeviceBuffer<double> d_image, d_image_alt; // the scene image in device memory, per lane set like the samples (render_rounds_kernel<.., DEVICE_IMAGE>)
     trt::GridView grids{};
     int dirgrid_cells = TRT_DIRGRID_CELLS, pointgrid_cells = TRT_POINTGRID_CELLS; // per side; 0 = no tables (sweep only)
     int dirgrid_slabs = TRT_DIRGRID_SLABS, pointgrid_shells = TRT_POINTGRID_SHELLS; // depth coordinate of the light tables (>= 1)
@@ -200,7 +201,10 @@ struct trt_context
     int rounds_blocks_per_cu = 0;
     int compact_blocks_per_cu = 0; // the same for the kernel with shading rings in LDS
     int big_blocks_per_cu = 0;     // ... and for the plain rounds in 1024-thread workgroups (render_rounds_kernel<.., BIG>; 0: not available)
+    int device_blocks_per_cu = 0;  // ... and for the plain rounds that read the scene image from device memory (no dynamic LDS; 0: not queried yet)
+    int scene_image = -1;          // trt_set_scene_image: -1 in device memory when the LDS image does not fit, 0 LDS only, 1 device memory always
     int last_variant = -1;         // the kernel the most recent launch ran (trt_render.hip: Variant); -1: none yet
+    int last_spp = 64;             // ... and its rays per pixel (the jitter is part of the image)
     // what the queue of each lane set was last left ready for (workgroups, waves per workgroup, words' shift; 0 workgroups: nothing):
     // the ordered-mean pass of a frame starts the queue for the next one, which then needs no kernel of its own in front of it
     unsigned queue_ready[2][3] = {{0, 0, 0}, {0, 0, 0}};

@@ -194,6 +194,7 @@ struct FrameView
     int tile_rows, tile_first, tile_step;
     int local_rows;
     int bounce_limit, spp;
+    const double *image;  // render_rounds_kernel<.., DEVICE_IMAGE>: the scene image of the launch in device memory (trt_rounds.hpp, image_layout)
 };
 
 // the same with the division as a multiply-high (f.tile_magic = min(ceil(2^32 / tile_rows), 2^32 - 1): off by at most one)

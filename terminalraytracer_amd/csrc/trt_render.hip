@@ -14,8 +14,8 @@ namespace trt_impl
 {
 
 // ---- which kernel a frame runs ----
-// The production kernel's instantiations (render_rounds_kernel<COUNT, REFRACT, COMPACT, PATCHES, BIG>), each with its counting
-// form where it has one (the rays trt_read_counters reports), and the reference-order kernel (trt_set_kernel(1)).
+// The production kernel's instantiations (render_rounds_kernel<COUNT, REFRACT, COMPACT, PATCHES, BIG, DEVICE_IMAGE>), each with its
+// counting form where it has one (the rays trt_read_counters reports), and the reference-order kernel (trt_set_kernel(1)).
 enum Variant : int
 {
     kPlain, kPlainCount,
@@ -23,7 +23,9 @@ enum Variant : int
     kPatchesBig,                 // ... in 1024-thread workgroups: one LDS image for sixteen waves
     kDecoupled, kDecoupledCount, // the shading decoupled from the owning lane (COMPACT, trt_rounds.hpp): rings in LDS
     kRefract, kRefractCount, kRefractPatches, kRefractPatchesCount, // the refraction extension (parity unpinned)
+    kPlainImage, kPlainImageCount, kPatchesImage, kPatchesImageCount, // the plain rounds with the scene image in device memory (DEVICE_IMAGE)
     kReference,                  // render_simple_kernel: one thread per pixel; not in kRounds
+    kReferenceImage,             // ... reading the scene's records from device memory
 };
 
 using RoundsKernel = void (*)(trt::SceneView, trt::CullView, trt::FrameView, trt::GridView);
@@ -32,6 +34,7 @@ struct RoundsVariant
     RoundsKernel fn;
     int block;  // threads per workgroup
     bool rings; // LDS: the image, then a shading ring per wave (compact_lds_bytes); otherwise the image alone
+    bool image; // the image in device memory (stage_image_kernel), no dynamic LDS
 };
 static const RoundsVariant kRounds[kReference] = {
     {trt::render_rounds_kernel<false>, trt::kPersistentBlock, false},
@@ -45,7 +48,25 @@ static const RoundsVariant kRounds[kReference] = {
     {trt::render_rounds_kernel<true, true>, trt::kPersistentBlock, false},
     {trt::render_rounds_kernel<false, true, false, true>, trt::kPersistentBlock, false},
     {trt::render_rounds_kernel<true, true, false, true>, trt::kPersistentBlock, false},
+    {trt::render_rounds_kernel<false, false, false, false, false, true>, trt::kPersistentBlock, false, true},
+    {trt::render_rounds_kernel<true, false, false, false, false, true>, trt::kPersistentBlock, false, true},
+    {trt::render_rounds_kernel<false, false, false, true, false, true>, trt::kPersistentBlock, false, true},
+    {trt::render_rounds_kernel<true, false, false, true, false, true>, trt::kPersistentBlock, false, true},
 };
+
+static bool image_in_device_memory(Variant v)
+{
+    return v == kReferenceImage || (v < kReference && kRounds[v].image);
+}
+
+// Does a frame of `spp` rays per pixel read its scene image from device memory (trt_set_scene_image)?  Automatic: only when the
+// image of the kernel it runs does not fit LDS, so that every scene that fits runs what it ran before there was a device image.
+static bool wants_device_image(const trt_context *ctx, int spp)
+{
+    if (ctx->scene_image >= 0)
+        return ctx->scene_image == 1;
+    return (ctx->kernel == 1 ? scene_lds_bytes(ctx->scene) : image_lds_bytes(ctx, spp)) > (size_t)ctx->lds_limit;
+}
 
 constexpr int kCompactionMinLights = 2; // trt_set_compaction(-1): decouple the shading from two lights up (with one it is a wash)
 
@@ -70,12 +91,15 @@ static bool renders_decoupled(const trt_context *ctx, long units)
 
 static Variant choose_variant(const trt_context *ctx, long units, int spp)
 {
+    const bool device_image = wants_device_image(ctx, spp);
     if (ctx->kernel == 1)
-        return kReference;
+        return device_image ? kReferenceImage : kReference;
     const bool count = ctx->counters_enabled;
     const bool patches = ctx->grids.path_enabled && ctx->grids.patch_m > 0;
-    if (ctx->ior_count)
+    if (ctx->ior_count) // no device-image form: a scene whose image does not fit LDS fails at render time
         return patches ? (count ? kRefractPatchesCount : kRefractPatches) : (count ? kRefractCount : kRefract);
+    if (device_image)
+        return patches ? (count ? kPatchesImageCount : kPatchesImage) : (count ? kPlainImageCount : kPlainImage);
     // scenes whose spheres have patches (dense ones) run the plain rounds; the rings must fit beside the image (the occupancy
     // figures were taken for 64 rays per pixel: with more, the jitter table may push the rings out of LDS)
     if (!patches && renders_decoupled(ctx, units) && compact_lds_bytes(ctx, spp) <= (size_t)ctx->lds_limit)
@@ -93,6 +117,11 @@ static Variant described_variant(const trt_context *ctx)
     return ctx->last_variant >= 0 ? (Variant)ctx->last_variant : choose_variant(ctx, kCompactionMinUnits, 64);
 }
 
+static int described_spp(const trt_context *ctx)
+{
+    return ctx->last_variant >= 0 ? ctx->last_spp : 64;
+}
+
 struct RenderPlan
 {
     Variant variant;
@@ -106,13 +135,13 @@ struct RenderPlan
 static RenderPlan plan_render(const trt_context *ctx, long units, int spp)
 {
     const Variant v = choose_variant(ctx, units, spp);
-    if (v == kReference)
-        return RenderPlan{v, (unsigned)((units / spp + 255) / 256), 256u, scene_lds_bytes(ctx->scene), 0u};
+    if (v == kReference || v == kReferenceImage)
+        return RenderPlan{v, (unsigned)((units / spp + 255) / 256), 256u, v == kReference ? scene_lds_bytes(ctx->scene) : 0u, 0u};
     const RoundsVariant &k = kRounds[v];
-    const int per_cu = k.rings ? ctx->compact_blocks_per_cu : k.block == trt::kBigBlock ? ctx->big_blocks_per_cu : ctx->rounds_blocks_per_cu;
+    const int per_cu = k.image ? ctx->device_blocks_per_cu : k.rings ? ctx->compact_blocks_per_cu : k.block == trt::kBigBlock ? ctx->big_blocks_per_cu : ctx->rounds_blocks_per_cu;
     const long cap = (long)(ctx->compute_units - (ctx->stream == ctx->own_stream ? ctx->reserved_cus : 0)) * std::max(per_cu, 1);
     const long want = (units + k.block - 1) / k.block;
-    RenderPlan p{v, (unsigned)std::max(1L, std::min(want, cap)), (unsigned)k.block, image_lds_bytes(ctx, spp), 0u};
+    RenderPlan p{v, (unsigned)std::max(1L, std::min(want, cap)), (unsigned)k.block, k.image ? 0u : image_lds_bytes(ctx, spp), 0u};
     if (k.rings)
     {
         p.lds = compact_lds_bytes(ctx, spp);
@@ -129,24 +158,34 @@ static hipError_t occupancy(const trt_context *ctx, Variant v, int *blocks)
 }
 
 // The production kernel's occupancy depends on the scene and its tables only through the size of the LDS image: queried once
-// per size, not once per frame.
+// per size, not once per frame.  The instantiations that read the image from device memory have no dynamic LDS: their occupancy,
+// queried once, sizes the launches of scenes whose image does not fit (trt_set_scene_image(ctx, 0): those fail, as they did
+// before there was a device image).
 int refresh_occupancy(trt_context *ctx)
 {
     const trt::SceneView &v = ctx->scene;
     const size_t lds_need = std::max(scene_lds_bytes(v), image_lds_bytes(ctx, 64));
-    if (lds_need > (size_t)ctx->lds_limit)
+    if (lds_need > (size_t)ctx->lds_limit && ctx->scene_image == 0)
         return fail(TRT_ERR_CAPACITY, "scene needs %zu B of LDS staging, device offers %d", lds_need, ctx->lds_limit);
-    if (ctx->occupancy_for_lds != image_lds_bytes(ctx, 64))
+    if (ctx->device_blocks_per_cu == 0)
     {
         int blocks = 0;
-        HIP_TRY(occupancy(ctx, kPlain, &blocks));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kRounds[kPlainImage].fn, kRounds[kPlainImage].block, 0));
+        ctx->device_blocks_per_cu = std::max(blocks, 1);
+    }
+    if (ctx->occupancy_for_lds != image_lds_bytes(ctx, 64))
+    {
+        const bool fits = image_lds_bytes(ctx, 64) <= (size_t)ctx->lds_limit;
+        int blocks = 0;
+        if (fits)
+            HIP_TRY(occupancy(ctx, kPlain, &blocks));
         ctx->rounds_blocks_per_cu = std::max(blocks, 1);
         ctx->occupancy_for_lds = image_lds_bytes(ctx, 64);
         ctx->compact_blocks_per_cu = 0;
         if (compact_lds_bytes(ctx, 64) <= (size_t)ctx->lds_limit)
             HIP_TRY(occupancy(ctx, kDecoupled, &ctx->compact_blocks_per_cu));
         ctx->big_blocks_per_cu = 0;
-        if (ctx->rounds_blocks_per_cu < 4) // the image no longer fits four times: one image for sixteen waves instead
+        if (fits && ctx->rounds_blocks_per_cu < 4) // the image no longer fits four times: one image for sixteen waves instead
             HIP_TRY(occupancy(ctx, kPatchesBig, &ctx->big_blocks_per_cu));
     }
     return TRT_OK;
@@ -197,9 +236,19 @@ int prepare_axes(trt_context *ctx, const Camera *cam, int width, int height)
 
 void allow_large_lds_render(const trt_context *ctx)
 {
-    (void)hipFuncSetAttribute((const void *)trt::render_simple_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
+    (void)hipFuncSetAttribute((const void *)trt::render_simple_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
     for (const RoundsVariant &k : kRounds)
-        (void)hipFuncSetAttribute((const void *)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
+        if (!k.image)
+            (void)hipFuncSetAttribute((const void *)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
+}
+
+// The scene image of a frame in device memory, for render_rounds_kernel<.., DEVICE_IMAGE>: one workgroup, since fill_image has
+// barriers between its phases.  It holds the frame's camera, jitter and the eye's families, so it is written on the frame's
+// stream in front of every launch that reads it.
+constexpr int kImageBlock = 1024;
+__global__ __launch_bounds__(kImageBlock) void stage_image_kernel(trt::SceneView s, trt::CullView cull, trt::FrameView f, trt::GridView grids)
+{
+    trt::fill_image(trt::image_layout(const_cast<double *>(f.image), s.num_spheres, s.num_dir, s.num_point, cull.padded, f.spp), s, cull, f, grids);
 }
 
 } // namespace trt_impl
@@ -315,10 +364,16 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
     const RenderPlan plan = plan_render(ctx, units, rays_per_pixel);
     const dim3 grid(plan.grid), block(plan.block);
     unsigned *const ready = ctx->queue_ready[lane_set];
-    if (plan.variant == kReference)
+    if (plan.lds > (size_t)ctx->lds_limit) // LDS only (trt_set_scene_image(ctx, 0)), or the refraction extension, which has no device-image form
+        return fail(TRT_ERR_CAPACITY, "%s and %d rays per pixel need %zu B of LDS staging, device offers %d%s", plan.variant == kReference ? "scene" : "scene image",
+                    rays_per_pixel, plan.lds, ctx->lds_limit, ctx->ior_count && plan.variant != kReference ? " (the refraction extension stages it in LDS only)" : "");
+    if (plan.variant == kReference || plan.variant == kReferenceImage)
     {
         HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
-        hipLaunchKernelGGL(trt::render_simple_kernel, grid, block, plan.lds, stream, ctx->scene, f);
+        if (plan.variant == kReference)
+            hipLaunchKernelGGL(trt::render_simple_kernel<false>, grid, block, plan.lds, stream, ctx->scene, f);
+        else
+            hipLaunchKernelGGL(trt::render_simple_kernel<true>, grid, block, 0, stream, ctx->scene, f);
         HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
         HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
     }
@@ -332,9 +387,15 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
         HIP_TRY(scratch.reserve((size_t)units * 3));
         f.samples = scratch.ptr;
         f.spp_magic = (unsigned)std::min<unsigned long long>((0x100000000ull + (unsigned)rays_per_pixel - 1) / (unsigned)rays_per_pixel, 0xffffffffull);
-        if (image_lds_bytes(ctx, rays_per_pixel) > (size_t)ctx->lds_limit)
-            return fail(TRT_ERR_CAPACITY, "scene and %d rays per pixel need %zu B of LDS staging, device offers %d", rays_per_pixel,
-                        image_lds_bytes(ctx, rays_per_pixel), ctx->lds_limit);
+        if (kRounds[plan.variant].image)
+        { // a buffer per lane set: trt_render_host renders bands on two streams at once
+            DeviceBuffer<double> &image = lane_set ? ctx->d_image_alt : ctx->d_image;
+            const size_t doubles = image_lds_bytes(ctx, rays_per_pixel) / sizeof(double);
+            if (image.capacity < doubles)
+                HIP_TRY(hipStreamSynchronize(stream)); // a frame in flight may still read the old image
+            HIP_TRY(image.reserve(doubles));
+            f.image = image.ptr;
+        }
         if (ctx->ior_count && ctx->ior_count != ctx->scene.num_spheres) // before the first event of the launch is recorded
             return fail(TRT_ERR_ARGUMENT, "trt_set_refraction was given %d indices, the scene has %d spheres", ctx->ior_count, ctx->scene.num_spheres);
         if (ctx->ior_count)
@@ -351,6 +412,8 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
         if (!left_ready)
             hipLaunchKernelGGL(trt::start_queue_kernel, dim3(1), dim3(64), 0, stream, f.queue, plan.grid, plan.block / 64, f.queue_shift);
         HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
+        if (kRounds[plan.variant].image)
+            hipLaunchKernelGGL(stage_image_kernel, dim3(1), dim3(kImageBlock), 0, stream, ctx->scene, ctx->cull, f, ctx->grids);
         hipLaunchKernelGGL(kRounds[plan.variant].fn, grid, block, plan.lds, stream, ctx->scene, ctx->cull, f, ctx->grids);
         HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
 #if !TRT_AB_SKIP_REDUCE // diagnostic build (profiles/r03: what the ordered mean's streaming pass costs in the pipelined loop)
@@ -364,10 +427,11 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
     }
     HIP_TRY(hipGetLastError());
 #if !TRT_AB_SKIP_REDUCE
-    if (plan.variant != kReference)
+    if (plan.variant != kReference && plan.variant != kReferenceImage)
         ready[0] = plan.grid, ready[1] = plan.block / 64, ready[2] = f.queue_shift;
 #endif
     ctx->last_variant = plan.variant;
+    ctx->last_spp = rays_per_pixel;
     ctx->launches++;
     return TRT_OK;
 }
@@ -572,9 +636,30 @@ extern "C" int trt_render_variant(trt_context *ctx, int *decoupled, int *workgro
         return fail(TRT_ERR_ARGUMENT, "ctx is NULL");
     const Variant v = described_variant(ctx);
     if (decoupled)
-        *decoupled = v != kReference && kRounds[v].rings ? 1 : 0;
+        *decoupled = v < kReference && kRounds[v].rings ? 1 : 0;
     if (workgroup_threads)
-        *workgroup_threads = v == kReference ? 256 : kRounds[v].block;
+        *workgroup_threads = v >= kReference ? 256 : kRounds[v].block;
+    return TRT_OK;
+}
+
+extern "C" int trt_set_scene_image(trt_context *ctx, int mode)
+{
+    if (!ctx || mode < -1 || mode > 1)
+        return fail(TRT_ERR_ARGUMENT, "scene image mode %d", mode);
+    ctx->scene_image = mode;
+    // LDS only on a scene that does not fit: its frames fail (render_device_on), as trt_set_scene would have
+    return ctx->have_scene && mode != 0 ? refresh_occupancy(ctx) : TRT_OK;
+}
+
+extern "C" int trt_render_image(trt_context *ctx, int *in_device_memory, unsigned long long *image_bytes)
+{
+    if (!ctx)
+        return fail(TRT_ERR_ARGUMENT, "ctx is NULL");
+    const Variant v = described_variant(ctx);
+    if (in_device_memory)
+        *in_device_memory = image_in_device_memory(v) ? 1 : 0;
+    if (image_bytes)
+        *image_bytes = !ctx->have_scene ? 0ull : v >= kReference ? scene_lds_bytes(ctx->scene) : image_lds_bytes(ctx, described_spp(ctx));
     return TRT_OK;
 }
 
@@ -586,7 +671,8 @@ extern "C" int trt_kernel_info(trt_context *ctx, int *vgprs, int *sgprs, int *st
     HIP_TRY(hipSetDevice(ctx->device));
     const Variant v = described_variant(ctx);
     hipFuncAttributes attr;
-    HIP_TRY(hipFuncGetAttributes(&attr, v == kReference ? (const void *)trt::render_simple_kernel : (const void *)kRounds[v].fn));
+    HIP_TRY(hipFuncGetAttributes(&attr, v == kReference ? (const void *)trt::render_simple_kernel<false>
+                                      : v == kReferenceImage ? (const void *)trt::render_simple_kernel<true> : (const void *)kRounds[v].fn));
     if (vgprs)
         *vgprs = attr.numRegs;
     if (sgprs)
@@ -597,7 +683,11 @@ extern "C" int trt_kernel_info(trt_context *ctx, int *vgprs, int *sgprs, int *st
     { // what the launch is sized by: the 256-thread variants by the plain instantiation's occupancy
         int blocks = 0;
         if (v == kReference)
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, trt::render_simple_kernel, 256, ctx->have_scene ? scene_lds_bytes(ctx->scene) : 0));
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, trt::render_simple_kernel<false>, 256, ctx->have_scene ? scene_lds_bytes(ctx->scene) : 0));
+        else if (v == kReferenceImage)
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, trt::render_simple_kernel<true>, 256, 0));
+        else if (kRounds[v].image)
+            blocks = ctx->device_blocks_per_cu;
         else if (kRounds[v].rings)
             blocks = ctx->compact_blocks_per_cu;
         else if (kRounds[v].block == trt::kBigBlock)

@@ -117,7 +117,8 @@ struct LdsImage
 // mat[(n+2)*5] (spheres, ground even, ground odd) | dir lights: unit to-light(3) colour(3) | point lights: pos(3) colour(3)
 // intensity | byte/255.0 [256] | camera | jitter x[spp] y[spp] | one fixed-direction culling table per directional
 // light | headers of the light-space tables | per sphere {mirror centre, |r|} of the path-ray families | the two families
-// of the eye | the patches of a sphere's surface (`patches` records).  rounds_lds_bytes and stage_lds_image must agree.
+// of the eye | the patches of a sphere's surface (`patches` records).  rounds_lds_bytes and image_layout must agree: the layout
+// ends at most rounds_lds_bytes from its base (the alignment double of the formula is always counted).
 inline size_t rounds_lds_bytes(const SceneView &s, int spp, int patches)
 {
     const size_t padded = ((size_t)s.num_spheres + kCullGroup - 1) / kCullGroup * kCullGroup;
@@ -127,94 +128,127 @@ inline size_t rounds_lds_bytes(const SceneView &s, int spp, int patches)
                              (size_t)s.num_spheres * 4 + 2 * TRT_RAYFAMILY_DOUBLES + (size_t)patches * TRT_PATCH_RECORD);
 }
 
-TRT_DEV LdsImage stage_lds_image(double *lds, const SceneView &s, const CullView &cull, const FrameView &f, const GridView &grids)
+// Where every part of the image lies from its base: one layout for the LDS image of a workgroup and for the device-memory image
+// of a launch (render_rounds_kernel<.., DEVICE_IMAGE>, whose scene does not fit LDS).  The base must be 16-byte aligned.
+struct ImageParts
+{
+    float4 *cull, *cull_dir;
+    double *sph, *mat, *dir, *pt, *b255, *cam, *jit, *dirgrid, *pointgrid, *fam, *eye, *patch;
+};
+
+TRT_DEV ImageParts image_layout(double *base, int n, int nd, int np, int padded, int spp)
+{
+    ImageParts p;
+    p.cull = (float4 *)base;
+    p.sph = base + padded * 2; // 16-byte aligned: the culling table before it is whole float4s
+    p.mat = p.sph + 4 * n;
+    p.dir = p.mat + (n + 2) * 5;
+    p.pt = p.dir + nd * kDirRecord;
+    p.b255 = p.pt + np * 7;
+    p.cam = p.b255 + 256;
+    p.jit = p.cam + kLdsCameraDoubles;
+    // fixed-direction tables behind everything else, on a 16-byte boundary (all offsets above are whole doubles)
+    p.cull_dir = (float4 *)(base + (((p.jit + 2 * spp) - base + 1) & ~1L));
+    // headers of the light-space tables behind the fixed-direction tables (whole doubles again: 4 floats per entry)
+    p.dirgrid = (double *)(p.cull_dir + nd * padded);
+    p.pointgrid = p.dirgrid + nd * kDirGridDoubles;
+    p.fam = p.pointgrid + np * kPointGridDoubles;
+    p.eye = p.fam + 4 * n;
+    p.patch = p.eye + 2 * TRT_RAYFAMILY_DOUBLES;
+    return p;
+}
+
+TRT_DEV LdsImage image_view(const ImageParts &p)
+{
+    return LdsImage{p.cull, p.cull_dir, p.sph, p.mat, p.dir, p.pt, p.b255, p.cam, p.jit,
+                    (const trt_dirgrid *)p.dirgrid, (const trt_pointgrid *)p.pointgrid, p.fam, p.eye, p.patch};
+}
+
+// The image of a frame, written by the threads of ONE workgroup (barriers between its phases): into LDS by every workgroup of the
+// production kernel, or into device memory by stage_image_kernel (trt_render.hip) in front of a launch that reads it from there.
+TRT_DEV void fill_image(const ImageParts &p, const SceneView &s, const CullView &cull, const FrameView &f, const GridView &grids)
 {
     const int n = s.num_spheres, nd = s.num_dir, np = s.num_point;
-    float4 *l_cull = (float4 *)lds;
-    double *l_sph = lds + cull.padded * 2; // 16-byte aligned: the culling table before it is whole float4s
-    double *l_mat = l_sph + 4 * n, *l_dir = l_mat + (n + 2) * 5, *l_pt = l_dir + nd * kDirRecord, *l_255 = l_pt + np * 7;
-    double *l_cam = l_255 + 256, *l_jit = l_cam + kLdsCameraDoubles;
     for (int i = threadIdx.x; i < cull.padded; i += blockDim.x)
-        l_cull[i] = ((const float4 *)cull.table)[i];
+        p.cull[i] = ((const float4 *)cull.table)[i];
     for (int i = threadIdx.x; i < n; i += blockDim.x)
     {
         const double *sp = s.spheres + (long)i * kSphereDoubles;
-        l_sph[4 * i + 0] = sp[0];
-        l_sph[4 * i + 1] = sp[1];
-        l_sph[4 * i + 2] = sp[2];
-        l_sph[4 * i + 3] = sp[3] * sp[3]; // radius*radius exactly as TRT.c:648 forms it
+        p.sph[4 * i + 0] = sp[0];
+        p.sph[4 * i + 1] = sp[1];
+        p.sph[4 * i + 2] = sp[2];
+        p.sph[4 * i + 3] = sp[3] * sp[3]; // radius*radius exactly as TRT.c:648 forms it
         for (int j = 0; j < 5; j++)
-            l_mat[i * 5 + j] = sp[4 + j];
+            p.mat[i * 5 + j] = sp[4 + j];
     }
     for (int i = threadIdx.x; i < 10; i += blockDim.x)
-        l_mat[n * 5 + i] = s.ground[6 + i];
+        p.mat[n * 5 + i] = s.ground[6 + i];
     for (int i = threadIdx.x; i < nd; i += blockDim.x)
     {
         const double *li = s.dir_lights + i * kDirLightDoubles;
         const d3 tl = unit(scale(load3(li), -1.0)); // TRT.c:903-904, the same value for every hit point
-        l_dir[i * kDirRecord + 0] = tl.x, l_dir[i * kDirRecord + 1] = tl.y, l_dir[i * kDirRecord + 2] = tl.z;
-        l_dir[i * kDirRecord + 3] = li[3], l_dir[i * kDirRecord + 4] = li[4], l_dir[i * kDirRecord + 5] = li[5];
-        l_dir[i * kDirRecord + 6] = dot(tl, tl);                     // a of ray_intersects_sphere (TRT.c:643) for every shadow ray towards this light
-        l_dir[i * kDirRecord + 7] = dot(tl, load3(s.ground + 3)); // d.n of ray_intersects_plane (TRT.c:679)
+        p.dir[i * kDirRecord + 0] = tl.x, p.dir[i * kDirRecord + 1] = tl.y, p.dir[i * kDirRecord + 2] = tl.z;
+        p.dir[i * kDirRecord + 3] = li[3], p.dir[i * kDirRecord + 4] = li[4], p.dir[i * kDirRecord + 5] = li[5];
+        p.dir[i * kDirRecord + 6] = dot(tl, tl);                     // a of ray_intersects_sphere (TRT.c:643) for every shadow ray towards this light
+        p.dir[i * kDirRecord + 7] = dot(tl, load3(s.ground + 3)); // d.n of ray_intersects_plane (TRT.c:679)
     }
     for (int i = threadIdx.x; i < np * 7; i += blockDim.x)
-        l_pt[i] = s.point_lights[i];
+        p.pt[i] = s.point_lights[i];
     for (int i = threadIdx.x; i < 256; i += blockDim.x)
-        l_255[i] = (double)i / 255.0; // TRT.c:866
+        p.b255[i] = (double)i / 255.0; // TRT.c:866
     for (int i = threadIdx.x; i < 12; i += blockDim.x)
-        l_cam[i] = f.cam[i];
+        p.cam[i] = f.cam[i];
     if (threadIdx.x < 3) // TRT.c:989, :1000-1002: basis z scaled by sz = -screen_distance, the same product for every primary ray
-        l_cam[13 + threadIdx.x] = f.cam[6 + threadIdx.x] * -f.cam[12];
+        p.cam[13 + threadIdx.x] = f.cam[6 + threadIdx.x] * -f.cam[12];
     if (threadIdx.x == 0)
-        l_cam[12] = -f.cam[12];
+        p.cam[12] = -f.cam[12];
     for (int i = threadIdx.x; i < 2 * f.spp; i += blockDim.x)
-        l_jit[i] = f.jitter[i];
-    // fixed-direction tables behind everything else, on a 16-byte boundary (all offsets above are whole doubles)
-    const long dir_tables_at = ((l_jit + 2 * f.spp) - lds + 1) & ~1L;
-    float4 *l_cull_dir = (float4 *)(lds + dir_tables_at);
+        p.jit[i] = f.jitter[i];
     __syncthreads();
     for (int i = threadIdx.x; i < nd * cull.padded; i += blockDim.x)
     {
         const int li = i / cull.padded, j = i - li * cull.padded;
-        const float4 e = l_cull[j];
-        const float dx = (float)l_dir[li * kDirRecord + 0], dy = (float)l_dir[li * kDirRecord + 1], dz = (float)l_dir[li * kDirRecord + 2]; // = trt_filter_setup's d
-        l_cull_dir[i] = float4{e.x, e.y, e.z, trt_filter_fixed_dir_kk(e.x, e.y, e.z, e.w, dx, dy, dz)};
+        const float4 e = p.cull[j];
+        const float dx = (float)p.dir[li * kDirRecord + 0], dy = (float)p.dir[li * kDirRecord + 1], dz = (float)p.dir[li * kDirRecord + 2]; // = trt_filter_setup's d
+        p.cull_dir[i] = float4{e.x, e.y, e.z, trt_filter_fixed_dir_kk(e.x, e.y, e.z, e.w, dx, dy, dz)};
     }
-    // headers of the light-space tables behind the fixed-direction tables (whole doubles again: 4 floats per entry)
-    double *l_dirgrid = (double *)(l_cull_dir + nd * cull.padded), *l_pointgrid = l_dirgrid + nd * kDirGridDoubles;
     if (grids.enabled)
     {
         for (int i = threadIdx.x; i < nd * kDirGridDoubles; i += blockDim.x)
-            l_dirgrid[i] = ((const double *)grids.dir)[i];
+            p.dirgrid[i] = ((const double *)grids.dir)[i];
         for (int i = threadIdx.x; i < np * kPointGridDoubles; i += blockDim.x)
-            l_pointgrid[i] = ((const double *)grids.point)[i];
+            p.pointgrid[i] = ((const double *)grids.point)[i];
     }
-    double *l_fam = l_pointgrid + np * kPointGridDoubles, *l_eye = l_fam + 4 * n, *l_patch = l_eye + 2 * TRT_RAYFAMILY_DOUBLES;
     if (grids.path_enabled)
     {
         for (int i = threadIdx.x; i < n * 4; i += blockDim.x)
-            l_fam[i] = grids.sphere_fam[i];
+            p.fam[i] = grids.sphere_fam[i];
         for (int i = threadIdx.x; i < 2 * TRT_RAYFAMILY_DOUBLES; i += blockDim.x)
-            l_eye[i] = ((const double *)grids.eye)[i];
+            p.eye[i] = ((const double *)grids.eye)[i];
         for (int i = threadIdx.x; i < grids.patch_count * TRT_PATCH_RECORD; i += blockDim.x)
-            l_patch[i] = grids.patch_rec[i];
+            p.patch[i] = grids.patch_rec[i];
     }
     __syncthreads();
     // A directional light's table is for rays along its UNIT direction (trt_lightgrid.h): a light whose direction could not be
     // normalised (TRT.c:444 leaves vectors shorter than 1e-4 alone) gets a range no origin is in -- "far" for every ray, its waves
-    // sweep -- here, once per workgroup, instead of the shading stage testing |sd.sd - 1| for every light in every pass.
+    // sweep -- here, once per image, instead of the shading stage testing |sd.sd - 1| for every light in every pass.
     if (grids.enabled)
     {
         for (int i = threadIdx.x; i < nd; i += blockDim.x)
         {
-            const d3 sd = load3(l_dir + i * kDirRecord);
+            const d3 sd = load3(p.dir + i * kDirRecord);
             if (!(__builtin_fabs(dot(sd, sd) - 1.0) <= 9.094947017729282e-13))
-                ((trt_dirgrid *)l_dirgrid)[i].rg2 = -1.0f;
+                ((trt_dirgrid *)p.dirgrid)[i].rg2 = -1.0f;
         }
         __syncthreads();
     }
-    return LdsImage{l_cull, l_cull_dir, l_sph, l_mat, l_dir, l_pt, l_255, l_cam, l_jit,
-                    (const trt_dirgrid *)l_dirgrid, (const trt_pointgrid *)l_pointgrid, l_fam, l_eye, l_patch};
+}
+
+TRT_DEV LdsImage stage_lds_image(double *lds, const SceneView &s, const CullView &cull, const FrameView &f, const GridView &grids)
+{
+    const ImageParts p = image_layout(lds, s.num_spheres, s.num_dir, s.num_point, cull.padded, f.spp);
+    fill_image(p, s, cull, f, grids);
+    return image_view(p);
 }
 
 struct Hit
@@ -915,14 +949,18 @@ constexpr int kBigBlock = 1024;
 // BIG (round 5): the plain rounds in workgroups of 1024 threads -- ONE LDS image per CU, shared by sixteen waves -- for scenes whose
 // image no longer fits four times into a CU's 160 KB (above ~290 spheres: 136 bytes a sphere): with 256-thread workgroups such a
 // scene runs three, two, one wave per SIMD (512 spheres: two).  Same code; the register allocator has to stay under 128.
-template <bool COUNT, bool REFRACT = false, bool COMPACT = false, bool PATCHES = false, bool BIG = false>
+// DEVICE_IMAGE: the scene image is not staged into LDS but read from f.image, where stage_image_kernel (trt_render.hip) wrote it
+// for this launch in the same layout: scenes whose image does not fit LDS.  No dynamic LDS; the plain rounds only.
+template <bool COUNT, bool REFRACT = false, bool COMPACT = false, bool PATCHES = false, bool BIG = false, bool DEVICE_IMAGE = false>
 __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersistentBlock, ((COMPACT && !COUNT) || BIG) ? 4 : TRT_ROUNDS_WAVES) void render_rounds_kernel(SceneView s, CullView cull, FrameView f, GridView grids)
 {
     static_assert(!(REFRACT && COMPACT), "the refraction extension runs on the plain rounds");
     static_assert(!(PATCHES && COMPACT), "scenes with patches run the plain rounds");
     static_assert(!BIG || (PATCHES && !COUNT && !REFRACT && !COMPACT), "1024-thread workgroups: the shipping patch instantiation only");
+    static_assert(!DEVICE_IMAGE || (!REFRACT && !COMPACT && !BIG), "the device-memory image: the plain rounds only");
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    const LdsImage L = stage_lds_image(lds, s, cull, f, grids);
+    const LdsImage L = DEVICE_IMAGE ? image_view(image_layout(const_cast<double *>(f.image), s.num_spheres, s.num_dir, s.num_point, cull.padded, f.spp))
+                                    : stage_lds_image(lds, s, cull, f, grids);
     const int n = s.num_spheres, nd = s.num_dir, nl = s.num_dir + s.num_point;
     const int lane = threadIdx.x & 63;
     const unsigned pixels_here = (unsigned)f.local_rows * (unsigned)f.width;

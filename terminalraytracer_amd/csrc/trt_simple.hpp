@@ -1,7 +1,8 @@
 // trt_simple.hpp -- reference-order kernel: one lane per pixel, samples and bounces looped in the
 // lane exactly as project_scene does (TRT.c:966-1069), every sphere tested exactly, no culling.
 // It is the on-device parity anchor for the production kernel (trt_rounds.hpp), an independent implementation of the
-// same path, and the code behind trt_probe_rays(..., production = 0).  Scene records are staged into LDS once per workgroup.
+// same path, and the code behind trt_probe_rays(..., production = 0).  Scene records are staged into LDS once per workgroup, or,
+// where they do not fit, read from device memory.
 #pragma once
 
 #include "trt_common.hpp"
@@ -150,11 +151,13 @@ TRT_DEV d3 lit_color(const SceneView &s, const LdsScene &l, d3 at, d3 normal, d3
     return d3{clampd(out.x, 0.0, 1.0), clampd(out.y, 0.0, 1.0), clampd(out.z, 0.0, 1.0)};
 }
 
-#ifdef TRT_UNIT_RENDER // a kernel that is not a template has ONE home among the library's translation units (trt_context.hpp)
+#ifdef TRT_UNIT_RENDER // the kernel's ONE home among the library's translation units (trt_context.hpp)
+// DEVICE_SCENE: the records are read where SceneView has them (the same layout), for scenes whose records do not fit LDS
+template <bool DEVICE_SCENE = false>
 __global__ __launch_bounds__(256) void render_simple_kernel(SceneView s, FrameView f)
 {
     extern __shared__ double lds[];
-    const LdsScene l = stage_scene(s, lds);
+    const LdsScene l = DEVICE_SCENE ? LdsScene{s.spheres, s.dir_lights, s.point_lights} : stage_scene(s, lds);
 
     const long pix = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= (long)f.local_rows * f.width)

@@ -84,6 +84,8 @@ SYMBOLS = {
     "trt_path_family_code": (_I, [_VP, _I, _I, _VP]),
     "trt_set_compaction": (_I, [_VP, _I]),
     "trt_render_variant": (_I, [_VP, C.POINTER(_I), C.POINTER(_I)]),
+    "trt_set_scene_image": (_I, [_VP, _I]),
+    "trt_render_image": (_I, [_VP, C.POINTER(_I), C.POINTER(C.c_ulonglong)]),
     "trt_read_path_tables": (C.c_long, [_VP, C.POINTER(L.Camera), _VP, C.c_size_t, _VP, C.c_size_t, C.POINTER(C.c_long)]),
     "trt_read_sweep_fallbacks": (_I, [_VP, C.POINTER(C.c_ulonglong)]),
     "trt_read_shading_passes": (_I, [_VP, C.POINTER(C.c_ulonglong)]),
@@ -270,6 +272,17 @@ class Context:
         d, t = _I(), _I()
         _check(lib().trt_render_variant(self._h, C.byref(d), C.byref(t)))
         return {"decoupled": bool(d.value), "workgroup_threads": t.value}
+
+    def set_scene_image(self, mode):
+        """where the kernels read the scene from: -1 device memory when the LDS image does not fit (default), 0 LDS only,
+        1 device memory always (trt_set_scene_image)"""
+        _check(lib().trt_set_scene_image(self._h, mode))
+
+    def render_image(self):
+        """{"in_device_memory": bool, "image_bytes": int} of the kernel render_variant() describes (trt_render_image)"""
+        d, b = _I(), C.c_ulonglong()
+        _check(lib().trt_render_image(self._h, C.byref(d), C.byref(b)))
+        return {"in_device_memory": bool(d.value), "image_bytes": b.value}
 
     def read_path_tables(self, camera_array):
         """(info dict, list cells uint64[], pool uint64[]) of the path rays' tables as built for this camera's eye"""

@@ -215,6 +215,25 @@ def synth_scene(n, sky, camera, seed=1234, mirror_fraction=0.0):
     return SceneData(synth_spheres(n, seed, mirror_fraction), demo_ground(), d, p, camera, sky)
 
 
+def ring_lights(count):
+    """`count` directional lights on a cone about the straight-down direction, each 1/count as bright, so that their sum stays
+    within the colour range: scenes of many lights (whose fixed-direction culling tables grow the LDS image by light)."""
+    k = np.arange(count, dtype=np.float64)
+    phi = 2.0 * PI * k / count
+    d = np.zeros((count, 6), dtype=np.float64)
+    d[:, 0] = 0.6 * np.cos(phi)
+    d[:, 1] = -1.0
+    d[:, 2] = 0.6 * np.sin(phi)
+    d[:, 3:6] = 1.0 / count
+    return d
+
+
+def synth_scene_lights(n, n_dir, sky, camera, seed=1234):
+    """SYNTH-v0 spheres lit by ring_lights(n_dir) and the demo's point light."""
+    _, p = demo_lights()
+    return SceneData(synth_spheres(n, seed), demo_ground(), ring_lights(n_dir), p, camera, sky)
+
+
 def synth_sky(dim=256, seed=7):
     """Procedural cubemap for bench / parity runs that must not depend on image files:
     a per-texel hash so that any wrong face, mirror, rotation or index shows up."""
