@@ -152,6 +152,31 @@ int trt_render_host(trt_context *ctx, const Camera *camera, const trt_rowset *ro
 int trt_render_host_rgb8(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
                          unsigned char *rgb);
 
+/* Several cameras of the current scene in one call: an orbit, a replay, a stereo pair, the faces of an environment probe. */
+#define TRT_BATCH_MAX 8 /* = the eye-table slots a scene's tables have */
+
+/* n cameras, one call, one context, one stream.  Frame b goes to d_pixels + b * (owned rows * width) Vectors, each frame in
+ * the layout trt_render_device writes; every frame is bit-identical to what trt_render_device gives for that camera.
+ * All cameras must have the same screen_width / screen_height / screen_distance (main() moves only camera.frame,
+ * TRT.c:1327-1336); 1 <= n <= TRT_BATCH_MAX.  Asynchronous on the context's stream.
+ * Where the production kernel has a form for it (image in LDS, no counters, no refraction, 256-thread or decoupled
+ * workgroups) ONE persistent launch works through the samples of all n frames, frame b's tail filled by frame b + 1's
+ * head; a batch whose larger LDS image (28 doubles per extra camera) would cost a resident workgroup is split into the
+ * largest batches that do not; everything else is served one launch per camera on the same stream (trt_batch_info).
+ * Errors, before anything is enqueued: NULL, n out of range, cameras whose screens differ, an invalid rowset, n frames
+ * of 2^31 samples or more -> TRT_ERR_ARGUMENT; no scene -> TRT_ERR_NO_SCENE; a buffer too small for n frames ->
+ * TRT_ERR_CAPACITY; n > 1 on a context whose tables are shared (trt_share_scene, either side: the eye slots a batch
+ * would build its tables in are the sharers') -> TRT_ERR_CAPACITY.  The sample scratch is n x 24 B x rays_per_pixel per
+ * pixel.  trt_kernel_times / trt_render_kernel_times count a batch as ONE entry (events around the whole batch). */
+int trt_render_device_batch(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                            int rays_per_pixel, void *d_pixels, size_t capacity_bytes);
+/* The same into HOST memory: pixels[b * owned rows * width ...] (synchronous; one copy-out through pinned staging). */
+int trt_render_host_batch(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                          int rays_per_pixel, Vector *pixels);
+/* The most recent batch call of this context: its frames, and how many render-kernel launches served them
+ * (1 = one launch over all frames; n = one launch per camera; between: the batch was split for LDS). */
+int trt_batch_info(trt_context *ctx, int *frames, int *render_launches);
+
 int trt_synchronize(trt_context *ctx);
 
 /* HIP-event durations (ms) of the most recent render-kernel launches on this context, newest

@@ -313,7 +313,7 @@ static void detach_tables(trt_context *ctx)
     ctx->T->device = ctx->device;
     ctx->T->eye_slots_taken = 1u;
     ctx->eye_slot = 0;
-    ctx->eye_tables_valid = false;
+    invalidate_eye_tables(ctx);
     ctx->grids = trt::GridView{};
     ctx->sky_dim = -1;
 }
@@ -358,7 +358,8 @@ extern "C" int trt_share_scene(trt_context *dst, trt_context *src)
     dst->cull = src->cull;
     dst->grids = src->grids;
     dst->grids.eye_at = (unsigned)((size_t)slot * 2 * 6 * (size_t)src->grids.g_eye * (size_t)src->grids.g_eye);
-    dst->eye_tables_valid = false;
+    invalidate_eye_tables(dst);
+    src->batch_eye_valid = 0; // the slots a batch of src's used may now be dst's (or another sharer's)
     // the settings the tables were built with travel along (a later trt_set_scene on dst then builds alike)
     dst->dirgrid_cells = src->dirgrid_cells, dst->pointgrid_cells = src->pointgrid_cells;
     dst->dirgrid_slabs = src->dirgrid_slabs, dst->pointgrid_shells = src->pointgrid_shells;

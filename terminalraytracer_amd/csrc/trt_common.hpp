@@ -102,6 +102,23 @@ __global__ __launch_bounds__(256) void reduce_samples_kernel(const double *sampl
     out[i] = mean * inv_spp;
 }
 
+// The same over the frames of a batch launch (trt_render_device_batch): blockIdx.y is the frame, its scratch is
+// samples[((frame * spp + k) * values + i)] and its pixels out[frame * values + i].  The queue is the launch's, started once.
+__global__ __launch_bounds__(256) void reduce_samples_batch_kernel(const double *samples, double *out, long values, int spp, double inv_spp,
+                                                                   unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
+{
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < (1u << shift))
+        queue[threadIdx.x * kQueueStride] = (grid > threadIdx.x ? (grid - threadIdx.x + (1u << shift) - 1) >> shift : 0u) * waves_per_group;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= values)
+        return;
+    const double *mine = samples + (size_t)blockIdx.y * (size_t)spp * (size_t)values;
+    double mean = 0.0;
+    for (int k = 0; k < spp; k++)
+        mean += mine[(long)k * values + i];
+    out[(size_t)blockIdx.y * (size_t)values + i] = mean * inv_spp;
+}
+
 // (int)(c*255) per channel, TRT.c:1157-1163
 __global__ void quantize_kernel(const double *px, long n_values, unsigned char *rgb)
 {

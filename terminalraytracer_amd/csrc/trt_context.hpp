@@ -184,6 +184,18 @@ struct trt_context
     bool moving_scene = false;
     double eye_built[3] = {0.0, 0.0, 0.0};
     bool eye_tables_valid = false;
+    // trt_render_device_batch builds frame b's eye tables into slot b of the context's own (unshared) tables.  Slot eye_slot is the
+    // single frames' and keeps its cache above; the others': the eye each was last built for, bit s of batch_eye_valid says whether it holds
+    double batch_eye[kEyeSlots][3] = {};
+    unsigned batch_eye_valid = 0;
+    int batch_frames = 0, batch_launches = 0; // trt_batch_info: the most recent batch call
+    struct BatchOccupancy
+    {
+        int variant;
+        size_t lds;
+        int blocks;
+    };
+    std::vector<BatchOccupancy> batch_occupancy; // workgroups per CU of the BATCH instantiations, per LDS size asked so far
     DeviceBuffer<double> d_ior; // refraction extension: per sphere, > 0 = index of refraction
     DeviceBuffer<unsigned char> d_rgb8; // trt_render_host_rgb8: the quantised frame before it crosses PCIe
     int ior_count = 0;          // 0 = off (the reference's path)
@@ -280,6 +292,13 @@ inline bool rowset_valid(const trt_rowset *r)
     return r && r->width > 0 && r->height > 0 && r->tile_rows > 0 && r->tile_first >= 0 && r->tile_step > 0;
 }
 
+// the eye's tables of every slot this context builds are stale (another scene, other tables, another slot)
+inline void invalidate_eye_tables(trt_context *ctx)
+{
+    ctx->eye_tables_valid = false;
+    ctx->batch_eye_valid = 0;
+}
+
 // ---- defined in trt_capi.hip
 int upload_skybox(trt_context *ctx, const Skybox *sky);
 unsigned long long skybox_stamp(const Skybox *sky);
@@ -291,6 +310,8 @@ extern int g_moving_after, g_still_after; // trt_set_scene_policy
 int patches_for(const trt_context *ctx, int n);
 int build_tables(trt_context *ctx, const trt_cull_scene &cs, const double *ground);
 int ensure_eye_tables(trt_context *ctx, const Camera *camera, hipStream_t stream);
+// the same for the n cameras of a batch: frame b's tables in slot b; families[b] = its two families (all zero without path tables)
+int ensure_batch_eye_tables(trt_context *ctx, const Camera *cameras, int n, hipStream_t stream, trt_rayfamily (*families)[2]);
 void allow_large_lds_tables(const trt_context *ctx); // dynamic LDS above the 64 KiB default needs the opt-in attribute, per kernel
 // ---- defined in trt_render.hip
 int refresh_occupancy(trt_context *ctx);

@@ -122,6 +122,74 @@ static int described_spp(const trt_context *ctx)
     return ctx->last_variant >= 0 ? ctx->last_spp : 64;
 }
 
+// ---- several cameras of one scene per launch (trt_render_device_batch) ----
+// The BATCH forms of the production kernel (trt_rounds.hpp): plain, patches, decoupled -- the non-counting instantiations with the
+// image in LDS.  Everything else a context may be set to render is served one launch per camera.
+using BatchKernel = void (*)(trt::SceneView, trt::CullView, trt::FrameView, trt::GridView, trt::BatchView);
+struct BatchVariant
+{
+    BatchKernel fn;
+    Variant single; // the single-frame instantiation it is the BATCH form of: block size, rings
+};
+enum : int { kBatchPlain, kBatchPatches, kBatchDecoupled, kBatchForms };
+static const BatchVariant kBatchRounds[kBatchForms] = {
+    {trt::render_rounds_kernel<false, false, false, false, false, false, true, trt::BatchView>, kPlain},
+    {trt::render_rounds_kernel<false, false, false, true, false, false, true, trt::BatchView>, kPatches},
+    {trt::render_rounds_kernel<false, false, true, false, false, false, true, trt::BatchView>, kDecoupled},
+};
+static_assert(TRT_BATCH_MAX == kEyeSlots && TRT_BATCH_MAX == trt::kBatchMax, "a frame of a batch has an eye slot of the scene's tables and a place in BatchView");
+
+// LDS of a BATCH launch of `frames` cameras: the image with a camera block and eye families per frame, then the rings as in compact_lds_bytes
+static size_t batch_image_bytes(const trt_context *ctx, int spp, int frames)
+{
+    return trt::rounds_lds_bytes(ctx->scene, spp, ctx->grids.path_enabled ? ctx->grids.patch_count : 0, frames);
+}
+static size_t batch_ring_at(const trt_context *ctx, int spp, int frames)
+{
+    return (batch_image_bytes(ctx, spp, frames) / sizeof(double) + 1) & ~(size_t)1;
+}
+static size_t batch_lds_bytes(const trt_context *ctx, int form, int spp, int frames)
+{
+    if (!kRounds[kBatchRounds[form].single].rings)
+        return batch_image_bytes(ctx, spp, frames);
+    return sizeof(double) * (batch_ring_at(ctx, spp, frames) + (size_t)(trt::kCompactBlock / 64) * trt::kRingDoubles);
+}
+
+// Which BATCH form `frames` cameras of `units` samples in all run; -1: none, the batch is served one launch per camera.  The
+// reasoning is choose_variant's, with the whole launch's units for the decoupling threshold: a batch of 1/8 shards is a large launch.
+static int choose_batch_variant(const trt_context *ctx, long units, int spp, int frames)
+{
+    if (ctx->kernel == 1 || ctx->counters_enabled || ctx->ior_count || wants_device_image(ctx, spp))
+        return -1;
+    const bool patches = ctx->grids.path_enabled && ctx->grids.patch_m > 0;
+    if (!patches)
+        return renders_decoupled(ctx, units) && batch_lds_bytes(ctx, kBatchDecoupled, spp, frames) <= (size_t)ctx->lds_limit ? kBatchDecoupled : kBatchPlain;
+    const bool big = ctx->big_blocks_per_cu * trt::kBigBlock > ctx->rounds_blocks_per_cu * trt::kPersistentBlock;
+    return big ? -1 : kBatchPatches; // 1024-thread patch workgroups have no BATCH form
+}
+
+// workgroups of a BATCH form that fit one CU with `lds` bytes of dynamic LDS (0: it does not fit); asked once per size
+static hipError_t batch_occupancy(trt_context *ctx, int form, size_t lds, int *blocks)
+{
+    for (const trt_context::BatchOccupancy &o : ctx->batch_occupancy)
+        if (o.variant == form && o.lds == lds)
+        {
+            *blocks = o.blocks;
+            return hipSuccess;
+        }
+    *blocks = 0;
+    if (lds <= (size_t)ctx->lds_limit)
+    {
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, kBatchRounds[form].fn, kRounds[kBatchRounds[form].single].block, lds);
+        if (e != hipSuccess)
+            return e;
+    }
+    if (ctx->batch_occupancy.size() >= 64)
+        ctx->batch_occupancy.clear();
+    ctx->batch_occupancy.push_back({form, lds, *blocks});
+    return hipSuccess;
+}
+
 struct RenderPlan
 {
     Variant variant;
@@ -240,6 +308,8 @@ void allow_large_lds_render(const trt_context *ctx)
     for (const RoundsVariant &k : kRounds)
         if (!k.image)
             (void)hipFuncSetAttribute((const void *)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
+    for (const BatchVariant &k : kBatchRounds)
+        (void)hipFuncSetAttribute((const void *)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
 }
 
 // The scene image of a frame in device memory, for render_rounds_kernel<.., DEVICE_IMAGE>: one workgroup, since fill_image has
@@ -291,8 +361,11 @@ extern "C" int trt_read_counters(trt_context *ctx, unsigned long long *path_rays
 
 // `lane_set` 0: the context's stream, queue word 0, d_samples; 1: the alternate stream, its own queue word and scratch
 // (trt_render_host renders odd bands there).
+// `entry`: a frame is one entry of the context's launch history (events, trt_kernel_times); the frames of a batch that is served
+// one launch per camera are one entry together -- the first opens it (and clears the counters), the last closes it.
+enum : int { kEntryOpens = 1, kEntryCloses = 2, kEntryWhole = kEntryOpens | kEntryCloses };
 static int render_device_on(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
-                            void *d_pixels, size_t capacity_bytes, int lane_set);
+                            void *d_pixels, size_t capacity_bytes, int lane_set, int entry = kEntryWhole);
 
 extern "C" int trt_render_device(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,
                                  int rays_per_pixel, void *d_pixels, size_t capacity_bytes)
@@ -301,7 +374,7 @@ extern "C" int trt_render_device(trt_context *ctx, const Camera *camera, const t
 }
 
 static int render_device_on(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
-                            void *d_pixels, size_t capacity_bytes, int lane_set)
+                            void *d_pixels, size_t capacity_bytes, int lane_set, int entry)
 {
     if (!ctx || !camera || !d_pixels)
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
@@ -358,7 +431,7 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
         return rc;
     const long pixels = (long)local_rows * rows->width;
     const long units = pixels * rays_per_pixel; // samples
-    if (ctx->counters_enabled)
+    if (ctx->counters_enabled && (entry & kEntryOpens))
         HIP_TRY(hipMemsetAsync(ctx->d_counters.ptr, 0, kCounterSlots * sizeof(unsigned long long), stream));
     const int slot = (int)(ctx->launches % kEventRing);
     const RenderPlan plan = plan_render(ctx, units, rays_per_pixel);
@@ -369,13 +442,17 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
                     rays_per_pixel, plan.lds, ctx->lds_limit, ctx->ior_count && plan.variant != kReference ? " (the refraction extension stages it in LDS only)" : "");
     if (plan.variant == kReference || plan.variant == kReferenceImage)
     {
-        HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
+        if (entry & kEntryOpens)
+            HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
         if (plan.variant == kReference)
             hipLaunchKernelGGL(trt::render_simple_kernel<false>, grid, block, plan.lds, stream, ctx->scene, f);
         else
             hipLaunchKernelGGL(trt::render_simple_kernel<true>, grid, block, 0, stream, ctx->scene, f);
-        HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
-        HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
+        if (entry & kEntryCloses)
+        {
+            HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
+            HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
+        }
     }
     else
     {
@@ -411,11 +488,13 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
         ready[0] = 0; // the render kernel uses it up; ready again once this frame's launches have gone in
         if (!left_ready)
             hipLaunchKernelGGL(trt::start_queue_kernel, dim3(1), dim3(64), 0, stream, f.queue, plan.grid, plan.block / 64, f.queue_shift);
-        HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
+        if (entry & kEntryOpens)
+            HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
         if (kRounds[plan.variant].image)
             hipLaunchKernelGGL(stage_image_kernel, dim3(1), dim3(kImageBlock), 0, stream, ctx->scene, ctx->cull, f, ctx->grids);
         hipLaunchKernelGGL(kRounds[plan.variant].fn, grid, block, plan.lds, stream, ctx->scene, ctx->cull, f, ctx->grids);
-        HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
+        if (entry & kEntryCloses)
+            HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
 #if !TRT_AB_SKIP_REDUCE // diagnostic build (profiles/r03: what the ordered mean's streaming pass costs in the pipelined loop)
         { // TRT.c:1063-1065: the mean over each pixel's samples, in sample order; it starts the queue for the next frame of this shape
             const long values = pixels * 3;
@@ -423,7 +502,8 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
                                (const double *)scratch.ptr, (double *)d_pixels, values, rays_per_pixel, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
         }
 #endif
-        HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
+        if (entry & kEntryCloses)
+            HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
     }
     HIP_TRY(hipGetLastError());
 #if !TRT_AB_SKIP_REDUCE
@@ -432,7 +512,8 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
 #endif
     ctx->last_variant = plan.variant;
     ctx->last_spp = rays_per_pixel;
-    ctx->launches++;
+    if (entry & kEntryCloses)
+        ctx->launches++;
     return TRT_OK;
 }
 
@@ -571,6 +652,216 @@ extern "C" int trt_render_host(trt_context *ctx, const Camera *camera, const trt
     if (print_host_times())
         fprintf(stderr, "trt_render_host: %d band(s), enqueue %.3f ms, render + copy-out of %zu bytes %.3f ms\n", bands, t_enqueued - t_begin, bytes,
                 host_now_ms() - t_enqueued);
+    return TRT_OK;
+}
+
+// ---- several cameras per call ----
+
+// How many of the next `remaining` frames go into ONE launch, and which BATCH form runs them: the most whose larger image costs no
+// resident workgroup against the image of one frame (a batch of one always goes).
+static int fit_batch(trt_context *ctx, long units_per_frame, int spp, int remaining, int *form_out, int *blocks_per_cu)
+{
+    for (int t = remaining;; t--)
+    {
+        const int form = choose_batch_variant(ctx, units_per_frame * t, spp, t);
+        int here = 0, alone = 0;
+        HIP_TRY(batch_occupancy(ctx, form, batch_lds_bytes(ctx, form, spp, t), &here));
+        HIP_TRY(batch_occupancy(ctx, form, batch_lds_bytes(ctx, form, spp, 1), &alone));
+        if (t == 1 || (here > 0 && here >= alone))
+        {
+            *form_out = form;
+            *blocks_per_cu = std::max(here, 1);
+            return t;
+        }
+    }
+}
+
+// One launch of a BATCH form over frames [first, first + m) of the batch, then their ordered means.  `f`: the frame view of the
+// batch (everything but the camera, the queue's shape and the rings' place); families[b]: frame b's eye families.
+static int launch_batch(trt_context *ctx, const Camera *cameras, const trt_rayfamily (*families)[2], int first, int m, int form, int blocks_per_cu,
+                        trt::FrameView f, long pixels, void *d_pixels, int slot)
+{
+    const hipStream_t stream = ctx->stream;
+    const RoundsVariant &k = kRounds[kBatchRounds[form].single];
+    const long units = pixels * f.spp; // of one frame
+    const long cap = (long)(ctx->compute_units - (ctx->stream == ctx->own_stream ? ctx->reserved_cus : 0)) * blocks_per_cu;
+    const unsigned grid = (unsigned)std::max(1L, std::min((units * m + k.block - 1) / k.block, cap));
+    const size_t lds = batch_lds_bytes(ctx, form, f.spp, m);
+    if (lds > (size_t)ctx->lds_limit)
+        return fail(TRT_ERR_CAPACITY, "scene image and %d rays per pixel need %zu B of LDS staging, device offers %d", f.spp, lds, ctx->lds_limit);
+    memcpy(f.cam, &cameras[first], sizeof(Camera));
+    f.ring_at = k.rings ? (unsigned)batch_ring_at(ctx, f.spp, m) : 0u;
+    const bool per_xcd = !(ctx->grids.path_enabled && ctx->grids.patch_m > 0) && grid >= (1u << trt::kQueueXcdShift);
+    f.queue_shift = per_xcd ? (unsigned)trt::kQueueXcdShift : 0u;
+    f.chunk = per_xcd ? trt::kQueueChunkSmall : trt::kQueueChunkSamples;
+    trt::GridView g = ctx->grids;
+    g.eye_at = (unsigned)((size_t)first * 2 * 6 * (size_t)g.g_eye * (size_t)g.g_eye); // frame b of the launch: eye slot first + b
+    g.eye[0] = families[first][0], g.eye[1] = families[first][1];
+    trt::BatchView batch{};
+    for (int b = 0; b < m; b++)
+    {
+        memcpy(batch.cam[b], &cameras[first + b], sizeof(Camera));
+        batch.eye[b][0] = families[first + b][0], batch.eye[b][1] = families[first + b][1];
+    }
+    batch.frames = (unsigned)m;
+    batch.units_per_frame = (unsigned)units;
+    batch.frame_magic = (unsigned)std::min<unsigned long long>((0x100000000ull + (unsigned long long)units - 1) / (unsigned long long)units, 0xffffffffull);
+    unsigned *const ready = ctx->queue_ready[0];
+    const bool left_ready = ready[0] == grid && ready[1] == (unsigned)k.block / 64 && ready[2] == f.queue_shift;
+    ready[0] = 0;
+    if (!left_ready)
+        hipLaunchKernelGGL(trt::start_queue_kernel, dim3(1), dim3(64), 0, stream, f.queue, grid, (unsigned)k.block / 64, f.queue_shift);
+    hipLaunchKernelGGL(kBatchRounds[form].fn, dim3(grid), dim3(k.block), lds, stream, ctx->scene, ctx->cull, f, g, batch);
+    HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream)); // the last launch's stays
+    const long values = pixels * 3;
+    hipLaunchKernelGGL(trt::reduce_samples_batch_kernel, dim3((unsigned)((values + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK), (unsigned)m), dim3(TRT_REDUCE_BLOCK), 0, stream,
+                       (const double *)f.samples, (double *)d_pixels + (size_t)first * values, values, f.spp, f.inv_spp, f.queue, grid, (unsigned)k.block / 64, f.queue_shift);
+    HIP_TRY(hipGetLastError());
+    ready[0] = grid, ready[1] = (unsigned)k.block / 64, ready[2] = f.queue_shift; // what the ordered mean left the queue ready for
+    ctx->last_variant = kBatchRounds[form].single;
+    ctx->last_spp = f.spp;
+    return TRT_OK;
+}
+
+extern "C" int trt_render_device_batch(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                       void *d_pixels, size_t capacity_bytes)
+{
+    if (!ctx || !cameras || !d_pixels)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (n < 1 || n > TRT_BATCH_MAX)
+        return fail(TRT_ERR_ARGUMENT, "a batch has 1 to %d cameras, %d given", TRT_BATCH_MAX, n);
+    if (!rowset_valid(rows))
+        return fail(TRT_ERR_ARGUMENT, "invalid rowset");
+    if (bounce_limit < 1 || rays_per_pixel < 1)
+        return fail(TRT_ERR_ARGUMENT, "bounce_limit %d / rays_per_pixel %d", bounce_limit, rays_per_pixel);
+    for (int b = 1; b < n; b++) // the jitter and the screen axes are the batch's (main() moves only camera.frame, TRT.c:1327-1336)
+        if (cameras[b].screen_width != cameras[0].screen_width || cameras[b].screen_height != cameras[0].screen_height ||
+            cameras[b].screen_distance != cameras[0].screen_distance)
+            return fail(TRT_ERR_ARGUMENT, "camera %d of the batch has another screen_width / screen_height / screen_distance than camera 0", b);
+    if (!ctx->have_scene)
+        return fail(TRT_ERR_NO_SCENE, "trt_set_scene has not been called");
+    const int local_rows = trt_rowset_rows(rows);
+    const size_t frame_bytes = (size_t)local_rows * rows->width * sizeof(Vector);
+    if (capacity_bytes < frame_bytes * n)
+        return fail(TRT_ERR_CAPACITY, "framebuffer of %d frames needs %zu B, %zu given", n, frame_bytes * n, capacity_bytes);
+    if ((unsigned long long)local_rows * rows->width >= 0x7fffffffull)
+        return fail(TRT_ERR_ARGUMENT, "%d x %d pixels exceed the 2^31 pixel index range", local_rows, rows->width);
+    const long pixels = (long)local_rows * rows->width, units = pixels * rays_per_pixel;
+    if (ctx->kernel == 0 && (unsigned long long)units * n >= 0x7fffffffull)
+        return fail(TRT_ERR_ARGUMENT, "%ld work units in %d frames exceed the 2^31 index range", units * n, n);
+    const bool shared = ctx->T.use_count() > 1;
+    if (n > 1 && shared)
+        return fail(TRT_ERR_CAPACITY, "this context's scene tables are shared with %ld other context(s) (trt_share_scene): their eye slots are the sharers', "
+                                      "a batch of %d cameras has none to build its tables in (one camera per call works)", ctx->T.use_count() - 1, n);
+    ctx->batch_frames = n;
+    ctx->batch_launches = 0;
+    if (local_rows == 0)
+        return TRT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t stream = ctx->stream;
+    // everything without a BATCH form -- and a bounce limit that leaves no room for the frame beside the bounce count -- one launch per camera
+    const bool per_camera = shared || bounce_limit > trt::kBatchBounceMask || choose_batch_variant(ctx, units * n, rays_per_pixel, n) < 0;
+    if (per_camera)
+    {
+        for (int b = 0; b < n; b++)
+        {
+            const int rc = render_device_on(ctx, &cameras[b], rows, bounce_limit, rays_per_pixel, (char *)d_pixels + (size_t)b * frame_bytes, frame_bytes, 0,
+                                            (b == 0 ? kEntryOpens : 0) | (b == n - 1 ? kEntryCloses : 0));
+            if (rc)
+                return rc;
+            ctx->batch_launches++;
+        }
+        return TRT_OK;
+    }
+    int rc = prepare_jitter(ctx, &cameras[0], rows->width, rows->height, rays_per_pixel);
+    if (rc)
+        return rc;
+    rc = prepare_axes(ctx, &cameras[0], rows->width, rows->height);
+    if (rc)
+        return rc;
+    trt_rayfamily families[TRT_BATCH_MAX][2];
+    rc = ensure_batch_eye_tables(ctx, cameras, n, stream, families);
+    if (rc)
+        return rc;
+    int form = 0, blocks_per_cu = 1;
+    int m = fit_batch(ctx, units, rays_per_pixel, n, &form, &blocks_per_cu);
+    if (m < 0)
+        return m;
+    // scratch [frame][k][pixel][3] of the largest launch (the first); the launches of a split batch follow one another on the stream
+    if (ctx->d_samples.capacity < (size_t)units * m * 3)
+        HIP_TRY(hipStreamSynchronize(stream)); // a frame in flight may still use the old scratch
+    HIP_TRY(ctx->d_samples.reserve((size_t)units * m * 3));
+
+    trt::FrameView f{};
+    f.jitter = ctx->d_jitter.ptr;
+    f.col_x = ctx->d_axes.ptr;
+    f.row_y = ctx->d_axes.ptr + rows->width;
+    f.inv_spp = 1.0 / rays_per_pixel;
+    f.width_magic = (unsigned)std::min<unsigned long long>((0x100000000ull + (unsigned)rows->width - 1) / (unsigned)rows->width, 0xffffffffull);
+    f.tile_magic = (unsigned)std::min<unsigned long long>((0x100000000ull + (unsigned)rows->tile_rows - 1) / (unsigned)rows->tile_rows, 0xffffffffull);
+    f.spp_magic = (unsigned)std::min<unsigned long long>((0x100000000ull + (unsigned)rays_per_pixel - 1) / (unsigned)rays_per_pixel, 0xffffffffull);
+    f.samples = ctx->d_samples.ptr;
+    f.out = (double *)d_pixels;
+    f.queue = ctx->d_queue.ptr;
+    f.width = rows->width;
+    f.height = rows->height;
+    f.tile_rows = rows->tile_rows;
+    f.tile_first = rows->tile_first;
+    f.tile_step = rows->tile_step;
+    f.local_rows = local_rows;
+    f.bounce_limit = bounce_limit;
+    f.spp = rays_per_pixel;
+
+    const int slot = (int)(ctx->launches % kEventRing);
+    HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
+    for (int first = 0; first < n; first += m)
+    {
+        if (first)
+        {
+            m = fit_batch(ctx, units, rays_per_pixel, std::min(m, n - first), &form, &blocks_per_cu);
+            if (m < 0)
+                return m;
+        }
+        rc = launch_batch(ctx, cameras, families, first, m, form, blocks_per_cu, f, pixels, d_pixels, slot);
+        if (rc)
+            return rc;
+        ctx->batch_launches++;
+    }
+    HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
+    ctx->launches++;
+    return TRT_OK;
+}
+
+extern "C" int trt_render_host_batch(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                     Vector *pixels)
+{
+    if (!ctx || !pixels)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (n < 1 || n > TRT_BATCH_MAX)
+        return fail(TRT_ERR_ARGUMENT, "a batch has 1 to %d cameras, %d given", TRT_BATCH_MAX, n);
+    if (!rowset_valid(rows))
+        return fail(TRT_ERR_ARGUMENT, "invalid rowset");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t count = (size_t)n * trt_rowset_rows(rows) * rows->width, bytes = count * sizeof(Vector);
+    HIP_TRY(ctx->d_fb.reserve(std::max<size_t>(count, 1) * 3));
+    HIP_TRY(ctx->h_staging.reserve(std::max<size_t>(bytes, 1)));
+    const int rc = trt_render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, ctx->d_fb.ptr, bytes);
+    if (rc || bytes == 0)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_fb.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(pixels, ctx->h_staging.ptr, bytes);
+    return TRT_OK;
+}
+
+extern "C" int trt_batch_info(trt_context *ctx, int *frames, int *render_launches)
+{
+    if (!ctx)
+        return fail(TRT_ERR_ARGUMENT, "ctx is NULL");
+    if (frames)
+        *frames = ctx->batch_frames;
+    if (render_launches)
+        *render_launches = ctx->batch_launches;
     return TRT_OK;
 }
 

@@ -119,13 +119,16 @@ struct LdsImage
 // light | headers of the light-space tables | per sphere {mirror centre, |r|} of the path-ray families | the two families
 // of the eye | the patches of a sphere's surface (`patches` records).  rounds_lds_bytes and image_layout must agree: the layout
 // ends at most rounds_lds_bytes from its base (the alignment double of the formula is always counted).
-inline size_t rounds_lds_bytes(const SceneView &s, int spp, int patches)
+// `frames` > 1 (the BATCH instantiations, several cameras per launch): a camera block and a pair of eye families per frame, where
+// a single frame has one of each; frames = 1 is the single-frame layout byte for byte.
+inline size_t rounds_lds_bytes(const SceneView &s, int spp, int patches, int frames = 1)
 {
     const size_t padded = ((size_t)s.num_spheres + kCullGroup - 1) / kCullGroup * kCullGroup;
     return sizeof(double) * (padded * 2 + (size_t)s.num_spheres * 4 + ((size_t)s.num_spheres + 2) * 5 + (size_t)s.num_dir * kDirRecord +
                              (size_t)s.num_point * 7 + 256 + kLdsCameraDoubles + 2 * (size_t)spp + 1 /* 16-B alignment */ +
                              (size_t)s.num_dir * padded * 2 + (size_t)s.num_dir * kDirGridDoubles + (size_t)s.num_point * kPointGridDoubles +
-                             (size_t)s.num_spheres * 4 + 2 * TRT_RAYFAMILY_DOUBLES + (size_t)patches * TRT_PATCH_RECORD);
+                             (size_t)s.num_spheres * 4 + 2 * TRT_RAYFAMILY_DOUBLES + (size_t)patches * TRT_PATCH_RECORD +
+                             (size_t)(frames - 1) * (kLdsCameraDoubles + 2 * TRT_RAYFAMILY_DOUBLES));
 }
 
 // Where every part of the image lies from its base: one layout for the LDS image of a workgroup and for the device-memory image
@@ -136,7 +139,7 @@ struct ImageParts
     double *sph, *mat, *dir, *pt, *b255, *cam, *jit, *dirgrid, *pointgrid, *fam, *eye, *patch;
 };
 
-TRT_DEV ImageParts image_layout(double *base, int n, int nd, int np, int padded, int spp)
+TRT_DEV ImageParts image_layout(double *base, int n, int nd, int np, int padded, int spp, int frames = 1)
 {
     ImageParts p;
     p.cull = (float4 *)base;
@@ -146,7 +149,7 @@ TRT_DEV ImageParts image_layout(double *base, int n, int nd, int np, int padded,
     p.pt = p.dir + nd * kDirRecord;
     p.b255 = p.pt + np * 7;
     p.cam = p.b255 + 256;
-    p.jit = p.cam + kLdsCameraDoubles;
+    p.jit = p.cam + frames * kLdsCameraDoubles;
     // fixed-direction tables behind everything else, on a 16-byte boundary (all offsets above are whole doubles)
     p.cull_dir = (float4 *)(base + (((p.jit + 2 * spp) - base + 1) & ~1L));
     // headers of the light-space tables behind the fixed-direction tables (whole doubles again: 4 floats per entry)
@@ -154,7 +157,7 @@ TRT_DEV ImageParts image_layout(double *base, int n, int nd, int np, int padded,
     p.pointgrid = p.dirgrid + nd * kDirGridDoubles;
     p.fam = p.pointgrid + np * kPointGridDoubles;
     p.eye = p.fam + 4 * n;
-    p.patch = p.eye + 2 * TRT_RAYFAMILY_DOUBLES;
+    p.patch = p.eye + frames * 2 * TRT_RAYFAMILY_DOUBLES;
     return p;
 }
 
@@ -564,7 +567,9 @@ TRT_DEV void point_light_search(const LdsImage &L, int n, d3 o, d3 d, bool activ
 // expected in (0 eye, 1 mirror eye, 2 + i sphere i, 2 + n + i mirror sphere i, < 0 none).  `fallback` is set for an active lane
 // whose ray fails the family's membership test (its line must pass within r_chk of the apex, its origin not more than r_chk
 // behind it, within the table's range; a unit direction) or whose cell has no list: the caller then sweeps.
-TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n, int fam, d3 o, d3 d, bool active, bool &fallback)
+// BATCH: the ray belongs to frame `frame` of a batch launch, whose eye families and tables it reads (0 and unused otherwise)
+template <bool BATCH = false>
+TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n, int fam, d3 o, d3 d, bool active, bool &fallback, int frame = 0)
 {
     const bool has = active && fam >= 0;
     const int f = has ? fam : 0;
@@ -573,7 +578,7 @@ TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n
     const double *rec = L.fam + 4 * i; // mirror image of the centre, r_chk of the sphere's family
     d3 apex = mirrored ? load3(rec) : load3(L.sph + 4 * i);
     double r_chk = mirrored ? rec[3] + TRT_FAMILY_SLACK : rec[3];
-    const double *E = L.eye + TRT_RAYFAMILY_DOUBLES * (f & 1);
+    const double *E = BATCH ? L.eye + frame * (2 * TRT_RAYFAMILY_DOUBLES) + TRT_RAYFAMILY_DOUBLES * (f & 1) : L.eye + TRT_RAYFAMILY_DOUBLES * (f & 1);
     const double rg2_eye = E[5];
     if (of_eye)
     {
@@ -590,7 +595,7 @@ TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n
     const int g = of_eye ? G.g_eye : G.g_sph;
     const int at = trt_cubemap_cell((float)d.x, (float)d.y, (float)d.z, 0.5f * (float)g, (float)(g - 1), g);
     const unsigned eye_cells = 6u * (unsigned)G.g_eye * (unsigned)G.g_eye, sph_cells = 6u * (unsigned)G.g_sph * (unsigned)G.g_sph;
-    const unsigned base = of_eye ? G.eye_at + (unsigned)f * eye_cells : G.sph_at + (unsigned)s * sph_cells;
+    const unsigned base = of_eye ? G.eye_at + (BATCH ? 2u * (unsigned)frame + (unsigned)f : (unsigned)f) * eye_cells : G.sph_at + (unsigned)s * sph_cells;
     unsigned long long cell = 0;
     if (has && member)
         cell = G.path_lists[base + (unsigned)at];
@@ -606,7 +611,8 @@ TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n
 // from the ground cannot hit the ground again).  `fallback` is set for an active lane whose ray fails the family's
 // membership test (its line must pass within r_chk of the apex, its origin not more than r_chk behind it, within the table's
 // range; a unit direction) or whose cell has no list: the caller then sweeps.
-TRT_DEV unsigned long long path_cell_patches(const LdsImage &L, const GridView &G, int n, int &fam, d3 o, d3 d, bool active, bool &fallback)
+template <bool BATCH = false>
+TRT_DEV unsigned long long path_cell_patches(const LdsImage &L, const GridView &G, int n, int &fam, d3 o, d3 d, bool active, bool &fallback, int frame = 0)
 {
     const bool has = active && fam >= 0;
     const int f = has ? fam : 0;
@@ -617,7 +623,7 @@ TRT_DEV unsigned long long path_cell_patches(const LdsImage &L, const GridView &
     // select of the address): the sphere's centre, its mirror image, or the eye / mirror eye, whose families are "patches" of
     // a sphere of radius 0 -- base + 0 t is the base, 0 rho + slack the slack
     const double *at_sphere = L.sph + 4 * i, *at_mirror = L.fam + 4 * i;
-    const double *src = of_eye ? L.eye + TRT_RAYFAMILY_DOUBLES * (f & 1) : (mirrored ? at_mirror : at_sphere);
+    const double *src = of_eye ? L.eye + (BATCH ? frame * (2 * TRT_RAYFAMILY_DOUBLES) : 0) + TRT_RAYFAMILY_DOUBLES * (f & 1) : (mirrored ? at_mirror : at_sphere);
     const d3 base_at = load3(src);
     // which patch of its sphere the ray starts on (FP32: the membership test below is what counts)
     const int here = trt_cubemap_cell((float)(o.x - base_at.x), (float)(o.y - base_at.y), (float)(o.z - base_at.z), 0.5f * (float)G.patch_m,
@@ -646,7 +652,7 @@ TRT_DEV unsigned long long path_cell_patches(const LdsImage &L, const GridView &
     const int at = trt_cubemap_cell((float)d.x, (float)d.y, (float)d.z, 0.5f * (float)g, (float)(g - 1), g);
     const unsigned eye_cells = 6u * (unsigned)G.g_eye * (unsigned)G.g_eye, sph_cells = 6u * (unsigned)G.g_sph * (unsigned)G.g_sph;
     const unsigned table = ((mirrored ? (unsigned)n : 0u) + (unsigned)i) * (unsigned)G.patch_count + (unsigned)k;
-    const unsigned base = of_eye ? G.eye_at + (unsigned)f * eye_cells : G.sph_at + table * sph_cells;
+    const unsigned base = of_eye ? G.eye_at + (BATCH ? 2u * (unsigned)frame + (unsigned)f : (unsigned)f) * eye_cells : G.sph_at + table * sph_cells;
     unsigned long long cell = 0;
     if (has && member)
         cell = G.path_lists[base + (unsigned)at];
@@ -685,9 +691,9 @@ struct PathHit
 // the NEXT path ray: it starts on the sphere that was hit, or it is the mirror image in the ground of a ray of this one's
 // family -- of the patch of its sphere this ray started on -- (a ray from the ground cannot hit the ground again; if it
 // does, it has no family).
-template <bool COUNT, bool REFRACT = false, bool PATCHES = false>
+template <bool COUNT, bool REFRACT = false, bool PATCHES = false, bool BATCH = false>
 TRT_DEV PathHit path_stage(const LdsImage &L, const CullView &cull, const GridView &grids, int n, d3 o, d3 d, int &fam, bool alive, d3 gp, d3 gn,
-                           Tally &tally, int inside = -1)
+                           Tally &tally, int inside = -1, int frame = 0)
 {
     bool p_list = false;
     unsigned long long p_cell = 0;
@@ -695,9 +701,9 @@ TRT_DEV PathHit path_stage(const LdsImage &L, const CullView &cull, const GridVi
     {
         bool fallback;
         if constexpr (PATCHES)
-            p_cell = path_cell_patches(L, grids, n, fam, o, d, alive, fallback); // fam: now what a reflection by the ground belongs to
+            p_cell = path_cell_patches<BATCH>(L, grids, n, fam, o, d, alive, fallback, frame); // fam: now what a reflection by the ground belongs to
         else
-            p_cell = path_cell(L, grids, n, fam, o, d, alive, fallback);
+            p_cell = path_cell<BATCH>(L, grids, n, fam, o, d, alive, fallback, frame);
         p_list = !__any(fallback);
     }
     if (COUNT && !p_list)
@@ -888,6 +894,29 @@ struct RenderKernelArguments
 static_assert(offsetof(RenderKernelArguments, cull) == kArgCull && offsetof(RenderKernelArguments, f) == kArgFrame &&
                   offsetof(RenderKernelArguments, grids) == kArgGrids,
               "TRT_FRESH_ARGS reads the kernel's arguments at these offsets");
+
+// BATCH (trt_render_device_batch): ONE launch works through the samples of up to kBatchMax frames of one scene.  The units are
+// frame-major (unit = frame * units_per_frame + pixel * spp + k) in the one queue of the launch, so that the tail of frame b is
+// filled by the head of frame b + 1.  What depends on the camera comes by value in a fifth kernel argument -- a batch still in
+// flight never shares a buffer with the next one -- and is staged into the image: a camera block and a pair of eye families per
+// frame.  Frame b's two eye tables are cells [eye_at + 2 b eye_cells, eye_at + (2 b + 2) eye_cells) of path_lists.  Jitter and the
+// col_x / row_y axes are shared: the cameras of a batch have the same screen.
+constexpr int kBatchMax = 8;
+struct BatchView
+{
+    double cam[kBatchMax][15];        // Camera of every frame (FrameView::cam is frame 0's)
+    trt_rayfamily eye[kBatchMax][2];  // families 0 and 1 of every frame (GridView::eye is frame 0's)
+    unsigned frames, units_per_frame; // units_per_frame = owned pixels * spp
+    unsigned frame_magic, reserved;   // min(ceil(2^32 / units_per_frame), 2^32 - 1): unit -> frame by multiply-high
+};
+constexpr size_t kArgBatch = (kArgGrids + sizeof(GridView) + alignof(BatchView) - 1) / alignof(BatchView) * alignof(BatchView);
+static_assert(kArgBatch + sizeof(BatchView) <= 4096, "the arguments of a BATCH launch fit the 4 KB kernarg segment");
+static_assert(sizeof(BatchView::cam) % 8 == 0 && offsetof(BatchView, eye) == sizeof(BatchView::cam) && offsetof(BatchView, frames) % 8 == 0,
+              "BatchView is read as whole 64-bit words");
+// A lane's frame of the batch lives as long as its sample: in the three bits above the bounce count, not in a register of its own
+constexpr int kBatchFrameShift = 28;
+constexpr int kBatchBounceMask = (1 << kBatchFrameShift) - 1; // a batch launch takes bounce limits up to this
+static_assert(kBatchMax <= 8, "three bits of `bounces` hold the frame");
 // A pointer that was read from memory is "generic" to the compiler: loads and stores through it would be FLAT instructions.
 // Every pointer in the argument structs is a device-memory address: say so (a round trip through the global address space,
 // from which the compiler's address-space inference takes it).
@@ -937,6 +966,41 @@ TRT_DEV GridView in_device_memory(GridView v)
     const d3 gp = load3(s.ground), gn = load3(s.ground + 3);                                       \
     (void)n, (void)nd, (void)nl, (void)total, (void)pixels_here, (void)gp, (void)gn, (void)cull, (void)grids
 
+// what the hand-out of a BATCH launch needs of the fifth argument: three scalars
+struct alignas(8) BatchShape
+{
+    unsigned frames, units_per_frame, frame_magic, reserved;
+};
+TRT_DEV BatchShape load_batch_shape()
+{
+    const char CONSTANT_AS *args = (const char CONSTANT_AS *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(args));
+    return load_kernel_argument<BatchShape>(args + kArgBatch + offsetof(BatchView, frames));
+}
+
+// The LDS image of a BATCH launch: the single-frame image with a camera block and a pair of eye families per frame.  Every
+// thread reads its words of the fifth argument through the constant address space (a vector load: the index is the thread's).
+TRT_DEV LdsImage stage_lds_image_batch(double *lds, const SceneView &s, const CullView &cull, const FrameView &f, const GridView &grids)
+{
+    const int frames = (int)load_batch_shape().frames;
+    const ImageParts p = image_layout(lds, s.num_spheres, s.num_dir, s.num_point, cull.padded, f.spp, frames);
+    fill_image(p, s, cull, f, grids); // frame 0's camera and families are FrameView's and GridView's; all of them follow
+    const double CONSTANT_AS *cams = (const double CONSTANT_AS *)((const char CONSTANT_AS *)__builtin_amdgcn_kernarg_segment_ptr() + kArgBatch);
+    const double CONSTANT_AS *eyes = cams + sizeof(BatchView::cam) / sizeof(double);
+    for (int i = threadIdx.x; i < frames * kLdsCameraDoubles; i += blockDim.x)
+    {
+        const int b = i / kLdsCameraDoubles, j = i - b * kLdsCameraDoubles;
+        const double CONSTANT_AS *c = cams + b * 15;
+        // as fill_image forms them: the camera's first twelve doubles, -screen_distance, basis z * -screen_distance (TRT.c:989, :1000-1002)
+        p.cam[i] = j < 12 ? c[j] : (j == 12 ? -c[12] : c[6 + (j - 13)] * -c[12]);
+    }
+    if (grids.path_enabled)
+        for (int i = threadIdx.x; i < frames * 2 * TRT_RAYFAMILY_DOUBLES; i += blockDim.x)
+            p.eye[i] = eyes[i];
+    __syncthreads();
+    return image_view(p);
+}
+
 #ifndef TRT_COMPACT_BLOCK
 #define TRT_COMPACT_BLOCK 1024 // one workgroup per CU: 16 rings and one image share the CU's 160 KB of LDS
 #endif
@@ -951,16 +1015,23 @@ constexpr int kBigBlock = 1024;
 // scene runs three, two, one wave per SIMD (512 spheres: two).  Same code; the register allocator has to stay under 128.
 // DEVICE_IMAGE: the scene image is not staged into LDS but read from f.image, where stage_image_kernel (trt_render.hip) wrote it
 // for this launch in the same layout: scenes whose image does not fit LDS.  No dynamic LDS; the plain rounds only.
-template <bool COUNT, bool REFRACT = false, bool COMPACT = false, bool PATCHES = false, bool BIG = false, bool DEVICE_IMAGE = false>
-__global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersistentBlock, ((COMPACT && !COUNT) || BIG) ? 4 : TRT_ROUNDS_WAVES) void render_rounds_kernel(SceneView s, CullView cull, FrameView f, GridView grids)
+// BATCH: several frames of one scene per launch (BatchView above); the launch has a fifth argument, `batch`, a BatchView, which the
+// kernel reads where it needs it (stage_lds_image_batch, load_batch_shape).  Every difference is behind `if constexpr (BATCH)` or a
+// constant that folds: the single-frame instantiations are what they were.
+template <bool COUNT, bool REFRACT = false, bool COMPACT = false, bool PATCHES = false, bool BIG = false, bool DEVICE_IMAGE = false, bool BATCH = false,
+          class... BatchArgument>
+__global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersistentBlock, ((COMPACT && !COUNT) || BIG) ? 4 : TRT_ROUNDS_WAVES) void render_rounds_kernel(SceneView s, CullView cull, FrameView f, GridView grids, BatchArgument... batch)
 {
+    static_assert(sizeof...(BatchArgument) == (BATCH ? 1 : 0), "a BATCH launch has one more argument, a BatchView; the others none");
+    static_assert(!BATCH || (!COUNT && !REFRACT && !BIG && !DEVICE_IMAGE), "several frames per launch: the plain, patch and decoupled rounds");
     static_assert(!(REFRACT && COMPACT), "the refraction extension runs on the plain rounds");
     static_assert(!(PATCHES && COMPACT), "scenes with patches run the plain rounds");
     static_assert(!BIG || (PATCHES && !COUNT && !REFRACT && !COMPACT), "1024-thread workgroups: the shipping patch instantiation only");
     static_assert(!DEVICE_IMAGE || (!REFRACT && !COMPACT && !BIG), "the device-memory image: the plain rounds only");
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    const LdsImage L = DEVICE_IMAGE ? image_view(image_layout(const_cast<double *>(f.image), s.num_spheres, s.num_dir, s.num_point, cull.padded, f.spp))
-                                    : stage_lds_image(lds, s, cull, f, grids);
+    const LdsImage L = BATCH ? stage_lds_image_batch(lds, s, cull, f, grids)
+                       : DEVICE_IMAGE ? image_view(image_layout(const_cast<double *>(f.image), s.num_spheres, s.num_dir, s.num_point, cull.padded, f.spp))
+                                      : stage_lds_image(lds, s, cull, f, grids);
     const int n = s.num_spheres, nd = s.num_dir, nl = s.num_dir + s.num_point;
     const int lane = threadIdx.x & 63;
     const unsigned pixels_here = (unsigned)f.local_rows * (unsigned)f.width;
@@ -974,7 +1045,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
     unsigned slot_id = 0;          // k*pixels + pixel: where the sample's colour goes in f.samples
     d3 sample = d3{0.0, 0.0, 0.0}; // pixel_color of the sample (TRT.c:1012)
     double weight = 1.0, weight_sum = 0.0;
-    int bounces = 0;
+    int bounces = 0;               // BATCH: the sample's frame of the batch in the bits from kBatchFrameShift up
     d3 o = d3{0.0, 0.0, 0.0}, d = d3{0.0, 0.0, -1.0}; // the pending path ray
     d3 next_dir = d;                                  // un-normalised direction of the next path ray
     int fam = 0;                                      // family of the pending path ray (trt_raygrid.h): 0 = it starts at the eye
@@ -1031,13 +1102,26 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
                 }
                 else
                     pool_next += wanted;
+                BatchShape shape{};
+                if constexpr (BATCH)
+                    shape = load_batch_shape();
                 if (want_unit)
                 {
-                    alive = mine < total;
+                    alive = mine < (BATCH ? shape.frames * total : total); // BATCH: `total` is one frame's units
                     if (alive)
                     {
                         // unit -> (pixel, k) -> (row, column) by multiply-high with min(ceil(2^32/x), 2^32-1): off by at most one
                         // either way; the correction is two selects each, not branches (three nested exec regions per lane before)
+                        unsigned frame = 0;
+                        if constexpr (BATCH)
+                        { // unit -> (frame, unit of the frame) in the same way, first: lanes of one wave may be in different frames
+                            frame = __umulhi(mine, shape.frame_magic);
+                            const int within = (int)(mine - frame * total); // in (-total, 2 total): no overflow, frames * total < 2^31
+                            const int under = within < 0, over = within >= (int)total;
+                            frame += (unsigned)(over - under);
+                            mine = (unsigned)(within + (under - over) * (int)total);
+                        }
+                        const double *const cam = L.cam + (BATCH ? frame * (unsigned)kLdsCameraDoubles : 0u);
                         unsigned pixel = __umulhi(mine, f.spp_magic);
                         int k = (int)(mine - pixel * (unsigned)f.spp);
                         {
@@ -1057,17 +1141,17 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
                         // rows dealt from tile 0 with step 1 (a whole frame, a one-rank shard): the local row IS the frame row
                         const double sy = f.row_y[f.tile_first == 0 && f.tile_step == 1 ? (int)row : frame_row_of_magic(f, row)] + L.jit[f.spp + k];
                         d3 dir = d3{0.0, 0.0, 0.0};
-                        dir = add(dir, scale(load3(L.cam + 0), sx));
-                        dir = add(dir, scale(load3(L.cam + 3), sy));
-                        dir = add(dir, load3(L.cam + 13)); // scale(basis z, sz), formed once per workgroup (stage_lds_image)
-                        next_dir = sub(dir, load3(L.cam + 9)); // sic, TRT.c:1005
-                        o = load3(L.cam + 9);
+                        dir = add(dir, scale(load3(cam + 0), sx));
+                        dir = add(dir, scale(load3(cam + 3), sy));
+                        dir = add(dir, load3(cam + 13)); // scale(basis z, sz), formed once per workgroup (stage_lds_image)
+                        next_dir = sub(dir, load3(cam + 9)); // sic, TRT.c:1005
+                        o = load3(cam + 9);
                         fam = 0;
                         inside = -1;
                         sample = d3{0.0, 0.0, 0.0};
                         weight = 1.0;
                         weight_sum = 0.0;
-                        bounces = 0;
+                        bounces = BATCH ? (int)(frame << kBatchFrameShift) : 0;
                     }
                     want_unit = false;
                 }
@@ -1087,7 +1171,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
         PathHit hit;
         {
             TRT_FRESH_ARGS;
-            hit = path_stage<COUNT, REFRACT, PATCHES>(L, cull, grids, n, o, d, fam, alive, gp, gn, tally, inside);
+            hit = path_stage<COUNT, REFRACT, PATCHES, BATCH>(L, cull, grids, n, o, d, fam, alive, gp, gn, tally, inside, BATCH ? bounces >> kBatchFrameShift : 0);
         }
         if constexpr (COMPACT)
         {
@@ -1117,7 +1201,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
                     parked[lane] = nd3.x, parked[64 + lane] = nd3.y, parked[128 + lane] = nd3.z;
                     weight *= L.mat[hit.mat * 5 + 3];
                     bounces++;
-                    end_sample = !(bounces < f.bounce_limit && weight > 0.00001); // TRT.c:1018
+                    end_sample = !((BATCH ? bounces & kBatchBounceMask : bounces) < f.bounce_limit && weight > 0.00001); // TRT.c:1018
                 }
                 q_tail += (unsigned)__builtin_popcountll(hits);
             }
@@ -1193,6 +1277,8 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
                     unsigned slot = slot_id;
                     asm volatile("" : "+v"(slot)); // the address is formed here, not kept as 64 bits for the life of the sample
                     double *out = f.samples + (size_t)slot * 3;
+                    if constexpr (BATCH) // scratch [frame][k][pixel][3]: the slot is the frame's, the frame's offset 64 bits
+                        out += (size_t)(unsigned)(bounces >> kBatchFrameShift) * total * 3;
                     out[0] = sample.x * q;
                     out[1] = sample.y * q;
                     out[2] = sample.z * q;
@@ -1284,7 +1370,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
             weight *= L.mat[h_mat * 5 + 3];
             bounces++;
             sample = add(sample, color);
-            if (bounces < f.bounce_limit && weight > 0.00001) // TRT.c:1018
+            if ((BATCH ? bounces & kBatchBounceMask : bounces) < f.bounce_limit && weight > 0.00001) // TRT.c:1018
                 weight_sum = weight_sum_new;
             else
                 end_sample = true;
@@ -1308,6 +1394,8 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
             {
                 TRT_FRESH_ARGS;
                 double *out = f.samples + (size_t)slot_id * 3;
+                if constexpr (BATCH) // scratch [frame][k][pixel][3]
+                    out += (size_t)(unsigned)(bounces >> kBatchFrameShift) * total * 3;
                 out[0] = sample.x * q; // plain stores: non-temporal ones (keeping the 498 MB stream out of L2) measured no different
                 out[1] = sample.y * q;
                 out[2] = sample.z * q;

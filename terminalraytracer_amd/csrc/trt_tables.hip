@@ -328,7 +328,7 @@ static int build_path_tables(trt_context *ctx, const trt_cull_scene &cs, const d
     trt::GridView &g = ctx->grids;
     g.path_enabled = 0;
     g.patch_m = g.patch_count = 0;
-    ctx->eye_tables_valid = false;
+    invalidate_eye_tables(ctx);
     ctx->T->path_built_for[0] = ctx->path_g_eye;
     ctx->T->path_built_for[1] = ctx->path_g_sph;
     ctx->T->path_built_for[2] = ctx->path_min_spheres;
@@ -443,6 +443,53 @@ int build_tables(trt_context *ctx, const trt_cull_scene &cs, const double *groun
     return rc;
 }
 
+// The two tables of an eye's families into eye slot `slot` of the scene's tables and its part of the pool, on `stream`.
+static int build_eye_slot(trt_context *ctx, const trt_rayfamily *families, int slot, hipStream_t stream)
+{
+    const trt::GridView &g = ctx->grids;
+    const int n = (int)(ctx->T->h_spheres.size() / 9), ge = g.g_eye;
+    const size_t eye_cells = 6 * (size_t)ge * ge;
+    // the slot's part of the pool: behind the scene's part and the parts of the slots before it
+    const size_t pool_from = ctx->T->pool_scene_words + (size_t)slot * ctx->T->pool_eye_words;
+    unsigned long long *const counter = ctx->T->d_pool_used.ptr + 16 * (1 + slot);
+    hipLaunchKernelGGL(set_pool_counter_kernel, dim3(1), dim3(1), 0, stream, counter, (unsigned long long)pool_from);
+    launch_family_builder(n, dim3(family_grid_blocks(ge, 1), 2u), stream, (const double *)ctx->T->d_spheres.ptr, (const trt_rayfamily *)nullptr, families[0], families[1], 1,
+                          ge, ctx->T->d_path_lists.ptr + (size_t)slot * 2 * eye_cells, ctx->T->d_pool.ptr, counter, (unsigned)(pool_from + ctx->T->pool_eye_words), 1);
+    HIP_TRY(hipGetLastError());
+    return TRT_OK;
+}
+
+// The n cameras of a batch (trt_render_device_batch; the context's tables are its own): frame b's tables in slot b, rebuilt where
+// the slot's cached eye differs.  Slot eye_slot is the single frames': it goes through ensure_eye_tables, whose cache so stays true.
+int ensure_batch_eye_tables(trt_context *ctx, const Camera *cameras, int n, hipStream_t stream, trt_rayfamily (*families)[2])
+{
+    memset(families, 0, (size_t)n * sizeof *families);
+    if (!ctx->grids.path_enabled)
+        return TRT_OK;
+    for (int b = 0; b < n; b++)
+    {
+        if (b == ctx->eye_slot)
+        {
+            const int rc = ensure_eye_tables(ctx, &cameras[b], stream);
+            if (rc)
+                return rc;
+            families[b][0] = ctx->grids.eye[0], families[b][1] = ctx->grids.eye[1];
+            continue;
+        }
+        const double eye[3] = {cameras[b].frame.origin.x, cameras[b].frame.origin.y, cameras[b].frame.origin.z};
+        trt_eye_families(eye, ctx->T->ground_built, &ctx->T->cull_scene, families[b]);
+        if ((ctx->batch_eye_valid >> b & 1u) && !memcmp(eye, ctx->batch_eye[b], sizeof eye))
+            continue;
+        ctx->batch_eye_valid &= ~(1u << b);
+        const int rc = build_eye_slot(ctx, families[b], b, stream);
+        if (rc)
+            return rc;
+        memcpy(ctx->batch_eye[b], eye, sizeof eye);
+        ctx->batch_eye_valid |= 1u << b;
+    }
+    return TRT_OK;
+}
+
 // The two families of the eye (trt_raygrid.h): rebuilt on `stream` whenever the eye (or the scene) changed since they were built.
 int ensure_eye_tables(trt_context *ctx, const Camera *camera, hipStream_t stream)
 {
@@ -453,14 +500,10 @@ int ensure_eye_tables(trt_context *ctx, const Camera *camera, hipStream_t stream
     if (ctx->eye_tables_valid && !memcmp(eye, ctx->eye_built, sizeof eye))
         return TRT_OK;
     trt_eye_families(eye, ctx->T->ground_built, &ctx->T->cull_scene, g.eye);
-    const int n = (int)(ctx->T->h_spheres.size() / 9), ge = g.g_eye;
-    // this context's part of the pool: behind the scene's part and the parts of the slots before it
-    const size_t pool_from = ctx->T->pool_scene_words + (size_t)ctx->eye_slot * ctx->T->pool_eye_words;
-    unsigned long long *const counter = ctx->T->d_pool_used.ptr + 16 * (1 + ctx->eye_slot);
-    hipLaunchKernelGGL(set_pool_counter_kernel, dim3(1), dim3(1), 0, stream, counter, (unsigned long long)pool_from);
-    launch_family_builder(n, dim3(family_grid_blocks(ge, 1), 2u), stream, (const double *)ctx->T->d_spheres.ptr, (const trt_rayfamily *)nullptr, g.eye[0], g.eye[1], 1,
-                          ge, ctx->T->d_path_lists.ptr + g.eye_at, ctx->T->d_pool.ptr, counter, (unsigned)(pool_from + ctx->T->pool_eye_words), 1);
-    HIP_TRY(hipGetLastError());
+    ctx->eye_tables_valid = false;
+    const int rc = build_eye_slot(ctx, g.eye, ctx->eye_slot, stream); // g.eye_at is this slot's place
+    if (rc)
+        return rc;
     memcpy(ctx->eye_built, eye, sizeof eye);
     ctx->eye_tables_valid = true;
     return TRT_OK;

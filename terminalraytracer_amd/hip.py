@@ -63,6 +63,9 @@ SYMBOLS = {
     "trt_quantize_device": (_I, [_VP, _VP, _SZ, _VP]),
     "trt_render_host": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP]),
     "trt_render_host_rgb8": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP]),
+    "trt_render_device_batch": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ]),
+    "trt_render_host_batch": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP]),
+    "trt_batch_info": (_I, [_VP, C.POINTER(_I), C.POINTER(_I)]),
     "trt_synchronize": (_I, [_VP]),
     "trt_kernel_times": (_I, [_VP, C.POINTER(C.c_float), _I]),
     "trt_render_kernel_times": (_I, [_VP, C.POINTER(C.c_float), C.POINTER(C.c_float), _I]),
@@ -365,6 +368,33 @@ class Context:
         cam = camera_struct(camera_array)
         _check(lib().trt_render_host_rgb8(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data))
         return out
+
+    @staticmethod
+    def _camera_batch(cameras):
+        cams = np.ascontiguousarray(cameras, dtype=np.float64)
+        if cams.ndim != 2 or cams.shape[1] != 15:
+            raise ValueError("cameras: float64 [n, 15] (Camera, TRT.c:178-184)")
+        return cams
+
+    def render_device_batch(self, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
+        """cameras[n, 15] of the current scene in one call; frame b at device_ptr + b * rows * width * 24 (trt_render_device_batch)"""
+        cams = self._camera_batch(cameras)
+        _check(lib().trt_render_device_batch(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
+                                             _VP(device_ptr), capacity_bytes))
+
+    def render_host_batch(self, cameras, rows, bounce_limit, rays_per_pixel):
+        """the same into host memory: float64 [n, rows, width, 3] (trt_render_host_batch)"""
+        cams = self._camera_batch(cameras)
+        out = np.zeros((cams.shape[0], lib().trt_rowset_rows(C.byref(rows)), rows.width, 3), dtype=np.float64)
+        _check(lib().trt_render_host_batch(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
+                                           out.ctypes.data))
+        return out
+
+    def batch_info(self):
+        """(frames, render-kernel launches) of this context's most recent batch call (trt_batch_info)"""
+        n, k = _I(), _I()
+        _check(lib().trt_batch_info(self._h, C.byref(n), C.byref(k)))
+        return n.value, k.value
 
     def synchronize(self):
         _check(lib().trt_synchronize(self._h))
