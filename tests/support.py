@@ -184,3 +184,38 @@ def full_scene(case):
     """The scene of a golden_full case: SYNTH-v0 spheres, procedural cubemap, the reference's stored camera."""
     return S.synth_scene(case["spheres"], S.synth_sky(case["sky_dim"], seed=case["sky_seed"]),
                          np.array(case["camera"], dtype=np.float64), seed=case["scene_seed"])
+
+
+def fuzz_scene(rng, w, h):
+    """A random scene of the kinds kernels go wrong on: exact ties, nested and degenerate spheres, tilted and non-unit ground normals, lights on
+    surfaces, cameras inside spheres and far away.  The fuzz tests share it; it draws from `rng` in a fixed order."""
+    n = int(rng.choice([0, 1, 2, 5, 9, 31, 32, 33, 64, 65, 100]))
+    sph = np.zeros((n, 9))
+    if n:
+        sph[:, :3] = rng.normal(size=(n, 3)) * rng.choice([0.5, 2.0, 6.0])
+        sph[:, 3] = rng.uniform(0.05, 1.2, n) * rng.choice([0.3, 1.0, 2.0])
+        sph[:, 4:7] = rng.uniform(0, 1, (n, 3))
+        sph[:, 7] = rng.choice([0.0, 0.3, 0.9, 1.0], n)
+        sph[:, 8] = 100.0
+        if n >= 5:  # exact ties: duplicated spheres with different materials (first index must win), nested and degenerate ones
+            sph[n // 2, :4] = sph[1, :4]
+            sph[n - 1, :4] = sph[1, :4]
+            sph[2, :3] = sph[3, :3]
+            sph[2, 3] = sph[3, 3] * 0.5  # concentric, smaller: always hidden from outside
+            sph[4, 3] = 0.0               # zero radius
+    ground = S.demo_ground().copy()
+    if rng.random() < 0.5:
+        ground[0:3] = rng.normal(size=3)
+        ground[3:6] = rng.normal(size=3) * rng.choice([1.0, 0.01, 30.0])  # non-unit normals too
+    ground[9] = rng.choice([0.0, 0.2, 1.0])
+    nd, npt = int(rng.integers(0, 3)), int(rng.integers(0, 4))
+    dl = np.concatenate([rng.normal(size=(nd, 3)), rng.uniform(0, 1.2, (nd, 3))], axis=1)
+    pl = np.concatenate([rng.normal(size=(npt, 3)) * 3, rng.uniform(0, 1.2, (npt, 3)), rng.uniform(0.1, 30, (npt, 1))], axis=1)
+    if npt and n:
+        pl[0, :3] = sph[0, :3] + np.array([0.0, sph[0, 3], 0.0])  # a light exactly on a sphere's surface
+    cam = bench_camera(w, h, float(rng.choice([0.0, 0.5, 2.5, 10.0, 33.3])))
+    if rng.random() < 0.3 and n:
+        cam[9:12] = sph[0, :3] + 0.3 * sph[0, 3]  # camera inside a sphere
+    if rng.random() < 0.3:
+        cam[9:12] = rng.normal(size=3) * 20
+    return S.SceneData(sph, ground, dl.reshape(-1, 6), pl.reshape(-1, 7), cam, sky("synth"))

@@ -47,6 +47,83 @@ def test_refusals_that_need_no_device():
     assert lib.trt_batch_info(None, None, None) == ARGUMENT
 
 
+# ---- fuzzed batches: the cases are plain data, made without a GPU ----
+
+FUZZ_SEEDS = tuple(range(12)) + (13, 24, 29, 44)  # 24 and 44: no lights; 29: no spheres
+FUZZ_TINY = (6, 13)  # seeds whose frames have fewer samples than a wave: one wave holds samples of several frames
+FUZZ_TABLES = (((0, 0), -1, -1), ((64, 32), 2, -1), ((64, 32), -1, 0), ((64, 32), -1, 1))  # path grids, patches, compaction
+FUZZ_NAN = (1, 3, 9, 10)  # seeds whose every fourth sphere has a colour that is not a number: the cameras that see one have NaN pixels
+
+
+@functools.lru_cache(maxsize=None)
+def fuzz_batch_case(seed):
+    """(scene, cameras[n, 15], w, h, bounce limit, rays per pixel) of a fuzzed batch: a fuzz scene seen by 1 to 8 cameras of one screen whose
+    eyes are drawn independently -- on the orbit, inside sphere 0, far away, on a point light, or the eye of ANOTHER camera of the
+    batch with another basis (the two legitimately share one eye-table key).  No finite camera makes the oracle's frame non-finite
+    (a NaN or infinite one sends the reference's own sky look-up out of its cubemap), so the NaN frames come from a material: in the
+    seeds of FUZZ_NAN every fourth sphere's colour is NaN, which reaches pixels through the shading arithmetic alone, never through geometry."""
+    rng = np.random.default_rng(2000 + seed)
+    w, h = int(rng.integers(8, 72)), int(rng.integers(4, 40))
+    b, spp = int(rng.integers(1, 9)), int(rng.choice([1, 3, 10]))
+    if seed in FUZZ_TINY:
+        w, h, spp = int(rng.integers(1, 8)), int(rng.integers(1, 4)), int(rng.choice([1, 2]))
+        assert w * h * spp < 64
+    scene = T.fuzz_scene(rng, w, h)
+    if seed in FUZZ_NAN:
+        spheres = scene.spheres.copy()
+        spheres[::4, 4:7] = np.nan
+        scene = scene.with_spheres(spheres)
+    n = int(rng.integers(1, 9))
+    cams = np.zeros((n, 15))
+    for k in range(n):
+        cams[k] = T.bench_camera(w, h, float(rng.choice([0.0, 0.5, 1.0, 2.5, 10.0, 33.3])))  # an orbit camera: its basis, eye and the batch's screen
+        kind = rng.choice(["orbit", "inside", "far", "same eye", "on a light"], p=[0.4, 0.15, 0.15, 0.25, 0.05])
+        if kind == "inside" and scene.num_spheres:
+            cams[k, 9:12] = scene.spheres[0, :3] + 0.3 * scene.spheres[0, 3]
+        elif kind == "far":
+            cams[k, 9:12] = rng.normal(size=3) * 20
+        elif kind == "same eye" and k:
+            cams[k, 9:12] = cams[int(rng.integers(0, k)), 9:12]
+        elif kind == "on a light" and scene.point_lights.shape[0]:
+            cams[k, 9:12] = scene.point_lights[0, :3]
+    if seed % 4 == 0:
+        cams[0] = scene.camera  # the camera the fuzz scene came with
+    return scene, cams, w, h, b, spp
+
+
+@functools.lru_cache(maxsize=None)
+def fuzz_batch_oracle(seed, k):
+    scene, cams, w, h, b, spp = fuzz_batch_case(seed)
+    with np.errstate(all="ignore"):
+        return T.oracle_render(scene.with_camera(cams[k]), w, h, b, spp)[0]
+
+
+def test_fuzzed_batch_cases_are_mostly_finite():
+    """Where the oracle's frame has NaNs the fuzz compares their positions and the finite values only; that branch hides little only
+    if it is rare: at most one case (camera x seed) in eight takes it, by the oracle alone.  And the cases are what they claim."""
+    assert len(FUZZ_SEEDS) >= 16
+    cases, nans, same_eye, lights = 0, 0, 0, set()
+    for seed in FUZZ_SEEDS:
+        scene, cams, w, h, b, spp = fuzz_batch_case(seed)
+        assert 1 <= len(cams) <= 8 and (cams[:, 12:15] == cams[0, 12:15]).all()
+        assert (w * h * spp < 64) == (seed in FUZZ_TINY)
+        lights.add(scene.dir_lights.shape[0] + scene.point_lights.shape[0])
+        eyes = [tuple(c[9:12]) for c in cams]
+        same_eye += sum(1 for k in range(len(cams)) for j in range(k) if eyes[j] == eyes[k] and not np.array_equal(cams[j, :9], cams[k, :9]))
+        for k in range(len(cams)):
+            cases += 1
+            nans += not np.isfinite(fuzz_batch_oracle(seed, k)).all()
+    print(f"{nans} of {cases} fuzzed batch frames are not finite")
+    assert nans >= 1 and nans * 8 <= cases, (nans, cases)
+    for seed in FUZZ_SEEDS:  # compaction 1 (the decoupled BATCH form) on scenes of two or more lights
+        if FUZZ_TABLES[seed % 4][2] == 1:
+            scene = fuzz_batch_case(seed)[0]
+            assert scene.dir_lights.shape[0] + scene.point_lights.shape[0] >= 2, seed
+    spheres = {fuzz_batch_case(s)[0].num_spheres for s in FUZZ_SEEDS}
+    assert same_eye >= 3 and 0 in lights and max(lights) >= 4 and 0 in spheres and len(spheres) >= 5
+    assert any(len(fuzz_batch_case(s)[1]) == 1 for s in FUZZ_SEEDS) and any(len(fuzz_batch_case(s)[1]) == 8 for s in FUZZ_SEEDS)
+
+
 # ---- on the GPU ----
 
 @pytest.fixture(scope="module")
@@ -66,6 +143,7 @@ def _defaults(request):
         c.set_refraction(None)
         c.set_path_grids(64, 32)
         c.set_path_patches(-1)
+        c.set_path_grids_min_spheres(12)
         c.set_compaction(-1)
 
 
@@ -293,3 +371,66 @@ def test_a_batch_whose_image_would_cost_a_workgroup_is_split(ctx):
     print("render launches of a batch of 8 by sphere count:", launches)
     assert any(1 < n for n in launches.values()), launches
     assert any(n == 1 for n in launches.values()), launches
+
+
+@gpu
+@pytest.mark.parametrize("seed", FUZZ_SEEDS, ids=[f"seed{s}" for s in FUZZ_SEEDS])
+def test_fuzzed_batches_match_the_oracle(ctx, seed):
+    """Batches of anything but the demo and SYNTH scenes seen from the orbit: no spheres, no lights, many lights, duplicated, nested
+    and zero-radius spheres, tilted and non-unit ground normals, cameras inside a sphere, far away, on a light, two cameras of one
+    eye -- under the table settings of test_table_settings_keep_the_frames_and_the_single_launch, with the path tables for scenes of
+    any size on every other seed.  Every frame is the oracle's and the single call's."""
+    scene, cams, w, h, b, spp = fuzz_batch_case(seed)
+    grids, patches, compaction = FUZZ_TABLES[seed % 4]
+    rows = hip.RowSet.whole(w, h)
+    ctx.set_path_grids(*grids)
+    ctx.set_path_patches(patches)
+    ctx.set_compaction(compaction)
+    ctx.set_path_grids_min_spheres(0 if seed % 2 else 12)
+    ctx.set_scene(scene)
+    got = ctx.render_host_batch(cams, rows, b, spp)
+    frames, launches = ctx.batch_info()
+    assert frames == len(cams) and 1 <= launches <= len(cams)
+    for k, cam in enumerate(cams):
+        want = fuzz_batch_oracle(seed, k)
+        single = ctx.render_host(cam, rows, b, spp)
+        finite = np.isfinite(want)
+        print(f"seed {seed} camera {k}: {w}x{h} b={b} spp={spp}, {scene.num_spheres} spheres, {int((~finite).sum())} non-finite values")
+        if finite.all():
+            assert np.array_equal(bits(got[k]), bits(want)), (seed, k)
+            assert np.array_equal(bits(got[k]), bits(single)), (seed, k)
+        else:  # as test_fuzzed_scenes_match_the_oracle: the NaNs in the same places, the finite values bit-equal
+            for frame in (got[k], single):
+                assert np.array_equal(np.isnan(frame), np.isnan(want)) and np.array_equal(bits(frame[finite]), bits(want[finite])), (seed, k)
+    ctx.set_scene(_scene("synth"))  # a scene the restored table settings build quickly for
+
+
+@gpu
+def test_the_frame_index_packed_beside_the_bounce_count(ctx):
+    """A BATCH launch keeps the frame's index in the three bits of the bounce count above kBatchBounceMask = 2^28 - 1 and masks on
+    every compare: the largest limit it takes must leave those bits alone (one launch, the oracle's frames), and one more must send
+    the call to the per-camera path (three launches, the same bits)."""
+    w, h, spp, indices = 32, 18, 2, [0, 19, 59]
+    cams = anim_cameras(indices, w, h)
+    spheres = S.synth_spheres(64)
+    spheres[:, 7] = np.minimum(spheres[:, 7], 0.9)
+    scene = S.synth_scene(64, T.sky("synth"), cams[0]).with_spheres(spheres)
+    # the guard, before anything is launched: nothing reflects more than 0.9, so every path ends by the reference's weight > 0.00001
+    # cut (0.9^110 < 0.00001) within 110 bounces whatever the limit -- a perfect mirror would keep a persistent kernel spinning
+    assert (scene.spheres[:, 7] <= 0.9).all() and scene.ground[9] <= 0.9 and scene.ground[14] <= 0.9
+    assert 0.9 ** 110 < 0.00001
+    mask = 2 ** 28 - 1
+    want = [T.oracle_render(scene.with_camera(cam), w, h, mask, spp)[0] for cam in cams]
+    for k, cam in enumerate(cams):  # the oracle at that limit is the oracle at any limit above the longest path
+        assert np.array_equal(bits(want[k]), bits(T.oracle_render(scene.with_camera(cam), w, h, 111, spp)[0]))
+        assert np.isfinite(want[k]).all()
+    rows = hip.RowSet.whole(w, h)
+    ctx.set_scene(scene)
+    assert ctx.read_path_tables(cams[0])[0]["enabled"]
+    got = ctx.render_host_batch(cams, rows, mask, spp)
+    assert ctx.batch_info() == (3, 1)
+    for k in range(3):
+        assert np.array_equal(bits(got[k]), bits(want[k])), k
+    again = ctx.render_host_batch(cams, rows, mask + 1, spp)
+    assert ctx.batch_info() == (3, 3)
+    assert np.array_equal(bits(again), bits(got))
