@@ -359,7 +359,7 @@ extern "C" int trt_share_scene(trt_context *dst, trt_context *src)
     dst->grids = src->grids;
     dst->grids.eye_at = (unsigned)((size_t)slot * 2 * 6 * (size_t)src->grids.g_eye * (size_t)src->grids.g_eye);
     invalidate_eye_tables(dst);
-    src->batch_eye_valid = 0; // the slots a batch of src's used may now be dst's (or another sharer's)
+    invalidate_eye_tables(src, src->eye_slot); // the slots a batch of src's used may now be dst's (or another sharer's)
     // the settings the tables were built with travel along (a later trt_set_scene on dst then builds alike)
     dst->dirgrid_cells = src->dirgrid_cells, dst->pointgrid_cells = src->pointgrid_cells;
     dst->dirgrid_slabs = src->dirgrid_slabs, dst->pointgrid_shells = src->pointgrid_shells;

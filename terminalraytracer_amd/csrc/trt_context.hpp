@@ -182,16 +182,20 @@ struct trt_context
     // the dominant cost at 128+ spheres), and once it has been still for a few calls the full tables are built (trt_set_scene_policy).
     int scene_changes_in_a_row = 0, scene_still_calls = 0;
     bool moving_scene = false;
-    double eye_built[3] = {0.0, 0.0, 0.0};
-    bool eye_tables_valid = false;
-    // trt_render_device_batch builds frame b's eye tables into slot b of the context's own (unshared) tables.  Slot eye_slot is the
-    // single frames' and keeps its cache above; the others': the eye each was last built for, bit s of batch_eye_valid says whether it holds
-    double batch_eye[kEyeSlots][3] = {};
-    unsigned batch_eye_valid = 0;
+    // The eye each of T's kEyeSlots places was last built for by THIS context, its two families, and whether the tables still hold.
+    // A single frame builds into slot eye_slot (whose families grids.eye repeats); frame b of a batch (trt_render_device_batch, the
+    // context's tables its own) into slot b.
+    struct EyeSlot
+    {
+        double eye[3];
+        trt_rayfamily families[2];
+        bool valid;
+    };
+    EyeSlot eye_slots[kEyeSlots] = {};
     int batch_frames = 0, batch_launches = 0; // trt_batch_info: the most recent batch call
     struct BatchOccupancy
     {
-        int variant;
+        const void *kernel;
         size_t lds;
         int blocks;
     };
@@ -254,21 +258,22 @@ struct trt_context
 namespace trt_impl
 {
 
-// LDS image of the production kernel for the context's scene and tables
-inline size_t image_lds_bytes(const trt_context *ctx, int spp)
+// LDS image of the production kernel for the context's scene and tables; with a camera block and a pair of eye families per
+// frame of a launch of several cameras
+inline size_t image_lds_bytes(const trt_context *ctx, int spp, int frames = 1)
 {
-    return trt::rounds_lds_bytes(ctx->scene, spp, ctx->grids.path_enabled ? ctx->grids.patch_count : 0);
+    return trt::rounds_lds_bytes(ctx->scene, spp, ctx->grids.path_enabled ? ctx->grids.patch_count : 0, frames);
 }
 
 // LDS of render_rounds_kernel<.., false, true>: the image, then one shading ring per wave of the workgroup
-inline size_t compact_ring_at(const trt_context *ctx, int spp)
+inline size_t compact_ring_at(const trt_context *ctx, int spp, int frames = 1)
 {
-    return (image_lds_bytes(ctx, spp) / sizeof(double) + 1) & ~(size_t)1; // in doubles, on a 16-byte boundary
+    return (image_lds_bytes(ctx, spp, frames) / sizeof(double) + 1) & ~(size_t)1; // in doubles, on a 16-byte boundary
 }
 
-inline size_t compact_lds_bytes(const trt_context *ctx, int spp)
+inline size_t compact_lds_bytes(const trt_context *ctx, int spp, int frames = 1)
 {
-    return sizeof(double) * (compact_ring_at(ctx, spp) + (size_t)(trt::kCompactBlock / 64) * trt::kRingDoubles);
+    return sizeof(double) * (compact_ring_at(ctx, spp, frames) + (size_t)(trt::kCompactBlock / 64) * trt::kRingDoubles);
 }
 
 inline size_t scene_lds_bytes(const trt::SceneView &s)
@@ -292,11 +297,12 @@ inline bool rowset_valid(const trt_rowset *r)
     return r && r->width > 0 && r->height > 0 && r->tile_rows > 0 && r->tile_first >= 0 && r->tile_step > 0;
 }
 
-// the eye's tables of every slot this context builds are stale (another scene, other tables, another slot)
-inline void invalidate_eye_tables(trt_context *ctx)
+// the eye's tables of every slot this context builds are stale (another scene, other tables, another slot); `keep`: but that slot's
+inline void invalidate_eye_tables(trt_context *ctx, int keep = -1)
 {
-    ctx->eye_tables_valid = false;
-    ctx->batch_eye_valid = 0;
+    for (int s = 0; s < kEyeSlots; s++)
+        if (s != keep)
+            ctx->eye_slots[s] = {};
 }
 
 // ---- defined in trt_capi.hip
@@ -309,9 +315,8 @@ extern int g_moving_after, g_still_after; // trt_set_scene_policy
 // ---- defined in trt_tables.hip
 int patches_for(const trt_context *ctx, int n);
 int build_tables(trt_context *ctx, const trt_cull_scene &cs, const double *ground);
-int ensure_eye_tables(trt_context *ctx, const Camera *camera, hipStream_t stream);
-// the same for the n cameras of a batch: frame b's tables in slot b; families[b] = its two families (all zero without path tables)
-int ensure_batch_eye_tables(trt_context *ctx, const Camera *cameras, int n, hipStream_t stream, trt_rayfamily (*families)[2]);
+// the tables of `camera`'s eye in eye slot `slot` (-1: the context's own, eye_slot) and the slot's families, built on `stream` unless they hold
+int ensure_eye_tables(trt_context *ctx, const Camera *camera, hipStream_t stream, int slot = -1);
 void allow_large_lds_tables(const trt_context *ctx); // dynamic LDS above the 64 KiB default needs the opt-in attribute, per kernel
 // ---- defined in trt_render.hip
 int refresh_occupancy(trt_context *ctx);

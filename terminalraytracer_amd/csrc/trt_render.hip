@@ -1,5 +1,6 @@
-// trt_render.hip -- render dispatch: which instantiation of the production kernel (csrc/trt_rounds.hpp) a frame runs and its launch,
-// occupancy, the copy-out to the host, kernel times and resource usage.
+// trt_render.hip -- render dispatch: which instantiation of the production kernel (csrc/trt_rounds.hpp) a launch runs -- a single
+// frame, or several cameras of one scene (a single frame is a batch of one) -- its plan and its launch, occupancy, the copy-out to
+// the host, kernel times and resource usage.
 // Compiled for gfx950 only, with -ffp-contract=off (see trt_device.hpp).
 #define TRT_UNIT_RENDER 1 // this unit is the home of the kernels that are not templates (trt_common.hpp, trt_simple.hpp)
 #include "trt_context.hpp"
@@ -29,20 +30,25 @@ enum Variant : int
 };
 
 using RoundsKernel = void (*)(trt::SceneView, trt::CullView, trt::FrameView, trt::GridView);
+// The BATCH form of an instantiation (trt_rounds.hpp; several cameras of one scene per launch, trt_render_device_batch): plain,
+// patches, decoupled -- the non-counting instantiations with the image in LDS.  Everything else a context may be set to render
+// is served one launch per camera.
+using BatchKernel = void (*)(trt::SceneView, trt::CullView, trt::FrameView, trt::GridView, trt::BatchView);
 struct RoundsVariant
 {
     RoundsKernel fn;
     int block;  // threads per workgroup
     bool rings; // LDS: the image, then a shading ring per wave (compact_lds_bytes); otherwise the image alone
     bool image; // the image in device memory (stage_image_kernel), no dynamic LDS
+    BatchKernel batch; // null: no BATCH form
 };
 static const RoundsVariant kRounds[kReference] = {
-    {trt::render_rounds_kernel<false>, trt::kPersistentBlock, false},
+    {trt::render_rounds_kernel<false>, trt::kPersistentBlock, false, false, trt::render_rounds_kernel<false, false, false, false, false, false, true, trt::BatchView>},
     {trt::render_rounds_kernel<true>, trt::kPersistentBlock, false},
-    {trt::render_rounds_kernel<false, false, false, true>, trt::kPersistentBlock, false},
+    {trt::render_rounds_kernel<false, false, false, true>, trt::kPersistentBlock, false, false, trt::render_rounds_kernel<false, false, false, true, false, false, true, trt::BatchView>},
     {trt::render_rounds_kernel<true, false, false, true>, trt::kPersistentBlock, false},
     {trt::render_rounds_kernel<false, false, false, true, true>, trt::kBigBlock, false},
-    {trt::render_rounds_kernel<false, false, true>, trt::kCompactBlock, true},
+    {trt::render_rounds_kernel<false, false, true>, trt::kCompactBlock, true, false, trt::render_rounds_kernel<false, false, true, false, false, false, true, trt::BatchView>},
     {trt::render_rounds_kernel<true, false, true>, trt::kCompactBlock, true},
     {trt::render_rounds_kernel<false, true>, trt::kPersistentBlock, false},
     {trt::render_rounds_kernel<true, true>, trt::kPersistentBlock, false},
@@ -53,6 +59,12 @@ static const RoundsVariant kRounds[kReference] = {
     {trt::render_rounds_kernel<false, false, false, true, false, true>, trt::kPersistentBlock, false, true},
     {trt::render_rounds_kernel<true, false, false, true, false, true>, trt::kPersistentBlock, false, true},
 };
+static_assert(TRT_BATCH_MAX == kEyeSlots && TRT_BATCH_MAX == trt::kBatchMax, "a frame of a batch has an eye slot of the scene's tables and a place in BatchView");
+
+static BatchKernel batch_form(Variant v)
+{
+    return v < kReference ? kRounds[v].batch : nullptr;
+}
 
 static bool image_in_device_memory(Variant v)
 {
@@ -89,20 +101,29 @@ static bool renders_decoupled(const trt_context *ctx, long units)
     return ctx->compaction > 0 || pays;
 }
 
-static Variant choose_variant(const trt_context *ctx, long units, int spp)
+// do the scene's spheres have patches?  (larger tables: one queue word, never decoupled)
+static bool has_patches(const trt_context *ctx)
+{
+    return ctx->grids.path_enabled && ctx->grids.patch_m > 0;
+}
+
+// Which kernel a launch of `frames` cameras and `units` samples in all runs.  A batch of 1/8 shards is a large launch: the
+// decoupling threshold sees the whole launch's units, and the rings must fit beside the image of all its frames.  Whether the
+// image goes to device memory is asked of ONE frame: a batch that does not fit LDS is split (fit_batch), not moved.
+static Variant choose_variant(const trt_context *ctx, long units, int spp, int frames = 1)
 {
     const bool device_image = wants_device_image(ctx, spp);
     if (ctx->kernel == 1)
         return device_image ? kReferenceImage : kReference;
     const bool count = ctx->counters_enabled;
-    const bool patches = ctx->grids.path_enabled && ctx->grids.patch_m > 0;
+    const bool patches = has_patches(ctx);
     if (ctx->ior_count) // no device-image form: a scene whose image does not fit LDS fails at render time
         return patches ? (count ? kRefractPatchesCount : kRefractPatches) : (count ? kRefractCount : kRefract);
     if (device_image)
         return patches ? (count ? kPatchesImageCount : kPatchesImage) : (count ? kPlainImageCount : kPlainImage);
     // scenes whose spheres have patches (dense ones) run the plain rounds; the rings must fit beside the image (the occupancy
     // figures were taken for 64 rays per pixel: with more, the jitter table may push the rings out of LDS)
-    if (!patches && renders_decoupled(ctx, units) && compact_lds_bytes(ctx, spp) <= (size_t)ctx->lds_limit)
+    if (!patches && renders_decoupled(ctx, units) && compact_lds_bytes(ctx, spp, frames) <= (size_t)ctx->lds_limit)
         return count ? kDecoupledCount : kDecoupled;
     if (!patches)
         return count ? kPlainCount : kPlain;
@@ -122,107 +143,82 @@ static int described_spp(const trt_context *ctx)
     return ctx->last_variant >= 0 ? ctx->last_spp : 64;
 }
 
-// ---- several cameras of one scene per launch (trt_render_device_batch) ----
-// The BATCH forms of the production kernel (trt_rounds.hpp): plain, patches, decoupled -- the non-counting instantiations with the
-// image in LDS.  Everything else a context may be set to render is served one launch per camera.
-using BatchKernel = void (*)(trt::SceneView, trt::CullView, trt::FrameView, trt::GridView, trt::BatchView);
-struct BatchVariant
+// dynamic LDS of a launch of `frames` frames of variant v
+static size_t launch_lds_bytes(const trt_context *ctx, Variant v, int spp, int frames = 1)
 {
-    BatchKernel fn;
-    Variant single; // the single-frame instantiation it is the BATCH form of: block size, rings
-};
-enum : int { kBatchPlain, kBatchPatches, kBatchDecoupled, kBatchForms };
-static const BatchVariant kBatchRounds[kBatchForms] = {
-    {trt::render_rounds_kernel<false, false, false, false, false, false, true, trt::BatchView>, kPlain},
-    {trt::render_rounds_kernel<false, false, false, true, false, false, true, trt::BatchView>, kPatches},
-    {trt::render_rounds_kernel<false, false, true, false, false, false, true, trt::BatchView>, kDecoupled},
-};
-static_assert(TRT_BATCH_MAX == kEyeSlots && TRT_BATCH_MAX == trt::kBatchMax, "a frame of a batch has an eye slot of the scene's tables and a place in BatchView");
-
-// LDS of a BATCH launch of `frames` cameras: the image with a camera block and eye families per frame, then the rings as in compact_lds_bytes
-static size_t batch_image_bytes(const trt_context *ctx, int spp, int frames)
-{
-    return trt::rounds_lds_bytes(ctx->scene, spp, ctx->grids.path_enabled ? ctx->grids.patch_count : 0, frames);
-}
-static size_t batch_ring_at(const trt_context *ctx, int spp, int frames)
-{
-    return (batch_image_bytes(ctx, spp, frames) / sizeof(double) + 1) & ~(size_t)1;
-}
-static size_t batch_lds_bytes(const trt_context *ctx, int form, int spp, int frames)
-{
-    if (!kRounds[kBatchRounds[form].single].rings)
-        return batch_image_bytes(ctx, spp, frames);
-    return sizeof(double) * (batch_ring_at(ctx, spp, frames) + (size_t)(trt::kCompactBlock / 64) * trt::kRingDoubles);
+    const RoundsVariant &k = kRounds[v];
+    return k.image ? 0u : k.rings ? compact_lds_bytes(ctx, spp, frames) : image_lds_bytes(ctx, spp, frames);
 }
 
-// Which BATCH form `frames` cameras of `units` samples in all run; -1: none, the batch is served one launch per camera.  The
-// reasoning is choose_variant's, with the whole launch's units for the decoupling threshold: a batch of 1/8 shards is a large launch.
-static int choose_batch_variant(const trt_context *ctx, long units, int spp, int frames)
+// Workgroups per CU a launch of variant v is sized by.  The single-frame instantiations: what refresh_occupancy stored for the
+// scene (every 256-thread variant with the image in LDS by the plain instantiation's occupancy).  The BATCH forms, whose image grows
+// with the frames of the launch: their own occupancy with `lds` bytes of dynamic LDS (0: it does not fit), asked once per size.
+static int blocks_per_cu(trt_context *ctx, Variant v, bool batch, size_t lds, int *blocks)
 {
-    if (ctx->kernel == 1 || ctx->counters_enabled || ctx->ior_count || wants_device_image(ctx, spp))
-        return -1;
-    const bool patches = ctx->grids.path_enabled && ctx->grids.patch_m > 0;
-    if (!patches)
-        return renders_decoupled(ctx, units) && batch_lds_bytes(ctx, kBatchDecoupled, spp, frames) <= (size_t)ctx->lds_limit ? kBatchDecoupled : kBatchPlain;
-    const bool big = ctx->big_blocks_per_cu * trt::kBigBlock > ctx->rounds_blocks_per_cu * trt::kPersistentBlock;
-    return big ? -1 : kBatchPatches; // 1024-thread patch workgroups have no BATCH form
-}
-
-// workgroups of a BATCH form that fit one CU with `lds` bytes of dynamic LDS (0: it does not fit); asked once per size
-static hipError_t batch_occupancy(trt_context *ctx, int form, size_t lds, int *blocks)
-{
+    const RoundsVariant &k = kRounds[v];
+    if (!batch)
+    {
+        *blocks = k.image ? ctx->device_blocks_per_cu : k.rings ? ctx->compact_blocks_per_cu : k.block == trt::kBigBlock ? ctx->big_blocks_per_cu : ctx->rounds_blocks_per_cu;
+        return TRT_OK;
+    }
     for (const trt_context::BatchOccupancy &o : ctx->batch_occupancy)
-        if (o.variant == form && o.lds == lds)
+        if (o.kernel == (const void *)k.batch && o.lds == lds)
         {
             *blocks = o.blocks;
-            return hipSuccess;
+            return TRT_OK;
         }
     *blocks = 0;
     if (lds <= (size_t)ctx->lds_limit)
-    {
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, kBatchRounds[form].fn, kRounds[kBatchRounds[form].single].block, lds);
-        if (e != hipSuccess)
-            return e;
-    }
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, k.batch, k.block, lds));
     if (ctx->batch_occupancy.size() >= 64)
         ctx->batch_occupancy.clear();
-    ctx->batch_occupancy.push_back({form, lds, *blocks});
-    return hipSuccess;
+    ctx->batch_occupancy.push_back({(const void *)k.batch, lds, *blocks});
+    return TRT_OK;
 }
 
 struct RenderPlan
 {
     Variant variant;
+    bool batch; // the variant's BATCH form
     unsigned grid, block;
-    size_t lds;       // dynamic LDS bytes
-    unsigned ring_at; // kDecoupled*: FrameView::ring_at
+    size_t lds;        // dynamic LDS bytes
+    unsigned ring_at;  // kDecoupled*: FrameView::ring_at
+    unsigned queue_shift, chunk; // FrameView::queue_shift, chunk
+    int per_cu;        // workgroups per CU the grid was sized by, before it is made at least one (0: the launch's LDS does not fit)
 };
 
-// The launch of a frame of `units` samples: the production kernel's workgroups fill the context's CUs as far as the units need
-// them; every 256-thread variant is sized by the plain instantiation's occupancy.
-static RenderPlan plan_render(const trt_context *ctx, long units, int spp)
+// The launch of `frames` frames of `units` samples in all -- a single frame, or `batch`: the BATCH form of what they run: the
+// production kernel's workgroups fill the context's CUs as far as the units need them.
+static int plan_render(trt_context *ctx, long units, int spp, int frames, bool batch, RenderPlan *plan)
 {
-    const Variant v = choose_variant(ctx, units, spp);
+    const Variant v = choose_variant(ctx, units, spp, frames);
     if (v == kReference || v == kReferenceImage)
-        return RenderPlan{v, (unsigned)((units / spp + 255) / 256), 256u, v == kReference ? scene_lds_bytes(ctx->scene) : 0u, 0u};
-    const RoundsVariant &k = kRounds[v];
-    const int per_cu = k.image ? ctx->device_blocks_per_cu : k.rings ? ctx->compact_blocks_per_cu : k.block == trt::kBigBlock ? ctx->big_blocks_per_cu : ctx->rounds_blocks_per_cu;
-    const long cap = (long)(ctx->compute_units - (ctx->stream == ctx->own_stream ? ctx->reserved_cus : 0)) * std::max(per_cu, 1);
-    const long want = (units + k.block - 1) / k.block;
-    RenderPlan p{v, (unsigned)std::max(1L, std::min(want, cap)), (unsigned)k.block, k.image ? 0u : image_lds_bytes(ctx, spp), 0u};
-    if (k.rings)
     {
-        p.lds = compact_lds_bytes(ctx, spp);
-        p.ring_at = (unsigned)compact_ring_at(ctx, spp);
+        *plan = RenderPlan{v, false, (unsigned)((units / spp + 255) / 256), 256u, v == kReference ? scene_lds_bytes(ctx->scene) : 0u};
+        return TRT_OK;
     }
-    return p;
+    const RoundsVariant &k = kRounds[v];
+    RenderPlan p{v, batch, 0u, (unsigned)k.block, launch_lds_bytes(ctx, v, spp, frames), k.rings ? (unsigned)compact_ring_at(ctx, spp, frames) : 0u};
+    const int rc = blocks_per_cu(ctx, v, batch, p.lds, &p.per_cu);
+    if (rc)
+        return rc;
+    const long cap = (long)(ctx->compute_units - (ctx->stream == ctx->own_stream ? ctx->reserved_cus : 0)) * std::max(p.per_cu, 1);
+    const long want = (units + k.block - 1) / k.block;
+    p.grid = (unsigned)std::max(1L, std::min(want, cap));
+    // The queue (trt_common.hpp, kQueueStride): a word per XCD and chunks of half the size for scenes whose tables are small enough
+    // that a wave may change its place in the image twice as often (no patches), when every word has workgroups; otherwise one
+    // word.  Every wave owns its first chunk without asking.
+    const bool per_xcd = !has_patches(ctx) && p.grid >= (1u << trt::kQueueXcdShift);
+    p.queue_shift = per_xcd ? (unsigned)trt::kQueueXcdShift : 0u;
+    p.chunk = per_xcd ? trt::kQueueChunkSmall : trt::kQueueChunkSamples;
+    *plan = p;
+    return TRT_OK;
 }
 
 // workgroups of a variant that fit one CU at the LDS of a frame of 64 rays per pixel
 static hipError_t occupancy(const trt_context *ctx, Variant v, int *blocks)
 {
-    const RoundsVariant &k = kRounds[v];
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, k.fn, k.block, k.rings ? compact_lds_bytes(ctx, 64) : image_lds_bytes(ctx, 64));
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, kRounds[v].fn, kRounds[v].block, launch_lds_bytes(ctx, v, 64));
 }
 
 // The production kernel's occupancy depends on the scene and its tables only through the size of the LDS image: queried once
@@ -306,10 +302,12 @@ void allow_large_lds_render(const trt_context *ctx)
 {
     (void)hipFuncSetAttribute((const void *)trt::render_simple_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
     for (const RoundsVariant &k : kRounds)
+    {
         if (!k.image)
             (void)hipFuncSetAttribute((const void *)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
-    for (const BatchVariant &k : kBatchRounds)
-        (void)hipFuncSetAttribute((const void *)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
+        if (k.batch)
+            (void)hipFuncSetAttribute((const void *)k.batch, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
+    }
 }
 
 // The scene image of a frame in device memory, for render_rounds_kernel<.., DEVICE_IMAGE>: one workgroup, since fill_image has
@@ -359,62 +357,62 @@ extern "C" int trt_read_counters(trt_context *ctx, unsigned long long *path_rays
     return TRT_OK;
 }
 
-// `lane_set` 0: the context's stream, queue word 0, d_samples; 1: the alternate stream, its own queue word and scratch
-// (trt_render_host renders odd bands there).
-// `entry`: a frame is one entry of the context's launch history (events, trt_kernel_times); the frames of a batch that is served
-// one launch per camera are one entry together -- the first opens it (and clears the counters), the last closes it.
-enum : int { kEntryOpens = 1, kEntryCloses = 2, kEntryWhole = kEntryOpens | kEntryCloses };
-static int render_device_on(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
-                            void *d_pixels, size_t capacity_bytes, int lane_set, int entry = kEntryWhole);
+// ---- the launch of a frame, or of several cameras of one scene (on the host a single frame is a batch of one) ----
 
-extern "C" int trt_render_device(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,
-                                 int rays_per_pixel, void *d_pixels, size_t capacity_bytes)
+// what both device entries refuse, for `frames` cameras into one framebuffer of `frames` frames of the rowset
+static int check_render_arguments(const trt_context *ctx, const Camera *cameras, int frames, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                  const void *d_pixels, size_t capacity_bytes)
 {
-    return render_device_on(ctx, camera, rows, bounce_limit, rays_per_pixel, d_pixels, capacity_bytes, 0);
-}
-
-static int render_device_on(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
-                            void *d_pixels, size_t capacity_bytes, int lane_set, int entry)
-{
-    if (!ctx || !camera || !d_pixels)
+    if (!ctx || !cameras || !d_pixels)
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (frames < 1 || frames > TRT_BATCH_MAX)
+        return fail(TRT_ERR_ARGUMENT, "a batch has 1 to %d cameras, %d given", TRT_BATCH_MAX, frames);
     if (!rowset_valid(rows))
         return fail(TRT_ERR_ARGUMENT, "invalid rowset");
     if (bounce_limit < 1 || rays_per_pixel < 1) // bounce_limit 0 divides 0 by 0 in the reference (TRT.c:1061)
         return fail(TRT_ERR_ARGUMENT, "bounce_limit %d / rays_per_pixel %d", bounce_limit, rays_per_pixel);
+    for (int b = 1; b < frames; b++) // the jitter and the screen axes are the batch's (main() moves only camera.frame, TRT.c:1327-1336)
+        if (cameras[b].screen_width != cameras[0].screen_width || cameras[b].screen_height != cameras[0].screen_height ||
+            cameras[b].screen_distance != cameras[0].screen_distance)
+            return fail(TRT_ERR_ARGUMENT, "camera %d of the batch has another screen_width / screen_height / screen_distance than camera 0", b);
     if (!ctx->have_scene)
         return fail(TRT_ERR_NO_SCENE, "trt_set_scene has not been called");
     const int local_rows = trt_rowset_rows(rows);
-    const size_t need = (size_t)local_rows * rows->width * sizeof(Vector);
+    const size_t need = (size_t)local_rows * rows->width * sizeof(Vector) * frames;
     if (capacity_bytes < need)
-        return fail(TRT_ERR_CAPACITY, "framebuffer needs %zu B, %zu given", need, capacity_bytes);
-    if (local_rows == 0)
-        return TRT_OK;
+        return fail(TRT_ERR_CAPACITY, "framebuffer of %d frame(s) needs %zu B, %zu given", frames, need, capacity_bytes);
     if ((unsigned long long)local_rows * rows->width >= 0x7fffffffull)
         return fail(TRT_ERR_ARGUMENT, "%d x %d pixels exceed the 2^31 pixel index range", local_rows, rows->width);
-    HIP_TRY(hipSetDevice(ctx->device));
-    const hipStream_t stream = lane_set ? ctx->alt_stream : ctx->stream;
-    DeviceBuffer<double> &scratch = lane_set ? ctx->d_samples_alt : ctx->d_samples;
-    int rc = prepare_jitter(ctx, camera, rows->width, rows->height, rays_per_pixel);
-    if (rc)
-        return rc;
-    rc = prepare_axes(ctx, camera, rows->width, rows->height);
-    if (rc)
-        return rc;
+    const unsigned long long units = (unsigned long long)local_rows * rows->width * rays_per_pixel * frames; // samples: the production kernel's work units
+    if (ctx->kernel == 0 && units >= 0x7fffffffull)
+        return fail(TRT_ERR_ARGUMENT, "%llu work units in %d frame(s) exceed the 2^31 index range", units, frames);
+    return TRT_OK;
+}
 
+// min(ceil(2^32 / d), 2^32 - 1): x / d by multiply-high (trt_device.hpp, trt_rounds.hpp)
+static unsigned division_magic(unsigned long long d)
+{
+    return (unsigned)std::min<unsigned long long>((0x100000000ull + d - 1) / d, 0xffffffffull);
+}
+
+// The frame view of `camera` over `rows` on lane set `lane_set`, but for what belongs to the launch (launch_render): the scratch, the
+// image in device memory, the refraction indices, the rings' place and the queue's shape.
+static trt::FrameView frame_view(const trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_pixels,
+                                 int lane_set)
+{
     trt::FrameView f{};
     memcpy(f.cam, camera, sizeof(Camera));
     f.jitter = ctx->d_jitter.ptr;
     f.col_x = ctx->d_axes.ptr;
     f.row_y = ctx->d_axes.ptr + rows->width;
     f.inv_spp = 1.0 / rays_per_pixel;
-    f.width_magic = (unsigned)std::min<unsigned long long>((0x100000000ull + (unsigned)rows->width - 1) / (unsigned)rows->width, 0xffffffffull);
-    f.tile_magic = (unsigned)std::min<unsigned long long>((0x100000000ull + (unsigned)rows->tile_rows - 1) / (unsigned)rows->tile_rows, 0xffffffffull);
+    f.width_magic = division_magic((unsigned)rows->width);
+    f.spp_magic = division_magic((unsigned)rays_per_pixel);
+    f.tile_magic = division_magic((unsigned)rows->tile_rows);
     f.out = (double *)d_pixels;
     f.counters = ctx->counters_enabled ? ctx->d_counters.ptr : nullptr;
 #if defined(TRT_MARKS) && TRT_MARKS == 2
     f.counters = ctx->d_counters.ptr; // the ISA profile of the SHIPPING instantiations lands there
-    HIP_TRY(hipMemsetAsync(ctx->d_counters.ptr, 0, kCounterSlots * sizeof(unsigned long long), lane_set ? ctx->alt_stream : ctx->stream));
 #endif
     f.queue = ctx->d_queue.ptr + trt::kQueueLaneWords * lane_set;
     f.width = rows->width;
@@ -422,25 +420,37 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
     f.tile_rows = rows->tile_rows;
     f.tile_first = rows->tile_first;
     f.tile_step = rows->tile_step;
-    f.local_rows = local_rows;
+    f.local_rows = trt_rowset_rows(rows);
     f.bounce_limit = bounce_limit;
     f.spp = rays_per_pixel;
+    return f;
+}
 
-    rc = ensure_eye_tables(ctx, camera, stream); // no-op unless the eye moved (trt_render_host builds them before it forks its streams)
-    if (rc)
-        return rc;
-    const long pixels = (long)local_rows * rows->width;
-    const long units = pixels * rays_per_pixel; // samples
-    if (ctx->counters_enabled && (entry & kEntryOpens))
-        HIP_TRY(hipMemsetAsync(ctx->d_counters.ptr, 0, kCounterSlots * sizeof(unsigned long long), stream));
+// `lane_set` 0: the context's stream, queue word 0, d_samples; 1: the alternate stream, its own queue word and scratch
+// (trt_render_host renders odd bands there).
+// `entry`: a frame is one entry of the context's launch history (events, trt_kernel_times); the frames of a batch that is served
+// one launch per camera are one entry together -- the first opens it (and clears the counters), the last closes it -- and so are
+// the launches of a batch that was split for LDS.
+enum : int { kEntryOpens = 1, kEntryCloses = 2, kEntryWhole = kEntryOpens | kEntryCloses };
+
+// Carries out a planned launch: the queue started unless the launch before left it ready, the image staged for the DEVICE_IMAGE
+// instantiations, the render kernel over the frame `f` -- with `batch`, the plan's BATCH form over the frames of `batch`, of which
+// f is the first -- and the ordered mean of every frame's `pixels` pixels into `out`.
+static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameView f, const trt::GridView &grids, const trt::BatchView *batch, double *out,
+                         long pixels, int lane_set, int entry)
+{
+    const hipStream_t stream = lane_set ? ctx->alt_stream : ctx->stream;
     const int slot = (int)(ctx->launches % kEventRing);
-    const RenderPlan plan = plan_render(ctx, units, rays_per_pixel);
     const dim3 grid(plan.grid), block(plan.block);
+    const bool reference = plan.variant == kReference || plan.variant == kReferenceImage;
     unsigned *const ready = ctx->queue_ready[lane_set];
     if (plan.lds > (size_t)ctx->lds_limit) // LDS only (trt_set_scene_image(ctx, 0)), or the refraction extension, which has no device-image form
         return fail(TRT_ERR_CAPACITY, "%s and %d rays per pixel need %zu B of LDS staging, device offers %d%s", plan.variant == kReference ? "scene" : "scene image",
-                    rays_per_pixel, plan.lds, ctx->lds_limit, ctx->ior_count && plan.variant != kReference ? " (the refraction extension stages it in LDS only)" : "");
-    if (plan.variant == kReference || plan.variant == kReferenceImage)
+                    f.spp, plan.lds, ctx->lds_limit, ctx->ior_count && plan.variant != kReference ? " (the refraction extension stages it in LDS only)" : "");
+#if defined(TRT_MARKS) && TRT_MARKS == 2
+    HIP_TRY(hipMemsetAsync(ctx->d_counters.ptr, 0, kCounterSlots * sizeof(unsigned long long), stream));
+#endif
+    if (reference)
     {
         if (entry & kEntryOpens)
             HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
@@ -457,17 +467,19 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
     else
     {
         // production (kernel 0): persistent waves, synchronous rounds over SAMPLE units, then the ordered mean per pixel
-        if ((unsigned long long)units >= 0x7fffffffull)
-            return fail(TRT_ERR_ARGUMENT, "%ld work units exceed the 2^31 index range", units);
-        if (scratch.capacity < (size_t)units * 3)
+        const RoundsVariant &k = kRounds[plan.variant];
+        const unsigned frames = batch ? batch->frames : 1u;
+        // scratch [frame][k][pixel][3]; the launches of a split batch follow one another on the stream
+        DeviceBuffer<double> &scratch = lane_set ? ctx->d_samples_alt : ctx->d_samples;
+        const size_t samples = (size_t)pixels * f.spp * frames * 3;
+        if (scratch.capacity < samples)
             HIP_TRY(hipStreamSynchronize(stream)); // a frame in flight may still use the old scratch
-        HIP_TRY(scratch.reserve((size_t)units * 3));
+        HIP_TRY(scratch.reserve(samples));
         f.samples = scratch.ptr;
-        f.spp_magic = (unsigned)std::min<unsigned long long>((0x100000000ull + (unsigned)rays_per_pixel - 1) / (unsigned)rays_per_pixel, 0xffffffffull);
-        if (kRounds[plan.variant].image)
+        if (k.image)
         { // a buffer per lane set: trt_render_host renders bands on two streams at once
             DeviceBuffer<double> &image = lane_set ? ctx->d_image_alt : ctx->d_image;
-            const size_t doubles = image_lds_bytes(ctx, rays_per_pixel) / sizeof(double);
+            const size_t doubles = image_lds_bytes(ctx, f.spp) / sizeof(double);
             if (image.capacity < doubles)
                 HIP_TRY(hipStreamSynchronize(stream)); // a frame in flight may still read the old image
             HIP_TRY(image.reserve(doubles));
@@ -478,28 +490,32 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
         if (ctx->ior_count)
             f.ior = ctx->d_ior.ptr;
         f.ring_at = plan.ring_at;
-        // The queue (trt_common.hpp, kQueueStride): a word per XCD and chunks of half the size for scenes whose tables are small enough
-        // that a wave may change its place in the image twice as often (no patches), when every word has workgroups; otherwise one
-        // word.  Every wave owns its first chunk without asking.
-        const bool per_xcd = !(ctx->grids.path_enabled && ctx->grids.patch_m > 0) && plan.grid >= (1u << trt::kQueueXcdShift);
-        f.queue_shift = per_xcd ? (unsigned)trt::kQueueXcdShift : 0u;
-        f.chunk = per_xcd ? trt::kQueueChunkSmall : trt::kQueueChunkSamples;
+        f.queue_shift = plan.queue_shift;
+        f.chunk = plan.chunk;
         const bool left_ready = ready[0] == plan.grid && ready[1] == plan.block / 64 && ready[2] == f.queue_shift; // by the frame before
         ready[0] = 0; // the render kernel uses it up; ready again once this frame's launches have gone in
         if (!left_ready)
             hipLaunchKernelGGL(trt::start_queue_kernel, dim3(1), dim3(64), 0, stream, f.queue, plan.grid, plan.block / 64, f.queue_shift);
         if (entry & kEntryOpens)
             HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
-        if (kRounds[plan.variant].image)
-            hipLaunchKernelGGL(stage_image_kernel, dim3(1), dim3(kImageBlock), 0, stream, ctx->scene, ctx->cull, f, ctx->grids);
-        hipLaunchKernelGGL(kRounds[plan.variant].fn, grid, block, plan.lds, stream, ctx->scene, ctx->cull, f, ctx->grids);
+        if (k.image)
+            hipLaunchKernelGGL(stage_image_kernel, dim3(1), dim3(kImageBlock), 0, stream, ctx->scene, ctx->cull, f, grids);
+        if (batch)
+            hipLaunchKernelGGL(k.batch, grid, block, plan.lds, stream, ctx->scene, ctx->cull, f, grids, *batch);
+        else
+            hipLaunchKernelGGL(k.fn, grid, block, plan.lds, stream, ctx->scene, ctx->cull, f, grids);
         if (entry & kEntryCloses)
-            HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
+            HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream)); // of a split batch: the last launch's
 #if !TRT_AB_SKIP_REDUCE // diagnostic build (profiles/r03: what the ordered mean's streaming pass costs in the pipelined loop)
         { // TRT.c:1063-1065: the mean over each pixel's samples, in sample order; it starts the queue for the next frame of this shape
             const long values = pixels * 3;
-            hipLaunchKernelGGL(trt::reduce_samples_kernel, dim3((unsigned)((values + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK)), dim3(TRT_REDUCE_BLOCK), 0, stream,
-                               (const double *)scratch.ptr, (double *)d_pixels, values, rays_per_pixel, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
+            const unsigned blocks = (unsigned)((values + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK);
+            if (batch)
+                hipLaunchKernelGGL(trt::reduce_samples_batch_kernel, dim3(blocks, frames), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr, out, values, f.spp,
+                                   f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
+            else
+                hipLaunchKernelGGL(trt::reduce_samples_kernel, dim3(blocks), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr, out, values, f.spp,
+                                   f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
         }
 #endif
         if (entry & kEntryCloses)
@@ -507,14 +523,50 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
     }
     HIP_TRY(hipGetLastError());
 #if !TRT_AB_SKIP_REDUCE
-    if (plan.variant != kReference && plan.variant != kReferenceImage)
+    if (!reference) // what the ordered mean left the queue ready for
         ready[0] = plan.grid, ready[1] = plan.block / 64, ready[2] = f.queue_shift;
 #endif
     ctx->last_variant = plan.variant;
-    ctx->last_spp = rays_per_pixel;
+    ctx->last_spp = f.spp;
     if (entry & kEntryCloses)
         ctx->launches++;
     return TRT_OK;
+}
+
+static int render_device_on(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_pixels,
+                            size_t capacity_bytes, int lane_set, int entry = kEntryWhole)
+{
+    int rc = check_render_arguments(ctx, camera, 1, rows, bounce_limit, rays_per_pixel, d_pixels, capacity_bytes);
+    if (rc)
+        return rc;
+    const long pixels = (long)trt_rowset_rows(rows) * rows->width;
+    if (pixels == 0)
+        return TRT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const hipStream_t stream = lane_set ? ctx->alt_stream : ctx->stream;
+    rc = prepare_jitter(ctx, camera, rows->width, rows->height, rays_per_pixel);
+    if (rc)
+        return rc;
+    rc = prepare_axes(ctx, camera, rows->width, rows->height);
+    if (rc)
+        return rc;
+    rc = ensure_eye_tables(ctx, camera, stream); // no-op unless the eye moved (trt_render_host builds them before it forks its streams)
+    if (rc)
+        return rc;
+    if (ctx->counters_enabled && (entry & kEntryOpens))
+        HIP_TRY(hipMemsetAsync(ctx->d_counters.ptr, 0, kCounterSlots * sizeof(unsigned long long), stream));
+    RenderPlan plan;
+    rc = plan_render(ctx, pixels * rays_per_pixel, rays_per_pixel, 1, false, &plan);
+    if (rc)
+        return rc;
+    return launch_render(ctx, plan, frame_view(ctx, camera, rows, bounce_limit, rays_per_pixel, d_pixels, lane_set), ctx->grids, nullptr, (double *)d_pixels, pixels,
+                         lane_set, entry);
+}
+
+extern "C" int trt_render_device(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,
+                                 int rays_per_pixel, void *d_pixels, size_t capacity_bytes)
+{
+    return render_device_on(ctx, camera, rows, bounce_limit, rays_per_pixel, d_pixels, capacity_bytes, 0);
 }
 
 extern "C" int trt_quantize_device(trt_context *ctx, const void *d_pixels, size_t num_pixels, void *d_rgb8)
@@ -657,178 +709,89 @@ extern "C" int trt_render_host(trt_context *ctx, const Camera *camera, const trt
 
 // ---- several cameras per call ----
 
-// How many of the next `remaining` frames go into ONE launch, and which BATCH form runs them: the most whose larger image costs no
-// resident workgroup against the image of one frame (a batch of one always goes).
-static int fit_batch(trt_context *ctx, long units_per_frame, int spp, int remaining, int *form_out, int *blocks_per_cu)
+// How many of the next `remaining` frames go into ONE launch, and its plan: the most whose larger image costs no resident
+// workgroup against the image of one frame (a batch of one always goes).  Negative: an error.
+static int fit_batch(trt_context *ctx, long units_per_frame, int spp, int remaining, RenderPlan *plan)
 {
     for (int t = remaining;; t--)
     {
-        const int form = choose_batch_variant(ctx, units_per_frame * t, spp, t);
-        int here = 0, alone = 0;
-        HIP_TRY(batch_occupancy(ctx, form, batch_lds_bytes(ctx, form, spp, t), &here));
-        HIP_TRY(batch_occupancy(ctx, form, batch_lds_bytes(ctx, form, spp, 1), &alone));
-        if (t == 1 || (here > 0 && here >= alone))
-        {
-            *form_out = form;
-            *blocks_per_cu = std::max(here, 1);
+        int rc = plan_render(ctx, units_per_frame * t, spp, t, true, plan), alone = 0;
+        if (!rc)
+            rc = blocks_per_cu(ctx, plan->variant, true, launch_lds_bytes(ctx, plan->variant, spp), &alone);
+        if (rc)
+            return rc;
+        if (t == 1 || (plan->per_cu > 0 && plan->per_cu >= alone))
             return t;
-        }
     }
-}
-
-// One launch of a BATCH form over frames [first, first + m) of the batch, then their ordered means.  `f`: the frame view of the
-// batch (everything but the camera, the queue's shape and the rings' place); families[b]: frame b's eye families.
-static int launch_batch(trt_context *ctx, const Camera *cameras, const trt_rayfamily (*families)[2], int first, int m, int form, int blocks_per_cu,
-                        trt::FrameView f, long pixels, void *d_pixels, int slot)
-{
-    const hipStream_t stream = ctx->stream;
-    const RoundsVariant &k = kRounds[kBatchRounds[form].single];
-    const long units = pixels * f.spp; // of one frame
-    const long cap = (long)(ctx->compute_units - (ctx->stream == ctx->own_stream ? ctx->reserved_cus : 0)) * blocks_per_cu;
-    const unsigned grid = (unsigned)std::max(1L, std::min((units * m + k.block - 1) / k.block, cap));
-    const size_t lds = batch_lds_bytes(ctx, form, f.spp, m);
-    if (lds > (size_t)ctx->lds_limit)
-        return fail(TRT_ERR_CAPACITY, "scene image and %d rays per pixel need %zu B of LDS staging, device offers %d", f.spp, lds, ctx->lds_limit);
-    memcpy(f.cam, &cameras[first], sizeof(Camera));
-    f.ring_at = k.rings ? (unsigned)batch_ring_at(ctx, f.spp, m) : 0u;
-    const bool per_xcd = !(ctx->grids.path_enabled && ctx->grids.patch_m > 0) && grid >= (1u << trt::kQueueXcdShift);
-    f.queue_shift = per_xcd ? (unsigned)trt::kQueueXcdShift : 0u;
-    f.chunk = per_xcd ? trt::kQueueChunkSmall : trt::kQueueChunkSamples;
-    trt::GridView g = ctx->grids;
-    g.eye_at = (unsigned)((size_t)first * 2 * 6 * (size_t)g.g_eye * (size_t)g.g_eye); // frame b of the launch: eye slot first + b
-    g.eye[0] = families[first][0], g.eye[1] = families[first][1];
-    trt::BatchView batch{};
-    for (int b = 0; b < m; b++)
-    {
-        memcpy(batch.cam[b], &cameras[first + b], sizeof(Camera));
-        batch.eye[b][0] = families[first + b][0], batch.eye[b][1] = families[first + b][1];
-    }
-    batch.frames = (unsigned)m;
-    batch.units_per_frame = (unsigned)units;
-    batch.frame_magic = (unsigned)std::min<unsigned long long>((0x100000000ull + (unsigned long long)units - 1) / (unsigned long long)units, 0xffffffffull);
-    unsigned *const ready = ctx->queue_ready[0];
-    const bool left_ready = ready[0] == grid && ready[1] == (unsigned)k.block / 64 && ready[2] == f.queue_shift;
-    ready[0] = 0;
-    if (!left_ready)
-        hipLaunchKernelGGL(trt::start_queue_kernel, dim3(1), dim3(64), 0, stream, f.queue, grid, (unsigned)k.block / 64, f.queue_shift);
-    hipLaunchKernelGGL(kBatchRounds[form].fn, dim3(grid), dim3(k.block), lds, stream, ctx->scene, ctx->cull, f, g, batch);
-    HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream)); // the last launch's stays
-    const long values = pixels * 3;
-    hipLaunchKernelGGL(trt::reduce_samples_batch_kernel, dim3((unsigned)((values + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK), (unsigned)m), dim3(TRT_REDUCE_BLOCK), 0, stream,
-                       (const double *)f.samples, (double *)d_pixels + (size_t)first * values, values, f.spp, f.inv_spp, f.queue, grid, (unsigned)k.block / 64, f.queue_shift);
-    HIP_TRY(hipGetLastError());
-    ready[0] = grid, ready[1] = (unsigned)k.block / 64, ready[2] = f.queue_shift; // what the ordered mean left the queue ready for
-    ctx->last_variant = kBatchRounds[form].single;
-    ctx->last_spp = f.spp;
-    return TRT_OK;
 }
 
 extern "C" int trt_render_device_batch(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
                                        void *d_pixels, size_t capacity_bytes)
 {
-    if (!ctx || !cameras || !d_pixels)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (n < 1 || n > TRT_BATCH_MAX)
-        return fail(TRT_ERR_ARGUMENT, "a batch has 1 to %d cameras, %d given", TRT_BATCH_MAX, n);
-    if (!rowset_valid(rows))
-        return fail(TRT_ERR_ARGUMENT, "invalid rowset");
-    if (bounce_limit < 1 || rays_per_pixel < 1)
-        return fail(TRT_ERR_ARGUMENT, "bounce_limit %d / rays_per_pixel %d", bounce_limit, rays_per_pixel);
-    for (int b = 1; b < n; b++) // the jitter and the screen axes are the batch's (main() moves only camera.frame, TRT.c:1327-1336)
-        if (cameras[b].screen_width != cameras[0].screen_width || cameras[b].screen_height != cameras[0].screen_height ||
-            cameras[b].screen_distance != cameras[0].screen_distance)
-            return fail(TRT_ERR_ARGUMENT, "camera %d of the batch has another screen_width / screen_height / screen_distance than camera 0", b);
-    if (!ctx->have_scene)
-        return fail(TRT_ERR_NO_SCENE, "trt_set_scene has not been called");
-    const int local_rows = trt_rowset_rows(rows);
-    const size_t frame_bytes = (size_t)local_rows * rows->width * sizeof(Vector);
-    if (capacity_bytes < frame_bytes * n)
-        return fail(TRT_ERR_CAPACITY, "framebuffer of %d frames needs %zu B, %zu given", n, frame_bytes * n, capacity_bytes);
-    if ((unsigned long long)local_rows * rows->width >= 0x7fffffffull)
-        return fail(TRT_ERR_ARGUMENT, "%d x %d pixels exceed the 2^31 pixel index range", local_rows, rows->width);
-    const long pixels = (long)local_rows * rows->width, units = pixels * rays_per_pixel;
-    if (ctx->kernel == 0 && (unsigned long long)units * n >= 0x7fffffffull)
-        return fail(TRT_ERR_ARGUMENT, "%ld work units in %d frames exceed the 2^31 index range", units * n, n);
+    int rc = check_render_arguments(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_pixels, capacity_bytes);
+    if (rc)
+        return rc;
+    const long pixels = (long)trt_rowset_rows(rows) * rows->width, units = pixels * rays_per_pixel, values = pixels * 3;
     const bool shared = ctx->T.use_count() > 1;
     if (n > 1 && shared)
         return fail(TRT_ERR_CAPACITY, "this context's scene tables are shared with %ld other context(s) (trt_share_scene): their eye slots are the sharers', "
                                       "a batch of %d cameras has none to build its tables in (one camera per call works)", ctx->T.use_count() - 1, n);
     ctx->batch_frames = n;
     ctx->batch_launches = 0;
-    if (local_rows == 0)
+    if (pixels == 0)
         return TRT_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     const hipStream_t stream = ctx->stream;
     // everything without a BATCH form -- and a bounce limit that leaves no room for the frame beside the bounce count -- one launch per camera
-    const bool per_camera = shared || bounce_limit > trt::kBatchBounceMask || choose_batch_variant(ctx, units * n, rays_per_pixel, n) < 0;
-    if (per_camera)
+    if (shared || bounce_limit > trt::kBatchBounceMask || !batch_form(choose_variant(ctx, units * n, rays_per_pixel, n)))
     {
         for (int b = 0; b < n; b++)
         {
-            const int rc = render_device_on(ctx, &cameras[b], rows, bounce_limit, rays_per_pixel, (char *)d_pixels + (size_t)b * frame_bytes, frame_bytes, 0,
-                                            (b == 0 ? kEntryOpens : 0) | (b == n - 1 ? kEntryCloses : 0));
+            rc = render_device_on(ctx, &cameras[b], rows, bounce_limit, rays_per_pixel, (double *)d_pixels + (size_t)b * values, (size_t)values * sizeof(double), 0,
+                                  (b == 0 ? kEntryOpens : 0) | (b == n - 1 ? kEntryCloses : 0));
             if (rc)
                 return rc;
             ctx->batch_launches++;
         }
         return TRT_OK;
     }
-    int rc = prepare_jitter(ctx, &cameras[0], rows->width, rows->height, rays_per_pixel);
+    rc = prepare_jitter(ctx, &cameras[0], rows->width, rows->height, rays_per_pixel);
     if (rc)
         return rc;
     rc = prepare_axes(ctx, &cameras[0], rows->width, rows->height);
     if (rc)
         return rc;
-    trt_rayfamily families[TRT_BATCH_MAX][2];
-    rc = ensure_batch_eye_tables(ctx, cameras, n, stream, families);
-    if (rc)
-        return rc;
-    int form = 0, blocks_per_cu = 1;
-    int m = fit_batch(ctx, units, rays_per_pixel, n, &form, &blocks_per_cu);
-    if (m < 0)
-        return m;
-    // scratch [frame][k][pixel][3] of the largest launch (the first); the launches of a split batch follow one another on the stream
-    if (ctx->d_samples.capacity < (size_t)units * m * 3)
-        HIP_TRY(hipStreamSynchronize(stream)); // a frame in flight may still use the old scratch
-    HIP_TRY(ctx->d_samples.reserve((size_t)units * m * 3));
-
-    trt::FrameView f{};
-    f.jitter = ctx->d_jitter.ptr;
-    f.col_x = ctx->d_axes.ptr;
-    f.row_y = ctx->d_axes.ptr + rows->width;
-    f.inv_spp = 1.0 / rays_per_pixel;
-    f.width_magic = (unsigned)std::min<unsigned long long>((0x100000000ull + (unsigned)rows->width - 1) / (unsigned)rows->width, 0xffffffffull);
-    f.tile_magic = (unsigned)std::min<unsigned long long>((0x100000000ull + (unsigned)rows->tile_rows - 1) / (unsigned)rows->tile_rows, 0xffffffffull);
-    f.spp_magic = (unsigned)std::min<unsigned long long>((0x100000000ull + (unsigned)rays_per_pixel - 1) / (unsigned)rays_per_pixel, 0xffffffffull);
-    f.samples = ctx->d_samples.ptr;
-    f.out = (double *)d_pixels;
-    f.queue = ctx->d_queue.ptr;
-    f.width = rows->width;
-    f.height = rows->height;
-    f.tile_rows = rows->tile_rows;
-    f.tile_first = rows->tile_first;
-    f.tile_step = rows->tile_step;
-    f.local_rows = local_rows;
-    f.bounce_limit = bounce_limit;
-    f.spp = rays_per_pixel;
-
-    const int slot = (int)(ctx->launches % kEventRing);
-    HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
+    for (int b = 0; b < n; b++) // frame b's eye tables in eye slot b of the context's own tables
+    {
+        rc = ensure_eye_tables(ctx, &cameras[b], stream, b);
+        if (rc)
+            return rc;
+    }
+    RenderPlan plan;
+    int m = n;
     for (int first = 0; first < n; first += m)
     {
-        if (first)
+        m = fit_batch(ctx, units, rays_per_pixel, std::min(m, n - first), &plan);
+        if (m < 0)
+            return m;
+        trt::GridView g = ctx->grids; // frame b of the launch: eye slot first + b
+        g.eye_at = (unsigned)((size_t)first * 2 * 6 * (size_t)g.g_eye * (size_t)g.g_eye);
+        trt::BatchView batch{};
+        for (int b = 0; b < m; b++)
         {
-            m = fit_batch(ctx, units, rays_per_pixel, std::min(m, n - first), &form, &blocks_per_cu);
-            if (m < 0)
-                return m;
+            memcpy(batch.cam[b], &cameras[first + b], sizeof(Camera));
+            batch.eye[b][0] = ctx->eye_slots[first + b].families[0], batch.eye[b][1] = ctx->eye_slots[first + b].families[1];
         }
-        rc = launch_batch(ctx, cameras, families, first, m, form, blocks_per_cu, f, pixels, d_pixels, slot);
+        g.eye[0] = batch.eye[0][0], g.eye[1] = batch.eye[0][1];
+        batch.frames = (unsigned)m;
+        batch.units_per_frame = (unsigned)units;
+        batch.frame_magic = division_magic((unsigned long long)units);
+        rc = launch_render(ctx, plan, frame_view(ctx, &cameras[first], rows, bounce_limit, rays_per_pixel, d_pixels, 0), g, &batch,
+                           (double *)d_pixels + (size_t)first * values, pixels, 0, (first == 0 ? kEntryOpens : 0) | (first + m == n ? kEntryCloses : 0));
         if (rc)
             return rc;
         ctx->batch_launches++;
     }
-    HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
-    ctx->launches++;
     return TRT_OK;
 }
 
@@ -977,14 +940,10 @@ extern "C" int trt_kernel_info(trt_context *ctx, int *vgprs, int *sgprs, int *st
             HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, trt::render_simple_kernel<false>, 256, ctx->have_scene ? scene_lds_bytes(ctx->scene) : 0));
         else if (v == kReferenceImage)
             HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, trt::render_simple_kernel<true>, 256, 0));
-        else if (kRounds[v].image)
-            blocks = ctx->device_blocks_per_cu;
-        else if (kRounds[v].rings)
-            blocks = ctx->compact_blocks_per_cu;
-        else if (kRounds[v].block == trt::kBigBlock)
-            blocks = ctx->big_blocks_per_cu;
+        else if (!ctx->have_scene) // nothing stored yet: the plain instantiation without an image
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kRounds[kPlain].fn, trt::kPersistentBlock, 0));
         else
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kRounds[kPlain].fn, trt::kPersistentBlock, ctx->have_scene ? image_lds_bytes(ctx, 64) : 0));
+            (void)blocks_per_cu(ctx, v, false, 0, &blocks);
         *max_blocks_per_cu = blocks;
     }
     if (compute_units)

@@ -459,53 +459,28 @@ static int build_eye_slot(trt_context *ctx, const trt_rayfamily *families, int s
     return TRT_OK;
 }
 
-// The n cameras of a batch (trt_render_device_batch; the context's tables are its own): frame b's tables in slot b, rebuilt where
-// the slot's cached eye differs.  Slot eye_slot is the single frames': it goes through ensure_eye_tables, whose cache so stays true.
-int ensure_batch_eye_tables(trt_context *ctx, const Camera *cameras, int n, hipStream_t stream, trt_rayfamily (*families)[2])
-{
-    memset(families, 0, (size_t)n * sizeof *families);
-    if (!ctx->grids.path_enabled)
-        return TRT_OK;
-    for (int b = 0; b < n; b++)
-    {
-        if (b == ctx->eye_slot)
-        {
-            const int rc = ensure_eye_tables(ctx, &cameras[b], stream);
-            if (rc)
-                return rc;
-            families[b][0] = ctx->grids.eye[0], families[b][1] = ctx->grids.eye[1];
-            continue;
-        }
-        const double eye[3] = {cameras[b].frame.origin.x, cameras[b].frame.origin.y, cameras[b].frame.origin.z};
-        trt_eye_families(eye, ctx->T->ground_built, &ctx->T->cull_scene, families[b]);
-        if ((ctx->batch_eye_valid >> b & 1u) && !memcmp(eye, ctx->batch_eye[b], sizeof eye))
-            continue;
-        ctx->batch_eye_valid &= ~(1u << b);
-        const int rc = build_eye_slot(ctx, families[b], b, stream);
-        if (rc)
-            return rc;
-        memcpy(ctx->batch_eye[b], eye, sizeof eye);
-        ctx->batch_eye_valid |= 1u << b;
-    }
-    return TRT_OK;
-}
-
-// The two families of the eye (trt_raygrid.h): rebuilt on `stream` whenever the eye (or the scene) changed since they were built.
-int ensure_eye_tables(trt_context *ctx, const Camera *camera, hipStream_t stream)
+// The two families of the eye (trt_raygrid.h) and their tables in eye slot `slot`: rebuilt on `stream` whenever the eye (or the scene)
+// changed since this context built them there.  The families of the context's own slot are also grids.eye, beside grids.eye_at.
+int ensure_eye_tables(trt_context *ctx, const Camera *camera, hipStream_t stream, int slot)
 {
     trt::GridView &g = ctx->grids;
     if (!g.path_enabled)
         return TRT_OK;
+    if (slot < 0)
+        slot = ctx->eye_slot;
+    trt_context::EyeSlot &built = ctx->eye_slots[slot];
     const double eye[3] = {camera->frame.origin.x, camera->frame.origin.y, camera->frame.origin.z};
-    if (ctx->eye_tables_valid && !memcmp(eye, ctx->eye_built, sizeof eye))
+    if (built.valid && !memcmp(eye, built.eye, sizeof eye))
         return TRT_OK;
-    trt_eye_families(eye, ctx->T->ground_built, &ctx->T->cull_scene, g.eye);
-    ctx->eye_tables_valid = false;
-    const int rc = build_eye_slot(ctx, g.eye, ctx->eye_slot, stream); // g.eye_at is this slot's place
+    built.valid = false;
+    trt_eye_families(eye, ctx->T->ground_built, &ctx->T->cull_scene, built.families);
+    if (slot == ctx->eye_slot)
+        g.eye[0] = built.families[0], g.eye[1] = built.families[1];
+    const int rc = build_eye_slot(ctx, built.families, slot, stream);
     if (rc)
         return rc;
-    memcpy(ctx->eye_built, eye, sizeof eye);
-    ctx->eye_tables_valid = true;
+    memcpy(built.eye, eye, sizeof eye);
+    built.valid = true;
     return TRT_OK;
 }
 
