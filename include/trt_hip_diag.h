@@ -8,7 +8,7 @@
  *   self-tests    device division / square root / normalisation / cube instructions / skybox estimate against their references
  *   probes        single rays through the reference-order kernel and through the production kernel's stages
  *   scene image   where the kernels read the scene from: LDS or device memory
- *   test hooks    the pool cap of the long candidate lists; a stand-in for RCCL so that several ranks can share one GPU
+ *   test hooks    the pool cap of the long candidate lists; a NaN fill of a launch's scratch and output; a stand-in for RCCL so that several ranks can share one GPU
  */
 #ifndef TRT_HIP_DIAG_H
 #define TRT_HIP_DIAG_H
@@ -127,6 +127,15 @@ int trt_set_scene_image(trt_context *ctx, int mode);
 /* The scene image of the kernel trt_render_variant describes: in_device_memory 1 when it reads the image from device memory,
  * image_bytes its size (the production kernel's image for that launch's rays per pixel, or the reference-order kernel's records). */
 int trt_render_image(trt_context *ctx, int *in_device_memory, unsigned long long *image_bytes);
+
+/* TEST HOOK: make stale data visible.  Nothing clears the per-context sample scratch the production kernel writes (and the ordered
+ * mean reads) or the framebuffer between launches: a render that drops a work unit finds the sample an earlier render of the same
+ * frame left there, and the frame still comes out right.  on = 1: every launch first fills exactly its own sample range of the
+ * scratch (pixels * rays per pixel * frames * 3 doubles) and exactly its own output range (pixels * frames * 3 doubles) with 0xFF
+ * bytes -- a NaN in every double -- on the launch's stream; the reference-order kernel, which has no scratch, its output range.
+ * A unit or a pixel that is not written then shows as NaN.  on = 0 (the default): a launch issues exactly what it issued before
+ * there was this switch. */
+int trt_set_scratch_fill(trt_context *ctx, int on);
 
 /* TEST HOOK: allow (1) or forbid (0, the default) the environment variable TRT_RCCL_LIB to name the library that trt_dist_* binds in
  * RCCL's place (tests/rccl_stub.cpp: send / recv through shared memory, so that several ranks can share the one GPU of a test

@@ -225,6 +225,7 @@ struct trt_context
     // the ordered-mean pass of a frame starts the queue for the next one, which then needs no kernel of its own in front of it
     unsigned queue_ready[2][3] = {{0, 0, 0}, {0, 0, 0}};
     int compaction = -1;           // trt_set_compaction: -1 when it costs no occupancy, 0 never, 1 whenever the rings fit
+    bool scratch_fill = false;     // trt_set_scratch_fill: a launch first fills its sample range and its output range with NaNs (tests)
     size_t occupancy_for_lds = (size_t)-1;
     Event ev_chunk[16]; // hand-over of framebuffer chunks to the host copy threads (trt_render_host)
     Event ev_band[8];   // a band of rows is rendered: its copy-out may start (trt_render_host)

@@ -329,6 +329,14 @@ extern "C" int trt_enable_counters(trt_context *ctx, int enable)
     return TRT_OK;
 }
 
+extern "C" int trt_set_scratch_fill(trt_context *ctx, int on)
+{
+    if (!ctx)
+        return fail(TRT_ERR_ARGUMENT, "ctx is NULL");
+    ctx->scratch_fill = on != 0;
+    return TRT_OK;
+}
+
 extern "C" int trt_read_counters(trt_context *ctx, unsigned long long *path_rays, unsigned long long *shadow_rays)
 {
     if (!ctx)
@@ -452,6 +460,8 @@ static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameVie
 #endif
     if (reference)
     {
+        if (ctx->scratch_fill) // trt_set_scratch_fill: the reference-order kernel has no scratch
+            HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)pixels * 3 * sizeof(double), stream));
         if (entry & kEntryOpens)
             HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
         if (plan.variant == kReference)
@@ -492,6 +502,11 @@ static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameVie
         f.ring_at = plan.ring_at;
         f.queue_shift = plan.queue_shift;
         f.chunk = plan.chunk;
+        if (ctx->scratch_fill)
+        { // trt_set_scratch_fill: exactly the launch's samples and exactly its pixels read as NaN until the launch writes them
+            HIP_TRY(hipMemsetAsync(scratch.ptr, 0xFF, samples * sizeof(double), stream));
+            HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)pixels * frames * 3 * sizeof(double), stream));
+        }
         const bool left_ready = ready[0] == plan.grid && ready[1] == plan.block / 64 && ready[2] == f.queue_shift; // by the frame before
         ready[0] = 0; // the render kernel uses it up; ready again once this frame's launches have gone in
         if (!left_ready)

@@ -89,6 +89,7 @@ SYMBOLS = {
     "trt_render_variant": (_I, [_VP, C.POINTER(_I), C.POINTER(_I)]),
     "trt_set_scene_image": (_I, [_VP, _I]),
     "trt_render_image": (_I, [_VP, C.POINTER(_I), C.POINTER(C.c_ulonglong)]),
+    "trt_set_scratch_fill": (_I, [_VP, _I]),
     "trt_read_path_tables": (C.c_long, [_VP, C.POINTER(L.Camera), _VP, C.c_size_t, _VP, C.c_size_t, C.POINTER(C.c_long)]),
     "trt_read_sweep_fallbacks": (_I, [_VP, C.POINTER(C.c_ulonglong)]),
     "trt_read_shading_passes": (_I, [_VP, C.POINTER(C.c_ulonglong)]),
@@ -286,6 +287,11 @@ class Context:
         d, b = _I(), C.c_ulonglong()
         _check(lib().trt_render_image(self._h, C.byref(d), C.byref(b)))
         return {"in_device_memory": bool(d.value), "image_bytes": b.value}
+
+    def set_scratch_fill(self, on=True):
+        """tests: every launch first fills its own range of the sample scratch and its own output range with NaNs, so that a
+        work unit or a pixel it does not write shows (trt_set_scratch_fill)"""
+        _check(lib().trt_set_scratch_fill(self._h, 1 if on else 0))
 
     def read_path_tables(self, camera_array):
         """(info dict, list cells uint64[], pool uint64[]) of the path rays' tables as built for this camera's eye"""
