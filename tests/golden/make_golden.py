@@ -54,9 +54,10 @@ def _oracle():
 class RefLib:
     """One compiled variant of the reference (bounce limit / rays per pixel / emitter size are macros there)."""
     _cache = {}
+    STEM = "libtrtref"  # oracle/Makefile: the reference's own -O3 build
 
     def __init__(self, b, s, w=480, h=280):
-        path = os.path.join(REFDIR, f"libtrtref_b{b}_s{s}_w{w}_h{h}.so")
+        path = os.path.join(REFDIR, f"{self.STEM}_b{b}_s{s}_w{w}_h{h}.so")
         self.lib = C.CDLL(path)
         self.b, self.s, self.w, self.h = b, s, w, h
         lib = self.lib

@@ -1,4 +1,5 @@
-"""Shared test plumbing: the oracle binding (checker only), golden loaders, hashes."""
+"""Shared test plumbing: the oracle binding (checker only), golden loaders, hashes, and the builders of the adversarial scenes
+(nothing here needs a device)."""
 import ctypes as C
 import functools
 import json
@@ -8,6 +9,7 @@ import zlib
 
 import numpy as np
 
+from terminalraytracer_amd import hip
 from terminalraytracer_amd import layout as L
 from terminalraytracer_amd import scenes as S
 
@@ -219,3 +221,234 @@ def fuzz_scene(rng, w, h):
     if rng.random() < 0.3:
         cam[9:12] = rng.normal(size=3) * 20
     return S.SceneData(sph, ground, dl.reshape(-1, 6), pl.reshape(-1, 7), cam, sky("synth"))
+
+
+# ---- the adversarial scene families: built here so that the GPU tests and tests/golden/make_golden_edges.py share them ----
+
+def degenerate_scenes():
+    base = S.synth_scene(24, sky("synth"), bench_camera(40, 24, 2.5), seed=3)
+
+    def with_ground(point=None, normal=None, refl=None):
+        g = base.ground.copy()
+        if point is not None:
+            g[0:3] = point
+        if normal is not None:
+            g[3:6] = normal
+        if refl is not None:
+            g[9] = g[14] = refl
+        return S.SceneData(base.spheres, g, base.dir_lights, base.point_lights, base.camera, base.sky)
+
+    out = [("ground without a normal", with_ground(normal=[0.0, 0.0, 0.0])),
+           ("ground with a vanishing normal", with_ground(normal=[0.0, 1e-200, 0.0])),
+           ("ground with a huge normal", with_ground(normal=[0.0, 1e150, 1e150], refl=1.0)),
+           ("vertical mirror ground through the scene", with_ground(point=[0.3, 0.0, 0.0], normal=[1.0, 0.0, 0.0], refl=1.0))]
+    cam = base.camera.copy()
+    cam[10] = -2.0  # the eye exactly on the ground plane
+    out.append(("eye on the ground plane", base.with_camera(cam)))
+    cam = base.camera.copy()
+    cam[9:12] = base.spheres[5, :3]  # the eye at a sphere's centre
+    out.append(("eye at a sphere's centre", base.with_camera(cam)))
+    sph = base.spheres.copy()
+    sph[0, 3] = -0.4   # a negative radius (r*r is what the reference uses)
+    sph[1, 3] = 0.0
+    sph[2, :3] = [1e7, -3e6, 2e6]  # one sphere very far away: the tables' range explodes
+    sph[3, :3] = sph[4, :3]        # concentric twins with equal radii: exact ties
+    sph[3, 3] = sph[4, 3]
+    out.append(("odd radii, a far sphere, exact twins", base.with_spheres(sph)))
+    far = base.spheres.copy()
+    far[:, :3] = far[:, :3] * 1e5  # an enormous scene: hit points lose digits against the 1e-6 nudge
+    far[:, 3] *= 1e5
+    gf = base.ground.copy()
+    gf[1] *= 1e5
+    cf = base.camera.copy()
+    cf[9:12] *= 1e5
+    out.append(("a scene 1e5 times larger", S.SceneData(far, gf, base.dir_lights, base.point_lights * np.array([1e5, 1e5, 1e5, 1, 1, 1, 1e10]), cf, base.sky)))
+    pl = base.point_lights.copy()
+    pl[0, :3] = base.camera[9:12]  # a light at the eye
+    out.append(("a light at the eye", S.SceneData(base.spheres, base.ground, base.dir_lights, pl, base.camera, base.sky)))
+    return out
+
+
+def blocker_scene(w=96, h=54):
+    """Ten point lights on, and within micrometres of, the surface of the demo sphere at (0,-1,0)."""
+    base = S.demo_scene(sky("synth"), bench_camera(w, h))
+    centre, radius = base.spheres[4, :3], base.spheres[4, 3]  # the sphere at (0,-1,0), just above the ground
+    lights = []
+    for k, eps in enumerate([0.0, 1e-6, -1e-6, 2e-6, -2e-6, 1.0000001e-6, 0.5e-6, -0.5e-6, 1e-5, -1e-5]):
+        n = np.array([np.cos(0.7 * k), -0.8, np.sin(0.7 * k)])
+        n /= np.linalg.norm(n)
+        lights.append(list(centre + n * (radius + eps)) + [1.0, 0.9, 0.8, 3.0])
+    return S.SceneData(base.spheres, base.ground, base.dir_lights, np.array(lights), base.camera, base.sky)
+
+
+VALUE_SIZE = (48, 27)
+VALUE_SHOTS = ((8, 3), (1, 1))  # (bounce limit, rays per pixel) of every value-domain scene
+VALUE_DEEP = (12, 10)           # ... and of those whose reflectivities decide how long a path lives
+# the scenes named for non-finite inputs: their frames must hold NaNs, from this bounce limit on.  A reflectivity is multiplied into
+# the path's weight after the bounce's colour is taken (TRT.c:1035-1041), so at a bounce limit of 1 it cannot reach the frame.
+NON_FINITE_VALUES = {"inf and NaN reflectivity": 2, "huge reflectivity": 2, "sphere colours out of range": 1}
+
+
+def must_hold_nans(case_name, bounce_limit):
+    parts = case_name.split("/")
+    return parts[0] == "values" and bounce_limit >= NON_FINITE_VALUES.get(parts[1], 1 << 30)
+
+
+def value_scenes():
+    """[(name, scene, deep)]: material, light and camera values outside the domain every other scene stays in -- reflectivities at the
+    END-round threshold, above one, negative, infinite, NaN and huge; light and sphere colours that are negative, huge, infinite or NaN;
+    intensities that are negative, zero, huge, denormal-small or infinite; eyes so far out that the checker's (int) conversion overflows
+    (2^31) or floor() is the identity (2^53).  `deep`: also rendered at VALUE_DEEP."""
+    w, h = VALUE_SIZE
+    base = S.synth_scene(24, sky("synth"), bench_camera(w, h, 2.5), seed=3)
+    inf, nan = np.inf, np.nan
+
+    def variant(refl=None, grefl=None, dcol=None, pcol=None, scol=None, eye=None, point_lights=None, ground_y=None):
+        sph, g, dl = base.spheres.copy(), base.ground.copy(), base.dir_lights.copy()
+        pl, cam = (base.point_lights if point_lights is None else point_lights).copy(), base.camera.copy()
+        if refl is not None:
+            sph[:, 7] = np.resize(refl, len(sph))
+        if scol is not None:
+            sph[:, 4:7] = np.resize(scol, (len(sph), 3))
+        if grefl is not None:
+            g[9], g[14] = grefl  # even, odd
+        if dcol is not None:
+            dl[:, 3:6] = np.resize(dcol, (len(dl), 3))
+        if pcol is not None:
+            pl[:, 3:6] = np.resize(pcol, (len(pl), 3))
+        if eye is not None:
+            cam[9:12] = eye
+        if ground_y is not None:
+            g[1] = ground_y
+        return S.SceneData(sph, g, dl, pl, cam, base.sky)
+
+    threshold = [1e-5, np.nextafter(1e-5, 1), np.nextafter(1e-5, 0), 0.003, 0.0032, 0.01, 0.05, 0.1, 1e-3, 0.99999]
+    # five point lights, one intensity each; the last lies on the ground plane straight under the eye, so that the nudged ground hits
+    # around it are a micrometre from it and its shadow rays run along the plane
+    eye = base.camera[9:12]
+    five = np.array([[0.0, 0.0, 0.0, 1.0, 1.0, 1.0, 0.0], [2.0, 3.0, -1.5, 0.9, 0.7, 0.3, 0.0], [-3.0, 0.5, 2.0, 0.2, 0.8, 0.9, 0.0],
+                     [1.5, 1.0, 2.5, 0.6, 0.6, 0.9, 0.0], [eye[0], base.ground[1], eye[2], 1.0, 0.9, 0.8, 0.0]])
+    five[:, 6] = np.resize([-1.0, 0.0, 1e308, 1e-300, inf], 5)
+    return [("threshold reflectivities", variant(refl=threshold, grefl=(0.0031, 0.0033)), True),
+            ("reflectivity above one", variant(refl=[1.5, 3.0, 1.0, 10.0], grefl=(2.0, 1.0)), False),
+            ("negative reflectivity", variant(refl=[-0.5, 0.5, -1.0, 1.0], grefl=(-0.2, 0.2)), False),
+            ("inf and NaN reflectivity", variant(refl=[inf, 0.5, nan, 1.0, -inf], grefl=(0.2, nan)), True),
+            ("huge reflectivity", variant(refl=[1e200, 1e-200, 1e308], grefl=(1e160, 1e-160)), True),
+            ("light colours out of range", variant(dcol=[-0.5, 2.0, 1e300], pcol=[5.0, -1e300, 0.5]), False),
+            ("point-light intensities", variant(point_lights=five), False),
+            ("sphere colours out of range", variant(scol=[[-1.0, 2.0, 1e300], [0.5, inf, -inf], [nan, 0.0, -0.0]]), False),
+            ("checker beyond 2^31", variant(eye=[3e9, 5.0, -7e9]), False),
+            ("checker beyond 2^53", variant(eye=[3e15, 5e3, -7e15]), False),
+            # A ray's direction is the screen point minus the eye (TRT.c:1005): from the far eyes above every ray heads for the origin and
+            # meets the checker, if at all, below -2^31, where x86-64's conversion and a saturating one agree (0x80000000).  Under a
+            # ground 3e9 below the scene, rays of every direction come down on both sides of +-2^31: above +2^31 the reference's tile is
+            # even (0x80000000) where a saturating conversion makes it odd (0x7fffffff).
+            ("checker beyond 2^31 on a ground 3e9 below", variant(ground_y=-3e9), False),
+            ("eye 1e6 above the ground", variant(eye=[0.5, 1e6, 0.25]), False)]
+
+
+def non_finite_light_scene():
+    """The value-domain base scene with a dim second directional light whose direction has a NaN component (normalize_vector leaves it
+    alone) and a second point light infinitely far away (strength 0, direction inf/inf).  A light direction that is not a number is the
+    only NaN operand fmin(n.l, 1.0) of TRT.c:911/945 can get; it answers 1.0, where a plain `1 < x ? 1 : x` would pass the NaN on.
+    The reference itself is not defined here: such a shadow ray hits nothing, and its sky look-up then indexes CUBEMAP_AXES[-1]
+    (TRT.c:703-717; the compiled reference ends in a segmentation fault on this scene).  So there is no recorded frame: the oracle,
+    whose shadow rays look nothing up, is the judge, and fmin's answer is the C standard's."""
+    w, h = VALUE_SIZE
+    base = S.synth_scene(24, sky("synth"), bench_camera(w, h, 2.5), seed=3)
+    dl = np.concatenate([base.dir_lights, [[np.nan, -1.0, -1.0, 0.3, 0.2, 0.1]]])
+    pl = np.concatenate([base.point_lights, [[np.inf, 3.0, 0.0, 0.9, 0.7, 0.3, 10.0]]])
+    return S.SceneData(base.spheres, base.ground, dl, pl, base.camera, base.sky)
+
+
+def fuzz_case(seed):
+    """(scene, w, h, bounce limit, rays per pixel) of fuzz seed `seed`, with the draws test_fuzzed_scenes_match_the_oracle makes"""
+    rng = np.random.default_rng(1000 + seed)
+    w, h = int(rng.integers(8, 72)), int(rng.integers(4, 40))
+    b, spp = int(rng.integers(1, 9)), int(rng.choice([1, 3, 10]))
+    return fuzz_scene(rng, w, h), w, h, b, spp
+
+
+def edge_case_inputs():
+    """Every case of tests/golden/golden_edges.json as its builder makes it: [(name, family, scene key, scene, w, h, b, spp)].  The
+    frames of one scene at several (b, spp) share the scene key, under which edges.npz holds the scene's arrays once."""
+    out = []
+    for name, scene in degenerate_scenes():
+        out.append((f"degenerate/{name}", "degenerate", f"degenerate/{name}", scene, 40, 24, 6, 3))
+    for seed in range(12):
+        scene, w, h, b, spp = fuzz_case(seed)
+        out.append((f"fuzz/{seed}", "fuzz", f"fuzz/{seed}", scene, w, h, b, spp))
+    out.append(("blocker/lights at blocker distance", "blocker", "blocker/lights at blocker distance", blocker_scene(), 96, 54, 4, 10))
+    for name, scene, deep in value_scenes():
+        for b, spp in VALUE_SHOTS + ((VALUE_DEEP,) if deep else ()):
+            out.append((f"values/{name}/b{b}_s{spp}", "values", f"values/{name}", scene, *VALUE_SIZE, b, spp))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def edge_meta():
+    with open(os.path.join(GOLDEN, "golden_edges.json")) as fh:
+        return json.load(fh)
+
+
+@functools.lru_cache(maxsize=None)
+def _edges():
+    return dict(np.load(os.path.join(GOLDEN, "edges.npz")))
+
+
+def edge_cases():
+    return edge_meta()["cases"]
+
+
+def edge_scene(case):
+    """the scene the reference rendered, from the record kept with its frame"""
+    return unpack_scene(_edges()[case["scene"]], case["spheres"], case["dir_lights"], case["point_lights"])
+
+
+def pack_scene(scene):
+    """one float64 record per scene (an archive member costs more than a small scene's arrays do): spheres, ground, lights, camera"""
+    return np.concatenate([scene.spheres.ravel(), scene.ground, scene.dir_lights.ravel(), scene.point_lights.ravel(), scene.camera])
+
+
+def unpack_scene(flat, spheres, dir_lights, point_lights):
+    cuts = np.cumsum([9 * spheres, 16, 6 * dir_lights, 7 * point_lights, 15])
+    assert flat.size == cuts[-1]
+    sph, ground, dl, pl, cam = np.split(flat, cuts[:-1])
+    return S.SceneData(sph, ground, dl, pl, cam, sky("synth"))
+
+
+def edge_fb(case):
+    """the reference's double framebuffer [h, w, 3] (read-only), or None where only its hash is recorded"""
+    if case["fb"] is None:
+        return None
+    fb = _edges()[case["fb"]]  # frames that are equal bit for bit are held once
+    fb.flags.writeable = False
+    return fb
+
+
+def canonical_nans(pixels):
+    """a copy with every NaN replaced by one quiet NaN: x86-64 and the GPU make different default NaNs, hashes are taken of this"""
+    out = np.array(pixels, dtype=np.float64)
+    out[np.isnan(out)] = np.float64("nan")
+    return out
+
+
+# ---- the render kernels the GPU parity tests go through ----
+# the production kernel as it ships (the shading decoupled from the owning lane for scenes of three lights or more,
+# trt_set_compaction(-1)), the same with the decoupling forced on, and the reference-order kernel -- an independent HIP
+# implementation of the path
+COMPACT = "production_rounds_compact"
+PLAIN = "production_rounds_plain"  # the decoupling forced off (what ships for scenes of one or two lights)
+KERNELS = [hip.Context.PRODUCTION, COMPACT, hip.Context.REFERENCE_ORDER]
+KERNEL_IDS = ["production_rounds", COMPACT, "reference_order"]
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint64)
+
+
+def render(ctx, scene, w, h, b, s, kernel=hip.Context.PRODUCTION, rows=None):
+    ctx.set_kernel(hip.Context.PRODUCTION if kernel in (COMPACT, PLAIN) else kernel)
+    ctx.set_compaction({COMPACT: 1, PLAIN: 0}.get(kernel, -1))
+    ctx.set_scene(scene)
+    return ctx.render_host(scene.camera, rows or hip.RowSet.whole(w, h), b, s)

@@ -16,13 +16,8 @@ pytestmark = pytest.mark.gpu
 
 SMALL = T.golden_cases(("small", "medium"))
 LARGE = T.golden_cases(("large",))
-# the production kernel as it ships (the shading decoupled from the owning lane for scenes of three lights or more,
-# trt_set_compaction(-1)), the same with the decoupling forced on, and the reference-order kernel -- an independent HIP
-# implementation of the path
-COMPACT = "production_rounds_compact"
-PLAIN = "production_rounds_plain"  # the decoupling forced off (what ships for scenes of one or two lights)
-KERNELS = [hip.Context.PRODUCTION, COMPACT, hip.Context.REFERENCE_ORDER]
-KERNEL_IDS = ["production_rounds", COMPACT, "reference_order"]
+# the render kernels and the way a frame is rendered through them are shared with test_edge_goldens.py (tests/support.py)
+from support import COMPACT, KERNEL_IDS, KERNELS, PLAIN, bits, render  # noqa: E402,F401
 
 
 @pytest.fixture(scope="module")
@@ -31,17 +26,6 @@ def ctx():
     c.set_path_grids_min_spheres(0)  # by default scenes of fewer than 12 spheres sweep: here the small goldens use the tables too
     yield c
     c.close()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def render(ctx, scene, w, h, b, s, kernel=hip.Context.PRODUCTION, rows=None):
-    ctx.set_kernel(hip.Context.PRODUCTION if kernel in (COMPACT, PLAIN) else kernel)
-    ctx.set_compaction({COMPACT: 1, PLAIN: 0}.get(kernel, -1))
-    ctx.set_scene(scene)
-    return ctx.render_host(scene.camera, rows or hip.RowSet.whole(w, h), b, s)
 
 
 def test_device_division_and_sqrt_are_correctly_rounded(ctx):
@@ -683,14 +667,7 @@ def test_point_light_at_blocker_distance_forces_the_exact_branch(ctx):
     surface put whole regions of the image inside and just outside that band (both sides), the blocker being the very
     sphere the light touches; every kernel must still equal the oracle bit for bit."""
     w, h = 96, 54
-    base = S.demo_scene(T.sky("synth"), T.bench_camera(w, h))
-    centre, radius = base.spheres[4, :3], base.spheres[4, 3]  # the sphere at (0,-1,0), just above the ground
-    lights = []
-    for k, eps in enumerate([0.0, 1e-6, -1e-6, 2e-6, -2e-6, 1.0000001e-6, 0.5e-6, -0.5e-6, 1e-5, -1e-5]):
-        n = np.array([np.cos(0.7 * k), -0.8, np.sin(0.7 * k)])
-        n /= np.linalg.norm(n)
-        lights.append(list(centre + n * (radius + eps)) + [1.0, 0.9, 0.8, 3.0])
-    scene = S.SceneData(base.spheres, base.ground, base.dir_lights, np.array(lights), base.camera, base.sky)
+    scene = T.blocker_scene(w, h)
     want, st = T.oracle_render(scene, w, h, 4, 10)
     assert st.shadow_rays > 10 * st.path_rays * 0.5  # eleven lights per hit
     for kernel in KERNELS:
@@ -701,7 +678,8 @@ def test_point_light_at_blocker_distance_forces_the_exact_branch(ctx):
 @pytest.mark.parametrize("w,h,n,b,spp", [(33, 17, 6, 1, 10), (64, 36, 64, 3, 1), (50, 20, 17, 5, 7), (40, 12, 64, 8, 64),
                                            (257, 3, 100, 4, 10), (3, 257, 33, 2, 5), (16, 9, 64, 3, 500)])
 def test_odd_parameters_against_the_oracle(ctx, w, h, n, b, spp):
-    """No goldens here: the oracle (itself pinned to the reference) is the checker.  Bounce limit 1, one and many
+    """The oracle (itself pinned to the reference, on benign scenes by tests/golden/golden.json and on the adversarial ones by
+    golden_edges.json) is the checker of these shapes; the reference's own frames of odd inputs are in test_edge_goldens.py.  Bounce limit 1, one and many
     rays per pixel (more than a wave's worth of samples per pixel; 500: the jitter table pushes the shading rings out of LDS and
     the decoupled kernel must step aside), sphere counts that are not multiples of 8/32/64, frames narrower than a wave."""
     spheres = S.demo_spheres() if n == 6 else S.synth_spheres(n, seed=99)
@@ -719,10 +697,8 @@ def test_odd_parameters_against_the_oracle(ctx, w, h, n, b, spp):
 
 @pytest.mark.parametrize("seed", range(12))
 def test_fuzzed_scenes_match_the_oracle(ctx, seed):
-    rng = np.random.default_rng(1000 + seed)
-    w, h = int(rng.integers(8, 72)), int(rng.integers(4, 40))
-    b, spp = int(rng.integers(1, 9)), int(rng.choice([1, 3, 10]))
-    scene = T.fuzz_scene(rng, w, h)
+    """The same twelve inputs also have frames of the reference itself (tests/golden/golden_edges.json, test_edge_goldens.py)."""
+    scene, w, h, b, spp = T.fuzz_case(seed)
     with np.errstate(all="ignore"):
         want, st = T.oracle_render(scene, w, h, b, spp)
     finite = np.isfinite(want).all()
@@ -875,55 +851,12 @@ def test_scenes_of_more_than_256_spheres_keep_their_tables(ctx, n):
         ctx.set_path_grids(64, 32)
 
 
-def _degenerate_scenes():
-    base = S.synth_scene(24, T.sky("synth"), T.bench_camera(40, 24, 2.5), seed=3)
-
-    def with_ground(point=None, normal=None, refl=None):
-        g = base.ground.copy()
-        if point is not None:
-            g[0:3] = point
-        if normal is not None:
-            g[3:6] = normal
-        if refl is not None:
-            g[9] = g[14] = refl
-        return S.SceneData(base.spheres, g, base.dir_lights, base.point_lights, base.camera, base.sky)
-
-    out = [("ground without a normal", with_ground(normal=[0.0, 0.0, 0.0])),
-           ("ground with a vanishing normal", with_ground(normal=[0.0, 1e-200, 0.0])),
-           ("ground with a huge normal", with_ground(normal=[0.0, 1e150, 1e150], refl=1.0)),
-           ("vertical mirror ground through the scene", with_ground(point=[0.3, 0.0, 0.0], normal=[1.0, 0.0, 0.0], refl=1.0))]
-    cam = base.camera.copy()
-    cam[10] = -2.0  # the eye exactly on the ground plane
-    out.append(("eye on the ground plane", base.with_camera(cam)))
-    cam = base.camera.copy()
-    cam[9:12] = base.spheres[5, :3]  # the eye at a sphere's centre
-    out.append(("eye at a sphere's centre", base.with_camera(cam)))
-    sph = base.spheres.copy()
-    sph[0, 3] = -0.4   # a negative radius (r*r is what the reference uses)
-    sph[1, 3] = 0.0
-    sph[2, :3] = [1e7, -3e6, 2e6]  # one sphere very far away: the tables' range explodes
-    sph[3, :3] = sph[4, :3]        # concentric twins with equal radii: exact ties
-    sph[3, 3] = sph[4, 3]
-    out.append(("odd radii, a far sphere, exact twins", base.with_spheres(sph)))
-    far = base.spheres.copy()
-    far[:, :3] = far[:, :3] * 1e5  # an enormous scene: hit points lose digits against the 1e-6 nudge
-    far[:, 3] *= 1e5
-    gf = base.ground.copy()
-    gf[1] *= 1e5
-    cf = base.camera.copy()
-    cf[9:12] *= 1e5
-    out.append(("a scene 1e5 times larger", S.SceneData(far, gf, base.dir_lights, base.point_lights * np.array([1e5, 1e5, 1e5, 1, 1, 1, 1e10]), cf, base.sky)))
-    pl = base.point_lights.copy()
-    pl[0, :3] = base.camera[9:12]  # a light at the eye
-    out.append(("a light at the eye", S.SceneData(base.spheres, base.ground, base.dir_lights, pl, base.camera, base.sky)))
-    return out
-
-
-@pytest.mark.parametrize("name,scene", _degenerate_scenes(), ids=[n for n, _ in _degenerate_scenes()])
+@pytest.mark.parametrize("name,scene", T.degenerate_scenes(), ids=[n for n, _ in T.degenerate_scenes()])
 def test_degenerate_scenes_match_the_oracle(ctx, name, scene):
     """Inputs the candidate tables must survive: grounds whose mirror images are NaN or astronomically far, the eye on the
     ground or at a sphere's centre, negative / zero radii, one sphere 1e7 away, exact twins, a scene 1e5 times larger, a
-    light at the eye.  NaN pixels must sit where the oracle's do; everything else bit for bit; counts equal."""
+    light at the eye.  NaN pixels must sit where the oracle's do; everything else bit for bit; counts equal.  The same scenes also
+    have frames of the reference itself (tests/golden/golden_edges.json, test_edge_goldens.py)."""
     w, h, b, spp = 40, 24, 6, 3
     with np.errstate(all="ignore"):
         want, st = T.oracle_render(scene, w, h, b, spp)
