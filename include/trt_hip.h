@@ -141,6 +141,15 @@ int trt_scene_info(trt_context *ctx, unsigned long long *table_bytes, int *share
 int trt_render_device(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,
                       int rays_per_pixel, void *d_pixels, size_t capacity_bytes);
 
+/* trt_render_device as the emitter's bytes: d_rgb8[(local_row*width + col)*3 + channel] = (int)(c*255) (TRT.c:1157-1163), written
+ * by the pass that forms the ordered mean over a pixel's samples -- no framebuffer of doubles is written or read on the way (the
+ * reference-order kernel, trt_set_kernel(ctx, 1), has no such pass: its frame goes through a framebuffer of the context's and
+ * trt_quantize_device's kernel).  Byte for byte what trt_render_device followed by trt_quantize_device gives.  d_rgb8 may have any
+ * alignment; capacity_bytes counts bytes of RGB8 (owned rows * width * 3); errors as trt_render_device.  Asynchronous on the context's
+ * stream.  One entry of trt_kernel_times; trt_render_kernel_times reports the pass as reduce_ms. */
+int trt_render_device_rgb8(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,
+                           int rays_per_pixel, void *d_rgb8, size_t capacity_bytes);
+
 /* (int)(c*255) per channel (TRT.c:1157-1163) on the device: 3 bytes per pixel. Asynchronous. */
 int trt_quantize_device(trt_context *ctx, const void *d_pixels, size_t num_pixels, void *d_rgb8);
 
@@ -148,7 +157,7 @@ int trt_quantize_device(trt_context *ctx, const void *d_pixels, size_t num_pixel
 int trt_render_host(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,
                     int rays_per_pixel, Vector *pixels);
 
-/* trt_render_host followed by the emitter's (int)(c*255) on the device: 3 bytes per pixel to HOST memory (synchronous). */
+/* trt_render_device_rgb8 into HOST memory: the emitter's (int)(c*255), 3 bytes per pixel (synchronous; pinned staging inside). */
 int trt_render_host_rgb8(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
                          unsigned char *rgb);
 
@@ -173,6 +182,15 @@ int trt_render_device_batch(trt_context *ctx, const Camera *cameras, int n, cons
 /* The same into HOST memory: pixels[b * owned rows * width ...] (synchronous; one copy-out through pinned staging). */
 int trt_render_host_batch(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
                           int rays_per_pixel, Vector *pixels);
+/* trt_render_device_batch as the emitter's bytes (trt_render_device_rgb8): frame b at d_rgb8 + b * owned rows * width * 3, which
+ * need not be aligned to anything; every frame is byte for byte what trt_render_device_rgb8 gives for that camera.  One launch, a
+ * split for LDS or one launch per camera exactly as trt_render_device_batch decides (trt_batch_info); the same errors, the capacity
+ * counted in bytes of RGB8 for n frames. */
+int trt_render_device_batch_rgb8(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                 int rays_per_pixel, void *d_rgb8, size_t capacity_bytes);
+/* The same into HOST memory: rgb[b * owned rows * width * 3 ...] (synchronous; one copy-out through pinned staging). */
+int trt_render_host_batch_rgb8(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                               int rays_per_pixel, unsigned char *rgb);
 /* The most recent batch call of this context: its frames, and how many render-kernel launches served them
  * (1 = one launch over all frames; n = one launch per camera; between: the batch was split for LDS). */
 int trt_batch_info(trt_context *ctx, int *frames, int *render_launches);

@@ -127,6 +127,85 @@ __global__ void quantize_kernel(const double *px, long n_values, unsigned char *
         rgb[i] = (unsigned char)d2i(px[i] * 255);
 }
 
+// The ordered mean and the emitter's cast in ONE pass, for the hosts whose only consumer of a frame is the emitter: per value what
+// reduce_samples_kernel and quantize_kernel compute one after the other -- (unsigned char)d2i((mean * inv_spp) * 255), the mean summed
+// from 0.0 in sample order -- without the 24 B per pixel of doubles written and read back in between.  A lane owns kRgb8Group
+// consecutive values: per k it reads them as 32 consecutive bytes of the scratch (16-byte loads) and at the end it stores them as ONE
+// aligned 32-bit word, so that a wave's store covers 256 consecutive bytes instead of 64.  `out` may have any byte alignment: the
+// groups start at the first 4-aligned ADDRESS, `head` = (-out) mod 4 values in (all of them, if there are fewer), and the up to three
+// values in front of the groups and the up to three behind them have a lane and a single-byte store each.  Lane i: group i while
+// i < groups, then the head's values, then the tail's; the grid has groups + head + tail lanes (rgb8_lanes), rounded up to workgroups.
+constexpr int kRgb8Group = 4;
+
+__host__ __device__ inline long rgb8_head(const unsigned char *out, long values)
+{
+    const long head = (long)((4 - ((unsigned long long)out & 3)) & 3);
+    return head < values ? head : values;
+}
+// lanes of a frame of `values` values that starts `head` values in front of a 4-aligned address
+__host__ __device__ inline long rgb8_lanes(long values, long head)
+{
+    return (values - head) / kRgb8Group + head + (values - head) % kRgb8Group;
+}
+
+__device__ __forceinline__ unsigned rgb8_byte(double mean, double inv_spp)
+{
+    return (unsigned)(unsigned char)d2i((mean * inv_spp) * 255); // TRT.c:1065, then TRT.c:1157-1163
+}
+
+// one frame's lane `i`: samples[k * values + v] -> out[v]
+__device__ __forceinline__ void reduce_samples_rgb8(const double *samples, unsigned char *out, long values, int spp, double inv_spp, long i)
+{
+    const long head = rgb8_head(out, values);
+    const long groups = (values - head) / kRgb8Group;
+    if (i < groups)
+    {
+        const long v = head + i * kRgb8Group;
+        double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0;
+#pragma unroll 4 // the loads of four samples in flight per lane; the sums stay in sample order
+        for (int k = 0; k < spp; k++)
+        {
+            const double *s = samples + ((long)k * values + v);
+            m0 += s[0];
+            m1 += s[1];
+            m2 += s[2];
+            m3 += s[3];
+        }
+        const unsigned word = rgb8_byte(m0, inv_spp) | rgb8_byte(m1, inv_spp) << 8 | rgb8_byte(m2, inv_spp) << 16 | rgb8_byte(m3, inv_spp) << 24;
+        *reinterpret_cast<unsigned *>(out + v) = word; // (out + head) is 4-aligned, and so is every group behind it
+        return;
+    }
+    const long j = i - groups; // the values the groups leave: the head's, then the tail's
+    const long v = j < head ? j : head + groups * kRgb8Group + (j - head);
+    if (v >= values)
+        return;
+    double mean = 0.0;
+    for (int k = 0; k < spp; k++)
+        mean += samples[(long)k * values + v];
+    out[v] = (unsigned char)rgb8_byte(mean, inv_spp);
+}
+
+// ... as the last kernel of a frame, in reduce_samples_kernel's place: it leaves the queue ready in the same way
+__global__ __launch_bounds__(256) void reduce_samples_rgb8_kernel(const double *samples, unsigned char *out, long values, int spp, double inv_spp,
+                                                                  unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
+{
+    if (blockIdx.x == 0 && threadIdx.x < (1u << shift)) // the render kernel that used the queue has finished
+        queue[threadIdx.x * kQueueStride] = (grid > threadIdx.x ? (grid - threadIdx.x + (1u << shift) - 1) >> shift : 0u) * waves_per_group;
+    reduce_samples_rgb8(samples, out, values, spp, inv_spp, (long)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// The same over the frames of a batch launch: blockIdx.y is the frame, as in reduce_samples_batch_kernel.  Frame b's bytes start at
+// out + b * values, which is 4-aligned for no b in general: every frame has a head and a tail of its own, and a grid sized for the
+// most lanes any alignment needs (at most values / 4 groups, three values in front, three behind; a frame's spare lanes find nothing to do).
+__global__ __launch_bounds__(256) void reduce_samples_rgb8_batch_kernel(const double *samples, unsigned char *out, long values, int spp, double inv_spp,
+                                                                        unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
+{
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < (1u << shift))
+        queue[threadIdx.x * kQueueStride] = (grid > threadIdx.x ? (grid - threadIdx.x + (1u << shift) - 1) >> shift : 0u) * waves_per_group;
+    reduce_samples_rgb8(samples + (size_t)blockIdx.y * (size_t)spp * (size_t)values, out + (size_t)blockIdx.y * (size_t)values, values, spp, inv_spp,
+                        (long)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
 #endif // TRT_UNIT_RENDER
 
 } // namespace trt

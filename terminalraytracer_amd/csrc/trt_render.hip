@@ -367,9 +367,18 @@ extern "C" int trt_read_counters(trt_context *ctx, unsigned long long *path_rays
 
 // ---- the launch of a frame, or of several cameras of one scene (on the host a single frame is a batch of one) ----
 
-// what both device entries refuse, for `frames` cameras into one framebuffer of `frames` frames of the rowset
+// What a launch leaves of a frame: the Screen's pixels of three doubles (TRT.c:188-193), or the emitter's three bytes per pixel
+// ((int)(c*255), TRT.c:1157-1163).
+enum Output : int { kDoubles, kBytes };
+
+static size_t value_bytes(Output kind)
+{
+    return kind == kBytes ? 1u : sizeof(double);
+}
+
+// what the device entries refuse, for `frames` cameras into one framebuffer of `frames` frames of the rowset
 static int check_render_arguments(const trt_context *ctx, const Camera *cameras, int frames, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
-                                  const void *d_pixels, size_t capacity_bytes)
+                                  const void *d_pixels, size_t capacity_bytes, Output kind = kDoubles)
 {
     if (!ctx || !cameras || !d_pixels)
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
@@ -386,7 +395,7 @@ static int check_render_arguments(const trt_context *ctx, const Camera *cameras,
     if (!ctx->have_scene)
         return fail(TRT_ERR_NO_SCENE, "trt_set_scene has not been called");
     const int local_rows = trt_rowset_rows(rows);
-    const size_t need = (size_t)local_rows * rows->width * sizeof(Vector) * frames;
+    const size_t need = (size_t)local_rows * rows->width * 3 * value_bytes(kind) * frames;
     if (capacity_bytes < need)
         return fail(TRT_ERR_CAPACITY, "framebuffer of %d frame(s) needs %zu B, %zu given", frames, need, capacity_bytes);
     if ((unsigned long long)local_rows * rows->width >= 0x7fffffffull)
@@ -443,9 +452,11 @@ enum : int { kEntryOpens = 1, kEntryCloses = 2, kEntryWhole = kEntryOpens | kEnt
 
 // Carries out a planned launch: the queue started unless the launch before left it ready, the image staged for the DEVICE_IMAGE
 // instantiations, the render kernel over the frame `f` -- with `batch`, the plan's BATCH form over the frames of `batch`, of which
-// f is the first -- and the ordered mean of every frame's `pixels` pixels into `out`.
-static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameView f, const trt::GridView &grids, const trt::BatchView *batch, double *out,
-                         long pixels, int lane_set, int entry)
+// f is the first -- and the ordered mean of every frame's `pixels` pixels into `out`: as doubles, or (kBytes) cast to the emitter's
+// bytes in the same pass.  The reference-order kernel has no scratch and no mean: its bytes are its doubles, rendered into the
+// context's framebuffer, through quantize_kernel.
+static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameView f, const trt::GridView &grids, const trt::BatchView *batch, void *out,
+                         Output kind, long pixels, int lane_set, int entry)
 {
     const hipStream_t stream = lane_set ? ctx->alt_stream : ctx->stream;
     const int slot = (int)(ctx->launches % kEventRing);
@@ -460,8 +471,19 @@ static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameVie
 #endif
     if (reference)
     {
+        if (kind == kBytes)
+        {
+            if (ctx->d_fb.capacity < (size_t)pixels * 3)
+                HIP_TRY(hipStreamSynchronize(stream)); // a frame in flight may still use the old framebuffer
+            HIP_TRY(ctx->d_fb.reserve((size_t)pixels * 3));
+            f.out = ctx->d_fb.ptr;
+        }
         if (ctx->scratch_fill) // trt_set_scratch_fill: the reference-order kernel has no scratch
-            HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)pixels * 3 * sizeof(double), stream));
+        {
+            HIP_TRY(hipMemsetAsync(f.out, 0xFF, (size_t)pixels * 3 * sizeof(double), stream));
+            if (kind == kBytes)
+                HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)pixels * 3, stream));
+        }
         if (entry & kEntryOpens)
             HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
         if (plan.variant == kReference)
@@ -469,10 +491,12 @@ static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameVie
         else
             hipLaunchKernelGGL(trt::render_simple_kernel<true>, grid, block, 0, stream, ctx->scene, f);
         if (entry & kEntryCloses)
-        {
             HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
+        if (kind == kBytes)
+            hipLaunchKernelGGL(trt::quantize_kernel, dim3((unsigned)((pixels * 3 + 255) / 256)), dim3(256), 0, stream, (const double *)f.out, pixels * 3,
+                               (unsigned char *)out);
+        if (entry & kEntryCloses)
             HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
-        }
     }
     else
     {
@@ -505,7 +529,7 @@ static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameVie
         if (ctx->scratch_fill)
         { // trt_set_scratch_fill: exactly the launch's samples and exactly its pixels read as NaN until the launch writes them
             HIP_TRY(hipMemsetAsync(scratch.ptr, 0xFF, samples * sizeof(double), stream));
-            HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)pixels * frames * 3 * sizeof(double), stream));
+            HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)pixels * frames * 3 * value_bytes(kind), stream));
         }
         const bool left_ready = ready[0] == plan.grid && ready[1] == plan.block / 64 && ready[2] == f.queue_shift; // by the frame before
         ready[0] = 0; // the render kernel uses it up; ready again once this frame's launches have gone in
@@ -524,12 +548,21 @@ static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameVie
 #if !TRT_AB_SKIP_REDUCE // diagnostic build (profiles/r03: what the ordered mean's streaming pass costs in the pipelined loop)
         { // TRT.c:1063-1065: the mean over each pixel's samples, in sample order; it starts the queue for the next frame of this shape
             const long values = pixels * 3;
-            const unsigned blocks = (unsigned)((values + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK);
-            if (batch)
-                hipLaunchKernelGGL(trt::reduce_samples_batch_kernel, dim3(blocks, frames), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr, out, values, f.spp,
-                                   f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
+            // bytes: a lane per group of four values and one per value of a frame's head and tail (trt_common.hpp); the frames of a batch
+            // start at any alignment, so its grid is sized for the most lanes an alignment needs
+            const long lanes = kind == kDoubles ? values : batch ? values / trt::kRgb8Group + 6 : trt::rgb8_lanes(values, trt::rgb8_head((const unsigned char *)out, values));
+            const unsigned blocks = (unsigned)((lanes + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK);
+            if (kind == kBytes && batch)
+                hipLaunchKernelGGL(trt::reduce_samples_rgb8_batch_kernel, dim3(blocks, frames), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr,
+                                   (unsigned char *)out, values, f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
+            else if (kind == kBytes)
+                hipLaunchKernelGGL(trt::reduce_samples_rgb8_kernel, dim3(blocks), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr, (unsigned char *)out,
+                                   values, f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
+            else if (batch)
+                hipLaunchKernelGGL(trt::reduce_samples_batch_kernel, dim3(blocks, frames), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr, (double *)out, values,
+                                   f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
             else
-                hipLaunchKernelGGL(trt::reduce_samples_kernel, dim3(blocks), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr, out, values, f.spp,
+                hipLaunchKernelGGL(trt::reduce_samples_kernel, dim3(blocks), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr, (double *)out, values, f.spp,
                                    f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
         }
 #endif
@@ -549,9 +582,9 @@ static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameVie
 }
 
 static int render_device_on(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_pixels,
-                            size_t capacity_bytes, int lane_set, int entry = kEntryWhole)
+                            size_t capacity_bytes, int lane_set, int entry = kEntryWhole, Output kind = kDoubles)
 {
-    int rc = check_render_arguments(ctx, camera, 1, rows, bounce_limit, rays_per_pixel, d_pixels, capacity_bytes);
+    int rc = check_render_arguments(ctx, camera, 1, rows, bounce_limit, rays_per_pixel, d_pixels, capacity_bytes, kind);
     if (rc)
         return rc;
     const long pixels = (long)trt_rowset_rows(rows) * rows->width;
@@ -574,14 +607,21 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
     rc = plan_render(ctx, pixels * rays_per_pixel, rays_per_pixel, 1, false, &plan);
     if (rc)
         return rc;
-    return launch_render(ctx, plan, frame_view(ctx, camera, rows, bounce_limit, rays_per_pixel, d_pixels, lane_set), ctx->grids, nullptr, (double *)d_pixels, pixels,
-                         lane_set, entry);
+    // only the reference-order kernel writes FrameView::out: doubles (launch_render gives it the context's framebuffer when bytes are asked for)
+    return launch_render(ctx, plan, frame_view(ctx, camera, rows, bounce_limit, rays_per_pixel, kind == kDoubles ? d_pixels : nullptr, lane_set), ctx->grids, nullptr,
+                         d_pixels, kind, pixels, lane_set, entry);
 }
 
 extern "C" int trt_render_device(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,
                                  int rays_per_pixel, void *d_pixels, size_t capacity_bytes)
 {
     return render_device_on(ctx, camera, rows, bounce_limit, rays_per_pixel, d_pixels, capacity_bytes, 0);
+}
+
+extern "C" int trt_render_device_rgb8(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_rgb8,
+                                      size_t capacity_bytes)
+{
+    return render_device_on(ctx, camera, rows, bounce_limit, rays_per_pixel, d_rgb8, capacity_bytes, 0, kEntryWhole, kBytes);
 }
 
 extern "C" int trt_quantize_device(trt_context *ctx, const void *d_pixels, size_t num_pixels, void *d_rgb8)
@@ -740,10 +780,11 @@ static int fit_batch(trt_context *ctx, long units_per_frame, int spp, int remain
     }
 }
 
-extern "C" int trt_render_device_batch(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
-                                       void *d_pixels, size_t capacity_bytes)
+// frame b's values in `kind` at d_pixels + b * values * value_bytes(kind)
+static int render_device_batch(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_pixels,
+                               size_t capacity_bytes, Output kind)
 {
-    int rc = check_render_arguments(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_pixels, capacity_bytes);
+    int rc = check_render_arguments(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_pixels, capacity_bytes, kind);
     if (rc)
         return rc;
     const long pixels = (long)trt_rowset_rows(rows) * rows->width, units = pixels * rays_per_pixel, values = pixels * 3;
@@ -762,8 +803,8 @@ extern "C" int trt_render_device_batch(trt_context *ctx, const Camera *cameras, 
     {
         for (int b = 0; b < n; b++)
         {
-            rc = render_device_on(ctx, &cameras[b], rows, bounce_limit, rays_per_pixel, (double *)d_pixels + (size_t)b * values, (size_t)values * sizeof(double), 0,
-                                  (b == 0 ? kEntryOpens : 0) | (b == n - 1 ? kEntryCloses : 0));
+            rc = render_device_on(ctx, &cameras[b], rows, bounce_limit, rays_per_pixel, (char *)d_pixels + (size_t)b * values * value_bytes(kind),
+                                  (size_t)values * value_bytes(kind), 0, (b == 0 ? kEntryOpens : 0) | (b == n - 1 ? kEntryCloses : 0), kind);
             if (rc)
                 return rc;
             ctx->batch_launches++;
@@ -801,12 +842,47 @@ extern "C" int trt_render_device_batch(trt_context *ctx, const Camera *cameras, 
         batch.frames = (unsigned)m;
         batch.units_per_frame = (unsigned)units;
         batch.frame_magic = division_magic((unsigned long long)units);
-        rc = launch_render(ctx, plan, frame_view(ctx, &cameras[first], rows, bounce_limit, rays_per_pixel, d_pixels, 0), g, &batch,
-                           (double *)d_pixels + (size_t)first * values, pixels, 0, (first == 0 ? kEntryOpens : 0) | (first + m == n ? kEntryCloses : 0));
+        rc = launch_render(ctx, plan, frame_view(ctx, &cameras[first], rows, bounce_limit, rays_per_pixel, kind == kDoubles ? d_pixels : nullptr, 0), g, &batch,
+                           (char *)d_pixels + (size_t)first * values * value_bytes(kind), kind, pixels, 0,
+                           (first == 0 ? kEntryOpens : 0) | (first + m == n ? kEntryCloses : 0));
         if (rc)
             return rc;
         ctx->batch_launches++;
     }
+    return TRT_OK;
+}
+
+extern "C" int trt_render_device_batch(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                       void *d_pixels, size_t capacity_bytes)
+{
+    return render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_pixels, capacity_bytes, kDoubles);
+}
+
+extern "C" int trt_render_device_batch_rgb8(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                            void *d_rgb8, size_t capacity_bytes)
+{
+    return render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_rgb8, capacity_bytes, kBytes);
+}
+
+extern "C" int trt_render_host_batch_rgb8(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                          unsigned char *rgb)
+{
+    if (!ctx || !rgb)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (n < 1 || n > TRT_BATCH_MAX)
+        return fail(TRT_ERR_ARGUMENT, "a batch has 1 to %d cameras, %d given", TRT_BATCH_MAX, n);
+    if (!rowset_valid(rows))
+        return fail(TRT_ERR_ARGUMENT, "invalid rowset");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n * trt_rowset_rows(rows) * rows->width * 3;
+    HIP_TRY(ctx->d_rgb8.reserve(std::max<size_t>(bytes, 1)));
+    HIP_TRY(ctx->h_staging.reserve(std::max<size_t>(bytes, 1)));
+    const int rc = trt_render_device_batch_rgb8(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, ctx->d_rgb8.ptr, bytes);
+    if (rc || bytes == 0)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_rgb8.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(rgb, ctx->h_staging.ptr, bytes);
     return TRT_OK;
 }
 
@@ -977,14 +1053,11 @@ extern "C" int trt_render_host_rgb8(trt_context *ctx, const Camera *camera, cons
     const size_t count = (size_t)trt_rowset_rows(rows) * rows->width;
     if (count == 0)
         return TRT_OK;
-    HIP_TRY(ctx->d_fb.reserve(count * 3));
     HIP_TRY(ctx->d_rgb8.reserve(count * 3));
     HIP_TRY(ctx->h_staging.reserve(count * 3));
     const double t_begin = host_now_ms();
-    int rc = trt_render_device(ctx, camera, rows, bounce_limit, rays_per_pixel, ctx->d_fb.ptr, count * sizeof(Vector));
-    if (rc)
-        return rc;
-    rc = trt_quantize_device(ctx, ctx->d_fb.ptr, count, ctx->d_rgb8.ptr); // (int)(c*255), TRT.c:1157-1163, on the device
+    // the ordered mean writes the bytes itself ((int)(c*255), TRT.c:1157-1163): no framebuffer of doubles on the way
+    const int rc = trt_render_device_rgb8(ctx, camera, rows, bounce_limit, rays_per_pixel, ctx->d_rgb8.ptr, count * 3);
     if (rc)
         return rc;
     HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_rgb8.ptr, count * 3, hipMemcpyDeviceToHost, ctx->stream));

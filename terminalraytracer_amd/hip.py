@@ -60,11 +60,14 @@ SYMBOLS = {
     "trt_set_stream": (_I, [_VP, _VP]),
     "trt_set_scene": (_I, [_VP, C.POINTER(L.Scene)]),
     "trt_render_device": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ]),
+    "trt_render_device_rgb8": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ]),
     "trt_quantize_device": (_I, [_VP, _VP, _SZ, _VP]),
     "trt_render_host": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP]),
     "trt_render_host_rgb8": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP]),
     "trt_render_device_batch": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ]),
     "trt_render_host_batch": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP]),
+    "trt_render_device_batch_rgb8": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ]),
+    "trt_render_host_batch_rgb8": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP]),
     "trt_batch_info": (_I, [_VP, C.POINTER(_I), C.POINTER(_I)]),
     "trt_synchronize": (_I, [_VP]),
     "trt_kernel_times": (_I, [_VP, C.POINTER(C.c_float), _I]),
@@ -356,6 +359,13 @@ class Context:
         _check(lib().trt_render_device(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel,
                                        _VP(device_ptr), capacity_bytes))
 
+    def render_device_rgb8(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
+        """the frame as the emitter's bytes in device memory, 3 per pixel at any alignment, written by the ordered-mean pass itself
+        (trt_render_device_rgb8)"""
+        cam = camera_struct(camera_array)
+        _check(lib().trt_render_device_rgb8(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel,
+                                            _VP(device_ptr), capacity_bytes))
+
     def quantize_device(self, device_ptr, num_pixels, rgb_ptr):
         _check(lib().trt_quantize_device(self._h, _VP(device_ptr), num_pixels, _VP(rgb_ptr)))
 
@@ -394,6 +404,20 @@ class Context:
         out = np.zeros((cams.shape[0], lib().trt_rowset_rows(C.byref(rows)), rows.width, 3), dtype=np.float64)
         _check(lib().trt_render_host_batch(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
                                            out.ctypes.data))
+        return out
+
+    def render_batch_rgb8(self, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
+        """cameras[n, 15] as the emitter's bytes in device memory; frame b at device_ptr + b * rows * width * 3 (trt_render_device_batch_rgb8)"""
+        cams = self._camera_batch(cameras)
+        _check(lib().trt_render_device_batch_rgb8(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
+                                                  _VP(device_ptr), capacity_bytes))
+
+    def render_host_batch_rgb8(self, cameras, rows, bounce_limit, rays_per_pixel):
+        """the same into host memory: uint8 [n, rows, width, 3] (trt_render_host_batch_rgb8)"""
+        cams = self._camera_batch(cameras)
+        out = np.zeros((cams.shape[0], lib().trt_rowset_rows(C.byref(rows)), rows.width, 3), dtype=np.uint8)
+        _check(lib().trt_render_host_batch_rgb8(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
+                                                out.ctypes.data))
         return out
 
     def batch_info(self):
