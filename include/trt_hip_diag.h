@@ -68,6 +68,16 @@ int trt_read_loop_diagnostics(trt_context *ctx, unsigned long long out[8]);
  * (cells * ceil(N/64); cells = slabs * g^2 resp. shells * 6 g^2), 0 when the tables are off, or a negative TRT_ERR_*. */
 long trt_read_light_grid(trt_context *ctx, int point_light, int index, unsigned long long *masks, size_t capacity_words);
 
+/* Copy the LIST CELLS of one light's table -- the form the kernels read: one 64-bit cell per table cell (csrc/trt_raygrid.h),
+ * packed on the device from the masks trt_read_light_grid returns -- and the scene's part of the pool of long lists, into which
+ * the pooled cells' offsets point (tests: every cell must list the spheres of its mask, in ascending order).
+ * point_light: 0 = directional light `index`, 1 = point light `index`.
+ * info: {cells of the light's table, bits per list entry (8 or 16), pool words of the scene's part, 1 when the tables are on}.
+ * cells = pool = NULL with both capacities 0 asks for the sizes only: info is filled and nothing is copied.
+ * Returns the number of cells of the table, 0 when the tables are off, or a negative TRT_ERR_*. */
+long trt_read_light_lists(trt_context *ctx, int point_light, int index, unsigned long long *cells, size_t capacity_cells,
+                          unsigned long long *pool, size_t capacity_pool, long info[4]);
+
 /* Device rounding self-test: quot[i] = a[i] / b[i], root[i] = sqrt(a[i]) computed by the same
  * device instructions sequences the kernels use (host arrays in/out). */
 int trt_selftest_div_sqrt(trt_context *ctx, const double *a, const double *b, size_t n, double *quot, double *root);

@@ -139,6 +139,34 @@ extern "C" long trt_read_light_grid(trt_context *ctx, int point_light, int index
     return (long)stride;
 }
 
+extern "C" long trt_read_light_lists(trt_context *ctx, int point_light, int index, unsigned long long *cells, size_t capacity_cells,
+                                     unsigned long long *pool, size_t capacity_pool, long info[4])
+{
+    const bool query = !cells && !pool && !capacity_cells && !capacity_pool; // sizes only: info is filled, nothing is copied
+    if (!ctx || !info || index < 0 || (!query && (!cells || !pool)))
+        return fail(TRT_ERR_ARGUMENT, "bad argument");
+    if (!ctx->have_scene)
+        return fail(TRT_ERR_NO_SCENE, "no scene");
+    const trt::GridView &g = ctx->grids;
+    const size_t stride = point_light ? g.point_stride : g.dir_stride; // list cells of one light's table
+    const size_t pool_words = ctx->T->pool_scene_words;                // the light tables' long lists live in the scene's part
+    info[0] = g.enabled ? (long)stride : 0, info[1] = g.list_bits, info[2] = g.enabled ? (long)pool_words : 0, info[3] = g.enabled;
+    if (!g.enabled)
+        return 0;
+    if (index >= (point_light ? ctx->scene.num_point : ctx->scene.num_dir))
+        return fail(TRT_ERR_ARGUMENT, "light %d", index);
+    if (query)
+        return (long)stride;
+    if (capacity_cells < stride || capacity_pool < pool_words)
+        return fail(TRT_ERR_CAPACITY, "table has %zu cells and %zu pool words", stride, pool_words);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(cells, (point_light ? ctx->T->d_point_lists.ptr : ctx->T->d_dir_lists.ptr) + stride * (size_t)index, stride * sizeof(unsigned long long),
+                      hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pool, ctx->T->d_pool.ptr, pool_words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return (long)stride;
+}
+
 extern "C" int trt_selftest_div_sqrt(trt_context *ctx, const double *a, const double *b, size_t n, double *quot, double *root)
 {
     if (!ctx || !a || !b || !quot || !root)

@@ -104,6 +104,7 @@ SYMBOLS = {
     "trt_selftest_unit": (_I, [_VP, _VP, C.c_size_t, _VP, _VP]),
     "trt_selftest_sky": (_I, [_VP, _VP, C.c_size_t, _I, _VP, _VP, _VP]),
     "trt_read_light_grid": (C.c_long, [_VP, _I, _I, _VP, C.c_size_t]),
+    "trt_read_light_lists": (C.c_long, [_VP, _I, _I, _VP, C.c_size_t, _VP, C.c_size_t, C.POINTER(C.c_long)]),
     "trt_kernel_info": (_I, [_VP] + [C.POINTER(_I)] * 5),
     "trt_selftest_div_sqrt": (_I, [_VP, _VP, _VP, _SZ, _VP, _VP]),
     "trt_probe_rays": (_I, [_VP, _VP, _SZ, _VP, _VP, _VP, _VP, _VP]),
@@ -353,6 +354,19 @@ class Context:
         if got < 0:
             _check(int(got))
         return out[:got]
+
+    def read_light_lists(self, point_light, index):
+        """(info dict, list cells uint64[], pool uint64[]) of one light's table in the form the kernels read (trt_read_light_lists)"""
+        info = (C.c_long * 4)()
+        got = lib().trt_read_light_lists(self._h, int(point_light), index, None, 0, None, 0, info)  # sizes only
+        if got < 0:
+            _check(int(got))
+        cells = np.zeros(max(1, info[0]), dtype=np.uint64)
+        pool = np.zeros(max(1, info[2]), dtype=np.uint64)
+        got = lib().trt_read_light_lists(self._h, int(point_light), index, cells.ctypes.data, cells.size, pool.ctypes.data, pool.size, info)
+        if got < 0:
+            _check(int(got))
+        return dict(zip(("cells", "list_bits", "pool_words", "enabled"), [int(x) for x in info])), cells[:got], pool
 
     def render_device(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
         cam = camera_struct(camera_array)

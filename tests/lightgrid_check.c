@@ -9,7 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "trt_lightgrid.h"
+#include "trt_raygrid.h" /* the packing of list cells; it includes trt_lightgrid.h */
 
 typedef struct
 {
@@ -383,4 +383,54 @@ long lightgrid_host_table(const double *spheres, int n, int kind, const double *
         free(cones);
     }
     return bits;
+}
+
+/* ---- helpers of tests/test_candidate_edges.py ---- */
+
+/* cell of the shadow ray that starts at o in the table of one light (kind and v as lightgrid_host_table), looked up as the kernel
+ * does; -1 when the origin is outside the table's range */
+long lightgrid_cell_of(const double *spheres, int n, int kind, const double *v, int g, int slabs, const double *o)
+{
+    const int padded = trt_cull_padded(n, 8);
+    float *table = (float *)malloc(sizeof(float) * 4 * (size_t)(padded ? padded : 1));
+    trt_cull_scene cs;
+    trt_cull_build(spheres, n, 8, table, &cs);
+    free(table);
+    int far = 0;
+    long cell;
+    if (kind == 0)
+    {
+        trt_dirgrid G;
+        trt_dirgrid_disc *discs = (trt_dirgrid_disc *)malloc(sizeof(trt_dirgrid_disc) * (size_t)(n ? n : 1));
+        trt_dirgrid_prepare(spheres, n, &cs, v, g, slabs, &G, discs);
+        free(discs);
+        cell = trt_dirgrid_cell(&G, o[0], o[1], o[2], &far);
+    }
+    else
+    {
+        trt_pointgrid G;
+        trt_pointgrid_cone *cones = (trt_pointgrid_cone *)malloc(sizeof(trt_pointgrid_cone) * (size_t)(n ? n : 1));
+        trt_pointgrid_prepare(spheres, n, &cs, v, g, slabs, &G, cones);
+        free(cones);
+        cell = trt_pointgrid_cell(&G, o[0], o[1], o[2], &far);
+    }
+    return far ? -1 : cell;
+}
+
+/* the masks of a table packed into list cells with trt_list_pack, as the library packs them (csrc/trt_tables.hip: pack_cell): returns the
+ * pool words used; a list that finds no room in `pool_cap` words leaves its cell TRT_LIST_NONE */
+long lightgrid_pack(const unsigned long long *masks, long cells, int words, int bits, unsigned long long *lists, unsigned long long *pool, long pool_cap)
+{
+    long used = 0;
+    for (long c = 0; c < cells; c++)
+    {
+        const unsigned long long *m = masks + c * words;
+        const int count = trt_list_count(m, words);
+        const long need = (long)trt_list_pool_words(count, bits);
+        const int room = count <= 0xffff && used + need <= pool_cap;
+        lists[c] = trt_list_pack(m, words, count, room ? pool : NULL, (unsigned)used, bits);
+        if (room)
+            used += need;
+    }
+    return used;
 }

@@ -371,3 +371,53 @@ double raygrid_patch_cover(int m, long samples, double *worst_rho, int *patches_
         *patches_seen += seen[k];
     return worst;
 }
+
+/* ---- helpers of tests/test_candidate_edges.py: where a directed ray lands in the tables, with the headers' own look-ups ---- */
+
+/* cell of direction d in a family's cube map of g cells per face side, as path_cell looks it up */
+int raygrid_cell_of(const double *d, int g) { return trt_cubemap_cell((float)d[0], (float)d[1], (float)d[2], 0.5f * (float)g, (float)(g - 1), g); }
+
+/* patch of a sphere (m cells per face side of the origin's cube map) on which a ray's origin lies: w = origin - centre, as path_cell looks it up */
+int raygrid_patch_of(int m, const double *w) { return trt_patch_of(m, w[0], w[1], w[2]); }
+
+/* is the ray (o, d) a member of table `table` of the scene's families (library order: eye, mirror eye, n P patches, their mirror
+ * images), unit direction included: what path_cell asks before it reads a cell */
+int raygrid_member(const double *spheres, int n, const double *ground, const double *eye, int patch_m, int table, const double *ray)
+{
+    trt_patchset P;
+    trt_patchset_init(&P, patch_m);
+    const int families = 2 + 2 * n * P.count;
+    if (table < 0 || table >= families)
+        return 0;
+    trt_rayfamily *fam = (trt_rayfamily *)malloc(sizeof(trt_rayfamily) * (size_t)families);
+    raygrid_families(spheres, n, ground, eye, patch_m, fam);
+    const double *o = ray, *d = ray + 3;
+    const double a = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+    const int member = fabs(a - 1.0) <= 9.094947017729282e-13 && trt_rayfamily_member(&fam[table], o[0], o[1], o[2], d[0], d[1], d[2]);
+    free(fam);
+    return member;
+}
+
+/* the prefilter of trace() (csrc/trt_rounds.hpp) on the host: how many of the `count` listed spheres the FP32 filter lets through
+ * for the ray (o, d); fixed_dir: the form of a directional light's shadow rays, whose table carries kk - (C.d)^2 for d = the ray's
+ * direction rounded to FP32 */
+int raygrid_filter_survivors(const double *spheres, int n, const double *ray, const int *list, int count, int fixed_dir)
+{
+    const int padded = trt_cull_padded(n, 8);
+    float *table = (float *)malloc(sizeof(float) * 4 * (size_t)(padded ? padded : 1));
+    trt_cull_scene cs;
+    trt_cull_build(spheres, n, 8, table, &cs);
+    const double *o = ray, *d = ray + 3;
+    trt_ray_filter flt;
+    trt_filter_setup(&flt, o[0], o[1], o[2], d[0], d[1], d[2], d[0] * d[0] + d[1] * d[1] + d[2] * d[2], cs.c0[0], cs.c0[1], cs.c0[2], cs.cn, cs.rm);
+    int kept = 0;
+    for (int k = 0; k < count; k++)
+    {
+        const float *e = table + 4 * list[k];
+        const unsigned sign = fixed_dir ? trt_filter_sign_fixed_dir(&flt, e[0], e[1], e[2], trt_filter_fixed_dir_kk(e[0], e[1], e[2], e[3], (float)d[0], (float)d[1], (float)d[2]))
+                                        : trt_filter_sign(&flt, e[0], e[1], e[2], e[3]);
+        kept += !flt.ok || !(sign >> 31);
+    }
+    free(table);
+    return kept;
+}

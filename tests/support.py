@@ -30,6 +30,18 @@ def checker_so(name):
     return os.path.join(build, name + ("_san" if SANITIZE else "") + ".so")
 
 
+@functools.lru_cache(maxsize=None)
+def lightgrid_checker():
+    """tests/lightgrid_check.c with the table headers it includes, compiled for the host: the one build recipe of its users"""
+    so = checker_so("liblightgridcheck")
+    src = os.path.join(ROOT, "tests", "lightgrid_check.c")
+    inc = os.path.join(ROOT, "terminalraytracer_amd", "csrc")
+    newest = max(os.path.getmtime(p) for p in [src] + [os.path.join(inc, h) for h in ("trt_raygrid.h", "trt_lightgrid.h", "trt_filter.h")])
+    if not os.path.exists(so) or os.path.getmtime(so) < newest:
+        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared"] + CHECKER_FLAGS + ["-I" + inc, "-o", so, src, "-lm"])
+    return C.CDLL(so)
+
+
 class OracleStats(C.Structure):
     _fields_ = [("path_rays", C.c_ulonglong), ("shadow_rays", C.c_ulonglong), ("sky_lookups", C.c_ulonglong),
                 ("samples", C.c_ulonglong)]
@@ -452,3 +464,304 @@ def render(ctx, scene, w, h, b, s, kernel=hip.Context.PRODUCTION, rows=None):
     ctx.set_compaction({COMPACT: 1, PLAIN: 0}.get(kernel, -1))
     ctx.set_scene(scene)
     return ctx.render_host(scene.camera, rows or hip.RowSet.whole(w, h), b, s)
+
+
+# ---- directed scenes of tests/test_candidate_edges.py: every ray's answer hangs on ONE known sphere at a known place of the sweep or of a list ----
+
+def index_colour(i):
+    """a colour that names sphere i (the probe returns the winner's material): three exactly representable components"""
+    return np.array([(i % 16 + 1) / 32.0, ((i // 16) % 16 + 1) / 32.0, (i // 256 + 1) / 32.0])
+
+
+def directed_spheres(centres, radii):
+    centres, radii = np.asarray(centres, dtype=np.float64).reshape(-1, 3), np.asarray(radii, dtype=np.float64).ravel()
+    sph = np.zeros((len(centres), 9))
+    sph[:, :3], sph[:, 3] = centres, radii
+    for i in range(len(sph)):
+        sph[i, 4:7] = index_colour(i)
+    sph[:, 7], sph[:, 8] = 0.3, 100.0
+    return sph
+
+
+def oracle_probe(scene, rays):
+    """what trt_oracle_trace_ray and trt_oracle_apply_lighting answer for every ray, in the probes' layout"""
+    rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+    sc, lib, n = scene.as_scene(), oracle(), len(rays)
+    out = {"obj": np.zeros(n, dtype=np.int32), "point": np.zeros((n, 3)), "normal": np.zeros((n, 3)), "material": np.zeros((n, 5)), "lit": np.zeros((n, 3))}
+    for i in range(n):
+        ray = L.Ray.from_buffer(rays[i])
+        pt, nr, mt = L.Vector(), L.Vector(), L.Material()
+        obj = lib.trt_oracle_trace_ray(C.byref(sc), C.byref(ray), C.byref(pt), C.byref(nr), C.byref(mt))
+        out["obj"][i] = obj
+        out["point"][i], out["normal"][i] = (pt.x, pt.y, pt.z), (nr.x, nr.y, nr.z)
+        out["material"][i] = (mt.color.x, mt.color.y, mt.color.z, mt.reflectivity, mt.specularity)
+        if obj != L.NONE:
+            lib.trt_oracle_apply_lighting(C.byref(sc), C.byref(pt), C.byref(nr), C.byref(mt), None)
+            out["lit"][i] = (mt.color.x, mt.color.y, mt.color.z)
+    return out
+
+
+def _unit(v):
+    v = np.asarray(v, dtype=np.float64)
+    return v / np.sqrt(v @ v)
+
+
+SWEEP_COUNTS = (1, 7, 8, 9, 31, 32, 33, 63, 64, 65, 96, 97, 127, 128, 129, 200)
+SWEEP_TWINS = ("ends", (31, 32), (63, 64), (62, 65))  # (i, j): sphere j repeats sphere i; "ends": (0, n - 1)
+# light travel directions at most 27 degrees off the vertical, point lights high above the layer: a line from a light through a sphere's centre
+# leaves the layer of spheres (2.4 thick) within 0.9 of that centre sideways, and the next sphere is 2.4 away
+SWEEP_DIR_LIGHTS = np.array([[-0.3, -1.0, -0.2, 0.15, 0.1, 0.05], [0.4, -1.0, 0.1, 0.05, 0.15, 0.1], [0.1, -1.0, -0.5, 0.1, 0.05, 0.15]])
+SWEEP_POINT_LIGHTS = np.array([[4.0, 40.0, -3.0, 0.15, 0.15, 0.05, 1500.0], [-6.0, 45.0, 5.0, 0.05, 0.1, 0.15, 1700.0]])
+
+
+def sweep_scene(n, n_dir=3, n_point=2, twins=()):
+    """n spheres in one layer on a lattice of pitch 3 (radii 0.3 .. 0.6, centres 2.7 .. 3.3 above the ground), lit from above"""
+    cols = int(np.ceil(np.sqrt(n)))
+    k = np.arange(n)
+    off = 1.5 * (cols - 1)
+    centres = np.stack([3.0 * (k % cols) - off, 1.0 + 0.15 * ((k * 7) % 5 - 2), 3.0 * (k // cols) - off], axis=1)
+    radii = 0.3 + 0.05 * ((k * 5) % 7)
+    for i, j in twins:
+        centres[j], radii[j] = centres[i], radii[i]
+    return S.SceneData(directed_spheres(centres, radii), S.demo_ground(), SWEEP_DIR_LIGHTS[:n_dir], SWEEP_POINT_LIGHTS[:n_point],
+                       bench_camera(40, 24), sky("synth"))
+
+
+def sweep_twins(n):
+    return [(0, n - 1) if t == "ends" else t for t in SWEEP_TWINS if (n >= 2 if t == "ends" else t[1] < n)]
+
+
+def sweep_sphere_rays(scene):
+    """(rays, wanted sphere or -1): ray i starts 0.4 outside sphere i and runs at its centre; then rays that meet the sky and the ground between the
+    spheres; then rays whose direction is not of unit length (the sweep then proposes EVERY sphere of a chunk, padding included)"""
+    sph, n = scene.spheres, len(scene.spheres)
+    rays, want = [], []
+    for i in range(n):
+        u = _unit([np.cos(0.7 * i), 0.8, np.sin(0.7 * i)])
+        rays.append(np.concatenate([sph[i, :3] + (sph[i, 3] + 0.4) * u, -u]))
+        want.append(i)
+    top = sph[:, 1].max() + 4.0
+    for q in range(4):
+        rays.append(np.concatenate([[sph[q % n, 0] + 1.5, top, sph[q % n, 2] + 1.5], _unit([0.3 * q - 0.4, 1.0, 0.2])]))  # sky
+        rays.append(np.concatenate([[sph[(5 * q) % n, 0] + 1.5, top, sph[(5 * q) % n, 2] + 1.5], [0.0, -1.0, 0.0]]))       # ground, between spheres
+        want += [-1, -1]
+    for q, i in enumerate(sorted({0, n // 2, n - 1, (n - 1) // 8 * 8, max(n - 2, 0)})):
+        scale = (2.0, 0.5, 3.0, 1.0 + 1e-9, 0.25)[q]
+        rays.append(np.concatenate([sph[i, :3] + np.array([0.0, sph[i, 3] + 0.4, 0.0]), [0.0, -scale, 0.0]]))
+        want.append(i)
+    rays.append(np.concatenate([[sph[0, 0] + 1.5, top, sph[0, 2] + 1.5], [0.6, 2.0, 0.2]]))    # not of unit length, and nothing hit: sky
+    rays.append(np.concatenate([[sph[0, 0] + 1.5, top, sph[0, 2] + 1.5], [0.0, -0.5, 0.0]]))  # ... the ground
+    want += [-1, -1]
+    return np.array(rays), np.array(want)
+
+
+def sweep_shadow_rays(scene):
+    """(rays, light, sphere): probe rays straight down onto ground points; from point (light l, sphere i) the centre of sphere i -- and no other
+    sphere -- stands between the point and light l (sphere -1: points well outside the lattice that nothing shadows)"""
+    sph, gy = scene.spheres, scene.ground[1]
+    rays, light, sphere = [], [], []
+    nd = len(scene.dir_lights)
+    for l in range(nd + len(scene.point_lights)):
+        for i in range(len(sph)):
+            c = sph[i, :3]
+            along = scene.dir_lights[l, :3] if l < nd else c - scene.point_lights[l - nd, :3]  # the way the light travels through the centre
+            g = c + along * ((gy - c[1]) / along[1])
+            rays.append([g[0], gy + 0.05, g[2], 0.0, -1.0, 0.0])
+            light.append(l), sphere.append(i)
+    far = np.abs(sph[:, [0, 2]]).max() + 8.0
+    for q in range(6):
+        rays.append([far + 2.0 * q, gy + 0.05, (far + 1.0 * q) * (-1.0 if q & 1 else 1.0), 0.0, -1.0, 0.0])
+        light.append(-1), sphere.append(-1)
+    return np.array(rays), np.array(light), np.array(sphere)
+
+
+def without_sphere(scene, i):
+    return scene.with_spheres(np.delete(scene.spheres, i, axis=0))
+
+
+# (c), (d): a CLUSTER of K spheres inside one table cell, seen from an apex (the eye; a point light; a ground point looking at a directional
+# light) along the cell's middle direction: `s` of them on the ray's line -- the nearest at list position p --, the others 1.2 .. 1.65 off the line
+# (radius 0.25: the FP32 filter rejects them).  List positions are ascending sphere indices: position k of the returned arrays.
+def cluster(apex, direction, K, s, p, twin=None):
+    d = _unit(direction)
+    e1 = _unit(np.cross(d, [0.0, 0.0, 1.0] if abs(d[2]) < 0.9 else [1.0, 0.0, 0.0]))
+    e2 = np.cross(d, e1)
+    on = [p]  # list positions on the line, nearest first: p, then from both ends of the list inwards
+    for k in (k for pair in zip(range(K), range(K - 1, -1, -1)) for k in pair):
+        if k not in on:
+            on.append(k)
+    on = on[:s]
+    centres = np.zeros((K, 3))
+    m = 0
+    for k in range(K):
+        if k in on:
+            centres[k] = apex + d * (12.0 + 1.5 * on.index(k))
+        else:
+            phi = 2.4 * m
+            centres[k] = apex + d * (14.0 + 0.5 * (m % 9)) + (1.2 + 0.15 * (m % 4)) * (np.cos(phi) * e1 + np.sin(phi) * e2)
+            m += 1
+    if twin:  # the second of the pair repeats the first, which is the nearest on the line
+        centres[twin[1]] = centres[twin[0]]
+    return centres, np.full(K, 0.25)
+
+
+WIDE_LOW = 3      # 16-bit entries: the cluster's first list position is this sphere, the others start at WIDE_FROM
+WIDE_FROM = 300
+
+
+def place_cluster(parts, wide, total=None):
+    """the numbering of a directed scene: parts = [(centres, radii)]; the first part's list positions 0 .. K - 1 become sphere 0 .. K - 1 (8-bit
+    entries) or WIDE_LOW, WIDE_FROM .. (16-bit), the other parts follow.  Returns ([sphere indices of each part], number of spheres of the
+    scene: at least `total`, more than 256 for 16-bit entries); the caller places the parts and fills the indices left over"""
+    K = len(parts[0][0])
+    first = ([WIDE_LOW] + list(range(WIDE_FROM, WIDE_FROM + K - 1))) if wide else list(range(K))
+    nxt = max(max(first) + 1, WIDE_FROM if wide else 0)  # 16-bit entries: more than 256 spheres whatever K is
+    index = [first]
+    for c, _ in parts[1:]:
+        index.append(list(range(nxt, nxt + len(c))))
+        nxt += len(c)
+    return index, max(nxt, total or 0)
+
+
+EYE = np.array([0.0, 1.0, -20.0])
+EYE_MAIN, EYE_SHORT, EYE_OVER = np.array([-0.25, 0.25, 1.0]), np.array([1.0, 0.25, -0.25]), np.array([-1.0, 0.25, 0.25])  # cell middles of a 4-cell face
+OVER_COUNT = 13  # a list longer than the prefilter's threshold, all of it on the ray: more survivors than the compaction holds
+
+
+def eye_list_scene(K, s, p, wide, twin=None):
+    """(scene, {"main", "short", "over"}: ray from the eye into the cell) for the eye's table at set_path_grids(4, 3): the directed cluster in one
+    cell, one sphere in a second cell, OVER_COUNT spheres in a row in a third; 16-bit entries: 300 + spheres, the fillers behind the eye"""
+    parts = [cluster(EYE, EYE_MAIN, K, s, p, twin), cluster(EYE, EYE_SHORT, 1, 1, 0), cluster(EYE, EYE_OVER, OVER_COUNT, OVER_COUNT, 0)]
+    index, n = place_cluster(parts, wide)
+    centres, radii = np.zeros((n, 3)), np.full(n, 0.1)
+    taken = np.zeros(n, dtype=bool)
+    for (c, r), idx in zip(parts, index):
+        centres[idx], radii[idx], taken[idx] = c, r, True
+    free = np.nonzero(~taken)[0]
+    q = np.arange(len(free))
+    centres[free] = EYE + np.stack([1.2 * (q % 18) - 10.0, 1.2 * (q // 18) + 2.0, np.full(len(q), -40.0)], axis=1)  # a wall behind the eye
+    cam = bench_camera(24, 16)
+    cam[9:12] = EYE
+    d, pl = S.demo_lights()
+    scene = S.SceneData(directed_spheres(centres, radii), S.demo_ground(), d * np.array([1, 1, 1, 0.3, 0.3, 0.3]), pl * np.array([1, 1, 1, 0.3, 0.3, 0.3, 60.0]),
+                        cam, sky("synth"))
+    rays = {k: np.concatenate([EYE, _unit(v)]) for k, v in (("main", EYE_MAIN), ("short", EYE_SHORT), ("over", EYE_OVER))}
+    return scene, rays, index[0]
+
+
+FAMILY_SOURCE = np.array([0.0, 4.0, 0.0])  # the sphere (radius 0.25, the scene's LAST index) the rays of a sphere's families start on
+# per role: the ray's direction -- the middle of a cell of a 3-cell face -- and where on the source sphere it (kind "sphere") or its parent (kind
+# "mirror") starts: well inside a patch for 1 and 2 patch cells per face side
+FAMILY_RAYS = {"sphere": {"main": ([0.0, 0.0, 1.0], [0.4, 0.3, 1.0]), "short": ([1.0, 0.0, 0.0], [1.0, 0.3, 0.4]), "over": ([-1.0, 0.0, 0.0], [-1.0, 0.3, 0.4])},
+               "mirror": {"main": ([0.0, 2.0 / 3.0, 1.0], [0.4, -2.0 / 3.0, 1.0]), "short": ([1.0, 2.0 / 3.0, 0.0], [1.0, -2.0 / 3.0, 0.4]),
+                          "over": ([-1.0, 2.0 / 3.0, 0.0], [-1.0, -2.0 / 3.0, 0.4])}}
+FAMILY_CASES = ((5, 1, 4), (9, 1, 8), (16, 4, 7), (16, 10, 8))  # (K, s, p) of the cluster: inline, pooled, prefiltered and compacted, prefiltered and overflowing
+
+
+def family_list_scene(kind, K, s, p):
+    """(scene, {"main", "short", "over"}: ray, the same: origin on the source sphere that names the patch, the cluster's sphere indices, the source's
+    index) for the tables of ONE sphere's families at set_path_grids(4, 3).  kind "sphere": the rays start on the source sphere; "mirror": they start on
+    the ground, where a ray from the source sphere was reflected.  Along the main ray a cluster as in eye_list_scene, along the others one sphere and
+    OVER_COUNT spheres in a row"""
+    ground = S.demo_ground()
+    gy, r = ground[1], 0.25
+    assert np.array_equal(ground[3:6], [0.0, 1.0, 0.0])
+    rays, starts, parts = {}, {}, []
+    for role, (Kc, sc, pc) in (("main", (K, s, p)), ("short", (1, 1, 0)), ("over", (OVER_COUNT, OVER_COUNT, 0))):
+        d, w = (_unit(v) for v in FAMILY_RAYS[kind][role])
+        o = FAMILY_SOURCE + r * w
+        starts[role] = o
+        if kind == "mirror":  # the parent leaves o downwards, with d's mirror image, and meets the ground at g
+            dp = d * np.array([1.0, -1.0, 1.0])
+            g = o + dp * ((gy - o[1]) / dp[1])
+            o = np.array([g[0], gy + 1e-6, g[2]])
+        rays[role] = np.concatenate([o, d])
+        parts.append(cluster(o, d, Kc, sc, pc))
+    parts.append((FAMILY_SOURCE[None, :], np.array([r])))
+    index, n = place_cluster(parts, False)
+    centres, radii = np.zeros((n, 3)), np.zeros(n)
+    for (c, rr), idx in zip(parts, index):
+        centres[idx], radii[idx] = c, rr
+    cam = bench_camera(24, 16)
+    cam[9:12] = EYE + np.array([0.0, 0.0, -40.0])
+    d, pl = S.demo_lights()
+    scene = S.SceneData(directed_spheres(centres, radii), ground, d * np.array([1, 1, 1, 0.3, 0.3, 0.3]), pl * np.array([1, 1, 1, 0.3, 0.3, 0.3, 60.0]), cam, sky("synth"))
+    return scene, rays, starts, index[0], index[3][0]
+
+
+def list_cases(wide):
+    """[(K, s, p)]: list lengths either side of inline / pooled / prefiltered and of a pool word; the nearest sphere first, last, and either side of a
+    pool-word boundary; for prefiltered lists (K > 12) survivors 1, the compaction's capacity, one more, all"""
+    per = 4 if wide else 8
+    out = []
+    for K in ((1, 3, 4, 5, 8, 9, 12, 13, 16, 17) if wide else (1, 7, 8, 9, 12, 13, 16, 17, 24, 25)):
+        for p in sorted({0, K - 1, per - 1, per} & set(range(K))):
+            for s in ((1, per, per + 1, K) if K > 12 else sorted({1, K})):
+                out.append((K, s, p))
+    return out
+
+
+def wave_layouts(rays, lane):
+    """two waves of 64 probe rays: the directed ray in lane `lane` among short-list neighbours; the same among neighbours whose long lists overflow the
+    prefilter's compaction"""
+    out = np.concatenate([np.tile(rays["short"], (64, 1)), np.tile(rays["over"], (64, 1))])
+    out[lane], out[64 + lane] = rays["main"], rays["main"]
+    return out
+
+
+POINT_LIGHT = np.array([0.0, 30.0, 0.0])
+POINT_MAIN, POINT_EMPTY, POINT_OVER = np.array([-0.5, -1.0, 0.5]), np.array([0.5, -1.0, -0.5]), np.array([0.5, -1.0, 0.5])  # cell middles of a 2-cell face of the light's cube map
+DIR_TRAVEL = np.array([0.3, -1.0, 0.2])
+
+
+def _dir_basis(to_light):
+    """the plane basis trt_dirgrid_prepare makes across a light direction"""
+    d = _unit(to_light)
+    t = np.zeros(3)
+    t[int(np.argmin(np.abs(d)))] = 1.0
+    e1 = _unit(np.cross(d, t))
+    return d, e1, np.cross(d, e1)
+
+
+def light_list_scene(kind, K, p, wide, unsure=False, total=None):
+    """(scene, {"main", "other", "over"}: probe rays onto ground points, sphere index of every list position) for ONE light's table at
+    set_light_grids(8, 2), set_light_slabs(1, 1).  kind 0: a directional light; 1: a point light.  From the main ground point the shadow ray's cell lists
+    the K spheres of a cluster, of which the one at list position p blocks the light.  From "other" the cell is empty; from "over" it lists OVER_COUNT
+    spheres in a row towards the light: a long list all of which the prefilter keeps.  unsure (point light): nothing of the cluster blocks; one more sphere, of the
+    highest index, lies behind the light with its surface through it: a hit as far as the light, which the any-hit search cannot decide"""
+    gy = S.demo_ground()[1]
+    if kind == 1:
+        o = POINT_LIGHT + POINT_MAIN * ((gy - POINT_LIGHT[1]) / POINT_MAIN[1])
+        other = POINT_LIGHT + POINT_EMPTY * ((gy - POINT_LIGHT[1]) / POINT_EMPTY[1])
+        over = POINT_LIGHT + POINT_OVER * ((gy - POINT_LIGHT[1]) / POINT_OVER[1])
+        parts = [cluster(POINT_LIGHT, POINT_MAIN, K, 0 if unsure else 1, p), cluster(POINT_LIGHT, POINT_OVER, OVER_COUNT, OVER_COUNT, 0)]
+        if unsure:
+            u = _unit(POINT_LIGHT - o)
+            parts.append((np.array([POINT_LIGHT + u * 0.5]), np.array([0.5])))
+    else:
+        d, e1, e2 = _dir_basis(-DIR_TRAVEL)
+        frame = [np.array([0.0, 10.0, 0.0]) + 50.0 * (a * e1 + b * e2) for a, b in ((-1, -1), (1, 1))]  # two far spheres size the grid: cells of 25
+        q = np.array([0.0, 10.0, 0.0]) + 12.5 * (e1 + e2)                    # the middle of a cell
+        o = q + DIR_TRAVEL * ((gy - q[1]) / DIR_TRAVEL[1])
+        q2 = np.array([0.0, 10.0, 0.0]) + 12.5 * (e1 - e2)                   # another, empty, cell
+        other = q2 + DIR_TRAVEL * ((gy - q2[1]) / DIR_TRAVEL[1])
+        q3 = np.array([0.0, 10.0, 0.0]) + 12.5 * (e2 - e1)                   # a third cell: a row of spheres towards the light
+        over = q3 + DIR_TRAVEL * ((gy - q3[1]) / DIR_TRAVEL[1])
+        parts = [cluster(o, d, K, 1, p), (np.array(frame), np.array([0.25, 0.25])), cluster(over, d, OVER_COUNT, OVER_COUNT, 0)]
+    index, n = place_cluster(parts, wide, total)
+    centres, radii = np.zeros((n, 3)), np.full(n, 0.1)
+    taken = np.zeros(n, dtype=bool)
+    for (c, r), idx in zip(parts, index):
+        centres[idx], radii[idx], taken[idx] = c, r, True
+    free = np.nonzero(~taken)[0]
+    k = np.arange(len(free))
+    side = int(np.ceil(np.sqrt(max(len(free), 1))))
+    if kind == 1:  # fillers above the light: other faces of its cube map
+        centres[free] = POINT_LIGHT + np.stack([1.2 * (k % side) - 0.6 * side, np.full(len(k), 15.0), 1.2 * (k // side) - 0.6 * side], axis=1)
+    else:          # fillers over the middle of another cell of the grid
+        centres[free] = np.array([0.0, 10.0, 0.0]) - 12.5 * (e1 + e2) + np.outer(20.0 / side * (k % side) - 10.0, e1) + np.outer(20.0 / side * (k // side) - 10.0, e2)
+    dl = np.array([[*DIR_TRAVEL, 0.5, 0.4, 0.3]]) if kind == 0 else np.zeros((0, 6))
+    pl = np.array([[*POINT_LIGHT, 0.5, 0.4, 0.3, 900.0]]) if kind == 1 else np.zeros((0, 7))
+    scene = S.SceneData(directed_spheres(centres, radii), S.demo_ground(), dl, pl, bench_camera(24, 16), sky("synth"))
+    rays = {k: np.array([v[0], gy + 0.05, v[2], 0.0, -1.0, 0.0]) for k, v in (("main", o), ("other", other), ("over", over))}
+    return scene, rays, index[0]

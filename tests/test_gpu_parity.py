@@ -974,15 +974,7 @@ def test_the_tables_serve_nearly_every_trace(ctx):
 def test_device_built_light_tables_equal_the_host_reference_builder(ctx):
     """The library marks the cells of the light-space tables on the GPU (one thread per cell); tests/test_lightgrid.py proves
     the HOST builder conservative.  Both run the same predicates (+ - * / sqrt only), so the tables must agree word for word."""
-    import os
-    import subprocess
-    build = os.path.join(T.ROOT, "tests", "_build")
-    os.makedirs(build, exist_ok=True)
-    so = os.path.join(build, "liblightgridcheck.so")
-    inc = os.path.join(T.ROOT, "terminalraytracer_amd", "csrc")
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-I" + inc, "-o", so,
-                           os.path.join(T.ROOT, "tests", "lightgrid_check.c"), "-lm"])
-    lib = C.CDLL(so)
+    lib = T.lightgrid_checker()
     lib.lightgrid_host_table.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.lightgrid_host_table.restype = C.c_long
     base = S.synth_scene(40, T.sky("synth"), T.bench_camera(32, 18), seed=5)

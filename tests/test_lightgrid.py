@@ -6,8 +6,6 @@ and driven with (a) every shadow ray the oracle traces in real frames and (b) ad
 offsets of +-1e-16..1e-3, origins far away, at and around the light, on cube-map edges and corners, lights
 inside and next to spheres."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -31,13 +29,7 @@ class AnyHitStats(C.Structure):
 
 @pytest.fixture(scope="module")
 def checker():
-    so = T.checker_so("liblightgridcheck")
-    src = os.path.join(T.ROOT, "tests", "lightgrid_check.c")
-    inc = os.path.join(T.ROOT, "terminalraytracer_amd", "csrc")
-    newest = max(os.path.getmtime(p) for p in (src, os.path.join(inc, "trt_lightgrid.h"), os.path.join(inc, "trt_filter.h")))
-    if not os.path.exists(so) or os.path.getmtime(so) < newest:
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared"] + T.CHECKER_FLAGS + ["-I" + inc, "-o", so, src, "-lm"])
-    lib = C.CDLL(so)
+    lib = T.lightgrid_checker()
     lib.dirgrid_check.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(Stats)]
     lib.dirgrid_check.restype = None
     lib.pointgrid_check.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(Stats)]
