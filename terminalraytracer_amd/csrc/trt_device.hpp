@@ -40,6 +40,16 @@ TRT_DEV d3 scale(d3 a, double s) { return d3{a.x * s, a.y * s, a.z * s}; }
 // the short ways below are the ones taken: say so, so that they are laid out as the fall-through (two taken branches fewer each)
 #define TRT_LIKELY(c) __builtin_expect(!!(c), 1)
 
+// ---- wave votes over conjunctions ----------------------------------------------------------------------------------
+// The lanes of the wave (among the active ones) for which `p` holds, as a wave-uniform word.  For a `p` that IS one compare this is
+// the compare's own result: no instruction.  A vote over a conjunction, __any(a && b), is another matter: the compiler ANDs the two
+// lane masks and then -- it cannot see that the AND holds no bit of an inactive lane -- turns the mask into 0 / 1 per lane with a
+// v_cndmask and compares that with 0: a select and a compare that compute nothing, ~25 times a round.  So the votes of the render
+// kernels are taken as (lanes_with(a) & lanes_with(b)) != 0, every operand ONE compare or a word formed this way earlier: the ANDs
+// are scalar.  A word formed under a wider exec mask may be ANDed into a vote under a narrower one (never the other way round):
+// the compare's word at the place of the vote holds the active lanes only.
+TRT_DEV unsigned long long lanes_with(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
 TRT_DEV unsigned hi32(double x) { return (unsigned)(__builtin_bit_cast(unsigned long long, x) >> 32); }
 
 // positive, finite, biased exponent in [723, 1323): 2^-300 <= x < 2^300
@@ -404,7 +414,7 @@ TRT_DEV uint32_t sky_texel_unit(const uint32_t *sky, int dim, d3 dir)
 // not finite or not of FP32's range) -- is ambiguous.  A WRONG FACE needs two components whose magnitudes agree to 2^-23: then
 // |c| / best is within 2^-22 of 1 and U' within E of 0 or dim: ambiguous.  dim >= 2^20 makes everything ambiguous, and so does a
 // direction whose largest component is below 2^-100 in magnitude (the instructions flush FP32 denormals).
-TRT_DEV long sky_index_estimate(int dim, float dim_f, d3 dir, bool &ambiguous)
+TRT_DEV long sky_index_estimate(int dim, float dim_f, d3 dir, bool &ambiguous, unsigned long long &sure_lanes)
 {
     const float x = (float)dir.x, y = (float)dir.y, z = (float)dir.z;
     const int face = (int)__builtin_amdgcn_cubeid(x, y, z);
@@ -420,17 +430,27 @@ TRT_DEV long sky_index_estimate(int dim, float dim_f, d3 dir, bool &ambiguous)
     // The cube instructions flush FP32 denormals: a direction whose LARGEST component is below 2^-100 (an un-normalised vector that
     // TRT.c:444 left alone) may have lost a smaller one altogether while the reference's FP64 ratio keeps it -- ambiguous.  With the
     // largest component above that, a component that flushes is below 2^-25 of it: inside E.
-    ambiguous = !(lo > e && hi < 1.0f - e) || !(__builtin_fabsf(ma) > 0x1p-100f); // NaN: ambiguous
+    const bool above = lo > e, below = hi < 1.0f - e, ranged = __builtin_fabsf(ma) > 0x1p-100f;
+    ambiguous = !(above && below) || !ranged; // NaN: ambiguous
+    sure_lanes = lanes_with(above) & lanes_with(below) & lanes_with(ranged); // the lanes that are not
     return ((long)face * dim + (long)(int)V) * dim + (long)(int)U;
+}
+
+TRT_DEV long sky_index_estimate(int dim, float dim_f, d3 dir, bool &ambiguous)
+{
+    unsigned long long sure_lanes;
+    return sky_index_estimate(dim, dim_f, dir, ambiguous, sure_lanes);
 }
 
 // the reference's index for the lanes with `active`: the estimate, and the FP64 form for a wave in which some lane's is ambiguous
 TRT_DEV long sky_index_unit(int dim, d3 dir, double dim_f);
-TRT_DEV uint32_t sky_texel_wave(const uint32_t *sky, int dim, d3 dir, double dim_f, bool active)
+// `active_lanes`: lanes_with(active), which the caller has
+TRT_DEV uint32_t sky_texel_wave(const uint32_t *sky, int dim, d3 dir, double dim_f, bool active, unsigned long long active_lanes)
 {
     bool ambiguous;
-    long idx = sky_index_estimate(dim, (float)dim_f, dir, ambiguous);
-    if (__any(active && ambiguous))
+    unsigned long long sure_lanes;
+    long idx = sky_index_estimate(dim, (float)dim_f, dir, ambiguous, sure_lanes);
+    if ((active_lanes & ~sure_lanes) != 0)
     {
         const long exact = sky_index_unit(dim, dir, dim_f);
         idx = ambiguous ? exact : idx;

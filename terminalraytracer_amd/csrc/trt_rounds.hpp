@@ -324,7 +324,7 @@ constexpr int kListPrefilter = 12;
 
 
 template <bool ANY_HIT, bool REFRACT = false, int MARK_BASE = 0>
-TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bool active, d3 gp, d3 gn, unsigned &phase2_rounds, unsigned &lane_tests,
+TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bool active, unsigned long long active_lanes, d3 gp, d3 gn, unsigned &phase2_rounds, unsigned &lane_tests,
                   const float4 *fixed, bool use_list, unsigned long long cell, const unsigned long long *pool, int list_bits, int inside = -1,
                   const double *shared_ad = nullptr) // every lane's ray has the SAME direction (a directional light's shadow rays): {d.d, d.gn} from the LDS image
 {
@@ -344,6 +344,11 @@ TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bo
         const unsigned at = (unsigned)cell; // pooled: offset of the list's words
         const unsigned entry_mask = (1u << list_bits) - 1u;
         const int per_shift = list_bits == 8 ? 3 : 2, per_mask = (1 << per_shift) - 1; // 8 or 4 entries per pool word
+        // The iterations that ask the lanes for a pool word are those with (k & per_mask) == fetch_at: 0 -- or, in a wave without a pooled list
+        // (an inactive lane's cell is 0: not pooled), per_mask + 1, which no k meets: such a wave never takes the vote of the lanes.  A number in an
+        // SGPR, not a condition (the empty asm): the loop's test stays one s_and and one s_cmp.
+        int fetch_at = lanes_with(pooled) != 0 ? 0 : per_mask + 1;
+        asm("" : "+s"(fetch_at));
         unsigned long long cur = cell;
         int k = 0;
         TRT_TRACE_MARK(0); // table load
@@ -360,9 +365,9 @@ TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bo
             for (int j = 0; __any(j < count); j++)
             {
                 const bool valid = j < count;
-                if ((j & per_mask) == 0) // the lanes are asked for a pool word only in the iterations that can need one
-                    if (__any(valid && pooled && (j & per_mask) == 0))
-                        if (valid && pooled && (j & per_mask) == 0)
+                if ((j & per_mask) == fetch_at) // the lanes are asked for a pool word only in the iterations that can need one
+                    if (__any(valid && pooled))
+                        if (valid && pooled)
                             word = pool[at + ((unsigned)j >> per_shift)];
                 const unsigned i = valid ? (unsigned)word & entry_mask : 0u;
                 word >>= list_bits;
@@ -389,6 +394,7 @@ TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bo
                 cur = kept;
                 count = nk;
                 pooled = false;
+                fetch_at = per_mask + 1;
             }
         }
         TRT_TRACE_MARK(1);
@@ -397,9 +403,9 @@ TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bo
             phase2_rounds++;
             const bool valid = k < count;
             lane_tests += valid;
-            if ((k & per_mask) == 0) // k is the wave's: seven iterations of eight ask nothing of the lanes
-                if (__any(valid && pooled && (k & per_mask) == 0))
-                    if (valid && pooled && (k & per_mask) == 0)
+            if ((k & per_mask) == fetch_at) // k is the wave's: seven iterations of eight ask nothing of the lanes
+                if (__any(valid && pooled))
+                    if (valid && pooled)
                         cur = pool[at + ((unsigned)k >> per_shift)];
             const int i = valid ? (int)((unsigned)cur & entry_mask) : 0;
             cur >>= list_bits;
@@ -471,9 +477,13 @@ TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bo
     // whatever the quotient's digits are), so a wave whose rays all head away from the plane skips the division.
     {
         const double denom = shared_ad ? shared_ad[1] : dot(d, gn), num = dot(sub(gp, o), gn);
-        const bool maybe = active && !(ANY_HIT && best.i >= 0) && __builtin_fabs(denom) > 0.00001 &&
-                           (long long)(__builtin_bit_cast(unsigned long long, num) ^ __builtin_bit_cast(unsigned long long, denom)) >= 0;
-        if (__any(maybe))
+        const bool steep = __builtin_fabs(denom) > 0.00001;
+        const bool same_sign = (long long)(__builtin_bit_cast(unsigned long long, num) ^ __builtin_bit_cast(unsigned long long, denom)) >= 0;
+        const bool maybe = active && !(ANY_HIT && best.i >= 0) && steep && same_sign;
+        unsigned long long maybe_lanes = active_lanes & lanes_with(steep) & lanes_with(same_sign);
+        if (ANY_HIT)
+            maybe_lanes &= ~lanes_with(best.i >= 0);
+        if (maybe_lanes != 0)
         {
             const double t = num / denom;
             const bool hit = maybe && t > 0.00001;
@@ -504,7 +514,7 @@ TRT_DEV Hit trace(const LdsImage &L, const CullView &cull, int n, d3 o, d3 d, bo
 // the light (q^2 >= hi) cannot matter and is passed over.  `unsure`: the lane met a hit (q > 0) that is neither, and found no
 // proof of "dark".  Neither flag: nothing nearer than the light is hit, the point is lit.  No division, no hit point, no running
 // minimum: 3 FP64 operations and two compares per hit on top of the discriminant and its root.
-TRT_DEV void point_light_search(const LdsImage &L, int n, d3 o, d3 d, bool active, d3 gp, d3 gn, unsigned &rounds, unsigned &lane_tests,
+TRT_DEV void point_light_search(const LdsImage &L, int n, d3 o, d3 d, bool active, unsigned long long active_lanes, d3 gp, d3 gn, unsigned &rounds, unsigned &lane_tests,
                                 unsigned long long cell, const unsigned long long *pool, int list_bits, double lo, double hi, bool &dark, bool &unsure)
 {
     (void)n;
@@ -515,6 +525,8 @@ TRT_DEV void point_light_search(const LdsImage &L, int n, d3 o, d3 d, bool activ
     const unsigned at = (unsigned)cell;
     const unsigned entry_mask = (1u << list_bits) - 1u;
     const int per_shift = list_bits == 8 ? 3 : 2, per_mask = (1 << per_shift) - 1;
+    int fetch_at = lanes_with(pooled) != 0 ? 0 : per_mask + 1; // as in trace(): a wave without a pooled list asks its lanes for no pool word
+    asm("" : "+s"(fetch_at));
     unsigned long long cur = cell;
     int k = 0;
     dark = false, unsure = false;
@@ -523,9 +535,9 @@ TRT_DEV void point_light_search(const LdsImage &L, int n, d3 o, d3 d, bool activ
         rounds++;
         const bool valid = k < count;
         lane_tests += valid;
-        if ((k & per_mask) == 0)
-            if (__any(valid && pooled && (k & per_mask) == 0))
-                if (valid && pooled && (k & per_mask) == 0)
+        if ((k & per_mask) == fetch_at)
+            if (__any(valid && pooled))
+                if (valid && pooled)
                     cur = pool[at + ((unsigned)k >> per_shift)];
         const int i = valid ? (int)((unsigned)cur & entry_mask) : 0;
         cur >>= list_bits;
@@ -548,8 +560,11 @@ TRT_DEV void point_light_search(const LdsImage &L, int n, d3 o, d3 d, bool activ
     // hit if |d.n| > 1e-5 and numerator and denominator of t have the same sign (opposite signs: t <= 0)
     {
         const double denom = dot(d, gn), num = dot(sub(gp, o), gn);
-        const bool maybe = active && !dark && __builtin_fabs(denom) > 0.00001 &&
-                           (long long)(__builtin_bit_cast(unsigned long long, num) ^ __builtin_bit_cast(unsigned long long, denom)) >= 0;
+        const bool steep = __builtin_fabs(denom) > 0.00001;
+        const bool same_sign = (long long)(__builtin_bit_cast(unsigned long long, num) ^ __builtin_bit_cast(unsigned long long, denom)) >= 0;
+        // `dark` and `unsure` are set inside the loop's per-lane region: words of them would be per-lane values there (a merge behind
+        // a divergent branch), so these two votes stay __any
+        const bool maybe = active && !dark && steep && same_sign;
         if (__any(maybe))
         {
             const double t = num / denom;
@@ -564,14 +579,18 @@ TRT_DEV void point_light_search(const LdsImage &L, int n, d3 o, d3 d, bool activ
 }
 
 // The list cell of a PATH ray (trt_raygrid.h), ONE FAMILY PER SPHERE (GridView::patch_m == 0).  `fam`: the family the ray is
-// expected in (0 eye, 1 mirror eye, 2 + i sphere i, 2 + n + i mirror sphere i, < 0 none).  `fallback` is set for an active lane
+// expected in (0 eye, 1 mirror eye, 2 + i sphere i, 2 + n + i mirror sphere i, < 0 none).  `fallback_lanes` holds the active lanes
 // whose ray fails the family's membership test (its line must pass within r_chk of the apex, its origin not more than r_chk
-// behind it, within the table's range; a unit direction) or whose cell has no list: the caller then sweeps.
+// behind it, within the table's range; a unit direction) or whose cell has no list: the caller then sweeps.  `active_lanes`:
+// lanes_with(active) (trt_device.hpp).
 // BATCH: the ray belongs to frame `frame` of a batch launch, whose eye families and tables it reads (0 and unused otherwise)
 template <bool BATCH = false>
-TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n, int fam, d3 o, d3 d, bool active, bool &fallback, int frame = 0)
+TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n, int fam, d3 o, d3 d, bool active, unsigned long long active_lanes,
+                                     unsigned long long &fallback_lanes, int frame = 0)
 {
-    const bool has = active && fam >= 0;
+    const bool in_family = fam >= 0;
+    const unsigned long long family_lanes = lanes_with(in_family); // next to its compare: a vote on a compare of another block is a select and a compare again
+    const bool has = active && in_family;
     const int f = has ? fam : 0;
     const int s = f >= 2 ? f - 2 : 0, i = s >= n ? s - n : s; // sphere of the family
     const bool of_eye = f < 2, mirrored = s >= n;
@@ -592,6 +611,7 @@ TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n
     const bool near_line = dot(c, c) <= r_chk * r_chk, ahead = dot(w, d) >= -r_chk, in_range = dot(w, w) <= rg2;
     const bool unit_dir = __builtin_fabs(dot(d, d) - 1.0) <= 9.094947017729282e-13;
     const bool member = near_line & ahead & in_range & unit_dir;
+    const unsigned long long member_lanes = family_lanes & lanes_with(near_line) & lanes_with(ahead) & lanes_with(in_range) & lanes_with(unit_dir);
     const int g = of_eye ? G.g_eye : G.g_sph;
     const int at = trt_cubemap_cell((float)d.x, (float)d.y, (float)d.z, 0.5f * (float)g, (float)(g - 1), g);
     const unsigned eye_cells = 6u * (unsigned)G.g_eye * (unsigned)G.g_eye, sph_cells = 6u * (unsigned)G.g_sph * (unsigned)G.g_sph;
@@ -599,7 +619,7 @@ TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n
     unsigned long long cell = 0;
     if (has && member)
         cell = G.path_lists[base + (unsigned)at];
-    fallback = active && (!has || !member || (unsigned)(cell >> 56) == TRT_LIST_NONE);
+    fallback_lanes = active_lanes & (~member_lanes | lanes_with((unsigned)(cell >> 56) == TRT_LIST_NONE)); // active && (!has || !member || no list)
     return cell;
 }
 
@@ -608,13 +628,16 @@ TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n
 // sphere i -- the patch of the sphere's surface follows from the origin --, 2 + n + (i << TRT_PATCH_SHIFT | k): reflected by the
 // ground, its parent started on patch k of sphere i; < 0 none).  `fam` becomes the family code of the ray's REFLECTION BY THE
 // GROUND, should it go on to hit the ground: the mirror family of this one's -- of the patch the ray started on -- or none (a ray
-// from the ground cannot hit the ground again).  `fallback` is set for an active lane whose ray fails the family's
+// from the ground cannot hit the ground again).  `fallback_lanes` holds the active lanes whose ray fails the family's
 // membership test (its line must pass within r_chk of the apex, its origin not more than r_chk behind it, within the table's
 // range; a unit direction) or whose cell has no list: the caller then sweeps.
 template <bool BATCH = false>
-TRT_DEV unsigned long long path_cell_patches(const LdsImage &L, const GridView &G, int n, int &fam, d3 o, d3 d, bool active, bool &fallback, int frame = 0)
+TRT_DEV unsigned long long path_cell_patches(const LdsImage &L, const GridView &G, int n, int &fam, d3 o, d3 d, bool active, unsigned long long active_lanes,
+                                             unsigned long long &fallback_lanes, int frame = 0)
 {
-    const bool has = active && fam >= 0;
+    const bool in_family = fam >= 0;
+    const unsigned long long family_lanes = lanes_with(in_family); // next to its compare: a vote on a compare of another block is a select and a compare again
+    const bool has = active && in_family;
     const int f = has ? fam : 0;
     const bool of_eye = f < 2, mirrored = f >= 2 + n;
     const int code = f - 2 - n; // mirrored: sphere and patch
@@ -648,6 +671,7 @@ TRT_DEV unsigned long long path_cell_patches(const LdsImage &L, const GridView &
     const bool near_line = dot(c, c) <= r_chk * r_chk, ahead = dot(w, d) >= -r_chk, in_range = dot(w, w) <= rg2;
     const bool unit_dir = __builtin_fabs(dot(d, d) - 1.0) <= 9.094947017729282e-13;
     const bool member = near_line & ahead & in_range & unit_dir;
+    const unsigned long long member_lanes = family_lanes & lanes_with(near_line) & lanes_with(ahead) & lanes_with(in_range) & lanes_with(unit_dir);
     const int g = of_eye ? G.g_eye : G.g_sph;
     const int at = trt_cubemap_cell((float)d.x, (float)d.y, (float)d.z, 0.5f * (float)g, (float)(g - 1), g);
     const unsigned eye_cells = 6u * (unsigned)G.g_eye * (unsigned)G.g_eye, sph_cells = 6u * (unsigned)G.g_sph * (unsigned)G.g_sph;
@@ -656,7 +680,7 @@ TRT_DEV unsigned long long path_cell_patches(const LdsImage &L, const GridView &
     unsigned long long cell = 0;
     if (has && member)
         cell = G.path_lists[base + (unsigned)at];
-    fallback = active && (!has || !member || (unsigned)(cell >> 56) == TRT_LIST_NONE);
+    fallback_lanes = active_lanes & (~member_lanes | lanes_with((unsigned)(cell >> 56) == TRT_LIST_NONE)); // active && (!has || !member || no list)
     return cell;
 }
 
@@ -681,6 +705,7 @@ struct PathHit
     Hit ph;     // closest hit as the intersection routine produced it (un-nudged point)
     bool hit;   // a sphere or the ground
     bool sky;   // nothing: the sample ends on the sky
+    unsigned long long hit_lanes, sky_lanes; // lanes_with(hit), lanes_with(sky) (trt_device.hpp)
     d3 back;    // hit: unit vector back along the ray (nudge direction, TRT.c:871-872); sky: the unit direction (TRT.c:702, :878)
     d3 normal;  // hit: unit surface normal (TRT.c:878)
     int mat;    // hit: index into L.mat (sphere i, n = ground even, n + 1 = ground odd; TRT.c:850-851)
@@ -692,33 +717,35 @@ struct PathHit
 // family -- of the patch of its sphere this ray started on -- (a ray from the ground cannot hit the ground again; if it
 // does, it has no family).
 template <bool COUNT, bool REFRACT = false, bool PATCHES = false, bool BATCH = false>
-TRT_DEV PathHit path_stage(const LdsImage &L, const CullView &cull, const GridView &grids, int n, d3 o, d3 d, int &fam, bool alive, d3 gp, d3 gn,
-                           Tally &tally, int inside = -1, int frame = 0)
+TRT_DEV PathHit path_stage(const LdsImage &L, const CullView &cull, const GridView &grids, int n, d3 o, d3 d, int &fam, bool alive, unsigned long long alive_lanes,
+                           d3 gp, d3 gn, Tally &tally, int inside = -1, int frame = 0)
 {
     bool p_list = false;
     unsigned long long p_cell = 0;
     if (grids.path_enabled)
     {
-        bool fallback;
+        unsigned long long fallback_lanes;
         if constexpr (PATCHES)
-            p_cell = path_cell_patches<BATCH>(L, grids, n, fam, o, d, alive, fallback, frame); // fam: now what a reflection by the ground belongs to
+            p_cell = path_cell_patches<BATCH>(L, grids, n, fam, o, d, alive, alive_lanes, fallback_lanes, frame); // fam: now what a reflection by the ground belongs to
         else
-            p_cell = path_cell<BATCH>(L, grids, n, fam, o, d, alive, fallback, frame);
-        p_list = !__any(fallback);
+            p_cell = path_cell<BATCH>(L, grids, n, fam, o, d, alive, alive_lanes, fallback_lanes, frame);
+        p_list = fallback_lanes == 0;
     }
     if (COUNT && !p_list)
         tally.swept++;
     PathHit r;
-    r.ph = trace<false, REFRACT, 2>(L, cull, n, o, d, alive, gp, gn, tally.iters[0], tally.tests[0], nullptr, p_list, p_cell, grids.pool, grids.list_bits, inside);
+    r.ph = trace<false, REFRACT, 2>(L, cull, n, o, d, alive, alive_lanes, gp, gn, tally.iters[0], tally.tests[0], nullptr, p_list, p_cell, grids.pool, grids.list_bits, inside);
     r.hit = alive && r.ph.i >= 0;
     r.sky = alive && r.ph.i < 0;
+    r.hit_lanes = alive_lanes & lanes_with(r.ph.i >= 0);
+    r.sky_lanes = alive_lanes & ~r.hit_lanes;
     if (r.hit)
         fam = r.ph.i < n ? 2 + r.ph.i : (PATCHES ? fam : (fam == 0 ? 1 : (fam >= 2 && fam < 2 + n ? fam + n : -1)));
     // one unit() for "back along the ray" (nudge, TRT.c:871-872) or the sky direction (TRT.c:702), one for the normal
     r.back = unit(r.hit ? sub(o, r.ph.p) : d);
     r.normal = d;
     r.mat = 0;
-    if (__any(r.hit))
+    if (r.hit_lanes != 0)
     {
         d3 raw = gn;
         r.mat = n + checker_odd(r.ph.p); // TRT.c:850-851 (only meaningful for a ground hit)
@@ -738,10 +765,10 @@ TRT_DEV PathHit path_stage(const LdsImage &L, const CullView &cull, const GridVi
 // its range; the lit colour is accumulated in the reference's light order, NOT yet clamped (TRT.c:960).
 template <bool COUNT>
 TRT_DEV d3 shadow_stage(const LdsImage &L, const CullView &cull, const GridView &grids, int n, int nd, int nl, d3 o, d3 normal, int mat,
-                        bool lit_lanes, d3 gp, d3 gn, Tally &tally)
+                        bool lit_lanes, unsigned long long lit_word, d3 gp, d3 gn, Tally &tally) // lit_word: lanes_with(lit_lanes) (trt_device.hpp)
 {
     d3 lit = d3{0.0, 0.0, 0.0};
-    if (!__any(lit_lanes))
+    if (lit_word == 0)
         return lit;
     for (int li = 0; li < nl; li++)
     {
@@ -764,12 +791,12 @@ TRT_DEV d3 shadow_stage(const LdsImage &L, const CullView &cull, const GridView 
                 const int c = trt_dirgrid_cell(G, o.x, o.y, o.z, &far); // a light without a unit direction: far (stage_lds_image)
                 if (lit_lanes && !far)
                     cell = grids.dir_lists[(size_t)li * grids.dir_stride + (unsigned)c];
-                use_list = !__any(lit_lanes && (far || (unsigned)(cell >> 56) == TRT_LIST_NONE));
+                use_list = (lit_word & (lanes_with(far != 0) | lanes_with((unsigned)(cell >> 56) == TRT_LIST_NONE))) == 0;
             }
             if (COUNT && !use_list)
                 tally.swept++;
             TRT_MARK_AT(8); // look-up
-            const Hit sh = trace<true, false, 9>(L, cull, n, o, sd, lit_lanes, gp, gn, tally.iters[1], tally.tests[1], L.cull_dir + li * cull.padded, use_list, cell, grids.pool, grids.list_bits,
+            const Hit sh = trace<true, false, 9>(L, cull, n, o, sd, lit_lanes, lit_word, gp, gn, tally.iters[1], tally.tests[1], L.cull_dir + li * cull.padded, use_list, cell, grids.pool, grids.list_bits,
                                                  -1, L.dir + li * kDirRecord + 6);
             is_lit = sh.i < 0;
             factor = min1(dot(normal, sd));
@@ -794,7 +821,7 @@ TRT_DEV d3 shadow_stage(const LdsImage &L, const CullView &cull, const GridView 
                 far |= !(__builtin_fabs(dot(sd, sd) - 1.0) <= 9.094947017729282e-13);
                 if (lit_lanes && !far)
                     cell = grids.point_lists[(size_t)(li - nd) * grids.point_stride + (unsigned)c];
-                use_list = !__any(lit_lanes && (far || (unsigned)(cell >> 56) == TRT_LIST_NONE));
+                use_list = (lit_word & (lanes_with(far != 0) | lanes_with((unsigned)(cell >> 56) == TRT_LIST_NONE))) == 0;
             }
             if (COUNT && !use_list)
                 tally.swept++;
@@ -810,7 +837,7 @@ TRT_DEV d3 shadow_stage(const LdsImage &L, const CullView &cull, const GridView 
                 double lo, hi;
                 trt_point_shadow_bounds(G, light_d2, dot(sd, sd), &lo, &hi);
                 bool dark, unsure;
-                point_light_search(L, n, o, sd, lit_lanes, gp, gn, tally.iters[2], tally.tests[2], cell, grids.pool, grids.list_bits, lo, hi, dark, unsure);
+                point_light_search(L, n, o, sd, lit_lanes, lit_word, gp, gn, tally.iters[2], tally.tests[2], cell, grids.pool, grids.list_bits, lo, hi, dark, unsure);
                 is_lit = !dark;
                 full = __any(lit_lanes && unsure);
                 TRT_MARK_AT(17); // any-hit search
@@ -819,7 +846,7 @@ TRT_DEV d3 shadow_stage(const LdsImage &L, const CullView &cull, const GridView 
             {
                 if (COUNT)
                     tally.full++;
-                const Hit sh = trace<false, false, 26>(L, cull, n, o, sd, lit_lanes, gp, gn, tally.iters[2], tally.tests[2], nullptr, use_list, cell, grids.pool, grids.list_bits);
+                const Hit sh = trace<false, false, 26>(L, cull, n, o, sd, lit_lanes, lit_word, gp, gn, tally.iters[2], tally.tests[2], nullptr, use_list, cell, grids.pool, grids.list_bits);
                 is_lit = sh.i < 0;
                 // A blocker: is it farther than the light?  The reference compares light_d2 with the squared distance to the
                 // blocker point NUDGED 1e-6 back along the ray (TRT.c:871-874, :939-942): (D - 1e-6)^2 up to ~1e-14 relative
@@ -1157,7 +1184,8 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
                 }
             }
         }
-        if (!__any(alive || (COMPACT && waiting)))
+        const unsigned long long alive_lanes = lanes_with(alive); // the round's votes AND their compares into it (trt_device.hpp, lanes_with)
+        if ((COMPACT ? alive_lanes | lanes_with(waiting) : alive_lanes) == 0)
             break;
         if (COUNT)
             tally.rounds++;
@@ -1171,7 +1199,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
         PathHit hit;
         {
             TRT_FRESH_ARGS;
-            hit = path_stage<COUNT, REFRACT, PATCHES, BATCH>(L, cull, grids, n, o, d, fam, alive, gp, gn, tally, inside, BATCH ? bounces >> kBatchFrameShift : 0);
+            hit = path_stage<COUNT, REFRACT, PATCHES, BATCH>(L, cull, grids, n, o, d, fam, alive, alive_lanes, gp, gn, tally, inside, BATCH ? bounces >> kBatchFrameShift : 0);
         }
         if constexpr (COMPACT)
         {
@@ -1181,10 +1209,10 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
             const double weight_before = weight;
             {
             TRT_FRESH_ARGS;
-            if (__any(path_sky))
-                sky_t = sky_texel_wave(s.sky, s.sky_dim, hit.back, s.sky_dim_f, path_sky); // TRT.c:858-867; added to the sample after the colours still on their way
+            if (hit.sky_lanes != 0)
+                sky_t = sky_texel_wave(s.sky, s.sky_dim, hit.back, s.sky_dim_f, path_sky, hit.sky_lanes); // TRT.c:858-867; added to the sample after the colours still on their way
             // ---- a hit becomes a task; what does not depend on its colour happens now (TRT.c:1036-1038, :1054) ----
-            const unsigned long long hits = __ballot(path_hit);
+            const unsigned long long hits = hit.hit_lanes;
             if (hits)
             {
                 if (path_hit)
@@ -1225,7 +1253,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
                 const int sm = ring_mat[at];
                 if (COUNT)
                     tally.passes++;
-                const d3 lit = shadow_stage<COUNT>(L, cull, grids, n, nd, nl, so, sn, sm, has, gp, gn, tally);
+                const d3 lit = shadow_stage<COUNT>(L, cull, grids, n, nd, nl, so, sn, sm, has, lanes_with(has), gp, gn, tally);
                 d3 color = d3{clampd(lit.x, 0.0, 1.0), clampd(lit.y, 0.0, 1.0), clampd(lit.z, 0.0, 1.0)}; // TRT.c:960-962
                 color = scale(color, ring[6 * kRingTasks + at]);                                          // TRT.c:1035
                 if (has) // the colour takes the place of the normal in the task's record; its owner collects it at the END of a round
@@ -1296,12 +1324,12 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
         bool end_sample = false;
         double weight_sum_new = weight_sum + weight; // TRT.c:1034
         uint32_t sky_t = 0;
-        if (__any(path_sky))
+        if (hit.sky_lanes != 0)
         { // TRT.c:858-867, :1044-1048: colour = texel, the sample ends here.  The texel is only LOADED here: it is a dependent read
           // from global memory, and what uses it (the sample's colour) is not needed before the END of the round, behind the other
           // lanes' shadow stages
             TRT_FRESH_ARGS;
-            sky_t = sky_texel_wave(s.sky, s.sky_dim, hit.back, s.sky_dim_f, path_sky);
+            sky_t = sky_texel_wave(s.sky, s.sky_dim, hit.back, s.sky_dim_f, path_sky, hit.sky_lanes);
             end_sample = path_sky;
         }
         d3 lit;
@@ -1314,11 +1342,11 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
             }
             TRT_MARK_AT(7); // P post: sky texel, reflection, nudge
             // ===================================== S(i): shadow rays =====================================
-            if (COUNT && __any(path_hit))
+            if (COUNT && hit.hit_lanes != 0)
                 tally.passes++;
             {
                 TRT_FRESH_ARGS;
-                lit = shadow_stage<COUNT>(L, cull, grids, n, nd, nl, o, h_normal, h_mat, path_hit, gp, gn, tally);
+                lit = shadow_stage<COUNT>(L, cull, grids, n, nd, nl, o, h_normal, h_mat, path_hit, hit.hit_lanes, gp, gn, tally); // !REFRACT: path_hit is hit.hit
             }
         }
         else
@@ -1357,7 +1385,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
                     o = shade_at;
                 }
             }
-            lit = shadow_stage<COUNT>(L, cull, grids, n, nd, nl, shade_at, h_normal, h_mat, path_hit, gp, gn, tally);
+            lit = shadow_stage<COUNT>(L, cull, grids, n, nd, nl, shade_at, h_normal, h_mat, path_hit, lanes_with(path_hit), gp, gn, tally);
         }
 
         TRT_MARK_AT(20); // lit accumulate
@@ -1459,10 +1487,10 @@ __global__ __launch_bounds__(kPersistentBlock) void probe_rounds_kernel(SceneVie
     const d3 o = load3(rays + 6 * at), d = load3(rays + 6 * at + 3);
     int fam = families ? families[at] : -1;
     Tally tally;
-    const PathHit hit = path_stage<false, false, PATCHES>(L, cull, grids, n, o, d, fam, alive, gp, gn, tally);
+    const PathHit hit = path_stage<false, false, PATCHES>(L, cull, grids, n, o, d, fam, alive, lanes_with(alive), gp, gn, tally);
     const d3 surface = hit.hit ? add(hit.ph.p, scale(hit.back, 0.000001)) : o; // TRT.c:873-874 / :860
-    const d3 lit = shadow_stage<false>(L, cull, grids, n, nd, nl, surface, hit.normal, hit.mat, hit.hit, gp, gn, tally);
-    const uint32_t sky_t = sky_texel_wave(s.sky, s.sky_dim, hit.back, s.sky_dim_f, alive && !hit.hit); // the render kernels' look-up
+    const d3 lit = shadow_stage<false>(L, cull, grids, n, nd, nl, surface, hit.normal, hit.mat, hit.hit, hit.hit_lanes, gp, gn, tally);
+    const uint32_t sky_t = sky_texel_wave(s.sky, s.sky_dim, hit.back, s.sky_dim_f, alive && !hit.hit, hit.sky_lanes); // the render kernels' look-up
     if (!alive)
         return;
     d3 color = d3{0.0, 0.0, 0.0};

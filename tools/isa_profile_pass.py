@@ -56,7 +56,7 @@ def main():
     in_instrumented_desc = set()
     while i < len(lines):
         l = lines[i]
-        if l.startswith("_ZN3trt20render_rounds_kernelILb0E") and ":" in l and l.split(":")[0].endswith("E"):
+        if l.startswith("_ZN3trt20render_rounds_kernelILb0E") and ":" in l and l.split(":")[0].endswith(("E", "_")):  # "_": the kernel's parameter pack (BatchArgument...) ends the mangled name
             name = l.split(":")[0]
             end = next(j for j in range(i + 1, len(lines)) if lines[j].strip().startswith(".Lfunc_end"))
             body = lines[i + 1:end]
