@@ -62,6 +62,12 @@ int render_frame(const Scene *scene, Screen *screen, int bounce_limit, int rays_
  * [0, 1) convert as the reference's cast does on x86-64. */
 int trt_render_frame_rgb8(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, unsigned char *rgb);
 
+/* The same frame as the TEXT the emitter makes of it: what buffered_draw_screen (TRT.c:1142-1172) writes to the terminal -- "\033[0;0H", per
+ * row `width` cells "\033[48;2;RRR;GGG;BBBm  \033[0m" and a newline, three NUL bytes -- formatted on the device by the pass that forms the
+ * ordered mean.  text holds trt_ansi_bytes(width, height) bytes, the whole of which the host writes with one fwrite: byte for byte the
+ * buffer of a trt_emitter (trt_host.h) after trt_emitter_patch_rgb8 of trt_render_frame_rgb8's bytes.  Lock and scene policy as above. */
+int trt_render_frame_ansi(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text);
+
 /* project_scene is a pure function of *scene (TRT.c:966): a caller may move a sphere before every call.  The drop-in entries
  * compare the primitives with the previous call's; a scene that has changed on `moving_after` consecutive calls counts as MOVING
  * and its candidate tables are rebuilt per call the cheap way (one family per sphere instead of 24 patches: ~4 ms instead of ~100 ms
@@ -153,6 +159,25 @@ int trt_render_device_rgb8(trt_context *ctx, const Camera *camera, const trt_row
 /* (int)(c*255) per channel (TRT.c:1157-1163) on the device: 3 bytes per pixel. Asynchronous. */
 int trt_quantize_device(trt_context *ctx, const void *d_pixels, size_t num_pixels, void *d_rgb8);
 
+/* Length of the terminal's text of a screen of `width` x `rows` owned rows: 8 + (25 * width + 1) * rows + 1 (sizeof(screenbuffer),
+ * TRT.c:1104; trt_emitter_size for every size), 0 unless both are positive. */
+size_t trt_ansi_bytes(int width, int rows);
+
+/* trt_render_device as the terminal's text: the 6 bytes "\033[0;0H"; per owned row, in ascending order, `width` cells of 25 bytes
+ * "\033[48;2;RRR;GGG;BBBm  \033[0m" and '\n'; three NUL bytes -- trt_ansi_bytes(width, owned rows) bytes, what trt_emitter_create(width,
+ * owned rows) and trt_emitter_patch_rgb8 of trt_render_device_rgb8's bytes leave in trt_emitter_buffer; for the whole frame the reference's
+ * screenbuffer.  Written by the pass that forms the ordered mean: neither doubles nor RGB8 bytes are written on the way, every byte of the
+ * text is stored exactly once (d_text need not be initialised) and none outside it (the reference-order kernel, trt_set_kernel(ctx, 1),
+ * goes through a framebuffer and bytes of the context's).  d_text may have any alignment; capacity_bytes counts bytes of text, to the
+ * byte; checks and errors as trt_render_device_rgb8.  Asynchronous on the context's stream.  One entry of trt_kernel_times;
+ * trt_render_kernel_times reports the pass as reduce_ms. */
+int trt_render_device_ansi(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,
+                           int rays_per_pixel, void *d_text, size_t capacity_bytes);
+
+/* The formatting alone, of a frame that exists as RGB8 bytes in device memory (d_rgb8[(row*width + col)*3 + channel], e.g. what rank 0 of
+ * a trt_dist_render_rgb8 gather holds): trt_ansi_bytes(width, rows) bytes at d_text, any alignment.  Asynchronous on the context's stream. */
+int trt_ansi_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text);
+
 /* Same as trt_render_device but into HOST memory (synchronous; pinned staging inside). */
 int trt_render_host(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,
                     int rays_per_pixel, Vector *pixels);
@@ -160,6 +185,10 @@ int trt_render_host(trt_context *ctx, const Camera *camera, const trt_rowset *ro
 /* trt_render_device_rgb8 into HOST memory: the emitter's (int)(c*255), 3 bytes per pixel (synchronous; pinned staging inside). */
 int trt_render_host_rgb8(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
                          unsigned char *rgb);
+
+/* trt_render_device_ansi into HOST memory: trt_ansi_bytes(width, owned rows) bytes (synchronous; one copy-out through pinned staging). */
+int trt_render_host_ansi(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                         char *text);
 
 /* Several cameras of the current scene in one call: an orbit, a replay, a stereo pair, the faces of an environment probe. */
 #define TRT_BATCH_MAX 8 /* = the eye-table slots a scene's tables have */
@@ -191,6 +220,14 @@ int trt_render_device_batch_rgb8(trt_context *ctx, const Camera *cameras, int n,
 /* The same into HOST memory: rgb[b * owned rows * width * 3 ...] (synchronous; one copy-out through pinned staging). */
 int trt_render_host_batch_rgb8(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
                                int rays_per_pixel, unsigned char *rgb);
+/* trt_render_device_batch as the terminal's text (trt_render_device_ansi): frame b at d_text + b * trt_ansi_bytes(width, owned rows),
+ * which is aligned to nothing in general (the text of 160 x 48 is 192057 bytes long); launches, splits and trt_batch_info exactly as
+ * trt_render_device_batch decides them; the same errors, the capacity counted in bytes of text for n frames. */
+int trt_render_device_batch_ansi(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                 int rays_per_pixel, void *d_text, size_t capacity_bytes);
+/* The same into HOST memory: text[b * trt_ansi_bytes(width, owned rows) ...] (synchronous; one copy-out through pinned staging). */
+int trt_render_host_batch_ansi(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                               int rays_per_pixel, char *text);
 /* The most recent batch call of this context: its frames, and how many render-kernel launches served them
  * (1 = one launch over all frames; n = one launch per camera; between: the batch was split for LDS). */
 int trt_batch_info(trt_context *ctx, int *frames, int *render_launches);

@@ -202,10 +202,12 @@ struct trt_context
     std::vector<BatchOccupancy> batch_occupancy; // workgroups per CU of the BATCH instantiations, per LDS size asked so far
     DeviceBuffer<double> d_ior; // refraction extension: per sphere, > 0 = index of refraction
     DeviceBuffer<unsigned char> d_rgb8; // trt_render_host_rgb8: the quantised frame before it crosses PCIe
+    DeviceBuffer<unsigned char> d_text; // trt_render_host_ansi: the terminal's text before it crosses PCIe
+    DeviceBuffer<unsigned char> d_text_rgb8; // text frames of the reference-order kernel: the bytes the text is formatted from
     int ior_count = 0;          // 0 = off (the reference's path)
     DeviceBuffer<unsigned long long> d_counters;
     DeviceBuffer<unsigned int> d_queue;
-    PinnedBuffer h_staging; // trt_render_host, trt_render_host_rgb8
+    PinnedBuffer h_staging; // trt_render_host, trt_render_host_rgb8, trt_render_host_ansi
 
     // cache keys of the per-frame tables (jitter; per-column / per-row screen coordinates)
     int jit_spp = -1;

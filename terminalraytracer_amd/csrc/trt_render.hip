@@ -8,6 +8,7 @@
 #define TRT_REDUCE_BLOCK 64 // one wave: fits beside the render kernels of the frames in flight wherever a wave retires (+0.8 % decoupled)
 #endif
 #include "trt_simple.hpp"
+#include "trt_ansi.hpp"
 
 using namespace trt_impl;
 
@@ -367,13 +368,16 @@ extern "C" int trt_read_counters(trt_context *ctx, unsigned long long *path_rays
 
 // ---- the launch of a frame, or of several cameras of one scene (on the host a single frame is a batch of one) ----
 
-// What a launch leaves of a frame: the Screen's pixels of three doubles (TRT.c:188-193), or the emitter's three bytes per pixel
-// ((int)(c*255), TRT.c:1157-1163).
-enum Output : int { kDoubles, kBytes };
+// What a launch leaves of a frame: the Screen's pixels of three doubles (TRT.c:188-193), the emitter's three bytes per pixel
+// ((int)(c*255), TRT.c:1157-1163), or the text the emitter makes of those bytes (TRT.c:1142-1172; trt_ansi.h).
+enum Output : int { kDoubles, kBytes, kText };
 
-static size_t value_bytes(Output kind)
+// bytes of one frame of `rows` rows of `width` pixels
+static size_t frame_bytes(Output kind, int width, int rows)
 {
-    return kind == kBytes ? 1u : sizeof(double);
+    if (kind == kText)
+        return (size_t)trt_ansi_text_bytes(width, rows);
+    return (size_t)rows * width * 3 * (kind == kBytes ? 1u : sizeof(double));
 }
 
 // what the device entries refuse, for `frames` cameras into one framebuffer of `frames` frames of the rowset
@@ -395,7 +399,7 @@ static int check_render_arguments(const trt_context *ctx, const Camera *cameras,
     if (!ctx->have_scene)
         return fail(TRT_ERR_NO_SCENE, "trt_set_scene has not been called");
     const int local_rows = trt_rowset_rows(rows);
-    const size_t need = (size_t)local_rows * rows->width * 3 * value_bytes(kind) * frames;
+    const size_t need = frame_bytes(kind, rows->width, local_rows) * frames;
     if (capacity_bytes < need)
         return fail(TRT_ERR_CAPACITY, "framebuffer of %d frame(s) needs %zu B, %zu given", frames, need, capacity_bytes);
     if ((unsigned long long)local_rows * rows->width >= 0x7fffffffull)
@@ -443,6 +447,14 @@ static trt::FrameView frame_view(const trt_context *ctx, const Camera *camera, c
     return f;
 }
 
+// the text of a frame that exists as RGB8 bytes: the formatting alone (trt_ansi.hpp)
+static void launch_ansi_from_rgb8(hipStream_t stream, const unsigned char *d_rgb8, int width, int rows, void *d_text)
+{
+    const unsigned long long bytes = trt_ansi_text_bytes(width, rows), waves = trt_ansi_waves(trt_ansi_split_of((unsigned long long)d_text, bytes).words);
+    hipLaunchKernelGGL(trt::ansi_from_rgb8_kernel, dim3((unsigned)((waves * 64 + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK)), dim3(TRT_REDUCE_BLOCK), 0, stream, d_rgb8,
+                       (unsigned char *)d_text, width, rows, trt_ansi_row_magic(width));
+}
+
 // `lane_set` 0: the context's stream, queue word 0, d_samples; 1: the alternate stream, its own queue word and scratch
 // (trt_render_host renders odd bands there).
 // `entry`: a frame is one entry of the context's launch history (events, trt_kernel_times); the frames of a batch that is served
@@ -452,9 +464,10 @@ enum : int { kEntryOpens = 1, kEntryCloses = 2, kEntryWhole = kEntryOpens | kEnt
 
 // Carries out a planned launch: the queue started unless the launch before left it ready, the image staged for the DEVICE_IMAGE
 // instantiations, the render kernel over the frame `f` -- with `batch`, the plan's BATCH form over the frames of `batch`, of which
-// f is the first -- and the ordered mean of every frame's `pixels` pixels into `out`: as doubles, or (kBytes) cast to the emitter's
-// bytes in the same pass.  The reference-order kernel has no scratch and no mean: its bytes are its doubles, rendered into the
-// context's framebuffer, through quantize_kernel.
+// f is the first -- and the ordered mean of every frame's `pixels` pixels into `out`: as doubles, (kBytes) cast to the emitter's
+// bytes in the same pass, or (kText) cast and formatted as the terminal's text in the same pass.  The reference-order kernel has no
+// scratch and no mean: its bytes are its doubles, rendered into the context's framebuffer, through quantize_kernel, and its text is
+// those bytes through ansi_from_rgb8_kernel.
 static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameView f, const trt::GridView &grids, const trt::BatchView *batch, void *out,
                          Output kind, long pixels, int lane_set, int entry)
 {
@@ -471,18 +484,20 @@ static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameVie
 #endif
     if (reference)
     {
-        if (kind == kBytes)
+        if (kind != kDoubles)
         {
-            if (ctx->d_fb.capacity < (size_t)pixels * 3)
+            if (ctx->d_fb.capacity < (size_t)pixels * 3 || (kind == kText && ctx->d_text_rgb8.capacity < (size_t)pixels * 3))
                 HIP_TRY(hipStreamSynchronize(stream)); // a frame in flight may still use the old framebuffer
             HIP_TRY(ctx->d_fb.reserve((size_t)pixels * 3));
+            if (kind == kText) // text: the framebuffer's bytes first, in a buffer of the context's
+                HIP_TRY(ctx->d_text_rgb8.reserve((size_t)pixels * 3));
             f.out = ctx->d_fb.ptr;
         }
         if (ctx->scratch_fill) // trt_set_scratch_fill: the reference-order kernel has no scratch
         {
             HIP_TRY(hipMemsetAsync(f.out, 0xFF, (size_t)pixels * 3 * sizeof(double), stream));
-            if (kind == kBytes)
-                HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)pixels * 3, stream));
+            if (kind != kDoubles)
+                HIP_TRY(hipMemsetAsync(out, 0xFF, frame_bytes(kind, f.width, f.local_rows), stream));
         }
         if (entry & kEntryOpens)
             HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
@@ -492,9 +507,11 @@ static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameVie
             hipLaunchKernelGGL(trt::render_simple_kernel<true>, grid, block, 0, stream, ctx->scene, f);
         if (entry & kEntryCloses)
             HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
-        if (kind == kBytes)
+        if (kind != kDoubles)
             hipLaunchKernelGGL(trt::quantize_kernel, dim3((unsigned)((pixels * 3 + 255) / 256)), dim3(256), 0, stream, (const double *)f.out, pixels * 3,
-                               (unsigned char *)out);
+                               kind == kText ? ctx->d_text_rgb8.ptr : (unsigned char *)out);
+        if (kind == kText)
+            launch_ansi_from_rgb8(stream, ctx->d_text_rgb8.ptr, f.width, f.local_rows, out);
         if (entry & kEntryCloses)
             HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
     }
@@ -529,7 +546,7 @@ static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameVie
         if (ctx->scratch_fill)
         { // trt_set_scratch_fill: exactly the launch's samples and exactly its pixels read as NaN until the launch writes them
             HIP_TRY(hipMemsetAsync(scratch.ptr, 0xFF, samples * sizeof(double), stream));
-            HIP_TRY(hipMemsetAsync(out, 0xFF, (size_t)pixels * frames * 3 * value_bytes(kind), stream));
+            HIP_TRY(hipMemsetAsync(out, 0xFF, frame_bytes(kind, f.width, f.local_rows) * frames, stream));
         }
         const bool left_ready = ready[0] == plan.grid && ready[1] == plan.block / 64 && ready[2] == f.queue_shift; // by the frame before
         ready[0] = 0; // the render kernel uses it up; ready again once this frame's launches have gone in
@@ -550,9 +567,23 @@ static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameVie
             const long values = pixels * 3;
             // bytes: a lane per group of four values and one per value of a frame's head and tail (trt_common.hpp); the frames of a batch
             // start at any alignment, so its grid is sized for the most lanes an alignment needs
-            const long lanes = kind == kDoubles ? values : batch ? values / trt::kRgb8Group + 6 : trt::rgb8_lanes(values, trt::rgb8_head((const unsigned char *)out, values));
+            const long lanes = kind == kDoubles || kind == kText ? values : batch ? values / trt::kRgb8Group + 6 : trt::rgb8_lanes(values, trt::rgb8_head((const unsigned char *)out, values));
             const unsigned blocks = (unsigned)((lanes + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK);
-            if (kind == kBytes && batch)
+            if (kind == kText)
+            { // text: a wave per TRT_ANSI_WAVE_WORDS aligned words (trt_ansi.h); a batch's grid is sized for the most words an alignment leaves
+                const unsigned long long bytes = trt_ansi_text_bytes(f.width, f.local_rows);
+                const unsigned long long waves = trt_ansi_waves(batch ? bytes / 4 : trt_ansi_split_of((unsigned long long)out, bytes).words);
+                const unsigned text_blocks = (unsigned)((waves * 64 + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK);
+                if (batch)
+                    hipLaunchKernelGGL(trt::reduce_samples_ansi_batch_kernel, dim3(text_blocks, frames), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr,
+                                       (unsigned char *)out, f.width, f.local_rows, trt_ansi_row_magic(f.width), f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64,
+                                       f.queue_shift);
+                else
+                    hipLaunchKernelGGL(trt::reduce_samples_ansi_kernel, dim3(text_blocks), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr,
+                                       (unsigned char *)out, f.width, f.local_rows, trt_ansi_row_magic(f.width), f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64,
+                                       f.queue_shift);
+            }
+            else if (kind == kBytes && batch)
                 hipLaunchKernelGGL(trt::reduce_samples_rgb8_batch_kernel, dim3(blocks, frames), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr,
                                    (unsigned char *)out, values, f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
             else if (kind == kBytes)
@@ -622,6 +653,29 @@ extern "C" int trt_render_device_rgb8(trt_context *ctx, const Camera *camera, co
                                       size_t capacity_bytes)
 {
     return render_device_on(ctx, camera, rows, bounce_limit, rays_per_pixel, d_rgb8, capacity_bytes, 0, kEntryWhole, kBytes);
+}
+
+extern "C" size_t trt_ansi_bytes(int width, int rows)
+{
+    return (size_t)trt_ansi_text_bytes(width, rows);
+}
+
+extern "C" int trt_render_device_ansi(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                                      size_t capacity_bytes)
+{
+    return render_device_on(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, 0, kEntryWhole, kText);
+}
+
+extern "C" int trt_ansi_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text)
+{
+    if (!ctx || !d_rgb8 || !d_text)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (width <= 0 || rows <= 0 || (unsigned long long)width * rows >= 0x7fffffffull)
+        return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, rows);
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_ansi_from_rgb8(ctx->stream, (const unsigned char *)d_rgb8, width, rows, d_text);
+    HIP_TRY(hipGetLastError());
+    return TRT_OK;
 }
 
 extern "C" int trt_quantize_device(trt_context *ctx, const void *d_pixels, size_t num_pixels, void *d_rgb8)
@@ -780,14 +834,15 @@ static int fit_batch(trt_context *ctx, long units_per_frame, int spp, int remain
     }
 }
 
-// frame b's values in `kind` at d_pixels + b * values * value_bytes(kind)
+// frame b in `kind` at d_pixels + b * frame_bytes(kind, width, owned rows)
 static int render_device_batch(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_pixels,
                                size_t capacity_bytes, Output kind)
 {
     int rc = check_render_arguments(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_pixels, capacity_bytes, kind);
     if (rc)
         return rc;
-    const long pixels = (long)trt_rowset_rows(rows) * rows->width, units = pixels * rays_per_pixel, values = pixels * 3;
+    const long pixels = (long)trt_rowset_rows(rows) * rows->width, units = pixels * rays_per_pixel;
+    const size_t each = frame_bytes(kind, rows->width, trt_rowset_rows(rows));
     const bool shared = ctx->T.use_count() > 1;
     if (n > 1 && shared)
         return fail(TRT_ERR_CAPACITY, "this context's scene tables are shared with %ld other context(s) (trt_share_scene): their eye slots are the sharers', "
@@ -803,8 +858,7 @@ static int render_device_batch(trt_context *ctx, const Camera *cameras, int n, c
     {
         for (int b = 0; b < n; b++)
         {
-            rc = render_device_on(ctx, &cameras[b], rows, bounce_limit, rays_per_pixel, (char *)d_pixels + (size_t)b * values * value_bytes(kind),
-                                  (size_t)values * value_bytes(kind), 0, (b == 0 ? kEntryOpens : 0) | (b == n - 1 ? kEntryCloses : 0), kind);
+            rc = render_device_on(ctx, &cameras[b], rows, bounce_limit, rays_per_pixel, (char *)d_pixels + (size_t)b * each, each, 0, (b == 0 ? kEntryOpens : 0) | (b == n - 1 ? kEntryCloses : 0), kind);
             if (rc)
                 return rc;
             ctx->batch_launches++;
@@ -843,7 +897,7 @@ static int render_device_batch(trt_context *ctx, const Camera *cameras, int n, c
         batch.units_per_frame = (unsigned)units;
         batch.frame_magic = division_magic((unsigned long long)units);
         rc = launch_render(ctx, plan, frame_view(ctx, &cameras[first], rows, bounce_limit, rays_per_pixel, kind == kDoubles ? d_pixels : nullptr, 0), g, &batch,
-                           (char *)d_pixels + (size_t)first * values * value_bytes(kind), kind, pixels, 0,
+                           (char *)d_pixels + (size_t)first * each, kind, pixels, 0,
                            (first == 0 ? kEntryOpens : 0) | (first + m == n ? kEntryCloses : 0));
         if (rc)
             return rc;
@@ -862,6 +916,33 @@ extern "C" int trt_render_device_batch_rgb8(trt_context *ctx, const Camera *came
                                             void *d_rgb8, size_t capacity_bytes)
 {
     return render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_rgb8, capacity_bytes, kBytes);
+}
+
+extern "C" int trt_render_device_batch_ansi(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                            void *d_text, size_t capacity_bytes)
+{
+    return render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, kText);
+}
+
+extern "C" int trt_render_host_batch_ansi(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text)
+{
+    if (!ctx || !text)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (n < 1 || n > TRT_BATCH_MAX)
+        return fail(TRT_ERR_ARGUMENT, "a batch has 1 to %d cameras, %d given", TRT_BATCH_MAX, n);
+    if (!rowset_valid(rows))
+        return fail(TRT_ERR_ARGUMENT, "invalid rowset");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n * trt_ansi_bytes(rows->width, trt_rowset_rows(rows));
+    HIP_TRY(ctx->d_text.reserve(std::max<size_t>(bytes, 1)));
+    HIP_TRY(ctx->h_staging.reserve(std::max<size_t>(bytes, 1)));
+    const int rc = trt_render_device_batch_ansi(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, bytes);
+    if (rc || bytes == 0)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_text.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(text, ctx->h_staging.ptr, bytes);
+    return TRT_OK;
 }
 
 extern "C" int trt_render_host_batch_rgb8(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
@@ -1068,3 +1149,27 @@ extern "C" int trt_render_host_rgb8(trt_context *ctx, const Camera *camera, cons
     return TRT_OK;
 }
 
+extern "C" int trt_render_host_ansi(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text)
+{
+    if (!ctx || !text)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (!rowset_valid(rows))
+        return fail(TRT_ERR_ARGUMENT, "invalid rowset");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = trt_ansi_bytes(rows->width, trt_rowset_rows(rows));
+    if (bytes == 0)
+        return TRT_OK;
+    HIP_TRY(ctx->d_text.reserve(bytes));
+    HIP_TRY(ctx->h_staging.reserve(bytes));
+    const double t_begin = host_now_ms();
+    // the ordered mean writes the text itself (TRT.c:1142-1172): neither doubles nor RGB8 bytes on the way, and no formatting on the host
+    const int rc = trt_render_device_ansi(ctx, camera, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, bytes);
+    if (rc)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_text.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(text, ctx->h_staging.ptr, bytes);
+    if (print_host_times())
+        fprintf(stderr, "trt_render_host_ansi: %.3f ms for %zu bytes of text\n", host_now_ms() - t_begin, bytes);
+    return TRT_OK;
+}

@@ -434,7 +434,10 @@ int build_tables(trt_context *ctx, const trt_cull_scene &cs, const double *groun
         if (rc || ctx->list_pool_cap)
             break; // a capped pool (tests) stays capped
         unsigned long long asked = 0;
-        HIP_TRY(hipMemcpy(&asked, ctx->T->d_pool_used.ptr, sizeof asked, hipMemcpyDeviceToHost)); // the builders have been synchronised
+        // on the context's stream, behind the memset above: with the light tables and the path tables both switched off no builder has
+        // synchronised it, and a copy on the null stream does not wait for a non-blocking one (it then read what hipMalloc handed out)
+        HIP_TRY(hipMemcpyAsync(&asked, ctx->T->d_pool_used.ptr, sizeof asked, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
         if (asked <= ctx->T->pool_scene_words)
             break;
         ctx->T->pool_scene_words = (size_t)asked + 1024;

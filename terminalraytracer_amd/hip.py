@@ -49,6 +49,7 @@ SYMBOLS = {
     "trt_render_frame": (_I, [C.POINTER(L.Scene), C.POINTER(L.Screen), _I, _I]),
     "render_frame": (_I, [C.POINTER(L.Scene), C.POINTER(L.Screen), _I, _I]),
     "trt_render_frame_rgb8": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP]),
+    "trt_render_frame_ansi": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP]),
     "trt_init": (_I, [_I]),
     "trt_shutdown": (_I, []),
     "trt_upload_skybox": (_I, [C.POINTER(L.Skybox)]),
@@ -62,12 +63,18 @@ SYMBOLS = {
     "trt_render_device": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ]),
     "trt_render_device_rgb8": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ]),
     "trt_quantize_device": (_I, [_VP, _VP, _SZ, _VP]),
+    "trt_ansi_bytes": (_SZ, [_I, _I]),
+    "trt_render_device_ansi": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ]),
+    "trt_ansi_from_rgb8_device": (_I, [_VP, _VP, _I, _I, _VP]),
     "trt_render_host": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP]),
     "trt_render_host_rgb8": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP]),
+    "trt_render_host_ansi": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP]),
     "trt_render_device_batch": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ]),
     "trt_render_host_batch": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP]),
     "trt_render_device_batch_rgb8": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ]),
     "trt_render_host_batch_rgb8": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP]),
+    "trt_render_device_batch_ansi": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ]),
+    "trt_render_host_batch_ansi": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP]),
     "trt_batch_info": (_I, [_VP, C.POINTER(_I), C.POINTER(_I)]),
     "trt_synchronize": (_I, [_VP]),
     "trt_kernel_times": (_I, [_VP, C.POINTER(C.c_float), _I]),
@@ -399,6 +406,24 @@ class Context:
         _check(lib().trt_render_host_rgb8(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data))
         return out
 
+    def render_device_ansi(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
+        """the frame as the terminal's text in device memory, ansi_bytes(width, owned rows) bytes at any alignment, formatted by the
+        ordered-mean pass itself (trt_render_device_ansi)"""
+        cam = camera_struct(camera_array)
+        _check(lib().trt_render_device_ansi(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel,
+                                            _VP(device_ptr), capacity_bytes))
+
+    def render_host_ansi(self, camera_array, rows, bounce_limit, rays_per_pixel):
+        """the frame as the terminal's text, formatted on the device: uint8 [ansi_bytes(width, owned rows)] (trt_render_host_ansi)"""
+        out = np.zeros(ansi_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows))), dtype=np.uint8)
+        cam = camera_struct(camera_array)
+        _check(lib().trt_render_host_ansi(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data))
+        return out
+
+    def ansi_from_rgb8(self, rgb_ptr, width, rows, text_ptr):
+        """the text of a width x rows frame of RGB8 bytes in device memory, at text_ptr (trt_ansi_from_rgb8_device)"""
+        _check(lib().trt_ansi_from_rgb8_device(self._h, _VP(rgb_ptr), width, rows, _VP(text_ptr)))
+
     @staticmethod
     def _camera_batch(cameras):
         cams = np.ascontiguousarray(cameras, dtype=np.float64)
@@ -431,6 +456,21 @@ class Context:
         cams = self._camera_batch(cameras)
         out = np.zeros((cams.shape[0], lib().trt_rowset_rows(C.byref(rows)), rows.width, 3), dtype=np.uint8)
         _check(lib().trt_render_host_batch_rgb8(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
+                                                out.ctypes.data))
+        return out
+
+    def render_batch_ansi(self, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
+        """cameras[n, 15] as the terminal's text in device memory; frame b at device_ptr + b * ansi_bytes(width, owned rows)
+        (trt_render_device_batch_ansi)"""
+        cams = self._camera_batch(cameras)
+        _check(lib().trt_render_device_batch_ansi(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
+                                                  _VP(device_ptr), capacity_bytes))
+
+    def render_host_batch_ansi(self, cameras, rows, bounce_limit, rays_per_pixel):
+        """the same into host memory: uint8 [n, ansi_bytes(width, owned rows)] (trt_render_host_batch_ansi)"""
+        cams = self._camera_batch(cameras)
+        out = np.zeros((cams.shape[0], ansi_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows)))), dtype=np.uint8)
+        _check(lib().trt_render_host_batch_ansi(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
                                                 out.ctypes.data))
         return out
 
@@ -539,6 +579,20 @@ def render_frame_rgb8(scene_data, width, height, bounce_limit=10, rays_per_pixel
     scene = scene_data.as_scene()
     out = np.zeros((height, width, 3), dtype=np.uint8)
     _check(lib().trt_render_frame_rgb8(C.byref(scene), width, height, bounce_limit, rays_per_pixel, out.ctypes.data))
+    return out
+
+
+def ansi_bytes(width, rows):
+    """length of the terminal's text of a width x rows screen: 8 + (25 * width + 1) * rows + 1, 0 unless both are positive (trt_ansi_bytes)"""
+    return int(lib().trt_ansi_bytes(width, rows))
+
+
+def render_frame_ansi(scene_data, width, height, bounce_limit=10, rays_per_pixel=10):
+    """Host-in, terminal-text-out frame: uint8 [ansi_bytes(width, height)], what buffered_draw_screen writes, formatted on the device
+    (trt_render_frame_ansi)."""
+    scene = scene_data.as_scene()
+    out = np.zeros(ansi_bytes(width, height), dtype=np.uint8)
+    _check(lib().trt_render_frame_ansi(C.byref(scene), width, height, bounce_limit, rays_per_pixel, out.ctypes.data))
     return out
 
 
