@@ -72,7 +72,10 @@ int trt_render_frame_ansi(const Scene *scene, int width, int height, int bounce_
  * compare the primitives with the previous call's; a scene that has changed on `moving_after` consecutive calls counts as MOVING
  * and its candidate tables are rebuilt per call the cheap way (one family per sphere instead of 24 patches: ~4 ms instead of ~100 ms
  * at 256 spheres), and after `still_after` consecutive unchanged calls the full tables are built once.  moving_after = 0: every
- * change builds the full tables.  Defaults 2 and 3.  Frames are bit-identical whichever tables serve them.
+ * change builds the full tables, and a scene that counts as moving when this is set stops doing so at once (its next call builds
+ * the full tables).  What counts as a change: the spheres, either light array, or the ground's point or normal differ bytewise from
+ * the previous call's; camera, ground materials, skybox, frame size, bounce limit and rays per pixel do not.  Defaults 2 and 3.
+ * Frames are bit-identical whichever tables serve them.
  * trt_scene_is_moving: 1 while the default context treats its scene as moving. */
 int trt_set_scene_policy(int moving_after, int still_after);
 int trt_scene_is_moving(void);
@@ -82,8 +85,11 @@ int trt_init(int device);
 int trt_shutdown(void);
 
 /* Pre-upload a cubemap for the default context (what load_skybox, TRT.c:388, produced).  The
- * default context otherwise uploads on first use and re-uploads only when the face pointers,
- * the dimension or trt_invalidate_skybox() say the texels changed. */
+ * default context otherwise uploads on first use and re-uploads only when the face pointers, the
+ * dimension, a stamp of sampled texels or trt_invalidate_skybox() say the texels changed.  The stamp
+ * hashes about 256 texels of every face at a fixed stride (texel 0 of each face among them) and the
+ * last texel of the last face, on every call: an image loaded into the same allocation shows.  Texels
+ * edited in place that the stamp does not sample are NOT noticed: call trt_invalidate_skybox(). */
 int trt_upload_skybox(const Skybox *skybox);
 int trt_invalidate_skybox(void);
 

@@ -8,6 +8,7 @@
  *   self-tests    device division / square root / normalisation / cube instructions / skybox estimate against their references
  *   probes        single rays through the reference-order kernel and through the production kernel's stages
  *   scene image   where the kernels read the scene from: LDS or device memory
+ *   drop-in       a borrowed handle to the default context; how many table builds and skybox uploads a context has performed
  *   test hooks    the pool cap of the long candidate lists; a NaN fill of a launch's scratch and output; a stand-in for RCCL so that several ranks can share one GPU
  */
 #ifndef TRT_HIP_DIAG_H
@@ -152,6 +153,18 @@ int trt_set_scratch_fill(trt_context *ctx, int on);
  * box).  Must be called before the process's first use of RCCL: fails with TRT_ERR_NOT_INITIALISED once RCCL has been bound.  A
  * process that never calls it ignores the variable.  trt_dist_rccl_library() (trt_hip.h) says what was bound. */
 int trt_dist_allow_rccl_override(int allow);
+
+/* Tests of the drop-in layer (trt_hip.h section 1), which hands out no context: the default context behind project_scene and its
+ * siblings, BORROWED -- NULL before the first call that creates it and after trt_shutdown, never to be destroyed by the caller, and
+ * dangling once trt_shutdown or a trt_init of another device has destroyed it.  The getters of both headers may be called on it
+ * between two drop-in calls of the same thread (trt_get_path_patches, trt_scene_info, trt_build_counts); nothing locks them. */
+trt_context *trt_default_context(void);
+
+/* What a context has built since it was created, two counts that only grow: table_builds, the builds of the scene's candidate
+ * tables (light tables and sphere families together: one per trt_set_scene, per table setter with a scene in place, and per drop-in
+ * call whose primitives changed or whose scene was promoted from moving to still), and skybox_uploads, the cubemaps sent to the
+ * device.  The eye's two tables, rebuilt on the GPU per camera, are not counted.  Either pointer may be NULL. */
+int trt_build_counts(trt_context *ctx, unsigned long long *table_builds, unsigned long long *skybox_uploads);
 
 #ifdef __cplusplus
 }

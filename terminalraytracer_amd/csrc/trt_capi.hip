@@ -62,6 +62,7 @@ int upload_skybox(trt_context *ctx, const Skybox *sky)
         ctx->sky_faces[f] = sky->colors[f];
     ctx->sky_dim = dim;
     ctx->sky_stamp = skybox_stamp(sky);
+    ctx->skybox_uploads++;
     return TRT_OK;
 }
 

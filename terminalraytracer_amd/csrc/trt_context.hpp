@@ -245,6 +245,8 @@ struct trt_context
     const void *sky_faces[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int sky_dim = -1;
     unsigned long long sky_stamp = 0; // content stamp of the faces (sampled texels): a free-and-reload at the same addresses is noticed
+    // trt_build_counts (trt_hip_diag.h): build_tables calls and cubemaps sent to the device since the context was created
+    unsigned long long table_builds = 0, skybox_uploads = 0;
 
     // After this body the members are destroyed in reverse order of declaration: the events and the two extra streams of
     // trt_render_host, then the buffers they copy, the scene tables (if this was their last context), own_stream last.

@@ -108,6 +108,11 @@ extern "C" int trt_set_scene_policy(int moving_after, int still_after)
     std::lock_guard<std::mutex> turn(g_default_mutex);
     g_moving_after = moving_after;
     g_still_after = still_after;
+    // "never": upload_primitives only ever sets the flag from a run of changes and clears it after still_after unchanged calls, so a
+    // context that is moving now would go on building the cheap tables for every further change.  Cleared here, the next call finds
+    // tables built for a moving scene under a scene that is not, and builds the full ones.
+    if (moving_after == 0 && g_default)
+        g_default->moving_scene = false;
     return TRT_OK;
 }
 
@@ -115,6 +120,24 @@ extern "C" int trt_scene_is_moving(void)
 {
     std::lock_guard<std::mutex> turn(g_default_mutex);
     return g_default && g_default->moving_scene ? 1 : 0;
+}
+
+// trt_hip_diag.h: the tests' handle on the default context and what it has built so far
+extern "C" trt_context *trt_default_context(void)
+{
+    std::lock_guard<std::mutex> turn(g_default_mutex);
+    return g_default;
+}
+
+extern "C" int trt_build_counts(trt_context *ctx, unsigned long long *table_builds, unsigned long long *skybox_uploads)
+{
+    if (!ctx)
+        return fail(TRT_ERR_ARGUMENT, "ctx is NULL");
+    if (table_builds)
+        *table_builds = ctx->table_builds;
+    if (skybox_uploads)
+        *skybox_uploads = ctx->skybox_uploads;
+    return TRT_OK;
 }
 
 extern "C" int trt_render_frame(const Scene *scene, Screen *screen, int bounce_limit, int rays_per_pixel)

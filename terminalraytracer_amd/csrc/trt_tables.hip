@@ -394,6 +394,7 @@ static int build_path_tables(trt_context *ctx, const trt_cull_scene &cs, const d
 // the eye's, which are rebuilt per camera), then the light tables, then the sphere families.
 int build_tables(trt_context *ctx, const trt_cull_scene &cs, const double *ground)
 {
+    ctx->table_builds++;
     const size_t n = ctx->T->h_spheres.size() / 9, nd = ctx->T->h_dir.size() / 6, np = ctx->T->h_point.size() / 7;
     const size_t gd = (size_t)ctx->dirgrid_cells, gp = (size_t)ctx->pointgrid_cells, ge = (size_t)ctx->path_g_eye, gs = (size_t)ctx->path_g_sph;
     const size_t sd = (size_t)std::max(ctx->dirgrid_slabs, 1), sp = (size_t)std::max(ctx->pointgrid_shells, 1);

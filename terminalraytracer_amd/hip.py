@@ -100,6 +100,8 @@ SYMBOLS = {
     "trt_set_scene_image": (_I, [_VP, _I]),
     "trt_render_image": (_I, [_VP, C.POINTER(_I), C.POINTER(C.c_ulonglong)]),
     "trt_set_scratch_fill": (_I, [_VP, _I]),
+    "trt_default_context": (_VP, []),
+    "trt_build_counts": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "trt_read_path_tables": (C.c_long, [_VP, C.POINTER(L.Camera), _VP, C.c_size_t, _VP, C.c_size_t, C.POINTER(C.c_long)]),
     "trt_read_sweep_fallbacks": (_I, [_VP, C.POINTER(C.c_ulonglong)]),
     "trt_read_shading_passes": (_I, [_VP, C.POINTER(C.c_ulonglong)]),
@@ -298,6 +300,12 @@ class Context:
         d, b = _I(), C.c_ulonglong()
         _check(lib().trt_render_image(self._h, C.byref(d), C.byref(b)))
         return {"in_device_memory": bool(d.value), "image_bytes": b.value}
+
+    def build_counts(self):
+        """(table builds, skybox uploads) this context has performed since it was created (trt_build_counts)"""
+        b, u = C.c_ulonglong(), C.c_ulonglong()
+        _check(lib().trt_build_counts(self._h, C.byref(b), C.byref(u)))
+        return b.value, u.value
 
     def set_scratch_fill(self, on=True):
         """tests: every launch first fills its own range of the sample scratch and its own output range with NaNs, so that a
@@ -563,6 +571,13 @@ class Context:
         _check(lib().trt_probe_rays_production(self._h, C.byref(cam), rays.ctypes.data, None if fam is None else fam.ctypes.data, n,
                                                obj.ctypes.data, point.ctypes.data, normal.ctypes.data, material.ctypes.data, lit.ctypes.data))
         return obj, point, normal, material, lit
+
+
+def default_context():
+    """The default context of the drop-in entries as a borrowed Context, None while there is none (trt_default_context); it dangles
+    once trt_shutdown has run."""
+    h = lib().trt_default_context()
+    return Context(0, _borrowed=h) if h else None
 
 
 def render_frame(scene_data, width, height, bounce_limit=10, rays_per_pixel=10, symbol="trt_render_frame"):

@@ -1043,7 +1043,9 @@ def test_lean_normalisation_and_sqrt_equal_the_plain_operators(ctx):
 
 def test_drop_in_symbol_may_be_called_from_several_threads(tmp_path):
     """The reference's project_scene is a pure function; a host may call it from several threads.  The drop-in layer shares
-    one device context behind a lock: four threads x five calls must all produce the same frame."""
+    one device context behind a lock: four threads x five calls, every thread with a scene of its own (2, 40, 130, 300 spheres, one
+    with its own cubemap), must each get the frame the program rendered for that scene before the threads started -- with the default
+    context thrashing between the scenes, which it must come to treat as one moving scene."""
     import os
     import subprocess
     exe = str(tmp_path / "mt_drop_in")
@@ -1051,7 +1053,7 @@ def test_drop_in_symbol_may_be_called_from_several_threads(tmp_path):
     subprocess.check_call(["gcc", "-O1", "-I" + os.path.join(T.ROOT, "include"), "-o", exe, os.path.join(T.ROOT, "tests", "mt_drop_in.c"),
                            "-L" + libdir, "-ltrt_hip", "-Wl,-rpath," + libdir, "-lpthread"])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "identical" in out.stdout, out.stdout + out.stderr
+    assert out.returncode == 0 and "identical" in out.stdout and "distinct" in out.stdout and "became moving" in out.stdout, out.stdout + out.stderr
 
 
 def _shadow_lane_activity(ctx, scene, w, h, b, spp, kernel):
@@ -1370,30 +1372,36 @@ def test_a_scene_that_changes_with_every_call_of_the_drop_in_entry(ctx):
     """project_scene is a pure function of *scene (TRT.c:966): a caller may move a sphere before EVERY call.  The drop-in layer then
     stops building the full tables (24 patches per sphere at 256 spheres: ~0.1 s) and builds the cheap ones (one family per sphere)
     per call; once the scene has been still for three calls it builds the full ones again.  20 calls with a sphere moved before
-    each, then 5 without: every frame is the oracle's, the layer says when it treats the scene as moving, and a moving call is
-    several times cheaper than a full build."""
+    each -- a far move, three units along x: tables left over from the call before would not serve it -- then 5 without: every frame
+    is the oracle's, the layer says when it treats the scene as moving, every changed call and the promotion build the tables exactly
+    once and no other call does (trt_build_counts on the borrowed default context), the moving scene's tables have no patches and the
+    still scene's have the automatic 24, and a moving call is several times cheaper than a full build."""
     import time
     scene = S.synth_scene(256, T.sky("synth"), T.bench_camera(96, 54))
     lib = hip.lib()
     hip._check(lib.trt_shutdown())  # a fresh default context: earlier tests have handed the drop-in entries other scenes
     hip._check(lib.trt_set_scene_policy(2, 3))
     try:
-        took, moving = [], []
+        took, moving, builds, patches = [], [], [], []
         for i in range(25):
             if i < 20:
                 sph = scene.spheres.copy()
-                sph[i % 256, 1] += 0.01 * (i + 1)
+                sph[i % 256, 0] += 3.0 if sph[i % 256, 0] < 0 else -3.0  # six radii at the least
                 scene = scene.with_spheres(sph)
             t0 = time.perf_counter()
             got = hip.render_frame(scene, 96, 54, 6, 4)
             took.append(time.perf_counter() - t0)
             moving.append(lib.trt_scene_is_moving())
+            builds.append(hip.default_context().build_counts()[0])
+            patches.append(hip.default_context().path_patches())
             if i in (0, 1, 2, 7, 19, 20, 22, 23, 24):
                 want, _ = T.oracle_render(scene, 96, 54, 6, 4)
                 assert np.array_equal(bits(got), bits(want)), i
         # call 0: the first scene (full tables); call 1: the second change in a row -> moving from here on; calls 20, 21 unchanged
         # but not yet still for three calls; call 22: still -> promoted (full build); 23, 24: nothing to build
         assert moving == [0] + [1] * 21 + [0] * 3, moving
+        assert builds == list(range(1, 21)) + [20, 20, 21, 21, 21], builds
+        assert patches == [(2, 24)] + [(0, 1)] * 21 + [(2, 24)] * 3, patches
         full, cheap, idle = took[22], float(np.median(took[3:20])), float(np.median(took[23:]))
         print(f"\nper call at 256 spheres, 96x54: full tables {full * 1e3:.1f} ms, moving scene {cheap * 1e3:.1f} ms, unchanged {idle * 1e3:.1f} ms")
         assert cheap < 0.5 * full and idle < cheap
@@ -1401,10 +1409,11 @@ def test_a_scene_that_changes_with_every_call_of_the_drop_in_entry(ctx):
         hip._check(lib.trt_set_scene_policy(0, 3))
         sph = scene.spheres.copy()
         for i in range(3):
-            sph[5, 0] += 0.02
+            sph[5, 0] += 2.5 if i % 2 == 0 else -2.5
             scene = scene.with_spheres(sph.copy())
             got = hip.render_frame(scene, 96, 54, 6, 4)
             assert lib.trt_scene_is_moving() == 0
+            assert hip.default_context().build_counts()[0] == 22 + i and hip.default_context().path_patches() == (2, 24)
         want, _ = T.oracle_render(scene, 96, 54, 6, 4)
         assert np.array_equal(bits(got), bits(want))
     finally:
