@@ -68,6 +68,13 @@ int trt_render_frame_rgb8(const Scene *scene, int width, int height, int bounce_
  * buffer of a trt_emitter (trt_host.h) after trt_emitter_patch_rgb8 of trt_render_frame_rgb8's bytes.  Lock and scene policy as above. */
 int trt_render_frame_ansi(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text);
 
+/* The frame as the DELTA text against the frame this entry returned before (trt_render_host_ansi_delta below, on the default context: its
+ * format, its rules for the host and its errors).  The first call, the first call of another size and the first call after trt_shutdown
+ * return a keyframe: trt_render_frame_ansi's text.  text holds capacity_bytes >= trt_ansi_delta_capacity(width, height) bytes; the host
+ * writes *bytes of them.  Lock and scene policy as above: the scene may change between calls, the delta is between the two frames. */
+int trt_render_frame_ansi_delta(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text,
+                                size_t capacity_bytes, size_t *bytes);
+
 /* project_scene is a pure function of *scene (TRT.c:966): a caller may move a sphere before every call.  The drop-in entries
  * compare the primitives with the previous call's; a scene that has changed on `moving_after` consecutive calls counts as MOVING
  * and its candidate tables are rebuilt per call the cheap way (one family per sphere instead of 24 patches: ~4 ms instead of ~100 ms
@@ -183,6 +190,63 @@ int trt_render_device_ansi(trt_context *ctx, const Camera *camera, const trt_row
 /* The formatting alone, of a frame that exists as RGB8 bytes in device memory (d_rgb8[(row*width + col)*3 + channel], e.g. what rank 0 of
  * a trt_dist_render_rgb8 gather holds): trt_ansi_bytes(width, rows) bytes at d_text, any alignment.  Asynchronous on the context's stream. */
 int trt_ansi_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text);
+
+/* ---- the delta text: only the cells that changed --------------------------------------------------------------------------------
+ * A terminal keeps what it was sent.  The text above repaints every cell of every frame, 25 bytes each; the DELTA text between the frame
+ * the terminal shows and the next one holds, for every CHANGED cell (its three RGB8 bytes differ), rows ascending, left to right:
+ *   "\033[RRRRR;CCCCCH"        14 bytes, where a run of consecutive changed cells of one row starts: RRRRR = owned row + 1,
+ *                              CCCCC = 2 * column + 1 (a cell is two columns wide), five digits each, zero-padded
+ *   "\033[48;2;RRR;GGG;BBBm"   19 bytes, where a run starts or the new colour differs from the new colour of the cell to the left
+ *   two spaces
+ *   "\033[0m"                   4 bytes, where the run ends (runs never continue into the next row)
+ * and nothing for an unchanged cell: no prefix, no newline, no NUL; two equal frames give 0 bytes.  A text has at most
+ * rows * (21 * width + 18) bytes (a run of L cells costs at most 18 + 21 L, and every further run of a row needs an unchanged cell
+ * between), reached when every cell changed and no two horizontal neighbours share a colour.  Limits: width <= 49999, rows <= 99999
+ * (five digits).  csrc/trt_ansi_delta.h is the format in code, trt_emitter_delta_rgb8 (trt_host.h) its sequential statement on the
+ * host.  On the demo orbit at 60 frames per second the text is a third of the full one with the reference's smooth cubemap and a half to four
+ * fifths with a noisy one (profiles/r11/a_delta.md).
+ *
+ * What a host of the render entries below must keep to:
+ *   - it writes exactly the `bytes` bytes it is given, not the capacity;
+ *   - a text it drops instead of writing is a frame the terminal never showed: call trt_ansi_delta_reset, the next text is a keyframe;
+ *   - nothing else may be printed over the picture (a status line belongs on stderr or below the last row);
+ *   - the refraction extension and the batch entries have no delta form; of a trt_dist_render_rgb8 gather rank 0 formats the
+ *     assembled bytes with trt_ansi_delta_from_rgb8_device. */
+
+/* Room for any text the delta entries write for a screen of `width` x `rows` owned rows: max(trt_ansi_bytes, rows * (21 * width + 18)),
+ * the keyframe or the longest delta; 0 when either is not positive or above the limits. */
+size_t trt_ansi_delta_capacity(int width, int rows);
+
+/* The formatting alone, of two frames that exist as RGB8 bytes in device memory (rows x width x 3 each, any alignment): the delta text
+ * that takes a terminal from d_shown_rgb8 to d_next_rgb8 at d_text (any alignment, need not be initialised), its length at *d_bytes --
+ * a DEVICE address, 8-byte aligned.  Three kernels in stream order (csrc/trt_ansi_delta.hpp): record lengths summed per tile of 1024
+ * cells, one workgroup's exclusive scan of the sums, the records stored at their offsets; every byte below the length is stored once,
+ * none at or behind it.  It neither reads nor changes the context's shown frame.  capacity_bytes >= trt_ansi_delta_capacity(width,
+ * rows), else TRT_ERR_CAPACITY; NULL or a size above the limits: TRT_ERR_ARGUMENT.  Asynchronous on the context's stream. */
+int trt_ansi_delta_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows,
+                                    void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+
+/* trt_render_device as the delta text against the context's SHOWN frame: the RGB8 bytes of the frame this entry (or the host entry
+ * below) rendered last, kept in one of two buffers of the context that swap per call.  The new frame's bytes are written by the RGB8
+ * form of the ordered-mean pass (trt_render_device_rgb8; the reference-order kernel goes through trt_quantize_device's kernel), then
+ * compared with the shown ones by the three kernels above.  When the context has no shown frame for exactly this rowset -- the first
+ * call, another trt_rowset, after trt_ansi_delta_reset or after a call that failed once it had begun to enqueue -- the call is a
+ * KEYFRAME: d_text is byte for byte trt_render_device_ansi's text and *d_bytes = trt_ansi_bytes(width, owned rows).  Either way the new
+ * frame becomes the shown one.  Every other render entry and trt_set_scene leave the shown frame alone: what the terminal shows did
+ * not change.  Rows count from the shard's first owned row, as in trt_render_device_ansi's shard texts.
+ * Errors, before anything is enqueued (the shown frame is kept): NULL, an invalid rowset, no owned row, a size above the limits ->
+ * TRT_ERR_ARGUMENT; no scene -> TRT_ERR_NO_SCENE; capacity_bytes < trt_ansi_delta_capacity(width, owned rows) -> TRT_ERR_CAPACITY.
+ * Asynchronous on the context's stream; d_bytes as above.  One entry of trt_kernel_times (the render and the ordered mean; the text
+ * kernels follow it). */
+int trt_render_device_ansi_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                 void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+/* The same into HOST memory, synchronous: the length is read back, then exactly *bytes bytes cross PCIe through the pinned staging --
+ * two small transfers instead of one large one.  capacity_bytes counts the bytes at text, checked as above. */
+int trt_render_host_ansi_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                               char *text, size_t capacity_bytes, size_t *bytes);
+/* Forget the shown frame: the next delta call returns a keyframe.  For a host that dropped a text, cleared its terminal or printed over
+ * the picture. */
+int trt_ansi_delta_reset(trt_context *ctx);
 
 /* Same as trt_render_device but into HOST memory (synchronous; pinned staging inside). */
 int trt_render_host(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,

@@ -166,6 +166,12 @@ trt_context *trt_default_context(void);
  * device.  The eye's two tables, rebuilt on the GPU per camera, are not counted.  Either pointer may be NULL. */
 int trt_build_counts(trt_context *ctx, unsigned long long *table_builds, unsigned long long *skybox_uploads);
 
+/* Measurement: trt_ansi_delta_from_rgb8_device (trt_hip.h) with a HIP event between its three kernels, SYNCHRONOUS: ms[0] the measure
+ * kernel (record lengths, a sum per tile), ms[1] the offsets kernel (one workgroup's scan of the sums, the length), ms[2] the write
+ * kernel (the records).  Same arguments, same text, same errors (tools/ansi_delta_bench.py). */
+int trt_ansi_delta_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                size_t capacity_bytes, unsigned long long *d_bytes, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,16 @@ size_t trt_emitter_size(const trt_emitter *e);
 int trt_emitter_patch(trt_emitter *e, const Screen *screen);
 /* the same from bytes already quantised on the GPU (trt_quantize_device): 3 bytes per pixel, width*height pixels */
 int trt_emitter_patch_rgb8(trt_emitter *e, const unsigned char *rgb);
+/* The DELTA text between two frames of such bytes (rows x width x 3 each): what a terminal that shows `shown` must be written to show
+ * `next`.  The reference has no such emitter; the format is the project's own (csrc/trt_ansi_delta.h).  Per changed cell,
+ * rows ascending, left to right: "\033[RRRRR;CCCCCH" (row + 1, 2 * column + 1) where a run of changed cells of one row starts,
+ * "\033[48;2;RRR;GGG;BBBm" where a run starts or the colour differs from the cell's to the left, two spaces, and "\033[0m" where the run
+ * ends.  No prefix, no newline, no NUL: equal frames give *bytes = 0.  At most rows * (21 * width + 18) bytes, which `capacity` must
+ * hold; rows <= 99999, width <= 49999.  The sequential statement the device kernels (trt_render_device_ansi_delta, trt_hip.h) are
+ * tested against, and the emitter of hosts that fetch RGB8 bytes.  TRT_HOST_ERR_ARGUMENT: NULL, a size that is not positive or above
+ * the limits, a capacity below the bound. */
+int trt_emitter_delta_rgb8(const unsigned char *shown, const unsigned char *next, int width, int rows, char *text, size_t capacity,
+                           size_t *bytes);
 /* TRT.c:1171: one fwrite of the whole buffer (trailing NULs included, as the reference does) */
 int trt_emitter_write(const trt_emitter *e, FILE *stream);
 /* TRT.c:1084-1099: the unbuffered printf form */

@@ -114,6 +114,72 @@ int trt_emitter_patch_rgb8(trt_emitter *e, const unsigned char *rgb)
     return TRT_HOST_OK;
 }
 
+/* The delta text (csrc/trt_ansi_delta.h holds the format): the obvious walk, a cell at a time, on purpose without that header -- this
+ * is what the header's arithmetic and the device kernels are held against. */
+static const char k_goto[] = "\033[00000;00000H";
+static const char k_reset[] = "\033[0m";
+enum
+{
+    GOTO_LEN = sizeof(k_goto) - 1,   /* 14 */
+    GOTO_ROW_AT = 2,
+    GOTO_COLUMN_AT = 8,
+    COLOUR_LEN = 19,                 /* pixel_str up to and including its 'm' */
+    RESET_LEN = sizeof(k_reset) - 1, /* 4 */
+    DELTA_MAX_ROWS = 99999,
+    DELTA_MAX_WIDTH = 49999
+};
+
+static void five_digits(char *at, int value)
+{
+    for (int place = 4; place >= 0; place--, value /= 10)
+        at[place] = (char)(value % 10 + '0');
+}
+
+int trt_emitter_delta_rgb8(const unsigned char *shown, const unsigned char *next, int width, int rows, char *text, size_t capacity, size_t *bytes)
+{
+    if (!shown || !next || !text || !bytes || width <= 0 || rows <= 0 || width > DELTA_MAX_WIDTH || rows > DELTA_MAX_ROWS)
+        return TRT_HOST_ERR_ARGUMENT;
+    if (capacity < (size_t)rows * ((size_t)21 * width + 18))
+        return TRT_HOST_ERR_ARGUMENT;
+    char *p = text;
+    for (int row = 0; row < rows; row++)
+    {
+        const unsigned char *was = shown + (size_t)row * width * 3, *now = next + (size_t)row * width * 3;
+        int in_run = 0;
+        for (int col = 0; col < width; col++)
+        {
+            const unsigned char *px = now + 3 * col;
+            if (memcmp(was + 3 * col, px, 3) == 0)
+                continue;
+            if (!in_run)
+            { /* the cursor to the cell's first column: rows and columns count from 1, a cell is two columns wide */
+                memcpy(p, k_goto, GOTO_LEN);
+                five_digits(p + GOTO_ROW_AT, row + 1);
+                five_digits(p + GOTO_COLUMN_AT, 2 * col + 1);
+                p += GOTO_LEN;
+            }
+            if (!in_run || memcmp(px - 3, px, 3) != 0)
+            { /* the background colour, unless the cell painted just before has it */
+                memcpy(p, k_cell, COLOUR_LEN);
+                three_digits(p + RED_AT, px[0]);
+                three_digits(p + GREEN_AT, px[1]);
+                three_digits(p + BLUE_AT, px[2]);
+                p += COLOUR_LEN;
+            }
+            *p++ = ' ';
+            *p++ = ' ';
+            in_run = col + 1 < width && memcmp(was + 3 * (col + 1), px + 3, 3) != 0;
+            if (!in_run)
+            {
+                memcpy(p, k_reset, RESET_LEN);
+                p += RESET_LEN;
+            }
+        }
+    }
+    *bytes = (size_t)(p - text);
+    return TRT_HOST_OK;
+}
+
 int trt_emitter_write(const trt_emitter *e, FILE *stream)
 {
     if (!e || !stream)

@@ -9,6 +9,7 @@
 #endif
 #include "trt_simple.hpp"
 #include "trt_ansi.hpp"
+#include "trt_ansi_delta.hpp"
 
 using namespace trt_impl;
 
@@ -1171,5 +1172,199 @@ extern "C" int trt_render_host_ansi(trt_context *ctx, const Camera *camera, cons
     memcpy(text, ctx->h_staging.ptr, bytes);
     if (print_host_times())
         fprintf(stderr, "trt_render_host_ansi: %.3f ms for %zu bytes of text\n", host_now_ms() - t_begin, bytes);
+    return TRT_OK;
+}
+
+// ---- the delta text (trt_ansi_delta.h: the format; trt_ansi_delta.hpp: the three kernels) ----
+
+extern "C" size_t trt_ansi_delta_capacity(int width, int rows)
+{
+    if (!trt_delta_size_ok(width, rows))
+        return 0;
+    return (size_t)std::max(trt_ansi_text_bytes(width, rows), trt_delta_bound(width, rows));
+}
+
+// measure, offsets, write on `stream`; marks: four events, recorded around and between the launches (trt_ansi_delta_kernel_times)
+static int launch_ansi_delta(trt_context *ctx, hipStream_t stream, const unsigned char *d_shown, const unsigned char *d_next, int width, int rows, void *d_text,
+                             size_t capacity_bytes, unsigned long long *d_bytes, const Event *marks = nullptr)
+{
+    const unsigned long long cells = (unsigned long long)width * (unsigned long long)rows, tiles = trt_delta_tiles(cells);
+    if (ctx->d_delta_tile_bytes.capacity < tiles || ctx->d_delta_tile_at.capacity < tiles)
+        HIP_TRY(hipStreamSynchronize(stream)); // a text in flight may still use the old sums
+    HIP_TRY(ctx->d_delta_tile_bytes.reserve((size_t)tiles));
+    HIP_TRY(ctx->d_delta_tile_at.reserve((size_t)tiles));
+    if (marks)
+        HIP_TRY(hipEventRecord(marks[0], stream));
+    hipLaunchKernelGGL(trt::ansi_delta_measure_kernel, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, cells, ctx->d_delta_tile_bytes.ptr);
+    if (marks)
+        HIP_TRY(hipEventRecord(marks[1], stream));
+    hipLaunchKernelGGL(trt::ansi_delta_offsets_kernel, dim3(1), dim3(TRT_DELTA_SCAN_BLOCK), 0, stream, (const unsigned *)ctx->d_delta_tile_bytes.ptr, tiles,
+                       ctx->d_delta_tile_at.ptr, d_bytes);
+    if (marks)
+        HIP_TRY(hipEventRecord(marks[2], stream));
+    hipLaunchKernelGGL(trt::ansi_delta_write_kernel, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, cells,
+                       (const unsigned long long *)ctx->d_delta_tile_at.ptr, (unsigned char *)d_text, (unsigned long long)capacity_bytes);
+    if (marks)
+        HIP_TRY(hipEventRecord(marks[3], stream));
+    HIP_TRY(hipGetLastError());
+    return TRT_OK;
+}
+
+static int check_delta_from_rgb8(const trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, const void *d_text, size_t capacity_bytes,
+                                 const unsigned long long *d_bytes)
+{
+    if (!ctx || !d_shown_rgb8 || !d_next_rgb8 || !d_text || !d_bytes)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (!trt_delta_size_ok(width, rows))
+        return fail(TRT_ERR_ARGUMENT, "screen %d x %d: a delta text has 1 to %d cells per row and 1 to %d rows", width, rows, TRT_DELTA_MAX_WIDTH, TRT_DELTA_MAX_ROWS);
+    if (capacity_bytes < trt_ansi_delta_capacity(width, rows))
+        return fail(TRT_ERR_CAPACITY, "the delta text of %d x %d needs room for %zu B, %zu given", width, rows, trt_ansi_delta_capacity(width, rows), capacity_bytes);
+    return TRT_OK;
+}
+
+extern "C" int trt_ansi_delta_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                               size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    const int rc = check_delta_from_rgb8(ctx, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
+    if (rc)
+        return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return launch_ansi_delta(ctx, ctx->stream, (const unsigned char *)d_shown_rgb8, (const unsigned char *)d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
+}
+
+extern "C" int trt_ansi_delta_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                           size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
+{
+    if (!ms)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    int rc = check_delta_from_rgb8(ctx, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
+    if (rc)
+        return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    Event marks[4];
+    for (Event &e : marks)
+        HIP_TRY(e.create());
+    rc = launch_ansi_delta(ctx, ctx->stream, (const unsigned char *)d_shown_rgb8, (const unsigned char *)d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes, marks);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (rc)
+        return rc;
+    for (int k = 0; k < 3; k++)
+        HIP_TRY(hipEventElapsedTime(&ms[k], marks[k], marks[k + 1]));
+    return TRT_OK;
+}
+
+extern "C" int trt_ansi_delta_reset(trt_context *ctx)
+{
+    if (!ctx)
+        return fail(TRT_ERR_ARGUMENT, "ctx is NULL");
+    ctx->shown_valid = false;
+    return TRT_OK;
+}
+
+// what both render entries refuse before anything is enqueued; `text`: the caller's buffer, on the device or on the host
+static int check_render_delta(const trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, const void *text,
+                              size_t capacity_bytes, const void *bytes)
+{
+    if (!bytes)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (rowset_valid(rows) && !trt_delta_size_ok(rows->width, trt_rowset_rows(rows)))
+        return fail(TRT_ERR_ARGUMENT, "%d x %d owned rows: a delta text has 1 to %d cells per row and 1 to %d rows", rows->width, trt_rowset_rows(rows), TRT_DELTA_MAX_WIDTH,
+                    TRT_DELTA_MAX_ROWS);
+    // the rest as the RGB8 entry checks it, whose frame these sizes let fit
+    const int rc = check_render_arguments(ctx, camera, 1, rows, bounce_limit, rays_per_pixel, text, (size_t)-1, kBytes);
+    if (rc)
+        return rc;
+    const size_t need = trt_ansi_delta_capacity(rows->width, trt_rowset_rows(rows));
+    if (capacity_bytes < need)
+        return fail(TRT_ERR_CAPACITY, "the text of %d x %d owned rows needs room for %zu B, %zu given", rows->width, trt_rowset_rows(rows), need, capacity_bytes);
+    return TRT_OK;
+}
+
+static bool same_rowset(const trt_rowset &a, const trt_rowset &b)
+{
+    return a.width == b.width && a.height == b.height && a.tile_rows == b.tile_rows && a.tile_first == b.tile_first && a.tile_step == b.tile_step;
+}
+
+extern "C" int trt_render_device_ansi_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                                            size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    int rc = check_render_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes);
+    if (rc)
+        return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int width = rows->width, owned = trt_rowset_rows(rows);
+    const size_t frame = (size_t)owned * width * 3;
+    const bool keyframe = !(ctx->shown_valid && same_rowset(ctx->shown_rows, *rows));
+    const int into = ctx->shown_at ^ 1;
+    if (ctx->d_shown[0].capacity < frame || ctx->d_shown[1].capacity < frame)
+    { // another size: a keyframe, which reads neither buffer's contents
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx->d_shown[0].reserve(frame));
+        HIP_TRY(ctx->d_shown[1].reserve(frame));
+    }
+    ctx->shown_valid = false; // a call that fails from here on has forgotten the shown frame
+    // the new frame's bytes: the RGB8 form of the ordered mean (the reference-order kernel: its doubles through quantize_kernel)
+    rc = render_device_on(ctx, camera, rows, bounce_limit, rays_per_pixel, ctx->d_shown[into].ptr, frame, 0, kEntryWhole, kBytes);
+    if (rc)
+        return rc;
+    if (keyframe)
+    { // the whole text, as trt_render_device_ansi writes it
+        launch_ansi_from_rgb8(ctx->stream, ctx->d_shown[into].ptr, width, owned, d_text);
+        hipLaunchKernelGGL(trt::ansi_delta_keyframe_bytes_kernel, dim3(1), dim3(1), 0, ctx->stream, d_bytes, trt_ansi_text_bytes(width, owned));
+        HIP_TRY(hipGetLastError());
+    }
+    else
+    {
+        rc = launch_ansi_delta(ctx, ctx->stream, ctx->d_shown[ctx->shown_at].ptr, ctx->d_shown[into].ptr, width, owned, d_text, capacity_bytes, d_bytes);
+        if (rc)
+            return rc;
+    }
+    ctx->shown_at = into;
+    ctx->shown_rows = *rows;
+    ctx->shown_valid = true;
+    return TRT_OK;
+}
+
+extern "C" int trt_render_host_ansi_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
+                                          size_t capacity_bytes, size_t *bytes)
+{
+    int rc = check_render_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes);
+    if (rc)
+        return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t room = trt_ansi_delta_capacity(rows->width, trt_rowset_rows(rows));
+    if (ctx->d_text.capacity < room)
+        HIP_TRY(hipStreamSynchronize(ctx->stream)); // a text in flight may still be written to the old buffer
+    HIP_TRY(ctx->d_text.reserve(room));
+    HIP_TRY(ctx->d_delta_bytes.reserve(1));
+    HIP_TRY(ctx->h_staging.reserve(room));
+    const double t_begin = host_now_ms();
+    rc = trt_render_device_ansi_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, room, ctx->d_delta_bytes.ptr);
+    if (rc)
+        return rc;
+    // two small transfers instead of one large one: the length, then exactly that many bytes
+    unsigned long long length = 0;
+    rc = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_delta_bytes.ptr, sizeof length, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        memcpy(&length, ctx->h_staging.ptr, sizeof length);
+        if (length > room)
+            return fail(TRT_ERR_CAPACITY, "a text of %llu B where %zu are the most", length, room);
+        if (length)
+        {
+            HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_text.ptr, (size_t)length, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            memcpy(text, ctx->h_staging.ptr, (size_t)length);
+        }
+        return TRT_OK;
+    }();
+    if (rc)
+    { // the host did not get the text: the terminal does not show this frame
+        ctx->shown_valid = false;
+        return rc;
+    }
+    *bytes = (size_t)length;
+    if (print_host_times())
+        fprintf(stderr, "trt_render_host_ansi_delta: %.3f ms for %llu bytes of text\n", host_now_ms() - t_begin, length);
     return TRT_OK;
 }

@@ -27,6 +27,7 @@ HOST_SYMBOLS = {
     "trt_emitter_size": (C.c_size_t, [_VP]),
     "trt_emitter_patch": (C.c_int, [_VP, C.POINTER(L.Screen)]),
     "trt_emitter_patch_rgb8": (C.c_int, [_VP, _VP]),
+    "trt_emitter_delta_rgb8": (_I, [_VP, _VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_write": (_I, [_VP, _VP]),
     "trt_draw_screen": (_I, [C.POINTER(L.Screen), _VP]),
     "trt_fnv1a64": (C.c_ulonglong, [_VP, C.c_size_t]),
@@ -102,6 +103,20 @@ class Emitter:
             self.close()
         except Exception:
             pass
+
+
+def emitter_delta_rgb8(shown, nxt):
+    """the delta text between two frames of bytes [rows, width, 3], formatted on the host: uint8 (trt_emitter_delta_rgb8)"""
+    a, b = np.ascontiguousarray(shown, dtype=np.uint8), np.ascontiguousarray(nxt, dtype=np.uint8)
+    rows, width, _ = b.shape
+    if a.shape != b.shape:
+        raise ValueError(f"frames of {a.shape} and {b.shape}")
+    out = np.empty(max(rows * (21 * width + 18), 1), dtype=np.uint8)
+    n = C.c_size_t(0)
+    rc = lib().trt_emitter_delta_rgb8(a.ctypes.data, b.ctypes.data, width, rows, out.ctypes.data, out.size, C.byref(n))
+    if rc != 0:
+        raise ValueError(f"trt_emitter_delta_rgb8({width}, {rows}) failed with {rc}")
+    return out[:n.value].copy()
 
 
 def fnv1a64(buf):
