@@ -74,26 +74,14 @@ __device__ __forceinline__ unsigned ansi_pixel_of_samples(const double *samples,
     return rgb8_byte(m0, inv_spp) | rgb8_byte(m1, inv_spp) << 8 | rgb8_byte(m2, inv_spp) << 16;
 }
 
-// The ordered mean, the emitter's cast and the terminal's text in ONE pass, as the last kernel of a frame in reduce_samples_kernel's
-// place: it leaves the queue ready in the same way.  The grid has trt_ansi_waves(words of the text at `out`) waves.
+// The ordered mean, the emitter's cast and the terminal's text in ONE pass, as the last kernel of a launch in reduce_samples_kernel's
+// place: blockIdx.y is the frame, and it leaves the queue ready in the same way.  Frame b's text starts at out + b * trt_ansi_text_bytes,
+// aligned to nothing in general: every frame has a head and a tail of its own.  A single frame's grid has trt_ansi_waves(words of the
+// text at `out`) waves; that of several frames the most waves an alignment needs (a frame's spare wave finds nothing to do).
 __global__ __launch_bounds__(256) void reduce_samples_ansi_kernel(const double *samples, unsigned char *out, int width, int rows, unsigned row_magic, int spp,
                                                                   double inv_spp, unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
 {
-    if (blockIdx.x == 0 && threadIdx.x < (1u << shift)) // the render kernel that used the queue has finished
-        queue[threadIdx.x * kQueueStride] = (grid > threadIdx.x ? (grid - threadIdx.x + (1u << shift) - 1) >> shift : 0u) * waves_per_group;
-    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long values = (long)width * rows * 3;
-    ansi_write(out, width, rows, row_magic, t >> 6, (int)(t & 63), [=](long long p) { return ansi_pixel_of_samples(samples, values, spp, inv_spp, p); });
-}
-
-// The same over the frames of a batch launch: blockIdx.y is the frame, as in reduce_samples_batch_kernel.  Frame b's text starts at
-// out + b * trt_ansi_text_bytes, aligned to nothing in general: every frame has a head and a tail of its own, and the grid is sized
-// for the most waves an alignment needs (a frame's spare wave finds nothing to do).
-__global__ __launch_bounds__(256) void reduce_samples_ansi_batch_kernel(const double *samples, unsigned char *out, int width, int rows, unsigned row_magic, int spp,
-                                                                        double inv_spp, unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
-{
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < (1u << shift))
-        queue[threadIdx.x * kQueueStride] = (grid > threadIdx.x ? (grid - threadIdx.x + (1u << shift) - 1) >> shift : 0u) * waves_per_group;
+    arm_queue(queue, grid, waves_per_group, shift);
     const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long values = (long)width * rows * 3;
     const double *mine = samples + (size_t)blockIdx.y * (size_t)spp * (size_t)values;

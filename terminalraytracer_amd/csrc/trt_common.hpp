@@ -1,6 +1,7 @@
 // trt_common.hpp -- what the kernels of the frame producer share: launch shape of the persistent grid, work-queue
-// constants, the LDS image size, the culling-table view, the ISA profile's stage marks and the two small streaming
-// kernels either side of the render kernel (ordered mean over a pixel's samples, RGB8 quantisation).
+// constants, the LDS image size, the culling-table view, the ISA profile's stage marks and the small streaming
+// kernels either side of the render kernel: the queue's start, the ordered mean over a pixel's samples -- one kernel per output kind
+// (doubles, RGB8 bytes; the text's is in trt_ansi.hpp), the frame of a launch in blockIdx.y -- and the RGB8 quantisation.
 #pragma once
 
 #include "trt_device.hpp"
@@ -76,40 +77,28 @@ constexpr int kLdsCameraDoubles = 16;                       // basis x,y,z (9) e
 constexpr int kDirGridDoubles = 14, kPointGridDoubles = 9;  // sizeof(trt_dirgrid) / 8, sizeof(trt_pointgrid) / 8 (asserted in trt_rounds.hpp)
 
 #ifdef TRT_UNIT_RENDER // kernels that are not templates have ONE home among the library's translation units: trt_render.hip
-// TRT.c:1063-1066 for frames rendered with samples as work units: pixel = (((0 + s0) + s1) + ...) * (1/spp),
-// samples in index order.  The scratch is sample-major, samples[(k*pixels + pixel)*3 + channel], so that for every k
-// consecutive threads read consecutive doubles (a pure streaming kernel: spp*24 B read + 24 B written per pixel).
-// every word of a launch's queue behind the first chunks of its workgroups (see kQueueStride)
-__global__ void start_queue_kernel(unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
-{
-    const unsigned x = threadIdx.x, words = 1u << shift;
-    if (x < words)
-        queue[x * kQueueStride] = (grid > x ? (grid - x + words - 1) >> shift : 0u) * waves_per_group;
-}
-// ... and, being the last kernel of a frame, it leaves the frame's queue ready for a launch of the same shape (start_queue_kernel's job:
-// the next frame of this context then has no kernel in front of its render kernel)
-__global__ __launch_bounds__(256) void reduce_samples_kernel(const double *samples, double *out, long values, int spp, double inv_spp,
-                                                             unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
-{
-    if (blockIdx.x == 0 && threadIdx.x < (1u << shift)) // the render kernel that used the queue has finished
-        queue[threadIdx.x * kQueueStride] = (grid > threadIdx.x ? (grid - threadIdx.x + (1u << shift) - 1) >> shift : 0u) * waves_per_group;
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x; // one thread per colour channel of a pixel
-    if (i >= values)
-        return;
-    double mean = 0.0;
-    for (int k = 0; k < spp; k++)
-        mean += samples[(long)k * values + i];
-    out[i] = mean * inv_spp;
-}
-
-// The same over the frames of a batch launch (trt_render_device_batch): blockIdx.y is the frame, its scratch is
-// samples[((frame * spp + k) * values + i)] and its pixels out[frame * values + i].  The queue is the launch's, started once.
-__global__ __launch_bounds__(256) void reduce_samples_batch_kernel(const double *samples, double *out, long values, int spp, double inv_spp,
-                                                                   unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
+// every word of a launch's queue behind the first chunks of its workgroups (see kQueueStride), written by workgroup (0, 0) of a grid
+__device__ __forceinline__ void arm_queue(unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
 {
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < (1u << shift))
         queue[threadIdx.x * kQueueStride] = (grid > threadIdx.x ? (grid - threadIdx.x + (1u << shift) - 1) >> shift : 0u) * waves_per_group;
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+}
+__global__ void start_queue_kernel(unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
+{
+    arm_queue(queue, grid, waves_per_group, shift);
+}
+// TRT.c:1063-1066 for frames rendered with samples as work units: pixel = (((0 + s0) + s1) + ...) * (1/spp),
+// samples in index order.  The scratch is sample-major, samples[(k*pixels + pixel)*3 + channel], so that for every k
+// consecutive threads read consecutive doubles (a pure streaming kernel: spp*24 B read + 24 B written per pixel).
+// Over the frames of a launch (a single frame is a launch of one): blockIdx.y is the frame, its scratch is
+// samples[((frame * spp + k) * values + i)] and its pixels out[frame * values + i].  Being the last kernel of a launch, it leaves the
+// launch's queue ready for a launch of the same shape (start_queue_kernel's job, once per launch: the render kernel that used the queue
+// has finished, and the next frame of this context then has no kernel in front of its render kernel)
+__global__ __launch_bounds__(256) void reduce_samples_kernel(const double *samples, double *out, long values, int spp, double inv_spp,
+                                                             unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
+{
+    arm_queue(queue, grid, waves_per_group, shift);
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x; // one thread per colour channel of a pixel
     if (i >= values)
         return;
     const double *mine = samples + (size_t)blockIdx.y * (size_t)spp * (size_t)values;
@@ -185,23 +174,14 @@ __device__ __forceinline__ void reduce_samples_rgb8(const double *samples, unsig
     out[v] = (unsigned char)rgb8_byte(mean, inv_spp);
 }
 
-// ... as the last kernel of a frame, in reduce_samples_kernel's place: it leaves the queue ready in the same way
+// ... as the last kernel of a launch, in reduce_samples_kernel's place: blockIdx.y is the frame, and it leaves the queue ready in the
+// same way.  Frame b's bytes start at out + b * values, which is 4-aligned for no b in general: every frame has a head and a tail of its
+// own.  A single frame's grid has exactly its lanes; that of several frames the most lanes any alignment needs (at most values / 4
+// groups, three values in front, three behind; a frame's spare lanes find nothing to do).
 __global__ __launch_bounds__(256) void reduce_samples_rgb8_kernel(const double *samples, unsigned char *out, long values, int spp, double inv_spp,
                                                                   unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
 {
-    if (blockIdx.x == 0 && threadIdx.x < (1u << shift)) // the render kernel that used the queue has finished
-        queue[threadIdx.x * kQueueStride] = (grid > threadIdx.x ? (grid - threadIdx.x + (1u << shift) - 1) >> shift : 0u) * waves_per_group;
-    reduce_samples_rgb8(samples, out, values, spp, inv_spp, (long)blockIdx.x * blockDim.x + threadIdx.x);
-}
-
-// The same over the frames of a batch launch: blockIdx.y is the frame, as in reduce_samples_batch_kernel.  Frame b's bytes start at
-// out + b * values, which is 4-aligned for no b in general: every frame has a head and a tail of its own, and a grid sized for the
-// most lanes any alignment needs (at most values / 4 groups, three values in front, three behind; a frame's spare lanes find nothing to do).
-__global__ __launch_bounds__(256) void reduce_samples_rgb8_batch_kernel(const double *samples, unsigned char *out, long values, int spp, double inv_spp,
-                                                                        unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
-{
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < (1u << shift))
-        queue[threadIdx.x * kQueueStride] = (grid > threadIdx.x ? (grid - threadIdx.x + (1u << shift) - 1) >> shift : 0u) * waves_per_group;
+    arm_queue(queue, grid, waves_per_group, shift);
     reduce_samples_rgb8(samples + (size_t)blockIdx.y * (size_t)spp * (size_t)values, out + (size_t)blockIdx.y * (size_t)values, values, spp, inv_spp,
                         (long)blockIdx.x * blockDim.x + threadIdx.x);
 }

@@ -140,12 +140,11 @@ extern "C" int trt_build_counts(trt_context *ctx, unsigned long long *table_buil
     return TRT_OK;
 }
 
-extern "C" int trt_render_frame(const Scene *scene, Screen *screen, int bounce_limit, int rays_per_pixel)
+// What the drop-in entries do once their own arguments have passed: the default context's turn, the caller's scene on it, and
+// render(ctx, rows) over the whole screen.
+template <class Render>
+static int render_default_frame(const Scene *scene, int width, int height, Render render)
 {
-    if (!scene || !screen || !screen->pixels)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (screen->width <= 0 || screen->height <= 0)
-        return fail(TRT_ERR_ARGUMENT, "screen %d x %d", screen->width, screen->height);
     std::lock_guard<std::mutex> turn(g_default_mutex);
     trt_context *ctx;
     int rc = default_context(&ctx);
@@ -154,8 +153,19 @@ extern "C" int trt_render_frame(const Scene *scene, Screen *screen, int bounce_l
     rc = refresh_default_scene(ctx, scene);
     if (rc)
         return rc;
-    const trt_rowset whole = {screen->width, screen->height, screen->height, 0, 1};
-    return trt_render_host(ctx, &scene->camera, &whole, bounce_limit, rays_per_pixel, screen->pixels);
+    const trt_rowset whole = {width, height, height, 0, 1};
+    return render(ctx, &whole);
+}
+
+extern "C" int trt_render_frame(const Scene *scene, Screen *screen, int bounce_limit, int rays_per_pixel)
+{
+    if (!scene || !screen || !screen->pixels)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (screen->width <= 0 || screen->height <= 0)
+        return fail(TRT_ERR_ARGUMENT, "screen %d x %d", screen->width, screen->height);
+    return render_default_frame(scene, screen->width, screen->height, [&](trt_context *ctx, const trt_rowset *whole) {
+        return trt_render_host(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, screen->pixels);
+    });
 }
 
 // north_star's name for the entry: the frame producer with the two macros of TRT.c:54, :58 as run-time values
@@ -170,16 +180,9 @@ extern "C" int trt_render_frame_rgb8(const Scene *scene, int width, int height, 
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
     if (width <= 0 || height <= 0)
         return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, height);
-    std::lock_guard<std::mutex> turn(g_default_mutex);
-    trt_context *ctx;
-    int rc = default_context(&ctx);
-    if (rc)
-        return rc;
-    rc = refresh_default_scene(ctx, scene);
-    if (rc)
-        return rc;
-    const trt_rowset whole = {width, height, height, 0, 1};
-    return trt_render_host_rgb8(ctx, &scene->camera, &whole, bounce_limit, rays_per_pixel, rgb);
+    return render_default_frame(scene, width, height, [&](trt_context *ctx, const trt_rowset *whole) {
+        return trt_render_host_rgb8(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, rgb);
+    });
 }
 
 extern "C" int trt_render_frame_ansi(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text)
@@ -188,16 +191,9 @@ extern "C" int trt_render_frame_ansi(const Scene *scene, int width, int height, 
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
     if (width <= 0 || height <= 0)
         return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, height);
-    std::lock_guard<std::mutex> turn(g_default_mutex);
-    trt_context *ctx;
-    int rc = default_context(&ctx);
-    if (rc)
-        return rc;
-    rc = refresh_default_scene(ctx, scene);
-    if (rc)
-        return rc;
-    const trt_rowset whole = {width, height, height, 0, 1};
-    return trt_render_host_ansi(ctx, &scene->camera, &whole, bounce_limit, rays_per_pixel, text);
+    return render_default_frame(scene, width, height, [&](trt_context *ctx, const trt_rowset *whole) {
+        return trt_render_host_ansi(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, text);
+    });
 }
 
 // the shown frame is the default context's: trt_shutdown forgets it with the context
@@ -210,16 +206,9 @@ extern "C" int trt_render_frame_ansi_delta(const Scene *scene, int width, int he
         return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, height);
     if (capacity_bytes < trt_ansi_delta_capacity(width, height))
         return fail(TRT_ERR_CAPACITY, "the text of %d x %d needs room for %zu B, %zu given", width, height, trt_ansi_delta_capacity(width, height), capacity_bytes);
-    std::lock_guard<std::mutex> turn(g_default_mutex);
-    trt_context *ctx;
-    int rc = default_context(&ctx);
-    if (rc)
-        return rc;
-    rc = refresh_default_scene(ctx, scene);
-    if (rc)
-        return rc;
-    const trt_rowset whole = {width, height, height, 0, 1};
-    return trt_render_host_ansi_delta(ctx, &scene->camera, &whole, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes);
+    return render_default_frame(scene, width, height, [&](trt_context *ctx, const trt_rowset *whole) {
+        return trt_render_host_ansi_delta(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes);
+    });
 }
 
 extern "C" void project_scene(Scene *scene, Screen *screen)

@@ -463,149 +463,160 @@ static void launch_ansi_from_rgb8(hipStream_t stream, const unsigned char *d_rgb
 // the launches of a batch that was split for LDS.
 enum : int { kEntryOpens = 1, kEntryCloses = 2, kEntryWhole = kEntryOpens | kEntryCloses };
 
-// Carries out a planned launch: the queue started unless the launch before left it ready, the image staged for the DEVICE_IMAGE
-// instantiations, the render kernel over the frame `f` -- with `batch`, the plan's BATCH form over the frames of `batch`, of which
-// f is the first -- and the ordered mean of every frame's `pixels` pixels into `out`: as doubles, (kBytes) cast to the emitter's
-// bytes in the same pass, or (kText) cast and formatted as the terminal's text in the same pass.  The reference-order kernel has no
-// scratch and no mean: its bytes are its doubles, rendered into the context's framebuffer, through quantize_kernel, and its text is
-// those bytes through ansi_from_rgb8_kernel.
-static int launch_render(trt_context *ctx, const RenderPlan &plan, trt::FrameView f, const trt::GridView &grids, const trt::BatchView *batch, void *out,
-                         Output kind, long pixels, int lane_set, int entry)
+// The reference-order kernel's launch: it has no scratch and no mean.  Its bytes are its doubles, rendered into the context's
+// framebuffer, through quantize_kernel, and its text is those bytes through ansi_from_rgb8_kernel.
+static int launch_reference(trt_context *ctx, const RenderPlan &plan, trt::FrameView f, void *out, Output kind, long pixels, hipStream_t stream, int entry)
+{
+    const int slot = (int)(ctx->launches % kEventRing);
+    if (kind != kDoubles)
+    {
+        if (ctx->d_fb.capacity < (size_t)pixels * 3 || (kind == kText && ctx->d_text_rgb8.capacity < (size_t)pixels * 3))
+            HIP_TRY(hipStreamSynchronize(stream)); // a frame in flight may still use the old framebuffer
+        HIP_TRY(ctx->d_fb.reserve((size_t)pixels * 3));
+        if (kind == kText) // text: the framebuffer's bytes first, in a buffer of the context's
+            HIP_TRY(ctx->d_text_rgb8.reserve((size_t)pixels * 3));
+        f.out = ctx->d_fb.ptr;
+    }
+    if (ctx->scratch_fill) // trt_set_scratch_fill: the reference-order kernel has no scratch
+    {
+        HIP_TRY(hipMemsetAsync(f.out, 0xFF, (size_t)pixels * 3 * sizeof(double), stream));
+        if (kind != kDoubles)
+            HIP_TRY(hipMemsetAsync(out, 0xFF, frame_bytes(kind, f.width, f.local_rows), stream));
+    }
+    if (entry & kEntryOpens)
+        HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
+    if (plan.variant == kReference)
+        hipLaunchKernelGGL(trt::render_simple_kernel<false>, dim3(plan.grid), dim3(plan.block), plan.lds, stream, ctx->scene, f);
+    else
+        hipLaunchKernelGGL(trt::render_simple_kernel<true>, dim3(plan.grid), dim3(plan.block), 0, stream, ctx->scene, f);
+    if (entry & kEntryCloses)
+        HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
+    if (kind != kDoubles)
+        hipLaunchKernelGGL(trt::quantize_kernel, dim3((unsigned)((pixels * 3 + 255) / 256)), dim3(256), 0, stream, (const double *)f.out, pixels * 3,
+                           kind == kText ? ctx->d_text_rgb8.ptr : (unsigned char *)out);
+    if (kind == kText)
+        launch_ansi_from_rgb8(stream, ctx->d_text_rgb8.ptr, f.width, f.local_rows, out);
+    if (entry & kEntryCloses)
+        HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
+    HIP_TRY(hipGetLastError());
+    return TRT_OK;
+}
+
+// TRT.c:1063-1065: the mean over each pixel's samples, in sample order, of the `frames` frames of a launch whose scratch is `samples`,
+// into `out` as `kind`: one kernel per kind, the frame in blockIdx.y.  It starts the queue for the next launch of this shape.  ONE
+// frame's grid has exactly the lanes or waves its output address needs; the frames of several start at any alignment, so their grid is
+// sized for the most an alignment needs (trt_common.hpp, trt_ansi.h).
+static void launch_ordered_mean(hipStream_t stream, const RenderPlan &plan, const trt::FrameView &f, const double *samples, void *out, Output kind, long pixels,
+                                unsigned frames)
+{
+    const long values = pixels * 3;
+    const dim3 block(TRT_REDUCE_BLOCK);
+    const auto blocks = [&](unsigned long long lanes) { return dim3((unsigned)((lanes + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK), frames); };
+    switch (kind)
+    {
+    case kDoubles: // a lane per value
+        hipLaunchKernelGGL(trt::reduce_samples_kernel, blocks(values), block, 0, stream, samples, (double *)out, values, f.spp, f.inv_spp, f.queue, plan.grid,
+                           plan.block / 64, f.queue_shift);
+        break;
+    case kBytes: // a lane per group of four values and one per value of a frame's head and tail
+        hipLaunchKernelGGL(trt::reduce_samples_rgb8_kernel,
+                           blocks(frames > 1 ? values / trt::kRgb8Group + 6 : trt::rgb8_lanes(values, trt::rgb8_head((const unsigned char *)out, values))), block, 0,
+                           stream, samples, (unsigned char *)out, values, f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
+        break;
+    case kText: // a wave per TRT_ANSI_WAVE_WORDS aligned words
+    {
+        const unsigned long long bytes = trt_ansi_text_bytes(f.width, f.local_rows);
+        const unsigned long long waves = trt_ansi_waves(frames > 1 ? bytes / 4 : trt_ansi_split_of((unsigned long long)out, bytes).words);
+        hipLaunchKernelGGL(trt::reduce_samples_ansi_kernel, blocks(waves * 64), block, 0, stream, samples, (unsigned char *)out, f.width, f.local_rows,
+                           trt_ansi_row_magic(f.width), f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
+        break;
+    }
+    }
+}
+
+// The production kernel's launch (kernel 0): the queue started unless the launch before left it ready, the image staged for the
+// DEVICE_IMAGE instantiations, persistent waves in synchronous rounds over SAMPLE units -- over the frame `f`, or with `batch` the plan's
+// BATCH form over the frames of `batch`, of which f is the first -- then the ordered mean of every frame's `pixels` pixels into `out`.
+static int launch_production(trt_context *ctx, const RenderPlan &plan, trt::FrameView f, const trt::GridView &grids, const trt::BatchView *batch, void *out,
+                             Output kind, long pixels, int lane_set, int entry)
 {
     const hipStream_t stream = lane_set ? ctx->alt_stream : ctx->stream;
     const int slot = (int)(ctx->launches % kEventRing);
     const dim3 grid(plan.grid), block(plan.block);
-    const bool reference = plan.variant == kReference || plan.variant == kReferenceImage;
     unsigned *const ready = ctx->queue_ready[lane_set];
+    const RoundsVariant &k = kRounds[plan.variant];
+    const unsigned frames = batch ? batch->frames : 1u;
+    // scratch [frame][k][pixel][3]; the launches of a split batch follow one another on the stream
+    DeviceBuffer<double> &scratch = lane_set ? ctx->d_samples_alt : ctx->d_samples;
+    const size_t samples = (size_t)pixels * f.spp * frames * 3;
+    if (scratch.capacity < samples)
+        HIP_TRY(hipStreamSynchronize(stream)); // a frame in flight may still use the old scratch
+    HIP_TRY(scratch.reserve(samples));
+    f.samples = scratch.ptr;
+    if (k.image)
+    { // a buffer per lane set: trt_render_host renders bands on two streams at once
+        DeviceBuffer<double> &image = lane_set ? ctx->d_image_alt : ctx->d_image;
+        const size_t doubles = image_lds_bytes(ctx, f.spp) / sizeof(double);
+        if (image.capacity < doubles)
+            HIP_TRY(hipStreamSynchronize(stream)); // a frame in flight may still read the old image
+        HIP_TRY(image.reserve(doubles));
+        f.image = image.ptr;
+    }
+    if (ctx->ior_count && ctx->ior_count != ctx->scene.num_spheres) // before the first event of the launch is recorded
+        return fail(TRT_ERR_ARGUMENT, "trt_set_refraction was given %d indices, the scene has %d spheres", ctx->ior_count, ctx->scene.num_spheres);
+    if (ctx->ior_count)
+        f.ior = ctx->d_ior.ptr;
+    f.ring_at = plan.ring_at;
+    f.queue_shift = plan.queue_shift;
+    f.chunk = plan.chunk;
+    if (ctx->scratch_fill)
+    { // trt_set_scratch_fill: exactly the launch's samples and exactly its pixels read as NaN until the launch writes them
+        HIP_TRY(hipMemsetAsync(scratch.ptr, 0xFF, samples * sizeof(double), stream));
+        HIP_TRY(hipMemsetAsync(out, 0xFF, frame_bytes(kind, f.width, f.local_rows) * frames, stream));
+    }
+    const bool left_ready = ready[0] == plan.grid && ready[1] == plan.block / 64 && ready[2] == f.queue_shift; // by the frame before
+    ready[0] = 0; // the render kernel uses it up; ready again once this frame's launches have gone in
+    if (!left_ready)
+        hipLaunchKernelGGL(trt::start_queue_kernel, dim3(1), dim3(64), 0, stream, f.queue, plan.grid, plan.block / 64, f.queue_shift);
+    if (entry & kEntryOpens)
+        HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
+    if (k.image)
+        hipLaunchKernelGGL(stage_image_kernel, dim3(1), dim3(kImageBlock), 0, stream, ctx->scene, ctx->cull, f, grids);
+    if (batch)
+        hipLaunchKernelGGL(k.batch, grid, block, plan.lds, stream, ctx->scene, ctx->cull, f, grids, *batch);
+    else
+        hipLaunchKernelGGL(k.fn, grid, block, plan.lds, stream, ctx->scene, ctx->cull, f, grids);
+    if (entry & kEntryCloses)
+        HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream)); // of a split batch: the last launch's
+#if !TRT_AB_SKIP_REDUCE // diagnostic build (profiles/r03: what the ordered mean's streaming pass costs in the pipelined loop)
+    launch_ordered_mean(stream, plan, f, scratch.ptr, out, kind, pixels, frames);
+#endif
+    if (entry & kEntryCloses)
+        HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
+    HIP_TRY(hipGetLastError());
+#if !TRT_AB_SKIP_REDUCE
+    ready[0] = plan.grid, ready[1] = plan.block / 64, ready[2] = f.queue_shift; // what the ordered mean left the queue ready for
+#endif
+    return TRT_OK;
+}
+
+// Carries out a planned launch on the route its variant takes, into `out` as `kind`: doubles, (kBytes) cast to the emitter's bytes in
+// the ordered mean's pass, or (kText) cast and formatted as the terminal's text in the same pass.
+static int launch_render(trt_context *ctx, const RenderPlan &plan, const trt::FrameView &f, const trt::GridView &grids, const trt::BatchView *batch, void *out,
+                         Output kind, long pixels, int lane_set, int entry)
+{
+    const hipStream_t stream = lane_set ? ctx->alt_stream : ctx->stream;
+    const bool reference = plan.variant == kReference || plan.variant == kReferenceImage;
     if (plan.lds > (size_t)ctx->lds_limit) // LDS only (trt_set_scene_image(ctx, 0)), or the refraction extension, which has no device-image form
         return fail(TRT_ERR_CAPACITY, "%s and %d rays per pixel need %zu B of LDS staging, device offers %d%s", plan.variant == kReference ? "scene" : "scene image",
                     f.spp, plan.lds, ctx->lds_limit, ctx->ior_count && plan.variant != kReference ? " (the refraction extension stages it in LDS only)" : "");
 #if defined(TRT_MARKS) && TRT_MARKS == 2
     HIP_TRY(hipMemsetAsync(ctx->d_counters.ptr, 0, kCounterSlots * sizeof(unsigned long long), stream));
 #endif
-    if (reference)
-    {
-        if (kind != kDoubles)
-        {
-            if (ctx->d_fb.capacity < (size_t)pixels * 3 || (kind == kText && ctx->d_text_rgb8.capacity < (size_t)pixels * 3))
-                HIP_TRY(hipStreamSynchronize(stream)); // a frame in flight may still use the old framebuffer
-            HIP_TRY(ctx->d_fb.reserve((size_t)pixels * 3));
-            if (kind == kText) // text: the framebuffer's bytes first, in a buffer of the context's
-                HIP_TRY(ctx->d_text_rgb8.reserve((size_t)pixels * 3));
-            f.out = ctx->d_fb.ptr;
-        }
-        if (ctx->scratch_fill) // trt_set_scratch_fill: the reference-order kernel has no scratch
-        {
-            HIP_TRY(hipMemsetAsync(f.out, 0xFF, (size_t)pixels * 3 * sizeof(double), stream));
-            if (kind != kDoubles)
-                HIP_TRY(hipMemsetAsync(out, 0xFF, frame_bytes(kind, f.width, f.local_rows), stream));
-        }
-        if (entry & kEntryOpens)
-            HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
-        if (plan.variant == kReference)
-            hipLaunchKernelGGL(trt::render_simple_kernel<false>, grid, block, plan.lds, stream, ctx->scene, f);
-        else
-            hipLaunchKernelGGL(trt::render_simple_kernel<true>, grid, block, 0, stream, ctx->scene, f);
-        if (entry & kEntryCloses)
-            HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
-        if (kind != kDoubles)
-            hipLaunchKernelGGL(trt::quantize_kernel, dim3((unsigned)((pixels * 3 + 255) / 256)), dim3(256), 0, stream, (const double *)f.out, pixels * 3,
-                               kind == kText ? ctx->d_text_rgb8.ptr : (unsigned char *)out);
-        if (kind == kText)
-            launch_ansi_from_rgb8(stream, ctx->d_text_rgb8.ptr, f.width, f.local_rows, out);
-        if (entry & kEntryCloses)
-            HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
-    }
-    else
-    {
-        // production (kernel 0): persistent waves, synchronous rounds over SAMPLE units, then the ordered mean per pixel
-        const RoundsVariant &k = kRounds[plan.variant];
-        const unsigned frames = batch ? batch->frames : 1u;
-        // scratch [frame][k][pixel][3]; the launches of a split batch follow one another on the stream
-        DeviceBuffer<double> &scratch = lane_set ? ctx->d_samples_alt : ctx->d_samples;
-        const size_t samples = (size_t)pixels * f.spp * frames * 3;
-        if (scratch.capacity < samples)
-            HIP_TRY(hipStreamSynchronize(stream)); // a frame in flight may still use the old scratch
-        HIP_TRY(scratch.reserve(samples));
-        f.samples = scratch.ptr;
-        if (k.image)
-        { // a buffer per lane set: trt_render_host renders bands on two streams at once
-            DeviceBuffer<double> &image = lane_set ? ctx->d_image_alt : ctx->d_image;
-            const size_t doubles = image_lds_bytes(ctx, f.spp) / sizeof(double);
-            if (image.capacity < doubles)
-                HIP_TRY(hipStreamSynchronize(stream)); // a frame in flight may still read the old image
-            HIP_TRY(image.reserve(doubles));
-            f.image = image.ptr;
-        }
-        if (ctx->ior_count && ctx->ior_count != ctx->scene.num_spheres) // before the first event of the launch is recorded
-            return fail(TRT_ERR_ARGUMENT, "trt_set_refraction was given %d indices, the scene has %d spheres", ctx->ior_count, ctx->scene.num_spheres);
-        if (ctx->ior_count)
-            f.ior = ctx->d_ior.ptr;
-        f.ring_at = plan.ring_at;
-        f.queue_shift = plan.queue_shift;
-        f.chunk = plan.chunk;
-        if (ctx->scratch_fill)
-        { // trt_set_scratch_fill: exactly the launch's samples and exactly its pixels read as NaN until the launch writes them
-            HIP_TRY(hipMemsetAsync(scratch.ptr, 0xFF, samples * sizeof(double), stream));
-            HIP_TRY(hipMemsetAsync(out, 0xFF, frame_bytes(kind, f.width, f.local_rows) * frames, stream));
-        }
-        const bool left_ready = ready[0] == plan.grid && ready[1] == plan.block / 64 && ready[2] == f.queue_shift; // by the frame before
-        ready[0] = 0; // the render kernel uses it up; ready again once this frame's launches have gone in
-        if (!left_ready)
-            hipLaunchKernelGGL(trt::start_queue_kernel, dim3(1), dim3(64), 0, stream, f.queue, plan.grid, plan.block / 64, f.queue_shift);
-        if (entry & kEntryOpens)
-            HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
-        if (k.image)
-            hipLaunchKernelGGL(stage_image_kernel, dim3(1), dim3(kImageBlock), 0, stream, ctx->scene, ctx->cull, f, grids);
-        if (batch)
-            hipLaunchKernelGGL(k.batch, grid, block, plan.lds, stream, ctx->scene, ctx->cull, f, grids, *batch);
-        else
-            hipLaunchKernelGGL(k.fn, grid, block, plan.lds, stream, ctx->scene, ctx->cull, f, grids);
-        if (entry & kEntryCloses)
-            HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream)); // of a split batch: the last launch's
-#if !TRT_AB_SKIP_REDUCE // diagnostic build (profiles/r03: what the ordered mean's streaming pass costs in the pipelined loop)
-        { // TRT.c:1063-1065: the mean over each pixel's samples, in sample order; it starts the queue for the next frame of this shape
-            const long values = pixels * 3;
-            // bytes: a lane per group of four values and one per value of a frame's head and tail (trt_common.hpp); the frames of a batch
-            // start at any alignment, so its grid is sized for the most lanes an alignment needs
-            const long lanes = kind == kDoubles || kind == kText ? values : batch ? values / trt::kRgb8Group + 6 : trt::rgb8_lanes(values, trt::rgb8_head((const unsigned char *)out, values));
-            const unsigned blocks = (unsigned)((lanes + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK);
-            if (kind == kText)
-            { // text: a wave per TRT_ANSI_WAVE_WORDS aligned words (trt_ansi.h); a batch's grid is sized for the most words an alignment leaves
-                const unsigned long long bytes = trt_ansi_text_bytes(f.width, f.local_rows);
-                const unsigned long long waves = trt_ansi_waves(batch ? bytes / 4 : trt_ansi_split_of((unsigned long long)out, bytes).words);
-                const unsigned text_blocks = (unsigned)((waves * 64 + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK);
-                if (batch)
-                    hipLaunchKernelGGL(trt::reduce_samples_ansi_batch_kernel, dim3(text_blocks, frames), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr,
-                                       (unsigned char *)out, f.width, f.local_rows, trt_ansi_row_magic(f.width), f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64,
-                                       f.queue_shift);
-                else
-                    hipLaunchKernelGGL(trt::reduce_samples_ansi_kernel, dim3(text_blocks), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr,
-                                       (unsigned char *)out, f.width, f.local_rows, trt_ansi_row_magic(f.width), f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64,
-                                       f.queue_shift);
-            }
-            else if (kind == kBytes && batch)
-                hipLaunchKernelGGL(trt::reduce_samples_rgb8_batch_kernel, dim3(blocks, frames), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr,
-                                   (unsigned char *)out, values, f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
-            else if (kind == kBytes)
-                hipLaunchKernelGGL(trt::reduce_samples_rgb8_kernel, dim3(blocks), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr, (unsigned char *)out,
-                                   values, f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
-            else if (batch)
-                hipLaunchKernelGGL(trt::reduce_samples_batch_kernel, dim3(blocks, frames), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr, (double *)out, values,
-                                   f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
-            else
-                hipLaunchKernelGGL(trt::reduce_samples_kernel, dim3(blocks), dim3(TRT_REDUCE_BLOCK), 0, stream, (const double *)scratch.ptr, (double *)out, values, f.spp,
-                                   f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
-        }
-#endif
-        if (entry & kEntryCloses)
-            HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
-    }
-    HIP_TRY(hipGetLastError());
-#if !TRT_AB_SKIP_REDUCE
-    if (!reference) // what the ordered mean left the queue ready for
-        ready[0] = plan.grid, ready[1] = plan.block / 64, ready[2] = f.queue_shift;
-#endif
+    const int rc = reference ? launch_reference(ctx, plan, f, out, kind, pixels, stream, entry)
+                             : launch_production(ctx, plan, f, grids, batch, out, kind, pixels, lane_set, entry);
+    if (rc)
+        return rc;
     ctx->last_variant = plan.variant;
     ctx->last_spp = f.spp;
     if (entry & kEntryCloses)
@@ -639,7 +650,7 @@ static int render_device_on(trt_context *ctx, const Camera *camera, const trt_ro
     rc = plan_render(ctx, pixels * rays_per_pixel, rays_per_pixel, 1, false, &plan);
     if (rc)
         return rc;
-    // only the reference-order kernel writes FrameView::out: doubles (launch_render gives it the context's framebuffer when bytes are asked for)
+    // only the reference-order kernel writes FrameView::out: doubles (launch_reference gives it the context's framebuffer when bytes or text are asked for)
     return launch_render(ctx, plan, frame_view(ctx, camera, rows, bounce_limit, rays_per_pixel, kind == kDoubles ? d_pixels : nullptr, lane_set), ctx->grids, nullptr,
                          d_pixels, kind, pixels, lane_set, entry);
 }
@@ -925,69 +936,70 @@ extern "C" int trt_render_device_batch_ansi(trt_context *ctx, const Camera *came
     return render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, kText);
 }
 
-extern "C" int trt_render_host_batch_ansi(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text)
+// The copy-out of the host entries: `n` cameras rendered as `kind` into the context's buffer of that kind, copied to pinned staging
+// and, the stream synchronised, to the caller's `host`.  The ordered mean writes the bytes ((int)(c*255), TRT.c:1157-1163) and the text
+// (TRT.c:1142-1172) itself: no framebuffer of doubles on the way, and no formatting on the host.  `batch`: the batch route, which picks
+// the render kernel's BATCH form and counts for trt_batch_info; otherwise the single frame's, timed as `name` under print_host_times().
+static int render_host_as(trt_context *ctx, const Camera *cameras, int n, bool batch, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *host,
+                          Output kind, const char *name = nullptr)
 {
-    if (!ctx || !text)
+    if (!ctx || !host)
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (n < 1 || n > TRT_BATCH_MAX)
+    if (batch && (n < 1 || n > TRT_BATCH_MAX))
         return fail(TRT_ERR_ARGUMENT, "a batch has 1 to %d cameras, %d given", TRT_BATCH_MAX, n);
     if (!rowset_valid(rows))
         return fail(TRT_ERR_ARGUMENT, "invalid rowset");
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)n * trt_ansi_bytes(rows->width, trt_rowset_rows(rows));
-    HIP_TRY(ctx->d_text.reserve(std::max<size_t>(bytes, 1)));
-    HIP_TRY(ctx->h_staging.reserve(std::max<size_t>(bytes, 1)));
-    const int rc = trt_render_device_batch_ansi(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, bytes);
+    const size_t bytes = (size_t)n * frame_bytes(kind, rows->width, trt_rowset_rows(rows));
+    if (!batch && bytes == 0)
+        return TRT_OK;
+    const size_t room = std::max<size_t>(bytes, 1);
+    if (kind == kDoubles)
+        HIP_TRY(ctx->d_fb.reserve((room + sizeof(double) - 1) / sizeof(double)));
+    else
+        HIP_TRY((kind == kBytes ? ctx->d_rgb8 : ctx->d_text).reserve(room));
+    void *const d_out = kind == kDoubles ? (void *)ctx->d_fb.ptr : kind == kBytes ? (void *)ctx->d_rgb8.ptr : (void *)ctx->d_text.ptr;
+    HIP_TRY(ctx->h_staging.reserve(room));
+    const double t_begin = host_now_ms();
+    const int rc = batch ? render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_out, bytes, kind)
+                         : render_device_on(ctx, cameras, rows, bounce_limit, rays_per_pixel, d_out, bytes, 0, kEntryWhole, kind);
     if (rc || bytes == 0)
         return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_text.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    memcpy(text, ctx->h_staging.ptr, bytes);
+    memcpy(host, ctx->h_staging.ptr, bytes);
+    if (name && print_host_times())
+        fprintf(stderr, kind == kBytes ? "%s: %.3f ms for %zu pixels\n" : "%s: %.3f ms for %zu bytes of text\n", name, host_now_ms() - t_begin,
+                kind == kBytes ? bytes / 3 : bytes);
     return TRT_OK;
 }
 
-extern "C" int trt_render_host_batch_rgb8(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
-                                          unsigned char *rgb)
+extern "C" int trt_render_host_rgb8(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                    unsigned char *rgb)
 {
-    if (!ctx || !rgb)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (n < 1 || n > TRT_BATCH_MAX)
-        return fail(TRT_ERR_ARGUMENT, "a batch has 1 to %d cameras, %d given", TRT_BATCH_MAX, n);
-    if (!rowset_valid(rows))
-        return fail(TRT_ERR_ARGUMENT, "invalid rowset");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)n * trt_rowset_rows(rows) * rows->width * 3;
-    HIP_TRY(ctx->d_rgb8.reserve(std::max<size_t>(bytes, 1)));
-    HIP_TRY(ctx->h_staging.reserve(std::max<size_t>(bytes, 1)));
-    const int rc = trt_render_device_batch_rgb8(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, ctx->d_rgb8.ptr, bytes);
-    if (rc || bytes == 0)
-        return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_rgb8.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    memcpy(rgb, ctx->h_staging.ptr, bytes);
-    return TRT_OK;
+    return render_host_as(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, rgb, kBytes, "trt_render_host_rgb8");
+}
+
+extern "C" int trt_render_host_ansi(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text)
+{
+    return render_host_as(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, text, kText, "trt_render_host_ansi");
 }
 
 extern "C" int trt_render_host_batch(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
                                      Vector *pixels)
 {
-    if (!ctx || !pixels)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (n < 1 || n > TRT_BATCH_MAX)
-        return fail(TRT_ERR_ARGUMENT, "a batch has 1 to %d cameras, %d given", TRT_BATCH_MAX, n);
-    if (!rowset_valid(rows))
-        return fail(TRT_ERR_ARGUMENT, "invalid rowset");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t count = (size_t)n * trt_rowset_rows(rows) * rows->width, bytes = count * sizeof(Vector);
-    HIP_TRY(ctx->d_fb.reserve(std::max<size_t>(count, 1) * 3));
-    HIP_TRY(ctx->h_staging.reserve(std::max<size_t>(bytes, 1)));
-    const int rc = trt_render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, ctx->d_fb.ptr, bytes);
-    if (rc || bytes == 0)
-        return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_fb.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    memcpy(pixels, ctx->h_staging.ptr, bytes);
-    return TRT_OK;
+    return render_host_as(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, pixels, kDoubles);
+}
+
+extern "C" int trt_render_host_batch_rgb8(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                          unsigned char *rgb)
+{
+    return render_host_as(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, rgb, kBytes);
+}
+
+extern "C" int trt_render_host_batch_ansi(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text)
+{
+    return render_host_as(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, kText);
 }
 
 extern "C" int trt_batch_info(trt_context *ctx, int *frames, int *render_launches)
@@ -1001,40 +1013,43 @@ extern "C" int trt_batch_info(trt_context *ctx, int *frames, int *render_launche
     return TRT_OK;
 }
 
+// The event slots of the context's last launches, at most `max` and oldest first, the stream synchronised: each(i, slot), which
+// returns an error or TRT_OK.  Returns how many launches there were, or the error.
+template <class Each>
+static int for_last_launches(trt_context *ctx, int max, Each each)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const long n = std::min<long>(std::min<long>(ctx->launches, kEventRing), max);
+    for (long i = 0; i < n; i++)
+    {
+        const int rc = each(i, (int)((ctx->launches - n + i) % kEventRing));
+        if (rc)
+            return rc;
+    }
+    return (int)n;
+}
+
 extern "C" int trt_kernel_times(trt_context *ctx, float *ms, int max)
 {
     if (!ctx || !ms || max < 0)
         return fail(TRT_ERR_ARGUMENT, "bad argument");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    const long have = std::min<long>(ctx->launches, kEventRing);
-    const long n = std::min<long>(have, max);
-    for (long i = 0; i < n; i++)
-    {
-        const long launch = ctx->launches - n + i;
-        const int slot = (int)(launch % kEventRing);
+    return for_last_launches(ctx, max, [&](long i, int slot) -> int {
         HIP_TRY(hipEventElapsedTime(&ms[i], ctx->ev_start[slot], ctx->ev_stop[slot]));
-    }
-    return (int)n;
+        return TRT_OK;
+    });
 }
 
 extern "C" int trt_render_kernel_times(trt_context *ctx, float *render_ms, float *reduce_ms, int max)
 {
     if (!ctx || !render_ms || max < 0)
         return fail(TRT_ERR_ARGUMENT, "bad argument");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    const long have = std::min<long>(ctx->launches, kEventRing);
-    const long n = std::min<long>(have, max);
-    for (long i = 0; i < n; i++)
-    {
-        const long launch = ctx->launches - n + i;
-        const int slot = (int)(launch % kEventRing);
+    return for_last_launches(ctx, max, [&](long i, int slot) -> int {
         HIP_TRY(hipEventElapsedTime(&render_ms[i], ctx->ev_start[slot], ctx->ev_mid[slot]));
         if (reduce_ms)
             HIP_TRY(hipEventElapsedTime(&reduce_ms[i], ctx->ev_mid[slot], ctx->ev_stop[slot]));
-    }
-    return (int)n;
+        return TRT_OK;
+    });
 }
 
 // trt_hip_diag.h: how many frames the context has launched, and the device time from the START of launch `first_launch` of context
@@ -1121,57 +1136,6 @@ extern "C" int trt_kernel_info(trt_context *ctx, int *vgprs, int *sgprs, int *st
     }
     if (compute_units)
         *compute_units = ctx->compute_units;
-    return TRT_OK;
-}
-
-extern "C" int trt_render_host_rgb8(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
-                                    unsigned char *rgb)
-{
-    if (!ctx || !rgb)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (!rowset_valid(rows))
-        return fail(TRT_ERR_ARGUMENT, "invalid rowset");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t count = (size_t)trt_rowset_rows(rows) * rows->width;
-    if (count == 0)
-        return TRT_OK;
-    HIP_TRY(ctx->d_rgb8.reserve(count * 3));
-    HIP_TRY(ctx->h_staging.reserve(count * 3));
-    const double t_begin = host_now_ms();
-    // the ordered mean writes the bytes itself ((int)(c*255), TRT.c:1157-1163): no framebuffer of doubles on the way
-    const int rc = trt_render_device_rgb8(ctx, camera, rows, bounce_limit, rays_per_pixel, ctx->d_rgb8.ptr, count * 3);
-    if (rc)
-        return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_rgb8.ptr, count * 3, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    memcpy(rgb, ctx->h_staging.ptr, count * 3);
-    if (print_host_times())
-        fprintf(stderr, "trt_render_host_rgb8: %.3f ms for %zu pixels\n", host_now_ms() - t_begin, count);
-    return TRT_OK;
-}
-
-extern "C" int trt_render_host_ansi(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text)
-{
-    if (!ctx || !text)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (!rowset_valid(rows))
-        return fail(TRT_ERR_ARGUMENT, "invalid rowset");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = trt_ansi_bytes(rows->width, trt_rowset_rows(rows));
-    if (bytes == 0)
-        return TRT_OK;
-    HIP_TRY(ctx->d_text.reserve(bytes));
-    HIP_TRY(ctx->h_staging.reserve(bytes));
-    const double t_begin = host_now_ms();
-    // the ordered mean writes the text itself (TRT.c:1142-1172): neither doubles nor RGB8 bytes on the way, and no formatting on the host
-    const int rc = trt_render_device_ansi(ctx, camera, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, bytes);
-    if (rc)
-        return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_text.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    memcpy(text, ctx->h_staging.ptr, bytes);
-    if (print_host_times())
-        fprintf(stderr, "trt_render_host_ansi: %.3f ms for %zu bytes of text\n", host_now_ms() - t_begin, bytes);
     return TRT_OK;
 }
 

@@ -218,6 +218,25 @@ def test_the_frames_of_a_batch_start_at_any_alignment(ctx):
             same_text(got[k], oracle("demo", w, h, index, 4, spp)[2], f"frame {k} of the batch, spp {spp}")
 
 
+ONE = [(67, 13, 3), (5, 1, 1)]  # 21 797 bytes, one more than a multiple of four: the text ends mid-word; 135 bytes: less than a wave's span
+
+
+@pytest.mark.parametrize("w,h,spp", ONE, ids=[f"{w}x{h}_spp{s}" for w, h, s in ONE])
+def test_a_batch_of_one_is_the_single_frame_entry_at_any_alignment(ctx, w, h, spp):
+    """one camera through trt_render_device_batch_ansi and through trt_render_device_ansi at every residue of the output address: the same
+    text, the emitter's, and not a byte outside it -- the two entries run ONE kernel, whose grid has exactly a single frame's waves"""
+    assert hip.ansi_bytes(w, h) % STORE == 1 or hip.ansi_bytes(w, h) < 64 * STORE
+    ctx.set_scene(scene("demo"))
+    cam = anim_cameras([7], w, h)[0]
+    want = oracle("demo", w, h, 7, 4, spp)[2]
+    for offset in range(STORE):
+        single = device_ansi(ctx, cam, w, h, 4, spp, offset, what=f"single, offset {offset}")
+        batch = batch_ansi(ctx, np.array([cam]), w, h, 4, spp, offset, what=f"batch of one, offset {offset}")
+        assert ctx.batch_info() == (1, 1)
+        same_text(batch[0], single, f"{w}x{h} spp {spp}: a batch of one against the single entry at offset {offset}")
+        same_text(single, want, f"{w}x{h} spp {spp} at offset {offset}")
+
+
 # ---- 4. every output kind on one context ----
 
 def test_every_output_kind_interleaved_on_one_context():

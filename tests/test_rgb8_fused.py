@@ -158,6 +158,25 @@ def test_the_frames_of_a_batch_start_at_any_alignment(ctx):
             same_bytes(got[k], oracle("demo", w, h, index, 4, spp)[1], f"frame {k} of the batch, spp {spp}")
 
 
+ONE = [(67, 13, 3), (5, 1, 1)]  # 2613 values, one more than a multiple of four: a head and a tail at every offset; 15 values: less than a wave
+
+
+@pytest.mark.parametrize("w,h,spp", ONE, ids=[f"{w}x{h}_spp{s}" for w, h, s in ONE])
+def test_a_batch_of_one_is_the_single_frame_entry_at_any_alignment(ctx, w, h, spp):
+    """one camera through trt_render_device_batch_rgb8 and through trt_render_device_rgb8 at every residue of the output address: the same
+    bytes, the oracle's, and not a byte outside them -- the two entries run ONE kernel, whose grid has exactly a single frame's lanes"""
+    assert (w * h * 3) % 4 == 1 or w * h * 3 < 64
+    ctx.set_scene(scene("demo"))
+    cam = anim_cameras([7], w, h)[0]
+    want = oracle("demo", w, h, 7, 4, spp)[1]
+    for offset in range(4):
+        single = device_rgb8(ctx, cam, w, h, 4, spp, offset, what=f"single, offset {offset}")
+        batch = batch_rgb8(ctx, np.array([cam]), w, h, 4, spp, offset, what=f"batch of one, offset {offset}")
+        assert ctx.batch_info() == (1, 1)
+        same_bytes(batch[0], single, f"{w}x{h} spp {spp}: a batch of one against the single entry at offset {offset}")
+        same_bytes(single, want, f"{w}x{h} spp {spp} at offset {offset}")
+
+
 # ---- 3. every output kind on one context ----
 
 def test_every_output_kind_interleaved_on_one_context():

@@ -439,6 +439,68 @@ def test_chunks_that_straddle_the_frames_of_a_batch(ctx, variant):
         reset(ctx)
 
 
+# The ordered mean of every output kind -- doubles, the emitter's bytes, the terminal's text -- is the last kernel of its launch and
+# leaves the queue armed for a launch of the same shape, which then runs no start_queue_kernel (trt_common.hpp: arm_queue).  The walk's
+# queue shapes, at one ray per pixel: "wide" 64x36 = 2304 units, nine 256-thread workgroups and a word per XCD (shift 3) -- eighteen
+# and twenty-seven workgroups for two and three cameras; "small" 8x4 = 32 units, ONE workgroup and one word (shift 0), for one, two or
+# three cameras alike; "big" 64x36 decoupled, 1024-thread workgroups of sixteen waves, one word; the reference-order kernel, which
+# neither uses nor arms the queue, in between.  (shape, cameras) in turn; the kind rotates with every launch, so a launch that finds
+# the queue armed finds it armed by another kind's kernel.
+ARMING_SHAPES = {"wide": ("plain", 64, 36), "small": ("plain", 8, 4), "big": ("decoupled", 64, 36), "reference": ("reference", 8, 4)}
+ARMING_WALK = [("wide", 1), ("wide", 1), ("wide", 1), ("wide", 2), ("wide", 2), ("wide", 1), ("small", 1), ("small", 1), ("small", 3), ("small", 2),
+               ("wide", 1), ("reference", 1), ("wide", 1), ("big", 1), ("big", 1), ("big", 2), ("big", 2), ("big", 3), ("reference", 2), ("big", 3),
+               ("wide", 3), ("wide", 3), ("small", 1), ("big", 1), ("wide", 1)]
+
+
+@functools.lru_cache(maxsize=None)
+def arming_oracle(w, h, cam):
+    """(doubles, bytes, text) of camera `cam` at 3 bounces and one ray per pixel: the oracle's frame, the checker's (int)(c*255) of it,
+    the emitter's text of those bytes"""
+    from test_ansi_text import emitter_text
+    px = oracle("s64", w, h, 3, 1, cam)[0]
+    rgb = T.oracle_rgb8(px).reshape(h, w, 3)
+    text = emitter_text(rgb)
+    rgb.setflags(write=False), text.setflags(write=False)
+    return px, rgb, text
+
+
+@gpu
+def test_every_kind_arms_the_queue_once_per_launch_for_single_frames_and_batches(ctx):
+    """the walk above, three times over (its length is a multiple of neither three nor two: every step meets every kind, a single camera both entries): every frame of every launch is
+    bit for bit the oracle's doubles, the oracle's bytes or the emitter's text of them -- a queue left unarmed, armed for another shape or
+    armed once per frame of a batch hands units out twice or not at all, which the fill's NaNs and the oracle show"""
+    assert len(ARMING_WALK) % 3 and len(ARMING_WALK) % 2 and 64 * 36 >= BLOCK << XCD_SHIFT and 3 * 8 * 4 <= BLOCK and 64 * 36 < COMPACT_BLOCK << XCD_SHIFT
+    cams = BATCH_CAMERAS[3]
+    single = [lambda c, r: ctx.render_host(c, r, 3, 1), lambda c, r: ctx.render_host_rgb8(c, r, 3, 1), lambda c, r: ctx.render_host_ansi(c, r, 3, 1)]
+    batch = [lambda c, r: ctx.render_host_batch(c, r, 3, 1), lambda c, r: ctx.render_host_batch_rgb8(c, r, 3, 1), lambda c, r: ctx.render_host_batch_ansi(c, r, 3, 1)]
+    seen = set()
+    try:
+        for step in range(3 * len(ARMING_WALK)):
+            shape, n = ARMING_WALK[step % len(ARMING_WALK)]
+            variant, w, h = ARMING_SHAPES[shape]
+            kind = step % 3
+            what = f"step {step}: {shape} x {n} as {('doubles', 'bytes', 'text')[kind]}"
+            configure(ctx, "s64", variant)
+            rows = hip.RowSet.whole(w, h)
+            before = ctx.launch_count()
+            if n == 1 and step % 2 == 0:  # a single camera through the single-frame entry and through the batch entry in turn
+                got = [single[kind](camera(cams[0]), rows)]
+            else:
+                got = batch[kind](np.array([camera(i) for i in cams[:n]]), rows)
+                assert ctx.batch_info() == (n, n if variant == "reference" else 1), (what, ctx.batch_info())
+            assert ran(ctx) == expected(variant) and ctx.launch_count() == before + 1, (what, ran(ctx))
+            for k in range(n):
+                want = arming_oracle(w, h, cams[k])[kind]
+                if kind == 0:
+                    same(got[k], want, f"{what}, frame {k}")
+                else:
+                    assert np.asarray(got[k]).dtype == np.uint8 and np.array_equal(np.asarray(got[k]).reshape(want.shape), want), f"{what}, frame {k}"
+            seen.add((shape, n, kind))
+        assert len(seen) == 3 * len(set(ARMING_WALK))
+    finally:
+        reset(ctx)
+
+
 # ---- (c) division by multiply-high on the device, at shapes the model picks ----
 
 def device_frame(ctx, key, variant, rows, b, spp, cam=None):
