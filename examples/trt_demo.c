@@ -2,12 +2,15 @@
  * host C builds the demo scene and the orbiting camera, the MI355X produces the frame through
  * the drop-in project_scene(), and the ANSI emitter stays on the host.
  *
- *   trt_demo <skybox-directory> [frames=0 (until Ctrl-C)] [width=160] [height=48] [--no-draw] [--rgb8] [--ansi] [--delta] [--step=SECONDS]
+ *   trt_demo <skybox-directory> [frames=0 (until Ctrl-C)] [width=160] [height=48] [--no-draw] [--rgb8] [--ansi] [--half] [--delta] [--step=SECONDS]
  *
  * --rgb8: the frame crosses PCIe as the 3 bytes per pixel the emitter makes of it (trt_render_frame_rgb8: the (int)(c*255) of
  * TRT.c:1157-1163 done on the device) instead of as 24-byte doubles; what reaches the terminal is the same.
  * --ansi: the frame crosses PCIe as the very text the terminal gets (trt_render_frame_ansi: the emitter's formatting done on the
  * device too), trt_ansi_bytes(width, height) bytes that one fwrite sends on; no trt_emitter on this route.
+ * --half: the text route with two pixel rows per line of text (trt_render_frame_ansi_half): upper-half-block glyphs whose foreground is the
+ * upper and whose background is the lower pixel, trt_ansi_half_bytes(width, height) bytes, one fwrite.  A pixel is one column by half a
+ * line, which is square: the camera's screen_width = 5 * width / height is unchanged.  The terminal must be in a UTF-8 locale.
  * --delta: the text route, but only what changed (trt_render_frame_ansi_delta): frame 0 arrives as the whole text, every later frame as the
  * records of the cells whose colour changed, each written with exactly the bytes the call reports.  Nothing else may be printed over
  * the picture, so the frames-per-second line goes to stderr once, at the end.
@@ -40,12 +43,12 @@ int main(int argc, char **argv)
 {
     if (argc < 2)
     {
-        fprintf(stderr, "usage: %s <skybox-directory> [frames] [width] [height] [--no-draw] [--rgb8] [--ansi] [--delta] [--step=SECONDS]\n", argv[0]);
+        fprintf(stderr, "usage: %s <skybox-directory> [frames] [width] [height] [--no-draw] [--rgb8] [--ansi] [--half] [--delta] [--step=SECONDS]\n", argv[0]);
         return 2;
     }
     const long frames = argc > 2 ? atol(argv[2]) : 0;
     const int width = argc > 3 ? atoi(argv[3]) : 160, height = argc > 4 ? atoi(argv[4]) : 48;
-    int draw = 1, bytes_only = 0, text_only = 0, delta = 0;
+    int draw = 1, bytes_only = 0, text_only = 0, delta = 0, half = 0;
     double step = -1.0;
     for (int i = 5; i < argc; i++)
     {
@@ -55,6 +58,8 @@ int main(int argc, char **argv)
             bytes_only = 1;
         else if (strcmp(argv[i], "--ansi") == 0)
             text_only = 1;
+        else if (strcmp(argv[i], "--half") == 0)
+            text_only = half = 1;
         else if (strcmp(argv[i], "--delta") == 0)
             text_only = delta = 1;
         else if (strncmp(argv[i], "--step=", 7) == 0)
@@ -94,7 +99,9 @@ int main(int argc, char **argv)
 
     Screen screen = {(Vector *)malloc(sizeof(Vector) * (size_t)width * height), width, height};
     unsigned char *rgb = (unsigned char *)malloc((size_t)width * height * 3);
-    const size_t text_room = delta ? trt_ansi_delta_capacity(width, height) : trt_ansi_bytes(width, height);
+    if (delta)
+        half = 0; /* the delta text has no half-block form */
+    const size_t text_room = delta ? trt_ansi_delta_capacity(width, height) : half ? trt_ansi_half_bytes(width, height) : trt_ansi_bytes(width, height);
     size_t text_bytes = text_room, written_bytes = 0;
     char *text = (char *)malloc(text_room ? text_room : 1);
     trt_emitter *emitter = NULL;
@@ -117,6 +124,14 @@ int main(int argc, char **argv)
             if (trt_render_frame_ansi_delta(&scene, width, height, TRT_REF_BOUNCE_LIMIT, TRT_REF_RAYS_PER_PIXEL, text, text_room, &text_bytes) != TRT_OK)
             {
                 fprintf(stderr, "trt_render_frame_ansi_delta: %s\n", trt_last_error());
+                return 1;
+            }
+        }
+        else if (half)
+        {
+            if (trt_render_frame_ansi_half(&scene, width, height, TRT_REF_BOUNCE_LIMIT, TRT_REF_RAYS_PER_PIXEL, text) != TRT_OK)
+            {
+                fprintf(stderr, "trt_render_frame_ansi_half: %s\n", trt_last_error());
                 return 1;
             }
         }
@@ -143,7 +158,7 @@ int main(int argc, char **argv)
         if (draw)
         {
             if (text_only)
-                written_bytes += fwrite(text, 1, text_bytes, stdout); /* --ansi: sizeof(screenbuffer), NULs included, as TRT.c:1171; --delta: what the call reported */
+                written_bytes += fwrite(text, 1, text_bytes, stdout); /* --ansi: sizeof(screenbuffer), NULs included, as TRT.c:1171; --half: the whole text; --delta: what the call reported */
             else
             {
                 if (bytes_only)
@@ -167,7 +182,7 @@ int main(int argc, char **argv)
                 trt_ansi_bytes(width, height));
     fprintf(stderr, "%ld frames %dx%d, frame producer %.3f ms/frame after a first call of %.1f ms (host-in/host-out%s, 10 bounces, 10 rays per pixel)\n",
             frame, width, height, frame > 1 ? 1e3 * producer_seconds / (frame - 1) : 0.0, 1e3 * first_call_seconds,
-            delta ? " as delta text" : text_only ? " as text" : bytes_only ? " as RGB8" : "");
+            delta ? " as delta text" : half ? " as half-block text" : text_only ? " as text" : bytes_only ? " as RGB8" : "");
 
     trt_emitter_destroy(emitter);
     free(screen.pixels);

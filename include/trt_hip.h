@@ -68,6 +68,12 @@ int trt_render_frame_rgb8(const Scene *scene, int width, int height, int bounce_
  * buffer of a trt_emitter (trt_host.h) after trt_emitter_patch_rgb8 of trt_render_frame_rgb8's bytes.  Lock and scene policy as above. */
 int trt_render_frame_ansi(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text);
 
+/* The same frame as the HALF-BLOCK text (trt_render_host_ansi_half below, on the default context: its format): two pixel rows per line of
+ * text, one terminal column by half a line per pixel, for a terminal in a UTF-8 locale.  text holds trt_ansi_half_bytes(width, height)
+ * bytes, the whole of which the host writes with one fwrite: byte for byte trt_emitter_half_rgb8 (trt_host.h) of trt_render_frame_rgb8's
+ * bytes.  Lock and scene policy as above. */
+int trt_render_frame_ansi_half(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text);
+
 /* The frame as the DELTA text against the frame this entry returned before (trt_render_host_ansi_delta below, on the default context: its
  * format, its rules for the host and its errors).  The first call, the first call of another size and the first call after trt_shutdown
  * return a keyframe: trt_render_frame_ansi's text.  text holds capacity_bytes >= trt_ansi_delta_capacity(width, height) bytes; the host
@@ -191,6 +197,38 @@ int trt_render_device_ansi(trt_context *ctx, const Camera *camera, const trt_row
  * a trt_dist_render_rgb8 gather holds): trt_ansi_bytes(width, rows) bytes at d_text, any alignment.  Asynchronous on the context's stream. */
 int trt_ansi_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text);
 
+/* ---- the half-block text: two pixel rows per line of text ---------------------------------------------------------------------
+ * The text above paints a pixel as two spaces on a background colour: two terminal columns and a whole line, 25 bytes.  The HALF-BLOCK
+ * text paints TWO pixels per character cell with the glyph U+2580 (upper half block; E2 96 80 in UTF-8, so the terminal must be in a
+ * UTF-8 locale): the foreground colour fills the upper half of the cell, the background colour the lower half.  One column and half a
+ * line make a square pixel, a terminal shows four times as many of them, and the text is 19.5 bytes per pixel.  For a screen of
+ * `width` x `rows` owned rows, T = (rows + 1) / 2 text rows, in order:
+ *   "\033[0;0H"                                                     6 bytes
+ *   per text row i = 0 .. T-1:
+ *     width cells "\033[38;2;RRR;GGG;BBB;48;2;rrr;ggg;bbbm" E2 96 80   39 bytes each: RRR;GGG;BBB the emitter's (int)(c*255) of owned row
+ *                                                                    2 i (the upper pixel), rrr;ggg;bbb those of owned row 2 i + 1 (the
+ *                                                                    lower pixel), three zero-padded digits each (TRT.c:1134-1139)
+ *     "\033[0m\n"                                                    5 bytes
+ * When rows is odd the last text row's lower pixel is 000;000;000.  No NUL follows (the full text's are the reference's sizeof; this
+ * format is the project's own).  Owned rows pair up in LOCAL order (local rows 2 i and 2 i + 1), as trt_render_device_ansi's shard
+ * texts count their rows: a sharding host wants an even tile_rows, so that the pairs are neighbours in the frame.
+ * csrc/trt_ansi_half.h is the format in code, trt_emitter_half_rgb8 (trt_host.h) its sequential statement on the host.  Checks, errors,
+ * stream behaviour and the trt_kernel_times accounting of every entry are those of the _ansi entry it mirrors (the batch and host forms
+ * stand with theirs below); capacities count bytes of text, to the byte.  None of them reads or changes the delta entries' shown
+ * frame. */
+
+/* Length of the half-block text: 6 + (39 * width + 5) * ((rows + 1) / 2), 0 unless both are positive. */
+size_t trt_ansi_half_bytes(int width, int rows);
+/* trt_render_device_ansi as the half-block text: trt_ansi_half_bytes(width, owned rows) bytes at d_text, any alignment, written by the
+ * pass that forms the ordered mean -- a lane forms both pixels of its cell; neither doubles nor RGB8 bytes are written on the way, every
+ * byte of the text is stored exactly once and none outside it (the reference-order kernel goes through a framebuffer and bytes of the
+ * context's). */
+int trt_render_device_ansi_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,
+                                int rays_per_pixel, void *d_text, size_t capacity_bytes);
+/* The formatting alone, of a frame that exists as RGB8 bytes in device memory (as trt_ansi_from_rgb8_device; e.g. what rank 0 of a
+ * trt_dist_render_rgb8 gather holds): trt_ansi_half_bytes(width, rows) bytes at d_text, any alignment.  Asynchronous. */
+int trt_ansi_half_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text);
+
 /* ---- the delta text: only the cells that changed --------------------------------------------------------------------------------
  * A terminal keeps what it was sent.  The text above repaints every cell of every frame, 25 bytes each; the DELTA text between the frame
  * the terminal shows and the next one holds, for every CHANGED cell (its three RGB8 bytes differ), rows ascending, left to right:
@@ -211,7 +249,8 @@ int trt_ansi_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, i
  *   - a text it drops instead of writing is a frame the terminal never showed: call trt_ansi_delta_reset, the next text is a keyframe;
  *   - nothing else may be printed over the picture (a status line belongs on stderr or below the last row);
  *   - the refraction extension and the batch entries have no delta form; of a trt_dist_render_rgb8 gather rank 0 formats the
- *     assembled bytes with trt_ansi_delta_from_rgb8_device. */
+ *     assembled bytes with trt_ansi_delta_from_rgb8_device;
+ *   - the half-block text has no delta form either (out of scope so far): the records here are of two-column cells of the full text. */
 
 /* Room for any text the delta entries write for a screen of `width` x `rows` owned rows: max(trt_ansi_bytes, rows * (21 * width + 18)),
  * the keyframe or the longest delta; 0 when either is not positive or above the limits. */
@@ -260,6 +299,11 @@ int trt_render_host_rgb8(trt_context *ctx, const Camera *camera, const trt_rowse
 int trt_render_host_ansi(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
                          char *text);
 
+/* trt_render_device_ansi_half into HOST memory: trt_ansi_half_bytes(width, owned rows) bytes (synchronous; one copy-out through pinned
+ * staging). */
+int trt_render_host_ansi_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                              char *text);
+
 /* Several cameras of the current scene in one call: an orbit, a replay, a stereo pair, the faces of an environment probe. */
 #define TRT_BATCH_MAX 8 /* = the eye-table slots a scene's tables have */
 
@@ -298,6 +342,14 @@ int trt_render_device_batch_ansi(trt_context *ctx, const Camera *cameras, int n,
 /* The same into HOST memory: text[b * trt_ansi_bytes(width, owned rows) ...] (synchronous; one copy-out through pinned staging). */
 int trt_render_host_batch_ansi(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
                                int rays_per_pixel, char *text);
+/* trt_render_device_batch as the half-block text (trt_render_device_ansi_half): frame b at d_text + b * trt_ansi_half_bytes(width, owned
+ * rows), aligned to nothing in general; launches, splits, trt_batch_info and errors as trt_render_device_batch_ansi, the capacity
+ * counted in bytes of text for n frames. */
+int trt_render_device_batch_ansi_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                      int rays_per_pixel, void *d_text, size_t capacity_bytes);
+/* The same into HOST memory: text[b * trt_ansi_half_bytes(width, owned rows) ...] (synchronous; one copy-out through pinned staging). */
+int trt_render_host_batch_ansi_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                    int rays_per_pixel, char *text);
 /* The most recent batch call of this context: its frames, and how many render-kernel launches served them
  * (1 = one launch over all frames; n = one launch per camera; between: the batch was split for LDS). */
 int trt_batch_info(trt_context *ctx, int *frames, int *render_launches);

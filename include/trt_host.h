@@ -75,6 +75,14 @@ int trt_emitter_patch_rgb8(trt_emitter *e, const unsigned char *rgb);
  * the limits, a capacity below the bound. */
 int trt_emitter_delta_rgb8(const unsigned char *shown, const unsigned char *next, int width, int rows, char *text, size_t capacity,
                            size_t *bytes);
+/* The HALF-BLOCK text of a frame of such bytes (rows x width x 3): two owned rows per line of text, one column and half a line per
+ * pixel.  The reference has no such emitter; the format is the project's own (csrc/trt_ansi_half.h).  "\033[0;0H"; per text
+ * row i < (rows + 1) / 2, width cells "\033[38;2;RRR;GGG;BBB;48;2;rrr;ggg;bbbm" and the glyph U+2580 in UTF-8 (E2 96 80) -- RRR;GGG;BBB
+ * the bytes of row 2 i (the foreground: the upper half), rrr;ggg;bbb those of row 2 i + 1 (the background: the lower half; 000;000;000
+ * behind the last row of an odd frame) -- then "\033[0m\n".  No NUL: *bytes = 6 + (39 * width + 5) * ((rows + 1) / 2), which `capacity`
+ * must hold.  The sequential statement the device kernels (trt_render_device_ansi_half, trt_hip.h) are tested against, and the emitter
+ * of hosts that fetch RGB8 bytes.  TRT_HOST_ERR_ARGUMENT: NULL, a size that is not positive, a capacity below the length. */
+int trt_emitter_half_rgb8(const unsigned char *rgb, int width, int rows, char *text, size_t capacity, size_t *bytes);
 /* TRT.c:1171: one fwrite of the whole buffer (trailing NULs included, as the reference does) */
 int trt_emitter_write(const trt_emitter *e, FILE *stream);
 /* TRT.c:1084-1099: the unbuffered printf form */

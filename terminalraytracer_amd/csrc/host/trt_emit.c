@@ -180,6 +180,49 @@ int trt_emitter_delta_rgb8(const unsigned char *shown, const unsigned char *next
     return TRT_HOST_OK;
 }
 
+/* The half-block text (csrc/trt_ansi_half.h holds the format): two owned rows per line of text, the upper one as the foreground and the
+ * lower one as the background colour of an upper-half-block glyph.  Plain loops, on purpose without that header -- this is what the
+ * header's arithmetic and the device kernels are held against. */
+static const char k_half_cell[] = "\033[38;2;000;000;000;48;2;000;000;000m\xe2\x96\x80";
+static const char k_half_end[] = "\033[0m\n";
+enum
+{
+    HALF_CELL_LEN = sizeof(k_half_cell) - 1, /* 39 */
+    HALF_END_LEN = sizeof(k_half_end) - 1,   /* 5 */
+    HALF_UPPER_AT = 7,                       /* "\033[38;2;" */
+    HALF_LOWER_AT = 24                       /* ... "RRR;GGG;BBB;48;2;" */
+};
+
+int trt_emitter_half_rgb8(const unsigned char *rgb, int width, int rows, char *text, size_t capacity, size_t *bytes)
+{
+    if (!rgb || !text || !bytes || width <= 0 || rows <= 0)
+        return TRT_HOST_ERR_ARGUMENT;
+    const size_t text_rows = ((size_t)rows + 1) / 2;
+    if (capacity < HOME_LEN + ((size_t)HALF_CELL_LEN * width + HALF_END_LEN) * text_rows)
+        return TRT_HOST_ERR_ARGUMENT;
+    char *p = text;
+    memcpy(p, k_home, HOME_LEN);
+    p += HOME_LEN;
+    for (int upper_row = 0; upper_row < rows; upper_row += 2)
+    {
+        const unsigned char *upper = rgb + (size_t)upper_row * width * 3;
+        const unsigned char *lower = upper_row + 1 < rows ? upper + (size_t)width * 3 : NULL; /* behind an odd frame's last row: black */
+        for (int col = 0; col < width; col++, p += HALF_CELL_LEN)
+        {
+            memcpy(p, k_half_cell, HALF_CELL_LEN);
+            for (int ch = 0; ch < 3; ch++)
+            {
+                three_digits(p + HALF_UPPER_AT + 4 * ch, upper[3 * col + ch]);
+                three_digits(p + HALF_LOWER_AT + 4 * ch, lower ? lower[3 * col + ch] : 0);
+            }
+        }
+        memcpy(p, k_half_end, HALF_END_LEN);
+        p += HALF_END_LEN;
+    }
+    *bytes = (size_t)(p - text);
+    return TRT_HOST_OK;
+}
+
 int trt_emitter_write(const trt_emitter *e, FILE *stream)
 {
     if (!e || !stream)

@@ -10,6 +10,7 @@
 #include "trt_simple.hpp"
 #include "trt_ansi.hpp"
 #include "trt_ansi_delta.hpp"
+#include "trt_ansi_half.hpp"
 
 using namespace trt_impl;
 
@@ -370,14 +371,19 @@ extern "C" int trt_read_counters(trt_context *ctx, unsigned long long *path_rays
 // ---- the launch of a frame, or of several cameras of one scene (on the host a single frame is a batch of one) ----
 
 // What a launch leaves of a frame: the Screen's pixels of three doubles (TRT.c:188-193), the emitter's three bytes per pixel
-// ((int)(c*255), TRT.c:1157-1163), or the text the emitter makes of those bytes (TRT.c:1142-1172; trt_ansi.h).
-enum Output : int { kDoubles, kBytes, kText };
+// ((int)(c*255), TRT.c:1157-1163), the text the emitter makes of those bytes (TRT.c:1142-1172; trt_ansi.h), or the half-block text of
+// them, two owned rows per line of text (trt_ansi_half.h).
+enum Output : int { kDoubles, kBytes, kText, kHalfText };
+
+static bool is_text(Output kind) { return kind == kText || kind == kHalfText; }
 
 // bytes of one frame of `rows` rows of `width` pixels
 static size_t frame_bytes(Output kind, int width, int rows)
 {
     if (kind == kText)
         return (size_t)trt_ansi_text_bytes(width, rows);
+    if (kind == kHalfText)
+        return (size_t)trt_ansi_half_text_bytes(width, rows);
     return (size_t)rows * width * 3 * (kind == kBytes ? 1u : sizeof(double));
 }
 
@@ -456,6 +462,15 @@ static void launch_ansi_from_rgb8(hipStream_t stream, const unsigned char *d_rgb
                        (unsigned char *)d_text, width, rows, trt_ansi_row_magic(width));
 }
 
+// the half-block text of such a frame (trt_ansi_half.hpp)
+static void launch_ansi_half_from_rgb8(hipStream_t stream, const unsigned char *d_rgb8, int width, int rows, void *d_text)
+{
+    const unsigned long long bytes = trt_ansi_half_text_bytes(width, rows),
+                             waves = trt_ansi_half_waves(trt_ansi_half_split_of((unsigned long long)d_text, bytes).words);
+    hipLaunchKernelGGL(trt::ansi_half_from_rgb8_kernel, dim3((unsigned)((waves * 64 + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK)), dim3(TRT_REDUCE_BLOCK), 0, stream, d_rgb8,
+                       (unsigned char *)d_text, width, rows, trt_ansi_half_row_magic(width), trt_ansi_half_width_magic(width));
+}
+
 // `lane_set` 0: the context's stream, queue word 0, d_samples; 1: the alternate stream, its own queue word and scratch
 // (trt_render_host renders odd bands there).
 // `entry`: a frame is one entry of the context's launch history (events, trt_kernel_times); the frames of a batch that is served
@@ -464,16 +479,16 @@ static void launch_ansi_from_rgb8(hipStream_t stream, const unsigned char *d_rgb
 enum : int { kEntryOpens = 1, kEntryCloses = 2, kEntryWhole = kEntryOpens | kEntryCloses };
 
 // The reference-order kernel's launch: it has no scratch and no mean.  Its bytes are its doubles, rendered into the context's
-// framebuffer, through quantize_kernel, and its text is those bytes through ansi_from_rgb8_kernel.
+// framebuffer, through quantize_kernel, and its text is those bytes through ansi_from_rgb8_kernel or ansi_half_from_rgb8_kernel.
 static int launch_reference(trt_context *ctx, const RenderPlan &plan, trt::FrameView f, void *out, Output kind, long pixels, hipStream_t stream, int entry)
 {
     const int slot = (int)(ctx->launches % kEventRing);
     if (kind != kDoubles)
     {
-        if (ctx->d_fb.capacity < (size_t)pixels * 3 || (kind == kText && ctx->d_text_rgb8.capacity < (size_t)pixels * 3))
+        if (ctx->d_fb.capacity < (size_t)pixels * 3 || (is_text(kind) && ctx->d_text_rgb8.capacity < (size_t)pixels * 3))
             HIP_TRY(hipStreamSynchronize(stream)); // a frame in flight may still use the old framebuffer
         HIP_TRY(ctx->d_fb.reserve((size_t)pixels * 3));
-        if (kind == kText) // text: the framebuffer's bytes first, in a buffer of the context's
+        if (is_text(kind)) // text: the framebuffer's bytes first, in a buffer of the context's
             HIP_TRY(ctx->d_text_rgb8.reserve((size_t)pixels * 3));
         f.out = ctx->d_fb.ptr;
     }
@@ -493,9 +508,11 @@ static int launch_reference(trt_context *ctx, const RenderPlan &plan, trt::Frame
         HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
     if (kind != kDoubles)
         hipLaunchKernelGGL(trt::quantize_kernel, dim3((unsigned)((pixels * 3 + 255) / 256)), dim3(256), 0, stream, (const double *)f.out, pixels * 3,
-                           kind == kText ? ctx->d_text_rgb8.ptr : (unsigned char *)out);
+                           is_text(kind) ? ctx->d_text_rgb8.ptr : (unsigned char *)out);
     if (kind == kText)
         launch_ansi_from_rgb8(stream, ctx->d_text_rgb8.ptr, f.width, f.local_rows, out);
+    if (kind == kHalfText)
+        launch_ansi_half_from_rgb8(stream, ctx->d_text_rgb8.ptr, f.width, f.local_rows, out);
     if (entry & kEntryCloses)
         HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
     HIP_TRY(hipGetLastError());
@@ -529,6 +546,15 @@ static void launch_ordered_mean(hipStream_t stream, const RenderPlan &plan, cons
         const unsigned long long waves = trt_ansi_waves(frames > 1 ? bytes / 4 : trt_ansi_split_of((unsigned long long)out, bytes).words);
         hipLaunchKernelGGL(trt::reduce_samples_ansi_kernel, blocks(waves * 64), block, 0, stream, samples, (unsigned char *)out, f.width, f.local_rows,
                            trt_ansi_row_magic(f.width), f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
+        break;
+    }
+    case kHalfText: // a wave per TRT_ANSI_HALF_WAVE_WORDS aligned words
+    {
+        const unsigned long long bytes = trt_ansi_half_text_bytes(f.width, f.local_rows);
+        const unsigned long long waves = trt_ansi_half_waves(frames > 1 ? bytes / 4 : trt_ansi_half_split_of((unsigned long long)out, bytes).words);
+        hipLaunchKernelGGL(trt::reduce_samples_ansi_half_kernel, blocks(waves * 64), block, 0, stream, samples, (unsigned char *)out, f.width, f.local_rows,
+                           trt_ansi_half_row_magic(f.width), trt_ansi_half_width_magic(f.width), f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64,
+                           f.queue_shift);
         break;
     }
     }
@@ -601,7 +627,7 @@ static int launch_production(trt_context *ctx, const RenderPlan &plan, trt::Fram
 }
 
 // Carries out a planned launch on the route its variant takes, into `out` as `kind`: doubles, (kBytes) cast to the emitter's bytes in
-// the ordered mean's pass, or (kText) cast and formatted as the terminal's text in the same pass.
+// the ordered mean's pass, or (kText, kHalfText) cast and formatted as the terminal's text in the same pass.
 static int launch_render(trt_context *ctx, const RenderPlan &plan, const trt::FrameView &f, const trt::GridView &grids, const trt::BatchView *batch, void *out,
                          Output kind, long pixels, int lane_set, int entry)
 {
@@ -676,6 +702,29 @@ extern "C" int trt_render_device_ansi(trt_context *ctx, const Camera *camera, co
                                       size_t capacity_bytes)
 {
     return render_device_on(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, 0, kEntryWhole, kText);
+}
+
+extern "C" size_t trt_ansi_half_bytes(int width, int rows)
+{
+    return (size_t)trt_ansi_half_text_bytes(width, rows);
+}
+
+extern "C" int trt_render_device_ansi_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                                           size_t capacity_bytes)
+{
+    return render_device_on(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, 0, kEntryWhole, kHalfText);
+}
+
+extern "C" int trt_ansi_half_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text)
+{
+    if (!ctx || !d_rgb8 || !d_text)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (width <= 0 || rows <= 0 || (unsigned long long)width * rows >= 0x7fffffffull)
+        return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, rows);
+    HIP_TRY(hipSetDevice(ctx->device));
+    launch_ansi_half_from_rgb8(ctx->stream, (const unsigned char *)d_rgb8, width, rows, d_text);
+    HIP_TRY(hipGetLastError());
+    return TRT_OK;
 }
 
 extern "C" int trt_ansi_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text)
@@ -957,7 +1006,7 @@ static int render_host_as(trt_context *ctx, const Camera *cameras, int n, bool b
     if (kind == kDoubles)
         HIP_TRY(ctx->d_fb.reserve((room + sizeof(double) - 1) / sizeof(double)));
     else
-        HIP_TRY((kind == kBytes ? ctx->d_rgb8 : ctx->d_text).reserve(room));
+        HIP_TRY((kind == kBytes ? ctx->d_rgb8 : ctx->d_text).reserve(room)); // either text in the context's text buffer
     void *const d_out = kind == kDoubles ? (void *)ctx->d_fb.ptr : kind == kBytes ? (void *)ctx->d_rgb8.ptr : (void *)ctx->d_text.ptr;
     HIP_TRY(ctx->h_staging.reserve(room));
     const double t_begin = host_now_ms();
@@ -1000,6 +1049,23 @@ extern "C" int trt_render_host_batch_rgb8(trt_context *ctx, const Camera *camera
 extern "C" int trt_render_host_batch_ansi(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text)
 {
     return render_host_as(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, kText);
+}
+
+extern "C" int trt_render_device_batch_ansi_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                                 void *d_text, size_t capacity_bytes)
+{
+    return render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, kHalfText);
+}
+
+extern "C" int trt_render_host_ansi_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text)
+{
+    return render_host_as(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, text, kHalfText, "trt_render_host_ansi_half");
+}
+
+extern "C" int trt_render_host_batch_ansi_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                               char *text)
+{
+    return render_host_as(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, kHalfText);
 }
 
 extern "C" int trt_batch_info(trt_context *ctx, int *frames, int *render_launches)

@@ -50,6 +50,7 @@ SYMBOLS = {
     "render_frame": (_I, [C.POINTER(L.Scene), C.POINTER(L.Screen), _I, _I]),
     "trt_render_frame_rgb8": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP]),
     "trt_render_frame_ansi": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP]),
+    "trt_render_frame_ansi_half": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP]),
     "trt_render_frame_ansi_delta": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
     "trt_init": (_I, [_I]),
     "trt_shutdown": (_I, []),
@@ -67,6 +68,12 @@ SYMBOLS = {
     "trt_ansi_bytes": (_SZ, [_I, _I]),
     "trt_render_device_ansi": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ]),
     "trt_ansi_from_rgb8_device": (_I, [_VP, _VP, _I, _I, _VP]),
+    "trt_ansi_half_bytes": (_SZ, [_I, _I]),
+    "trt_render_device_ansi_half": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ]),
+    "trt_ansi_half_from_rgb8_device": (_I, [_VP, _VP, _I, _I, _VP]),
+    "trt_render_host_ansi_half": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP]),
+    "trt_render_device_batch_ansi_half": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ]),
+    "trt_render_host_batch_ansi_half": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP]),
     "trt_ansi_delta_capacity": (_SZ, [_I, _I]),
     "trt_ansi_delta_from_rgb8_device": (_I, [_VP, _VP, _VP, _I, _I, _VP, _SZ, _VP]),
     "trt_ansi_delta_kernel_times": (_I, [_VP, _VP, _VP, _I, _I, _VP, _SZ, _VP, C.POINTER(C.c_float)]),
@@ -439,6 +446,24 @@ class Context:
         """the text of a width x rows frame of RGB8 bytes in device memory, at text_ptr (trt_ansi_from_rgb8_device)"""
         _check(lib().trt_ansi_from_rgb8_device(self._h, _VP(rgb_ptr), width, rows, _VP(text_ptr)))
 
+    def render_device_ansi_half(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
+        """the frame as the half-block text in device memory, two owned rows per line of text: ansi_half_bytes(width, owned rows) bytes at
+        any alignment, formatted by the ordered-mean pass itself (trt_render_device_ansi_half)"""
+        cam = camera_struct(camera_array)
+        _check(lib().trt_render_device_ansi_half(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel,
+                                                 _VP(device_ptr), capacity_bytes))
+
+    def render_host_ansi_half(self, camera_array, rows, bounce_limit, rays_per_pixel):
+        """the same into host memory: uint8 [ansi_half_bytes(width, owned rows)] (trt_render_host_ansi_half)"""
+        out = np.zeros(ansi_half_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows))), dtype=np.uint8)
+        cam = camera_struct(camera_array)
+        _check(lib().trt_render_host_ansi_half(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data))
+        return out
+
+    def ansi_half_from_rgb8(self, rgb_ptr, width, rows, text_ptr):
+        """the half-block text of a width x rows frame of RGB8 bytes in device memory, at text_ptr (trt_ansi_half_from_rgb8_device)"""
+        _check(lib().trt_ansi_half_from_rgb8_device(self._h, _VP(rgb_ptr), width, rows, _VP(text_ptr)))
+
     def ansi_delta_from_rgb8(self, shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr):
         """the delta text between two width x rows frames of RGB8 bytes in device memory, at text_ptr, its length (a uint64) at the device
         address bytes_ptr (trt_ansi_delta_from_rgb8_device)"""
@@ -519,6 +544,21 @@ class Context:
         out = np.zeros((cams.shape[0], ansi_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows)))), dtype=np.uint8)
         _check(lib().trt_render_host_batch_ansi(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
                                                 out.ctypes.data))
+        return out
+
+    def render_batch_ansi_half(self, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
+        """cameras[n, 15] as the half-block text in device memory; frame b at device_ptr + b * ansi_half_bytes(width, owned rows)
+        (trt_render_device_batch_ansi_half)"""
+        cams = self._camera_batch(cameras)
+        _check(lib().trt_render_device_batch_ansi_half(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
+                                                       _VP(device_ptr), capacity_bytes))
+
+    def render_host_batch_ansi_half(self, cameras, rows, bounce_limit, rays_per_pixel):
+        """the same into host memory: uint8 [n, ansi_half_bytes(width, owned rows)] (trt_render_host_batch_ansi_half)"""
+        cams = self._camera_batch(cameras)
+        out = np.zeros((cams.shape[0], ansi_half_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows)))), dtype=np.uint8)
+        _check(lib().trt_render_host_batch_ansi_half(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
+                                                     out.ctypes.data))
         return out
 
     def batch_info(self):
@@ -641,6 +681,23 @@ def ansi_bytes(width, rows):
     return int(lib().trt_ansi_bytes(width, rows))
 
 
+def ansi_half_bytes(width, rows):
+    """length of the half-block text of a width x rows screen: 6 + (39 * width + 5) * ((rows + 1) // 2), 0 unless both are positive
+    (trt_ansi_half_bytes)"""
+    return int(lib().trt_ansi_half_bytes(width, rows))
+
+
+def _header_constant(header, name):
+    """an integer #define of a header under csrc/: the layout headers are what the kernels compile, the binding reads them, it does not restate them"""
+    import re
+    with open(os.path.join(_HERE, "csrc", header)) as fh:
+        return int(re.search(r"^#define\s+" + name + r"\s+(\d+)", fh.read(), re.M).group(1))
+
+
+# words of the half-block text a wave of the device pass stores (csrc/trt_ansi_half.h): a wave's span is four times as many bytes
+ANSI_HALF_WAVE_WORDS = _header_constant("trt_ansi_half.h", "TRT_ANSI_HALF_WAVE_WORDS")
+
+
 def ansi_delta_capacity(width, rows):
     """room for any text the delta entries write: max(ansi_bytes, rows * (21 * width + 18)); 0 when a size is not positive or above the
     format's limits (trt_ansi_delta_capacity)"""
@@ -663,6 +720,15 @@ def render_frame_ansi(scene_data, width, height, bounce_limit=10, rays_per_pixel
     scene = scene_data.as_scene()
     out = np.zeros(ansi_bytes(width, height), dtype=np.uint8)
     _check(lib().trt_render_frame_ansi(C.byref(scene), width, height, bounce_limit, rays_per_pixel, out.ctypes.data))
+    return out
+
+
+def render_frame_ansi_half(scene_data, width, height, bounce_limit=10, rays_per_pixel=10):
+    """Host-in, half-block-text-out frame: uint8 [ansi_half_bytes(width, height)], two pixel rows per line of text, formatted on the
+    device (trt_render_frame_ansi_half)."""
+    scene = scene_data.as_scene()
+    out = np.zeros(ansi_half_bytes(width, height), dtype=np.uint8)
+    _check(lib().trt_render_frame_ansi_half(C.byref(scene), width, height, bounce_limit, rays_per_pixel, out.ctypes.data))
     return out
 
 

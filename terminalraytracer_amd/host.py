@@ -28,6 +28,7 @@ HOST_SYMBOLS = {
     "trt_emitter_patch": (C.c_int, [_VP, C.POINTER(L.Screen)]),
     "trt_emitter_patch_rgb8": (C.c_int, [_VP, _VP]),
     "trt_emitter_delta_rgb8": (_I, [_VP, _VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "trt_emitter_half_rgb8": (_I, [_VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_write": (_I, [_VP, _VP]),
     "trt_draw_screen": (_I, [C.POINTER(L.Screen), _VP]),
     "trt_fnv1a64": (C.c_ulonglong, [_VP, C.c_size_t]),
@@ -117,6 +118,19 @@ def emitter_delta_rgb8(shown, nxt):
     if rc != 0:
         raise ValueError(f"trt_emitter_delta_rgb8({width}, {rows}) failed with {rc}")
     return out[:n.value].copy()
+
+
+def emitter_half_rgb8(rgb):
+    """the half-block text of a frame of bytes [rows, width, 3], two rows per line of text, formatted on the host: uint8
+    [6 + (39 width + 5) ((rows + 1) // 2)] (trt_emitter_half_rgb8)"""
+    a = np.ascontiguousarray(rgb, dtype=np.uint8)
+    rows, width, _ = a.shape
+    out = np.empty(6 + (39 * width + 5) * ((rows + 1) // 2), dtype=np.uint8)
+    n = C.c_size_t(0)
+    rc = lib().trt_emitter_half_rgb8(a.ctypes.data, width, rows, out.ctypes.data, out.size, C.byref(n))
+    if rc != 0 or n.value != out.size:
+        raise ValueError(f"trt_emitter_half_rgb8({width}, {rows}) failed with {rc}, {n.value} bytes")
+    return out
 
 
 def fnv1a64(buf):
