@@ -6,6 +6,7 @@
 
 #include "trt_device.hpp"
 #include "trt_filter.h"
+#include "trt_mean_lanes.h"
 
 namespace trt
 {
@@ -93,19 +94,77 @@ __global__ void start_queue_kernel(unsigned int *queue, unsigned grid, unsigned 
 // Over the frames of a launch (a single frame is a launch of one): blockIdx.y is the frame, its scratch is
 // samples[((frame * spp + k) * values + i)] and its pixels out[frame * values + i].  Being the last kernel of a launch, it leaves the
 // launch's queue ready for a launch of the same shape (start_queue_kernel's job, once per launch: the render kernel that used the queue
-// has finished, and the next frame of this context then has no kernel in front of its render kernel)
+// has finished, and the next frame of this context then has no kernel in front of its render kernel).
+// WIDE AND DEEP (profiles/r14/a_ordered_mean.md): beside the render kernels of the frames in flight this pass costs the wave slots it
+// holds and for how long, so a wave is to make few round trips to memory with much in flight.  A lane owns kMeanGroup consecutive
+// values (trt_mean_lanes.h: the groups, then a lane per value they leave) and issues the loads of kMeanDeep samples -- one 16-byte
+// load each -- before the first add; the adds follow in sample order as the loads land.  spp is whole blocks of kMeanDeep, then a
+// remainder a sample at a time; the reference's spp = 10 is two blocks.  Two values x five samples is 30 VGPRs: a wave fits into the
+// 32 registers that four plain render waves of 119 leave a SIMD, which deeper and wider shapes (50, 54) do not, and config 5 pays for.
+// Frame, values and out are 8-byte aligned and no more: the 16-byte accesses are the hardware's unaligned ones, as
+// reduce_samples_rgb8's are.
+#ifndef TRT_REDUCE_DEEP
+#define TRT_REDUCE_DEEP 5
+#endif
+#ifndef TRT_REDUCE_NT
+#define TRT_REDUCE_NT 0 // 1: non-temporal loads of the scratch (A/B in profiles/r14/a_ordered_mean.md)
+#endif
+constexpr int kMeanGroup = TRT_MEAN_GROUP, kMeanDeep = TRT_REDUCE_DEEP;
+
+__device__ __forceinline__ double mean_sample(const double *p)
+{
+#if TRT_REDUCE_NT
+    return __builtin_nontemporal_load(p);
+#else
+    return *p;
+#endif
+}
+
 __global__ __launch_bounds__(256) void reduce_samples_kernel(const double *samples, double *out, long values, int spp, double inv_spp,
                                                              unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
 {
     arm_queue(queue, grid, waves_per_group, shift);
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x; // one thread per colour channel of a pixel
-    if (i >= values)
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int owned = trt_mean_lane_values(values, i);
+    if (owned == 0)
         return;
-    const double *mine = samples + (size_t)blockIdx.y * (size_t)spp * (size_t)values;
-    double mean = 0.0;
-    for (int k = 0; k < spp; k++)
-        mean += mine[(long)k * values + i];
-    out[(size_t)blockIdx.y * (size_t)values + i] = mean * inv_spp;
+    const long v = (long)trt_mean_lane_first(values, i);
+    const double *s = samples + (size_t)blockIdx.y * (size_t)spp * (size_t)values + v; // sample k of the lane's values: s + k * values
+    double *to = out + (size_t)blockIdx.y * (size_t)values + v;
+    if (owned == kMeanGroup)
+    {
+        double mean[kMeanGroup];
+#pragma unroll
+        for (int g = 0; g < kMeanGroup; g++)
+            mean[g] = 0.0;
+        int k = 0;
+        for (; k + kMeanDeep <= spp; k += kMeanDeep)
+        {
+            double block[kMeanDeep][kMeanGroup];
+#pragma unroll
+            for (int d = 0; d < kMeanDeep; d++, s += values)
+#pragma unroll
+                for (int g = 0; g < kMeanGroup; g++)
+                    block[d][g] = mean_sample(s + g);
+#pragma unroll
+            for (int d = 0; d < kMeanDeep; d++) // in sample order
+#pragma unroll
+                for (int g = 0; g < kMeanGroup; g++)
+                    mean[g] += block[d][g];
+        }
+        for (; k < spp; k++, s += values)
+#pragma unroll
+            for (int g = 0; g < kMeanGroup; g++)
+                mean[g] += mean_sample(s + g);
+#pragma unroll
+        for (int g = 0; g < kMeanGroup; g++)
+            to[g] = mean[g] * inv_spp;
+        return;
+    }
+    double mean = 0.0; // a value behind the groups
+    for (int k = 0; k < spp; k++, s += values)
+        mean += mean_sample(s);
+    *to = mean * inv_spp;
 }
 
 // (int)(c*255) per channel, TRT.c:1157-1163

@@ -531,8 +531,8 @@ static void launch_ordered_mean(hipStream_t stream, const RenderPlan &plan, cons
     const auto blocks = [&](unsigned long long lanes) { return dim3((unsigned)((lanes + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK), frames); };
     switch (kind)
     {
-    case kDoubles: // a lane per value
-        hipLaunchKernelGGL(trt::reduce_samples_kernel, blocks(values), block, 0, stream, samples, (double *)out, values, f.spp, f.inv_spp, f.queue, plan.grid,
+    case kDoubles: // a lane per group of values and one per value the groups leave
+        hipLaunchKernelGGL(trt::reduce_samples_kernel, blocks((unsigned long long)trt_mean_lanes(values)), block, 0, stream, samples, (double *)out, values, f.spp, f.inv_spp, f.queue, plan.grid,
                            plan.block / 64, f.queue_shift);
         break;
     case kBytes: // a lane per group of four values and one per value of a frame's head and tail
