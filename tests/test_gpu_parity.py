@@ -29,6 +29,8 @@ def ctx():
 
 
 def test_device_division_and_sqrt_are_correctly_rounded(ctx):
+    """Random operands, judged by the host's arithmetic.  They come no nearer to a rounding boundary than some 2^-22 ulp: the
+    constructed worst cases, judged by exact integers, are in tests/test_hard_roundings.py."""
     rng = np.random.default_rng(1)
     n = 1 << 20
     a = rng.uniform(0.0, 1.0, n) * 10.0 ** rng.uniform(-30, 30, n)
@@ -1010,7 +1012,9 @@ def test_lean_normalisation_and_sqrt_equal_the_plain_operators(ctx):
     """unit() shares one reciprocal refinement between its three divisions and takes a square root without the compiler's
     range handling when a whole wave is mid-range, and falls back to the plain operators otherwise (csrc/trt_device.hpp).
     Both must give the bits of `/` and sqrt: millions of vectors of every kind, laid out so that some waves are uniformly
-    mid-range (short path taken) and others mix in zeros, denormals, huge, tiny, inf and NaN (fallback taken)."""
+    mid-range (short path taken) and others mix in zeros, denormals, huge, tiny, inf and NaN (fallback taken).
+    The operands are random: vectors whose length is a worst-case divisor, roots next to a midpoint and the windows' exact
+    edges are in tests/test_hard_roundings.py."""
     rng = np.random.default_rng(3)
     n = 1 << 21
     v = rng.normal(size=(n, 4)) * 10.0 ** rng.uniform(-3, 3, (n, 1))
