@@ -14,6 +14,8 @@
  * --delta: the text route, but only what changed (trt_render_frame_ansi_delta): frame 0 arrives as the whole text, every later frame as the
  * records of the cells whose colour changed, each written with exactly the bytes the call reports.  Nothing else may be printed over
  * the picture, so the frames-per-second line goes to stderr once, at the end.
+ * --half --delta: the same in half-block cells (trt_render_frame_ansi_delta_half): frame 0 arrives as --half's whole text, every later frame
+ * as the records of the one-column cells either of whose two pixels changed.
  * --step=SECONDS: frame k is rendered at orbit time k * SECONDS instead of at the wall clock's (a replay: the same frames every run).
  *
  * The scene literals are the reference's (TRT.c:1256-1288). */
@@ -99,9 +101,9 @@ int main(int argc, char **argv)
 
     Screen screen = {(Vector *)malloc(sizeof(Vector) * (size_t)width * height), width, height};
     unsigned char *rgb = (unsigned char *)malloc((size_t)width * height * 3);
-    if (delta)
-        half = 0; /* the delta text has no half-block form */
-    const size_t text_room = delta ? trt_ansi_delta_capacity(width, height) : half ? trt_ansi_half_bytes(width, height) : trt_ansi_bytes(width, height);
+    const size_t text_room = delta  ? (half ? trt_ansi_delta_half_capacity(width, height) : trt_ansi_delta_capacity(width, height))
+                             : half ? trt_ansi_half_bytes(width, height)
+                                    : trt_ansi_bytes(width, height);
     size_t text_bytes = text_room, written_bytes = 0;
     char *text = (char *)malloc(text_room ? text_room : 1);
     trt_emitter *emitter = NULL;
@@ -119,7 +121,15 @@ int main(int argc, char **argv)
         trt_orbit_camera(&scene.camera, step >= 0.0 ? step * (double)frame : t);
 
         const double before = seconds_since(&start);
-        if (delta)
+        if (delta && half)
+        {
+            if (trt_render_frame_ansi_delta_half(&scene, width, height, TRT_REF_BOUNCE_LIMIT, TRT_REF_RAYS_PER_PIXEL, text, text_room, &text_bytes) != TRT_OK)
+            {
+                fprintf(stderr, "trt_render_frame_ansi_delta_half: %s\n", trt_last_error());
+                return 1;
+            }
+        }
+        else if (delta)
         {
             if (trt_render_frame_ansi_delta(&scene, width, height, TRT_REF_BOUNCE_LIMIT, TRT_REF_RAYS_PER_PIXEL, text, text_room, &text_bytes) != TRT_OK)
             {
@@ -178,11 +188,11 @@ int main(int argc, char **argv)
         }
     }
     if (delta)
-        fprintf(stderr, "\033[%d;1H\n%.02f fps, %zu bytes of text for %ld frames (%zu each as whole texts)\n", height, (double)frame / seconds_since(&start), written_bytes, frame,
-                trt_ansi_bytes(width, height));
+        fprintf(stderr, "\033[%d;1H\n%.02f fps, %zu bytes of text for %ld frames (%zu each as whole texts)\n", half ? (height + 1) / 2 : height,
+                (double)frame / seconds_since(&start), written_bytes, frame, half ? trt_ansi_half_bytes(width, height) : trt_ansi_bytes(width, height));
     fprintf(stderr, "%ld frames %dx%d, frame producer %.3f ms/frame after a first call of %.1f ms (host-in/host-out%s, 10 bounces, 10 rays per pixel)\n",
             frame, width, height, frame > 1 ? 1e3 * producer_seconds / (frame - 1) : 0.0, 1e3 * first_call_seconds,
-            delta ? " as delta text" : half ? " as half-block text" : text_only ? " as text" : bytes_only ? " as RGB8" : "");
+            delta && half ? " as half-block delta text" : delta ? " as delta text" : half ? " as half-block text" : text_only ? " as text" : bytes_only ? " as RGB8" : "");
 
     trt_emitter_destroy(emitter);
     free(screen.pixels);

@@ -81,6 +81,12 @@ int trt_render_frame_ansi_half(const Scene *scene, int width, int height, int bo
 int trt_render_frame_ansi_delta(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text,
                                 size_t capacity_bytes, size_t *bytes);
 
+/* The same in HALF-BLOCK cells (trt_render_host_ansi_delta_half below, on the default context): the keyframe is
+ * trt_render_frame_ansi_half's text, capacity_bytes >= trt_ansi_delta_half_capacity(width, height).  The default context keeps ONE shown
+ * frame: a call of this entry after one of trt_render_frame_ansi_delta, or the other way round, returns a keyframe. */
+int trt_render_frame_ansi_delta_half(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text,
+                                     size_t capacity_bytes, size_t *bytes);
+
 /* project_scene is a pure function of *scene (TRT.c:966): a caller may move a sphere before every call.  The drop-in entries
  * compare the primitives with the previous call's; a scene that has changed on `moving_after` consecutive calls counts as MOVING
  * and its candidate tables are rebuilt per call the cheap way (one family per sphere instead of 24 patches: ~4 ms instead of ~100 ms
@@ -250,7 +256,8 @@ int trt_ansi_half_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int wid
  *   - nothing else may be printed over the picture (a status line belongs on stderr or below the last row);
  *   - the refraction extension and the batch entries have no delta form; of a trt_dist_render_rgb8 gather rank 0 formats the
  *     assembled bytes with trt_ansi_delta_from_rgb8_device;
- *   - the half-block text has no delta form either (out of scope so far): the records here are of two-column cells of the full text. */
+ *   - the records here are of two-column cells of the full text; the half-block text has a delta form of its own, below, and a
+ *     context remembers which of the two its shown frame was sent as: changing over is a keyframe. */
 
 /* Room for any text the delta entries write for a screen of `width` x `rows` owned rows: max(trt_ansi_bytes, rows * (21 * width + 18)),
  * the keyframe or the longest delta; 0 when either is not positive or above the limits. */
@@ -269,7 +276,8 @@ int trt_ansi_delta_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, 
  * below) rendered last, kept in one of two buffers of the context that swap per call.  The new frame's bytes are written by the RGB8
  * form of the ordered-mean pass (trt_render_device_rgb8; the reference-order kernel goes through trt_quantize_device's kernel), then
  * compared with the shown ones by the three kernels above.  When the context has no shown frame for exactly this rowset -- the first
- * call, another trt_rowset, after trt_ansi_delta_reset or after a call that failed once it had begun to enqueue -- the call is a
+ * call, another trt_rowset, after trt_ansi_delta_reset, after a call that failed once it had begun to enqueue, or after a call of
+ * the half-block kind (trt_render_device_ansi_delta_half below), whose shown frame was sent as another text -- the call is a
  * KEYFRAME: d_text is byte for byte trt_render_device_ansi's text and *d_bytes = trt_ansi_bytes(width, owned rows).  Either way the new
  * frame becomes the shown one.  Every other render entry and trt_set_scene leave the shown frame alone: what the terminal shows did
  * not change.  Rows count from the shard's first owned row, as in trt_render_device_ansi's shard texts.
@@ -283,9 +291,53 @@ int trt_render_device_ansi_delta(trt_context *ctx, const Camera *camera, const t
  * two small transfers instead of one large one.  capacity_bytes counts the bytes at text, checked as above. */
 int trt_render_host_ansi_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
                                char *text, size_t capacity_bytes, size_t *bytes);
-/* Forget the shown frame: the next delta call returns a keyframe.  For a host that dropped a text, cleared its terminal or printed over
- * the picture. */
+/* Forget the shown frame: the next delta call, of either kind, returns a keyframe.  For a host that dropped a text, cleared its
+ * terminal or printed over the picture. */
 int trt_ansi_delta_reset(trt_context *ctx);
+
+/* ---- the delta text in half-block cells ------------------------------------------------------------------------------------------
+ * The delta text of a terminal that shows the HALF-BLOCK text: the cells are that text's, T = (rows + 1) / 2 text rows of `width`
+ * one-column cells, cell (t, c) with the upper pixel of owned row 2 t and the lower pixel of owned row 2 t + 1 (000;000;000 behind an
+ * odd frame's last row, in both frames; never read from memory).  A cell is CHANGED when either pixel differs.  For every changed
+ * cell, text rows ascending, left to right:
+ *   "\033[RRRRR;CCCCCH"        14 bytes, where a run of consecutive changed cells of one text row starts: RRRRR = t + 1, CCCCC = c + 1
+ *   the colours, against the new colours of the cell to the left, which the run has just painted:
+ *     "\033[38;2;RRR;GGG;BBB;48;2;rrr;ggg;bbbm"   36 bytes, where a run starts or BOTH differ
+ *     "\033[38;2;RRR;GGG;BBBm"                    19 bytes, where only the upper colour differs
+ *     "\033[48;2;rrr;ggg;bbbm"                    19 bytes, where only the lower colour differs
+ *     nothing                                     where neither differs
+ *   E2 96 80                    3 bytes, the glyph U+2580
+ *   "\033[0m"                   4 bytes, where the run ends
+ * so a record has 3, 7, 22, 26, 39, 43, 53 or 57 bytes; no prefix, no newline, no NUL; equal frames give 0 bytes.  A text has at most
+ * T * (39 * width + 18) bytes, reached when every cell changed and both colours differ from the left neighbour's everywhere.  Limits:
+ * width <= 99999, T <= 99999 (rows <= 199998).  csrc/trt_ansi_delta_half.h is the format in code, trt_emitter_delta_half_rgb8
+ * (trt_host.h) its sequential statement on the host; the measured bytes and times are in profiles/r15/a_delta_half.md.  The rules for
+ * the host are those of the delta text above.  There is no batch form and no refraction form. */
+
+/* Room for any text the half-block delta entries write: max(trt_ansi_half_bytes, ((rows + 1) / 2) * (39 * width + 18)), the keyframe or
+ * the longest delta; 0 when either size is not positive or above the limits. */
+size_t trt_ansi_delta_half_capacity(int width, int rows);
+
+/* trt_ansi_delta_from_rgb8_device for half-block cells: the text that takes a terminal from the half-block text of d_shown_rgb8 to that
+ * of d_next_rgb8 (rows x width x 3 bytes each, any alignment; nothing behind an odd frame's last row is read).  Three kernels in stream
+ * order (csrc/trt_ansi_delta_half.hpp; the scan of the tiles' sums is the delta text's own).  It neither reads nor changes the context's
+ * shown frame; it is what rank 0 applies to a trt_dist_render_rgb8 gather.  capacity_bytes >= trt_ansi_delta_half_capacity(width, rows),
+ * else TRT_ERR_CAPACITY; NULL or a size above the limits: TRT_ERR_ARGUMENT.  Asynchronous on the context's stream. */
+int trt_ansi_delta_half_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows,
+                                         void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+
+/* trt_render_device_ansi_delta in half-block cells, on the same shown frame.  A context keeps ONE shown frame and remembers which
+ * text it was sent as: this call is a KEYFRAME when there is no shown frame for exactly this rowset AND this kind -- the first call,
+ * another trt_rowset, after trt_ansi_delta_reset, after a call that failed once it had begun to enqueue, or after a
+ * trt_render_*_ansi_delta call of the full-text kind (which in turn is a keyframe after one of these: a terminal that shows two-column
+ * cells cannot be patched with one-column records).  The keyframe is byte for byte trt_render_device_ansi_half's text and *d_bytes =
+ * trt_ansi_half_bytes(width, owned rows).  Errors as trt_render_device_ansi_delta, with trt_ansi_delta_half_capacity and this kind's
+ * limits. */
+int trt_render_device_ansi_delta_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                      void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+/* The same into HOST memory, synchronous: the 8-byte length is read back, then exactly *bytes bytes cross PCIe. */
+int trt_render_host_ansi_delta_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                    char *text, size_t capacity_bytes, size_t *bytes);
 
 /* Same as trt_render_device but into HOST memory (synchronous; pinned staging inside). */
 int trt_render_host(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,

@@ -171,6 +171,10 @@ int trt_build_counts(trt_context *ctx, unsigned long long *table_builds, unsigne
  * kernel (the records).  Same arguments, same text, same errors (tools/ansi_delta_bench.py). */
 int trt_ansi_delta_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
                                 size_t capacity_bytes, unsigned long long *d_bytes, float *ms);
+/* The same of trt_ansi_delta_half_from_rgb8_device: its measure kernel, the shared offsets kernel, its write kernel
+ * (tools/ansi_delta_half_bench.py). */
+int trt_ansi_delta_half_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                     size_t capacity_bytes, unsigned long long *d_bytes, float *ms);
 
 #ifdef __cplusplus
 }

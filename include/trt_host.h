@@ -83,6 +83,18 @@ int trt_emitter_delta_rgb8(const unsigned char *shown, const unsigned char *next
  * must hold.  The sequential statement the device kernels (trt_render_device_ansi_half, trt_hip.h) are tested against, and the emitter
  * of hosts that fetch RGB8 bytes.  TRT_HOST_ERR_ARGUMENT: NULL, a size that is not positive, a capacity below the length. */
 int trt_emitter_half_rgb8(const unsigned char *rgb, int width, int rows, char *text, size_t capacity, size_t *bytes);
+/* The DELTA text between two such frames in HALF-BLOCK cells: what a terminal that shows `shown` as the half-block text must be written
+ * to show `next`.  The format is the project's own (csrc/trt_ansi_delta_half.h).  A cell of text row t < (rows + 1) / 2
+ * has the pixels of rows 2 t and 2 t + 1 (black behind an odd frame's last row, in both frames, and not read) and is changed when either
+ * differs.  Per changed cell, text rows ascending, left to right: "\033[RRRRR;CCCCCH" (text row + 1, column + 1: a cell is one column
+ * wide) where a run of changed cells of one text row starts; the colours that differ from the cell's to the left (both where a run
+ * starts): "\033[38;2;RRR;GGG;BBB;48;2;rrr;ggg;bbbm", "\033[38;2;RRR;GGG;BBBm", "\033[48;2;rrr;ggg;bbbm" or nothing; the glyph E2 96 80;
+ * and "\033[0m" where the run ends.  No prefix, no newline, no NUL: equal frames give *bytes = 0.  At most
+ * ((rows + 1) / 2) * (39 * width + 18) bytes, which `capacity` must hold; width <= 99999, rows <= 199998.  The sequential statement the
+ * device kernels (trt_render_device_ansi_delta_half, trt_hip.h) are tested against.  TRT_HOST_ERR_ARGUMENT: NULL, a size that is not
+ * positive or above the limits, a capacity below the bound. */
+int trt_emitter_delta_half_rgb8(const unsigned char *shown, const unsigned char *next, int width, int rows, char *text, size_t capacity,
+                                size_t *bytes);
 /* TRT.c:1171: one fwrite of the whole buffer (trailing NULs included, as the reference does) */
 int trt_emitter_write(const trt_emitter *e, FILE *stream);
 /* TRT.c:1084-1099: the unbuffered printf form */

@@ -223,6 +223,84 @@ int trt_emitter_half_rgb8(const unsigned char *rgb, int width, int rows, char *t
     return TRT_HOST_OK;
 }
 
+/* The half-block delta text (csrc/trt_ansi_delta_half.h holds the format): the delta's walk over the half-block text's cells, one
+ * column each, the upper pixel's colour as the foreground and the lower one's as the background.  Plain loops, on purpose without
+ * that header -- this is what the header's arithmetic and the device kernels are held against. */
+static const char k_upper[] = "\033[38;2;000;000;000";
+static const char k_lower[] = "48;2;000;000;000";
+static const char k_glyph[] = "\xe2\x96\x80";
+enum
+{
+    UPPER_LEN = sizeof(k_upper) - 1, /* 18 */
+    LOWER_LEN = sizeof(k_lower) - 1, /* 16 */
+    GLYPH_LEN = sizeof(k_glyph) - 1, /* 3 */
+    DELTA_HALF_MAX_TEXT_ROWS = 99999,
+    DELTA_HALF_MAX_WIDTH = 99999
+};
+
+int trt_emitter_delta_half_rgb8(const unsigned char *shown, const unsigned char *next, int width, int rows, char *text, size_t capacity, size_t *bytes)
+{
+    static const unsigned char black[3] = {0, 0, 0};
+    if (!shown || !next || !text || !bytes || width <= 0 || rows <= 0 || width > DELTA_HALF_MAX_WIDTH || rows > 2 * DELTA_HALF_MAX_TEXT_ROWS)
+        return TRT_HOST_ERR_ARGUMENT;
+    const size_t text_rows = ((size_t)rows + 1) / 2;
+    if (capacity < text_rows * ((size_t)39 * width + 18))
+        return TRT_HOST_ERR_ARGUMENT;
+    char *p = text;
+    for (size_t t = 0; t < text_rows; t++)
+    {
+        const int has_lower = 2 * t + 1 < (size_t)rows; /* behind an odd frame's last row: black in both frames, and not read */
+        const unsigned char *was_up = shown + 2 * t * width * 3, *now_up = next + 2 * t * width * 3;
+        const unsigned char *was_low = has_lower ? was_up + (size_t)width * 3 : NULL, *now_low = has_lower ? now_up + (size_t)width * 3 : NULL;
+        int in_run = 0;
+        for (int col = 0; col < width; col++)
+        {
+            const unsigned char *up = now_up + 3 * col, *low = has_lower ? now_low + 3 * col : black;
+            if (memcmp(was_up + 3 * col, up, 3) == 0 && (!has_lower || memcmp(was_low + 3 * col, low, 3) == 0))
+                continue;
+            if (!in_run)
+            { /* the cursor to the cell: text rows and columns count from 1, a cell is one column wide */
+                memcpy(p, k_goto, GOTO_LEN);
+                five_digits(p + GOTO_ROW_AT, (int)t + 1);
+                five_digits(p + GOTO_COLUMN_AT, col + 1);
+                p += GOTO_LEN;
+            }
+            /* the colours, unless the cell painted just before has them */
+            const int set_upper = !in_run || memcmp(up - 3, up, 3) != 0, set_lower = !in_run || (has_lower && memcmp(low - 3, low, 3) != 0);
+            if (set_upper)
+            {
+                memcpy(p, k_upper, UPPER_LEN);
+                for (int ch = 0; ch < 3; ch++)
+                    three_digits(p + HALF_UPPER_AT + 4 * ch, up[ch]);
+                p += UPPER_LEN;
+            }
+            if (set_lower)
+            {
+                *p++ = set_upper ? ';' : '\033';
+                if (!set_upper)
+                    *p++ = '[';
+                memcpy(p, k_lower, LOWER_LEN);
+                for (int ch = 0; ch < 3; ch++)
+                    three_digits(p + 5 + 4 * ch, low[ch]);
+                p += LOWER_LEN;
+            }
+            if (set_upper || set_lower)
+                *p++ = 'm';
+            memcpy(p, k_glyph, GLYPH_LEN);
+            p += GLYPH_LEN;
+            in_run = col + 1 < width &&
+                     (memcmp(was_up + 3 * (col + 1), up + 3, 3) != 0 || (has_lower && memcmp(was_low + 3 * (col + 1), now_low + 3 * (col + 1), 3) != 0));
+            if (!in_run)
+            {
+                memcpy(p, k_reset, RESET_LEN);
+                p += RESET_LEN;
+            }
+        }
+    }
+    *bytes = (size_t)(p - text);
+    return TRT_HOST_OK;
+}
+
 int trt_emitter_write(const trt_emitter *e, FILE *stream)
 {
     if (!e || !stream)

@@ -222,6 +222,20 @@ extern "C" int trt_render_frame_ansi_delta(const Scene *scene, int width, int he
     });
 }
 
+extern "C" int trt_render_frame_ansi_delta_half(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text, size_t capacity_bytes,
+                                                size_t *bytes)
+{
+    if (!scene || !text || !bytes)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (width <= 0 || height <= 0 || trt_ansi_delta_half_capacity(width, height) == 0)
+        return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, height);
+    if (capacity_bytes < trt_ansi_delta_half_capacity(width, height))
+        return fail(TRT_ERR_CAPACITY, "the text of %d x %d needs room for %zu B, %zu given", width, height, trt_ansi_delta_half_capacity(width, height), capacity_bytes);
+    return render_default_frame(scene, width, height, [&](trt_context *ctx, const trt_rowset *whole) {
+        return trt_render_host_ansi_delta_half(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes);
+    });
+}
+
 extern "C" void project_scene(Scene *scene, Screen *screen)
 {
     const int rc = trt_render_frame(scene, screen, TRT_REF_BOUNCE_LIMIT, TRT_REF_RAYS_PER_PIXEL);

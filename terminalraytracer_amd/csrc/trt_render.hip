@@ -10,6 +10,7 @@
 #include "trt_simple.hpp"
 #include "trt_ansi.hpp"
 #include "trt_ansi_delta.hpp"
+#include "trt_ansi_delta_half.hpp"
 #include "trt_ansi_half.hpp"
 
 using namespace trt_impl;
@@ -1205,7 +1206,7 @@ extern "C" int trt_kernel_info(trt_context *ctx, int *vgprs, int *sgprs, int *st
     return TRT_OK;
 }
 
-// ---- the delta text (trt_ansi_delta.h: the format; trt_ansi_delta.hpp: the three kernels) ----
+// ---- the delta texts (trt_ansi_delta.h, trt_ansi_delta.hpp: the full text's cells; trt_ansi_delta_half.h, trt_ansi_delta_half.hpp: half-block cells) ----
 
 extern "C" size_t trt_ansi_delta_capacity(int width, int rows)
 {
@@ -1214,67 +1215,103 @@ extern "C" size_t trt_ansi_delta_capacity(int width, int rows)
     return (size_t)std::max(trt_ansi_text_bytes(width, rows), trt_delta_bound(width, rows));
 }
 
-// measure, offsets, write on `stream`; marks: four events, recorded around and between the launches (trt_ansi_delta_kernel_times)
-static int launch_ansi_delta(trt_context *ctx, hipStream_t stream, const unsigned char *d_shown, const unsigned char *d_next, int width, int rows, void *d_text,
+extern "C" size_t trt_ansi_delta_half_capacity(int width, int rows)
+{
+    if (!trt_delta_half_size_ok(width, rows))
+        return 0;
+    return (size_t)std::max(trt_ansi_half_text_bytes(width, rows), trt_delta_half_bound(width, rows));
+}
+
+// room for any text of the kind: half-block cells or the full text's
+static size_t delta_capacity(bool half, int width, int rows) { return half ? trt_ansi_delta_half_capacity(width, rows) : trt_ansi_delta_capacity(width, rows); }
+
+// measure, offsets, write on `stream`, of the full text's cells or of half-block cells (the tiles are then of the text rows' cells; the
+// offsets kernel is the same); marks: four events, recorded around and between the launches (trt_ansi_delta_kernel_times)
+static int launch_ansi_delta(trt_context *ctx, hipStream_t stream, bool half, const unsigned char *d_shown, const unsigned char *d_next, int width, int rows, void *d_text,
                              size_t capacity_bytes, unsigned long long *d_bytes, const Event *marks = nullptr)
 {
-    const unsigned long long cells = (unsigned long long)width * (unsigned long long)rows, tiles = trt_delta_tiles(cells);
+    const unsigned long long cells = (unsigned long long)width * (unsigned long long)(half ? trt_ansi_half_text_rows(rows) : rows), tiles = trt_delta_tiles(cells);
     if (ctx->d_delta_tile_bytes.capacity < tiles || ctx->d_delta_tile_at.capacity < tiles)
         HIP_TRY(hipStreamSynchronize(stream)); // a text in flight may still use the old sums
     HIP_TRY(ctx->d_delta_tile_bytes.reserve((size_t)tiles));
     HIP_TRY(ctx->d_delta_tile_at.reserve((size_t)tiles));
     if (marks)
         HIP_TRY(hipEventRecord(marks[0], stream));
-    hipLaunchKernelGGL(trt::ansi_delta_measure_kernel, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, cells, ctx->d_delta_tile_bytes.ptr);
+    if (half)
+        hipLaunchKernelGGL(trt::ansi_delta_half_measure_kernel, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, rows, ctx->d_delta_tile_bytes.ptr);
+    else
+        hipLaunchKernelGGL(trt::ansi_delta_measure_kernel, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, cells, ctx->d_delta_tile_bytes.ptr);
     if (marks)
         HIP_TRY(hipEventRecord(marks[1], stream));
     hipLaunchKernelGGL(trt::ansi_delta_offsets_kernel, dim3(1), dim3(TRT_DELTA_SCAN_BLOCK), 0, stream, (const unsigned *)ctx->d_delta_tile_bytes.ptr, tiles,
                        ctx->d_delta_tile_at.ptr, d_bytes);
     if (marks)
         HIP_TRY(hipEventRecord(marks[2], stream));
-    hipLaunchKernelGGL(trt::ansi_delta_write_kernel, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, cells,
-                       (const unsigned long long *)ctx->d_delta_tile_at.ptr, (unsigned char *)d_text, (unsigned long long)capacity_bytes);
+    if (half)
+        hipLaunchKernelGGL(trt::ansi_delta_half_write_kernel, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, rows,
+                           (const unsigned long long *)ctx->d_delta_tile_at.ptr, (unsigned char *)d_text, (unsigned long long)capacity_bytes);
+    else
+        hipLaunchKernelGGL(trt::ansi_delta_write_kernel, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, cells,
+                           (const unsigned long long *)ctx->d_delta_tile_at.ptr, (unsigned char *)d_text, (unsigned long long)capacity_bytes);
     if (marks)
         HIP_TRY(hipEventRecord(marks[3], stream));
     HIP_TRY(hipGetLastError());
     return TRT_OK;
 }
 
-static int check_delta_from_rgb8(const trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, const void *d_text, size_t capacity_bytes,
-                                 const unsigned long long *d_bytes)
+static int check_delta_from_rgb8(const trt_context *ctx, bool half, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, const void *d_text,
+                                 size_t capacity_bytes, const unsigned long long *d_bytes)
 {
     if (!ctx || !d_shown_rgb8 || !d_next_rgb8 || !d_text || !d_bytes)
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (!trt_delta_size_ok(width, rows))
+    if (!half && !trt_delta_size_ok(width, rows))
         return fail(TRT_ERR_ARGUMENT, "screen %d x %d: a delta text has 1 to %d cells per row and 1 to %d rows", width, rows, TRT_DELTA_MAX_WIDTH, TRT_DELTA_MAX_ROWS);
-    if (capacity_bytes < trt_ansi_delta_capacity(width, rows))
-        return fail(TRT_ERR_CAPACITY, "the delta text of %d x %d needs room for %zu B, %zu given", width, rows, trt_ansi_delta_capacity(width, rows), capacity_bytes);
+    if (half && !trt_delta_half_size_ok(width, rows))
+        return fail(TRT_ERR_ARGUMENT, "screen %d x %d: a half-block delta text has 1 to %d cells per row and 1 to %d text rows", width, rows, TRT_DELTA_HALF_MAX_WIDTH,
+                    TRT_DELTA_HALF_MAX_TEXT_ROWS);
+    if (capacity_bytes < delta_capacity(half, width, rows))
+        return fail(TRT_ERR_CAPACITY, "the delta text of %d x %d needs room for %zu B, %zu given", width, rows, delta_capacity(half, width, rows), capacity_bytes);
     return TRT_OK;
+}
+
+// trt_ansi_delta_from_rgb8_device and trt_ansi_delta_half_from_rgb8_device
+static int delta_from_rgb8(trt_context *ctx, bool half, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text, size_t capacity_bytes,
+                           unsigned long long *d_bytes)
+{
+    const int rc = check_delta_from_rgb8(ctx, half, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
+    if (rc)
+        return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return launch_ansi_delta(ctx, ctx->stream, half, (const unsigned char *)d_shown_rgb8, (const unsigned char *)d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
 }
 
 extern "C" int trt_ansi_delta_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
                                                size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    const int rc = check_delta_from_rgb8(ctx, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
-    if (rc)
-        return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    return launch_ansi_delta(ctx, ctx->stream, (const unsigned char *)d_shown_rgb8, (const unsigned char *)d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
+    return delta_from_rgb8(ctx, false, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
 }
 
-extern "C" int trt_ansi_delta_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
-                                           size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
+extern "C" int trt_ansi_delta_half_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                                    size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return delta_from_rgb8(ctx, true, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
+}
+
+// trt_ansi_delta_kernel_times and trt_ansi_delta_half_kernel_times
+static int delta_kernel_times(trt_context *ctx, bool half, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text, size_t capacity_bytes,
+                              unsigned long long *d_bytes, float *ms)
 {
     if (!ms)
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    int rc = check_delta_from_rgb8(ctx, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
+    int rc = check_delta_from_rgb8(ctx, half, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     Event marks[4];
     for (Event &e : marks)
         HIP_TRY(e.create());
-    rc = launch_ansi_delta(ctx, ctx->stream, (const unsigned char *)d_shown_rgb8, (const unsigned char *)d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes, marks);
+    rc = launch_ansi_delta(ctx, ctx->stream, half, (const unsigned char *)d_shown_rgb8, (const unsigned char *)d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes,
+                           marks);
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (rc)
         return rc;
@@ -1282,6 +1319,20 @@ extern "C" int trt_ansi_delta_kernel_times(trt_context *ctx, const void *d_shown
         HIP_TRY(hipEventElapsedTime(&ms[k], marks[k], marks[k + 1]));
     return TRT_OK;
 }
+
+extern "C" int trt_ansi_delta_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                           size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
+{
+    return delta_kernel_times(ctx, false, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes, ms);
+}
+
+extern "C" int trt_ansi_delta_half_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                                size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
+{
+    return delta_kernel_times(ctx, true, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes, ms);
+}
+
+// ---- the render entries of both delta texts: one shown frame, which remembers the kind of text it was sent as ----
 
 extern "C" int trt_ansi_delta_reset(trt_context *ctx)
 {
@@ -1291,20 +1342,23 @@ extern "C" int trt_ansi_delta_reset(trt_context *ctx)
     return TRT_OK;
 }
 
-// what both render entries refuse before anything is enqueued; `text`: the caller's buffer, on the device or on the host
+// what the render entries refuse before anything is enqueued; `text`: the caller's buffer, on the device or on the host
 static int check_render_delta(const trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, const void *text,
-                              size_t capacity_bytes, const void *bytes)
+                              size_t capacity_bytes, const void *bytes, bool half)
 {
     if (!bytes)
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (rowset_valid(rows) && !trt_delta_size_ok(rows->width, trt_rowset_rows(rows)))
+    if (!half && rowset_valid(rows) && !trt_delta_size_ok(rows->width, trt_rowset_rows(rows)))
         return fail(TRT_ERR_ARGUMENT, "%d x %d owned rows: a delta text has 1 to %d cells per row and 1 to %d rows", rows->width, trt_rowset_rows(rows), TRT_DELTA_MAX_WIDTH,
                     TRT_DELTA_MAX_ROWS);
+    if (half && rowset_valid(rows) && !trt_delta_half_size_ok(rows->width, trt_rowset_rows(rows)))
+        return fail(TRT_ERR_ARGUMENT, "%d x %d owned rows: a half-block delta text has 1 to %d cells per row and 1 to %d text rows", rows->width, trt_rowset_rows(rows),
+                    TRT_DELTA_HALF_MAX_WIDTH, TRT_DELTA_HALF_MAX_TEXT_ROWS);
     // the rest as the RGB8 entry checks it, whose frame these sizes let fit
     const int rc = check_render_arguments(ctx, camera, 1, rows, bounce_limit, rays_per_pixel, text, (size_t)-1, kBytes);
     if (rc)
         return rc;
-    const size_t need = trt_ansi_delta_capacity(rows->width, trt_rowset_rows(rows));
+    const size_t need = delta_capacity(half, rows->width, trt_rowset_rows(rows));
     if (capacity_bytes < need)
         return fail(TRT_ERR_CAPACITY, "the text of %d x %d owned rows needs room for %zu B, %zu given", rows->width, trt_rowset_rows(rows), need, capacity_bytes);
     return TRT_OK;
@@ -1315,16 +1369,17 @@ static bool same_rowset(const trt_rowset &a, const trt_rowset &b)
     return a.width == b.width && a.height == b.height && a.tile_rows == b.tile_rows && a.tile_first == b.tile_first && a.tile_step == b.tile_step;
 }
 
-extern "C" int trt_render_device_ansi_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
-                                            size_t capacity_bytes, unsigned long long *d_bytes)
+// trt_render_device_ansi_delta and trt_render_device_ansi_delta_half
+static int render_device_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text, size_t capacity_bytes,
+                               unsigned long long *d_bytes, bool half)
 {
-    int rc = check_render_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes);
+    int rc = check_render_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, half);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const int width = rows->width, owned = trt_rowset_rows(rows);
     const size_t frame = (size_t)owned * width * 3;
-    const bool keyframe = !(ctx->shown_valid && same_rowset(ctx->shown_rows, *rows));
+    const bool keyframe = !(ctx->shown_valid && ctx->shown_half == half && same_rowset(ctx->shown_rows, *rows));
     const int into = ctx->shown_at ^ 1;
     if (ctx->d_shown[0].capacity < frame || ctx->d_shown[1].capacity < frame)
     { // another size: a keyframe, which reads neither buffer's contents
@@ -1338,38 +1393,56 @@ extern "C" int trt_render_device_ansi_delta(trt_context *ctx, const Camera *came
     if (rc)
         return rc;
     if (keyframe)
-    { // the whole text, as trt_render_device_ansi writes it
-        launch_ansi_from_rgb8(ctx->stream, ctx->d_shown[into].ptr, width, owned, d_text);
-        hipLaunchKernelGGL(trt::ansi_delta_keyframe_bytes_kernel, dim3(1), dim3(1), 0, ctx->stream, d_bytes, trt_ansi_text_bytes(width, owned));
+    { // the whole text, as trt_render_device_ansi or trt_render_device_ansi_half writes it
+        if (half)
+            launch_ansi_half_from_rgb8(ctx->stream, ctx->d_shown[into].ptr, width, owned, d_text);
+        else
+            launch_ansi_from_rgb8(ctx->stream, ctx->d_shown[into].ptr, width, owned, d_text);
+        hipLaunchKernelGGL(trt::ansi_delta_keyframe_bytes_kernel, dim3(1), dim3(1), 0, ctx->stream, d_bytes,
+                           half ? trt_ansi_half_text_bytes(width, owned) : trt_ansi_text_bytes(width, owned));
         HIP_TRY(hipGetLastError());
     }
     else
     {
-        rc = launch_ansi_delta(ctx, ctx->stream, ctx->d_shown[ctx->shown_at].ptr, ctx->d_shown[into].ptr, width, owned, d_text, capacity_bytes, d_bytes);
+        rc = launch_ansi_delta(ctx, ctx->stream, half, ctx->d_shown[ctx->shown_at].ptr, ctx->d_shown[into].ptr, width, owned, d_text, capacity_bytes, d_bytes);
         if (rc)
             return rc;
     }
     ctx->shown_at = into;
     ctx->shown_rows = *rows;
+    ctx->shown_half = half;
     ctx->shown_valid = true;
     return TRT_OK;
 }
 
-extern "C" int trt_render_host_ansi_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
-                                          size_t capacity_bytes, size_t *bytes)
+extern "C" int trt_render_device_ansi_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                                            size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    int rc = check_render_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes);
+    return render_device_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, false);
+}
+
+extern "C" int trt_render_device_ansi_delta_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                                                 size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return render_device_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, true);
+}
+
+// trt_render_host_ansi_delta and trt_render_host_ansi_delta_half
+static int render_host_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text, size_t capacity_bytes,
+                             size_t *bytes, bool half)
+{
+    int rc = check_render_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, half);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t room = trt_ansi_delta_capacity(rows->width, trt_rowset_rows(rows));
+    const size_t room = delta_capacity(half, rows->width, trt_rowset_rows(rows));
     if (ctx->d_text.capacity < room)
         HIP_TRY(hipStreamSynchronize(ctx->stream)); // a text in flight may still be written to the old buffer
     HIP_TRY(ctx->d_text.reserve(room));
     HIP_TRY(ctx->d_delta_bytes.reserve(1));
     HIP_TRY(ctx->h_staging.reserve(room));
     const double t_begin = host_now_ms();
-    rc = trt_render_device_ansi_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, room, ctx->d_delta_bytes.ptr);
+    rc = render_device_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, room, ctx->d_delta_bytes.ptr, half);
     if (rc)
         return rc;
     // two small transfers instead of one large one: the length, then exactly that many bytes
@@ -1395,6 +1468,18 @@ extern "C" int trt_render_host_ansi_delta(trt_context *ctx, const Camera *camera
     }
     *bytes = (size_t)length;
     if (print_host_times())
-        fprintf(stderr, "trt_render_host_ansi_delta: %.3f ms for %llu bytes of text\n", host_now_ms() - t_begin, length);
+        fprintf(stderr, "trt_render_host_ansi_delta%s: %.3f ms for %llu bytes of text\n", half ? "_half" : "", host_now_ms() - t_begin, length);
     return TRT_OK;
+}
+
+extern "C" int trt_render_host_ansi_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
+                                          size_t capacity_bytes, size_t *bytes)
+{
+    return render_host_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, false);
+}
+
+extern "C" int trt_render_host_ansi_delta_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
+                                               size_t capacity_bytes, size_t *bytes)
+{
+    return render_host_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, true);
 }

@@ -74,6 +74,12 @@ SYMBOLS = {
     "trt_render_host_ansi_half": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP]),
     "trt_render_device_batch_ansi_half": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ]),
     "trt_render_host_batch_ansi_half": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP]),
+    "trt_render_frame_ansi_delta_half": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
+    "trt_ansi_delta_half_capacity": (_SZ, [_I, _I]),
+    "trt_ansi_delta_half_from_rgb8_device": (_I, [_VP, _VP, _VP, _I, _I, _VP, _SZ, _VP]),
+    "trt_ansi_delta_half_kernel_times": (_I, [_VP, _VP, _VP, _I, _I, _VP, _SZ, _VP, C.POINTER(C.c_float)]),
+    "trt_render_device_ansi_delta_half": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ, _VP]),
+    "trt_render_host_ansi_delta_half": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
     "trt_ansi_delta_capacity": (_SZ, [_I, _I]),
     "trt_ansi_delta_from_rgb8_device": (_I, [_VP, _VP, _VP, _I, _I, _VP, _SZ, _VP]),
     "trt_ansi_delta_kernel_times": (_I, [_VP, _VP, _VP, _I, _I, _VP, _SZ, _VP, C.POINTER(C.c_float)]),
@@ -493,8 +499,37 @@ class Context:
         return out[:n.value]
 
     def ansi_delta_reset(self):
-        """forget the shown frame: the next delta text is a keyframe (trt_ansi_delta_reset)"""
+        """forget the shown frame: the next delta text, of either kind, is a keyframe (trt_ansi_delta_reset)"""
         _check(lib().trt_ansi_delta_reset(self._h))
+
+    def ansi_delta_half_from_rgb8(self, shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr):
+        """the delta text in half-block cells between two width x rows frames of RGB8 bytes in device memory, at text_ptr, its length (a
+        uint64) at the device address bytes_ptr (trt_ansi_delta_half_from_rgb8_device)"""
+        _check(lib().trt_ansi_delta_half_from_rgb8_device(self._h, _VP(shown_ptr), _VP(next_ptr), width, rows, _VP(text_ptr), capacity_bytes, _VP(bytes_ptr)))
+
+    def ansi_delta_half_kernel_times(self, shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr):
+        """the same, synchronous: ms of the (measure, offsets, write) kernels by HIP events (trt_ansi_delta_half_kernel_times)"""
+        ms = (C.c_float * 3)()
+        _check(lib().trt_ansi_delta_half_kernel_times(self._h, _VP(shown_ptr), _VP(next_ptr), width, rows, _VP(text_ptr), capacity_bytes, _VP(bytes_ptr), ms))
+        return tuple(ms)
+
+    def render_device_ansi_delta_half(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr):
+        """the frame as the half-block delta text against the context's shown frame (a keyframe, the half-block text, when there is none
+        for this rowset and this kind) in device memory, its length (a uint64) at the device address bytes_ptr
+        (trt_render_device_ansi_delta_half)"""
+        cam = camera_struct(camera_array)
+        _check(lib().trt_render_device_ansi_delta_half(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, _VP(device_ptr), capacity_bytes,
+                                                       _VP(bytes_ptr)))
+
+    def render_host_ansi_delta_half(self, camera_array, rows, bounce_limit, rays_per_pixel, out=None):
+        """the same into host memory: the uint8 text, exactly as long as the host is to write it (trt_render_host_ansi_delta_half); `out`:
+        a uint8 buffer of ansi_delta_half_capacity bytes to reuse"""
+        if out is None:
+            out = np.empty(ansi_delta_half_capacity(rows.width, lib().trt_rowset_rows(C.byref(rows))), dtype=np.uint8)
+        n = _SZ(0)
+        cam = camera_struct(camera_array)
+        _check(lib().trt_render_host_ansi_delta_half(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data, out.size, C.byref(n)))
+        return out[:n.value]
 
     @staticmethod
     def _camera_batch(cameras):
@@ -711,6 +746,22 @@ def render_frame_ansi_delta(scene_data, width, height, bounce_limit=10, rays_per
     out = np.empty(ansi_delta_capacity(width, height), dtype=np.uint8)
     n = _SZ(0)
     _check(lib().trt_render_frame_ansi_delta(C.byref(scene), width, height, bounce_limit, rays_per_pixel, out.ctypes.data, out.size, C.byref(n)))
+    return out[:n.value]
+
+
+def ansi_delta_half_capacity(width, rows):
+    """room for any text the half-block delta entries write: max(ansi_half_bytes, ((rows + 1) // 2) * (39 * width + 18)); 0 when a size
+    is not positive or above the format's limits (trt_ansi_delta_half_capacity)"""
+    return int(lib().trt_ansi_delta_half_capacity(width, rows))
+
+
+def render_frame_ansi_delta_half(scene_data, width, height, bounce_limit=10, rays_per_pixel=10):
+    """Host-in frame as the half-block delta text against the frame this entry returned before (a keyframe the first time): the uint8
+    text, as long as the host is to write it (trt_render_frame_ansi_delta_half)."""
+    scene = scene_data.as_scene()
+    out = np.empty(ansi_delta_half_capacity(width, height), dtype=np.uint8)
+    n = _SZ(0)
+    _check(lib().trt_render_frame_ansi_delta_half(C.byref(scene), width, height, bounce_limit, rays_per_pixel, out.ctypes.data, out.size, C.byref(n)))
     return out[:n.value]
 
 

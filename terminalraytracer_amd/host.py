@@ -29,6 +29,7 @@ HOST_SYMBOLS = {
     "trt_emitter_patch_rgb8": (C.c_int, [_VP, _VP]),
     "trt_emitter_delta_rgb8": (_I, [_VP, _VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_half_rgb8": (_I, [_VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "trt_emitter_delta_half_rgb8": (_I, [_VP, _VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_write": (_I, [_VP, _VP]),
     "trt_draw_screen": (_I, [C.POINTER(L.Screen), _VP]),
     "trt_fnv1a64": (C.c_ulonglong, [_VP, C.c_size_t]),
@@ -131,6 +132,21 @@ def emitter_half_rgb8(rgb):
     if rc != 0 or n.value != out.size:
         raise ValueError(f"trt_emitter_half_rgb8({width}, {rows}) failed with {rc}, {n.value} bytes")
     return out
+
+
+def emitter_delta_half_rgb8(shown, nxt):
+    """the delta text in half-block cells between two frames of bytes [rows, width, 3], formatted on the host: uint8
+    (trt_emitter_delta_half_rgb8)"""
+    a, b = np.ascontiguousarray(shown, dtype=np.uint8), np.ascontiguousarray(nxt, dtype=np.uint8)
+    rows, width, _ = b.shape
+    if a.shape != b.shape:
+        raise ValueError(f"frames of {a.shape} and {b.shape}")
+    out = np.empty(max(((rows + 1) // 2) * (39 * width + 18), 1), dtype=np.uint8)
+    n = C.c_size_t(0)
+    rc = lib().trt_emitter_delta_half_rgb8(a.ctypes.data, b.ctypes.data, width, rows, out.ctypes.data, out.size, C.byref(n))
+    if rc != 0:
+        raise ValueError(f"trt_emitter_delta_half_rgb8({width}, {rows}) failed with {rc}")
+    return out[:n.value].copy()
 
 
 def fnv1a64(buf):

@@ -1,0 +1,386 @@
+"""The delta text in half-block cells written on the device (trt_ansi_delta_half_from_rgb8_device, trt_render_device_ansi_delta_half,
+trt_render_host_ansi_delta_half, trt_render_frame_ansi_delta_half; csrc/trt_ansi_delta_half.h, trt_ansi_delta_half.hpp): three kernels place
+every changed cell's record by a prefix sum over the text rows' cells.  The expected bytes never come from the device route: they are the
+sequential host statement host.emitter_delta_half_rgb8 of pattern frames or of consecutive T.oracle_rgb8 frames, keyframes
+host.emitter_half_rgb8's text, and a model of a terminal (ansi_delta_half_support.Terminal) must show every oracle frame after its text.
+Every device buffer stands between guard bytes of 0xA5, which also fill the text's room behind its length: none of them may change."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import ansi_delta_half_support as H
+import ansi_delta_support as D
+import support as T
+from terminalraytracer_amd import hip, host
+
+pytestmark = pytest.mark.gpu
+ARGUMENT, NO_SCENE, CAPACITY = -2, -3, -4
+GUARD = 64
+SENTINEL = 0x5A5A5A5A5A5A5A5A
+W, H_, B, SPP = 160, 48, 4, 10
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = hip.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(autouse=True)
+def _defaults(request):
+    yield
+    if "ctx" in request.fixturenames:
+        c = request.getfixturevalue("ctx")
+        c.set_kernel(hip.Context.PRODUCTION)
+        c.ansi_delta_reset()
+
+
+class Room:
+    """`capacity` bytes of device memory `offset` bytes behind an 8-aligned address, filled with 0xA5 and with GUARD such bytes either side, and a
+    uint64 on the device for the text's length"""
+
+    def __init__(self, capacity, offset=0):
+        import torch
+        self.capacity, self.start = capacity, GUARD + offset
+        self.buf = torch.full((GUARD + 8 + capacity + GUARD,), 0xA5, dtype=torch.uint8, device="cuda:0")
+        self.length = torch.full((1,), SENTINEL, dtype=torch.int64, device="cuda:0")
+        assert self.buf.data_ptr() % 8 == 0 and self.length.data_ptr() % 8 == 0
+        torch.cuda.synchronize()  # the fills are on torch's stream, the kernels on the context's
+
+    @property
+    def ptr(self):
+        return self.buf.data_ptr() + self.start
+
+    @property
+    def length_ptr(self):
+        return self.length.data_ptr()
+
+    def untouched(self, ctx):
+        ctx.synchronize()
+        return int(self.length.cpu()[0]) == SENTINEL and bool((self.buf == 0xA5).all().cpu())
+
+    def text(self, ctx, what=""):
+        """the text, once every byte in front of it, behind its length and behind its room has been seen unchanged"""
+        ctx.synchronize()
+        n = int(self.length.cpu()[0])
+        assert 0 <= n <= self.capacity, f"{what}: a length of {n} in a room of {self.capacity}"
+        got = self.buf.cpu().numpy()
+        outside = np.concatenate([got[:self.start], got[self.start + n:]])
+        assert (outside == 0xA5).all(), f"{what}: {int((outside != 0xA5).sum())} bytes outside the text's {n} were written"
+        return got[self.start:self.start + n].copy()
+
+
+def same_text(got, want, what):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.dtype == np.uint8 and got.size == want.size, f"{what}: {got.size} bytes for {want.size}"
+    wrong = got != want
+    if wrong.any():
+        at = int(np.argmax(wrong))
+        raise AssertionError(f"{what}: {int(wrong.sum())} of {wrong.size} bytes differ from the host's, the first at {at}: "
+                             f"{bytes(got[max(at - 8, 0):at + 8])!r} for {bytes(want[max(at - 8, 0):at + 8])!r}")
+
+
+def at_odd_address(frame, behind=None):
+    """the frame's bytes on the device, one byte behind an aligned address, followed directly by the bytes `behind` where given: (the
+    tensor that owns them, the frame's address)"""
+    import torch
+    tail = 0 if behind is None else behind.size
+    t = torch.zeros(frame.size + 1 + tail, dtype=torch.uint8, device="cuda:0")
+    t[1:1 + frame.size] = torch.from_numpy(np.ascontiguousarray(frame).reshape(-1)).to("cuda:0")
+    if tail:
+        t[1 + frame.size:] = torch.from_numpy(behind).to("cuda:0")
+    torch.cuda.synchronize()
+    return t, t.data_ptr() + 1
+
+
+def device_delta(ctx, shown, nxt, offset=0, what="", trap=False):
+    """trap: a further pixel row behind each frame, 0x00 behind `shown` and 0xFF behind `next` -- changed cells to a kernel that loaded it"""
+    rows, w, _ = shown.shape
+    a, pa = at_odd_address(shown, np.full(w * 3, 0x00, dtype=np.uint8) if trap else None)
+    b, pb = at_odd_address(nxt, np.full(w * 3, 0xFF, dtype=np.uint8) if trap else None)
+    room = Room(hip.ansi_delta_half_capacity(w, rows), offset)
+    ctx.ansi_delta_half_from_rgb8(pa, pb, w, rows, room.ptr, room.capacity, room.length_ptr)
+    return room.text(ctx, what)
+
+
+# ---- 1. the formatting alone ----
+
+SIZES = [(1, 1), (1, 2), (2, 1), (1, 3), (63, 2), (64, 3), (65, 5), (160, 47)]  # 160 x 47: 3840 cells, three tiles and a partial one, an odd last row
+
+
+@pytest.mark.parametrize("family", H.FAMILIES)
+def test_the_formatting_alone_on_every_pattern_family(ctx, family):
+    """one cell, one text row, one column, odd and even frames, rows around a wave's 256 cells, several tiles with a partial last one; the text
+    at every residue of its address modulo 4 and both frames at odd addresses: length and bytes are the host's, nothing else is written,
+    equal frames write nothing"""
+    for w, rows in SIZES:
+        shown, nxt = H.pair(family, w, rows)
+        want = host.emitter_delta_half_rgb8(shown, nxt)
+        for offset in range(4):
+            same_text(device_delta(ctx, shown, nxt, offset, f"{family} {w}x{rows}"), want, f"{family} {w}x{rows} at offset {offset}")
+        if family == "nothing":
+            assert want.size == 0
+        if family == "all different" and rows % 2 == 0:
+            assert want.size == H.bound(w, rows) == hip.ansi_delta_half_capacity(w, rows)
+    shown, _ = H.pair(family, 65, 5)
+    assert device_delta(ctx, shown, shown.copy(), 1, "equal frames").size == 0
+
+
+@pytest.mark.parametrize("family", ["nothing", "all different", "full palette 0.4", "upper only", "last only"])
+def test_nothing_behind_an_odd_frame_is_read(ctx, family):
+    """the odd-row sizes, each frame followed directly by width * 3 bytes that differ between the two allocations: a kernel that loaded a lower
+    row there would see changed cells; the text is still the host's"""
+    for w, rows in [(w, rows) for w, rows in SIZES if rows % 2]:
+        shown, nxt = H.pair(family, w, rows)
+        same_text(device_delta(ctx, shown, nxt, 1, f"{family} {w}x{rows}", trap=True), host.emitter_delta_half_rgb8(shown, nxt), f"{family} {w}x{rows} with a trap row")
+
+
+def test_more_tiles_than_one_turn_of_the_offsets_scan(ctx):
+    """2048 x 1101: 1 128 448 cells in 551 text rows, 1102 tiles, two turns of the one workgroup's 1024-sum scan with its running total; 40 % of
+    the pixels changed, and the longest text there is (every cell changed, all neighbours different: the bound but for the odd frame's last
+    text row)"""
+    rng = np.random.default_rng(1101)
+    w, rows = 2048, 1101
+    shown = rng.integers(0, 256, (rows, w, 3), dtype=np.uint8)
+    nxt = shown.copy()
+    change = rng.random((rows, w)) < 0.4
+    nxt[change] = rng.integers(0, 256, (int(change.sum()), 3), dtype=np.uint8)
+    same_text(device_delta(ctx, shown, nxt, 3, "2048x1101, p = 0.4"), host.emitter_delta_half_rgb8(shown, nxt), "2048x1101, p = 0.4")
+    nxt = shown ^ np.uint8(0x80)
+    nxt[:, 1::2] ^= np.uint8(0x01)  # horizontal neighbours differ in the new frame wherever they were equal, and mostly anyway
+    want = host.emitter_delta_half_rgb8(shown, nxt)
+    same_text(device_delta(ctx, shown, nxt, 1, "2048x1101, everything changed", trap=True), want, "2048x1101, everything changed")
+    assert want.size > 0.99 * H.bound(w, rows)
+
+
+def test_the_formatting_entry_refuses_before_it_enqueues(ctx):
+    lib = hip.lib()
+    shown, nxt = H.pair("full palette 0.4", 7, 3)
+    a, pa = at_odd_address(shown)
+    b, pb = at_odd_address(nxt)
+    cap = hip.ansi_delta_half_capacity(7, 3)
+    assert cap == max(hip.ansi_half_bytes(7, 3), H.bound(7, 3)) and hip.ansi_delta_half_capacity(1, 1) == 57
+    assert hip.ansi_delta_half_capacity(160, 48) == hip.ansi_delta_half_capacity(160, 47) == 150192
+    assert hip.ansi_delta_half_capacity(100000, 1) == hip.ansi_delta_half_capacity(1, 199999) == hip.ansi_delta_half_capacity(0, 1) == 0
+    room = Room(cap)
+    call = lambda c=ctx._h, s=pa, n=pb, w=7, r=3, t=room.ptr, k=cap, l=room.length_ptr: lib.trt_ansi_delta_half_from_rgb8_device(c, s, n, w, r, t, k, l)
+    for bad in (dict(c=None), dict(s=None), dict(n=None), dict(t=None), dict(l=None), dict(w=0), dict(r=0), dict(w=100000), dict(r=199999)):
+        assert call(**bad) == ARGUMENT, bad
+    assert call(k=cap - 1) == CAPACITY
+    assert room.untouched(ctx)
+    assert call() == 0
+    same_text(room.text(ctx), host.emitter_delta_half_rgb8(shown, nxt), "the good call after the refusals")
+    ms = ctx.ansi_delta_half_kernel_times(pa, pb, 7, 3, room.ptr, cap, room.length_ptr)
+    assert len(ms) == 3 and all(t >= 0 for t in ms)
+    same_text(room.text(ctx), host.emitter_delta_half_rgb8(shown, nxt), "the timing entry writes the same text")
+
+
+# ---- 2. the render entries ----
+
+def frames_of(kind, indices, rows=None, b=B, h=H_):
+    out = [D.oracle_rgb(kind, "synth", W, h, k, b, SPP) for k in indices]
+    if rows is not None:
+        owned = [hip.lib().trt_rowset_frame_row(C.byref(rows), i) for i in range(hip.lib().trt_rowset_rows(C.byref(rows)))]
+        out = [np.ascontiguousarray(f[owned]) for f in out]
+    return out
+
+
+def owned_rows(rows):
+    return hip.lib().trt_rowset_rows(C.byref(rows))
+
+
+def render_half(ctx, cam, rows, offset=0, what=""):
+    room = Room(hip.ansi_delta_half_capacity(rows.width, owned_rows(rows)), offset)
+    ctx.render_device_ansi_delta_half(cam, rows, B, SPP, room.ptr, room.capacity, room.length_ptr)
+    return room.text(ctx, what)
+
+
+def render_full(ctx, cam, rows, offset=0, what=""):
+    room = Room(hip.ansi_delta_capacity(rows.width, owned_rows(rows)), offset)
+    ctx.render_device_ansi_delta(cam, rows, B, SPP, room.ptr, room.capacity, room.length_ptr)
+    return room.text(ctx, what)
+
+
+def check_sequence(ctx, kind, rows, indices=(0, 1, 2, 3), between=None, what="", h=H_):
+    """a keyframe, then deltas: the texts are the host's of the oracle's frames, and the terminal shows every frame"""
+    cams = D.anim_cameras(indices, W, h)
+    frames = frames_of(kind, indices, rows, h=h)
+    term = H.Terminal(W, frames[0].shape[0])
+    for k in range(len(indices)):
+        got = render_half(ctx, cams[k], rows, offset=k % 4, what=f"{what} call {k}")
+        want = host.emitter_half_rgb8(frames[0]) if k == 0 else host.emitter_delta_half_rgb8(frames[k - 1], frames[k])
+        same_text(got, want, f"{what} call {k}")
+        term.feed(got).shows(frames[k], f"{what} call {k}")
+        if between:
+            between(k)
+
+
+@pytest.mark.parametrize("kind", ["demo", "synth64"])
+@pytest.mark.parametrize("kernel", [hip.Context.PRODUCTION, hip.Context.REFERENCE_ORDER], ids=["production", "reference_order"])
+def test_a_keyframe_then_the_deltas_of_the_orbit(ctx, kind, kernel):
+    ctx.set_scene(D.scene(kind))
+    ctx.set_kernel(kernel)
+    check_sequence(ctx, kind, hip.RowSet.whole(W, H_), what=f"{kind} whole frame")
+    ctx.ansi_delta_reset()
+    check_sequence(ctx, kind, hip.RowSet(W, H_, 8, 1, 3), what=f"{kind} shard")
+
+
+def test_a_keyframe_then_the_deltas_of_an_odd_frame(ctx):
+    """160 x 47: the last text row's lower halves are black in every text"""
+    sc = D.scene("demo")
+    ctx.set_scene(sc)
+    check_sequence(ctx, "demo", hip.RowSet.whole(W, 47), what="demo 160x47", h=47)
+
+
+def test_the_shown_frame_across_kinds(ctx):
+    """half-block keyframe, half-block delta, a full-text delta call, a half-block call: a terminal that shows two-column cells cannot be patched
+    with one-column records, so a change of kind is a keyframe, either way"""
+    ctx.set_scene(D.scene("demo"))
+    rows = hip.RowSet.whole(W, H_)
+    cams = D.anim_cameras([0, 1, 2, 3, 4], W, H_)
+    f = frames_of("demo", [0, 1, 2, 3, 4])
+    same_text(render_half(ctx, cams[0], rows), host.emitter_half_rgb8(f[0]), "half-block keyframe")
+    same_text(render_half(ctx, cams[1], rows, 1), host.emitter_delta_half_rgb8(f[0], f[1]), "half-block delta")
+    same_text(render_full(ctx, cams[2], rows, 2), D.full_text(f[2]), "a full-text delta call after a half-block one: the full keyframe")
+    same_text(render_half(ctx, cams[3], rows, 3), host.emitter_half_rgb8(f[3]), "a half-block call after a full-text one: the half-block keyframe again")
+    same_text(render_half(ctx, cams[4], rows), host.emitter_delta_half_rgb8(f[3], f[4]), "and a delta after it")
+    # the existing entries among themselves, as before
+    ctx.ansi_delta_reset()
+    same_text(render_full(ctx, cams[0], rows), D.full_text(f[0]), "full-text keyframe")
+    same_text(render_full(ctx, cams[1], rows, 1), host.emitter_delta_rgb8(f[0], f[1]), "full-text delta")
+
+
+def test_other_render_entries_leave_the_shown_frame_alone(ctx):
+    """trt_render_device_rgb8, _ansi and _ansi_half calls of another camera, and a trt_set_scene, between the delta calls"""
+    import torch
+    ctx.set_scene(D.scene("demo"))
+    rows = hip.RowSet.whole(W, H_)
+    other = D.anim_cameras([40], W, H_)[0]
+    scratch = torch.zeros(hip.ansi_bytes(W, H_), dtype=torch.uint8, device="cuda:0")
+
+    def between(k):
+        ctx.render_device_rgb8(other, rows, B, SPP, scratch.data_ptr(), W * H_ * 3)
+        ctx.render_device_ansi(other, rows, B, SPP, scratch.data_ptr(), hip.ansi_bytes(W, H_))
+        ctx.render_device_ansi_half(other, rows, B, SPP, scratch.data_ptr(), hip.ansi_half_bytes(W, H_))
+        if k == 1:
+            ctx.set_scene(D.scene("demo"))
+
+    check_sequence(ctx, "demo", rows, between=between, what="interleaved")
+
+
+def test_reset_and_another_size_give_a_keyframe_and_the_host_entry_the_same_bytes(ctx):
+    ctx.set_scene(D.scene("demo"))
+    rows = hip.RowSet.whole(W, H_)
+    cams = D.anim_cameras([0, 1, 2, 3], W, H_)
+    f = frames_of("demo", [0, 1, 2, 3])
+    same_text(ctx.render_host_ansi_delta_half(cams[0], rows, B, SPP), host.emitter_half_rgb8(f[0]), "host entry, keyframe")
+    same_text(ctx.render_host_ansi_delta_half(cams[1], rows, B, SPP), host.emitter_delta_half_rgb8(f[0], f[1]), "host entry, delta")
+    same_text(render_half(ctx, cams[2], rows, 1), host.emitter_delta_half_rgb8(f[1], f[2]), "device entry after the host entry")
+    ctx.ansi_delta_reset()
+    same_text(render_half(ctx, cams[3], rows, 2), host.emitter_half_rgb8(f[3]), "after trt_ansi_delta_reset")
+    same_text(ctx.render_host_ansi_delta_half(cams[3], rows, B, SPP), np.zeros(0, dtype=np.uint8), "the same frame again")
+    shard = hip.RowSet(W, H_, 8, 1, 3)
+    same_text(ctx.render_host_ansi_delta_half(cams[2], shard, B, SPP), host.emitter_half_rgb8(frames_of("demo", [2], shard)[0]), "another rowset")
+    same_text(render_half(ctx, cams[2], rows, 3), host.emitter_half_rgb8(f[2]), "and back: the whole frame is no longer the shown one")
+    small = hip.RowSet.whole(33, 3)
+    got = ctx.render_host_ansi_delta_half(D.anim_cameras([7], 33, 3)[0], small, B, 3)
+    same_text(got, host.emitter_half_rgb8(T.oracle_rgb8(T.oracle_render(D.scene("demo").with_camera(D.anim_cameras([7], 33, 3)[0]), 33, 3, B, 3)[0])), "another size")
+
+
+def test_refusals_keep_the_shown_frame(ctx):
+    lib = hip.lib()
+    rows, bad_rows, wide = hip.RowSet.whole(W, H_), hip.RowSet(0, H_, H_, 0, 1), hip.RowSet.whole(100000, 1)
+    cams = D.anim_cameras([0, 1, 2], W, H_)
+    f = frames_of("demo", [0, 1, 2])
+    cam = [hip.camera_struct(c) for c in cams]
+    cap = hip.ansi_delta_half_capacity(W, H_)
+    room = Room(max(cap, hip.ansi_delta_half_capacity(99999, 1)))
+    text = np.full(room.capacity, 0xA5, dtype=np.uint8)
+    n = C.c_size_t(77)
+    with hip.Context(0) as empty:
+        assert lib.trt_render_device_ansi_delta_half(empty._h, C.byref(cam[0]), C.byref(rows), B, SPP, room.ptr, cap, room.length_ptr) == NO_SCENE
+        assert lib.trt_render_host_ansi_delta_half(empty._h, C.byref(cam[0]), C.byref(rows), B, SPP, text.ctypes.data, cap, C.byref(n)) == NO_SCENE
+        empty.set_scene(D.scene("demo"))
+        same_text(empty.render_host_ansi_delta_half(cams[0], rows, B, SPP), host.emitter_half_rgb8(f[0]), "a good call after no scene")
+    ctx.set_scene(D.scene("demo"))
+    same_text(render_half(ctx, cams[0], rows), host.emitter_half_rgb8(f[0]), "keyframe")
+    device = lambda c=ctx._h, camera=C.byref(cam[1]), rs=C.byref(rows), bl=B, out=room.ptr, k=cap, l=room.length_ptr: \
+        lib.trt_render_device_ansi_delta_half(c, camera, rs, bl, SPP, out, k, l)
+    hosted = lambda c=ctx._h, camera=C.byref(cam[1]), rs=C.byref(rows), bl=B, out=text.ctypes.data, k=cap, l=C.byref(n): \
+        lib.trt_render_host_ansi_delta_half(c, camera, rs, bl, SPP, out, k, l)
+    for entry in (device, hosted):
+        for bad in (dict(c=None), dict(camera=None), dict(rs=None), dict(out=None), dict(l=None), dict(rs=C.byref(bad_rows)), dict(bl=0),
+                    dict(rs=C.byref(wide), k=room.capacity)):
+            assert entry(**bad) == ARGUMENT, bad
+        assert entry(k=cap - 1) == CAPACITY
+    assert room.untouched(ctx), "a refused device entry wrote to the caller's buffer"
+    assert (text == 0xA5).all() and n.value == 77, "a refused host entry wrote to the caller's buffer"
+    same_text(render_half(ctx, cams[1], rows, 1), host.emitter_delta_half_rgb8(f[0], f[1]), "the good call after the refusals is still a delta")
+    assert hosted(camera=C.byref(cam[2])) == 0
+    same_text(text[:n.value], host.emitter_delta_half_rgb8(f[1], f[2]), "and so is the host entry's")
+    assert (text[n.value:] == 0xA5).all()
+
+
+# ---- 3. the drop-in entry ----
+
+def test_the_default_contexts_entry(ctx):
+    """keyframe, delta, a sphere moved between two calls (the delta is between the two frames whatever changed), trt_shutdown, keyframe"""
+    hip._check(hip.lib().trt_shutdown())  # a fresh default context: earlier tests have handed the drop-in entries other scenes
+    cams = D.anim_cameras([0, 1, 2], W, H_)
+    base = D.scene("demo")
+    f0, f1 = frames_of("demo", [0, 1])
+    f2 = D.oracle_rgb("demo", "synth", W, H_, 2, B, SPP, moved=True)
+    term = H.Terminal(W, H_)
+    try:
+        got = hip.render_frame_ansi_delta_half(base.with_camera(cams[0]), W, H_, B, SPP)
+        same_text(got, host.emitter_half_rgb8(f0), "keyframe")
+        term.feed(got).shows(f0, "keyframe")
+        got = hip.render_frame_ansi_delta_half(base.with_camera(cams[1]), W, H_, B, SPP)
+        same_text(got, host.emitter_delta_half_rgb8(f0, f1), "delta")
+        term.feed(got).shows(f1, "delta")
+        got = hip.render_frame_ansi_delta_half(D.moved_scene(base.with_camera(cams[2])), W, H_, B, SPP)
+        same_text(got, host.emitter_delta_half_rgb8(f1, f2), "a sphere moved")
+        term.feed(got).shows(f2, "a sphere moved")
+        assert (f2 != D.oracle_rgb("demo", "synth", W, H_, 2, B, SPP)).any()
+        hip._check(hip.lib().trt_shutdown())
+        same_text(hip.render_frame_ansi_delta_half(base.with_camera(cams[1]), W, H_, B, SPP), host.emitter_half_rgb8(f1), "keyframe after trt_shutdown")
+        lib, scene, n = hip.lib(), base.as_scene(), C.c_size_t(0)
+        out = np.full(hip.ansi_delta_half_capacity(W, H_), 0xA5, dtype=np.uint8)
+        assert lib.trt_render_frame_ansi_delta_half(None, W, H_, B, SPP, out.ctypes.data, out.size, C.byref(n)) == ARGUMENT
+        assert lib.trt_render_frame_ansi_delta_half(C.byref(scene), W, H_, B, SPP, None, out.size, C.byref(n)) == ARGUMENT
+        assert lib.trt_render_frame_ansi_delta_half(C.byref(scene), W, H_, B, SPP, out.ctypes.data, out.size, None) == ARGUMENT
+        assert lib.trt_render_frame_ansi_delta_half(C.byref(scene), 100000, 1, B, SPP, out.ctypes.data, out.size, C.byref(n)) == ARGUMENT
+        assert lib.trt_render_frame_ansi_delta_half(C.byref(scene), W, H_, B, SPP, out.ctypes.data, out.size - 1, C.byref(n)) == CAPACITY
+        assert (out == 0xA5).all()
+    finally:
+        hip._check(hip.lib().trt_shutdown())
+
+
+# ---- 4. the demo ----
+
+def test_demo_program_draws_the_orbit_from_a_half_block_keyframe_and_deltas(tmp_path):
+    """examples/trt_demo --half --delta: the half-block keyframe and three delta texts on stdout and nothing else -- the fps line goes to
+    stderr -- leave the terminal with the picture that --half's last whole text of the same replay paints"""
+    import os
+    import subprocess
+    exe = os.path.join(T.ROOT, "examples", "trt_demo")
+    if not os.path.exists(exe):
+        subprocess.check_call(["make", "-C", T.ROOT, "demo"])
+    sky = tmp_path / "colors"
+    sky.mkdir()
+    for f in T.FACES:
+        (sky / (f + ".ppm")).write_bytes(T.golden_ppm_raw("colors", f))
+    n = hip.ansi_half_bytes(W, H_)
+    delta = subprocess.run([exe, str(sky), "4", str(W), str(H_), "--half", "--delta", "--step=0.0166667"], capture_output=True, timeout=120)
+    assert delta.returncode == 0, delta.stderr[-500:]
+    assert b"4 frames 160x48" in delta.stderr and b"as half-block delta text" in delta.stderr and b" fps, " in delta.stderr
+    whole = subprocess.run([exe, str(sky), "4", str(W), str(H_), "--half", "--step=0.0166667"], capture_output=True, timeout=120)
+    assert whole.returncode == 0, whole.stderr[-500:]
+    assert n < len(delta.stdout) < 4 * n and delta.stdout[:n] == whole.stdout[:n]
+    assert b"\xe2\x96\x80" in delta.stdout[n:] and b"  " not in delta.stdout  # one-column records, not the full text's two spaces
+    last = whole.stdout.rindex(b"\033[0;0H\033[38;2;")
+    want = H.Terminal(W, H_).feed(whole.stdout[last:last + n])
+    got = H.Terminal(W, H_).feed(delta.stdout)
+    assert (want.grid >= 0).all() and np.array_equal(got.grid, want.grid)
