@@ -320,7 +320,7 @@ size_t trt_ansi_delta_half_capacity(int width, int rows);
 
 /* trt_ansi_delta_from_rgb8_device for half-block cells: the text that takes a terminal from the half-block text of d_shown_rgb8 to that
  * of d_next_rgb8 (rows x width x 3 bytes each, any alignment; nothing behind an odd frame's last row is read).  Three kernels in stream
- * order (csrc/trt_ansi_delta_half.hpp; the scan of the tiles' sums is the delta text's own).  It neither reads nor changes the context's
+ * order (csrc/trt_ansi_delta.hpp; the scan of the tiles' sums is the delta text's own).  It neither reads nor changes the context's
  * shown frame; it is what rank 0 applies to a trt_dist_render_rgb8 gather.  capacity_bytes >= trt_ansi_delta_half_capacity(width, rows),
  * else TRT_ERR_CAPACITY; NULL or a size above the limits: TRT_ERR_ARGUMENT.  Asynchronous on the context's stream. */
 int trt_ansi_delta_half_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows,

@@ -22,14 +22,24 @@
  *
  * The limits.  Five decimal digits for r + 1 and for 2 c + 1: rows <= 99999, width <= 49999.
  *
- * How the device writes it (trt_ansi_delta.hpp; tests/ansi_delta_check.c walks the same steps on the host): cells are numbered
- * row-major, a TILE is TRT_DELTA_TILE consecutive cells, a lane owns TRT_DELTA_LANE_CELLS consecutive cells of it.  Lengths per cell,
- * sums per tile, an exclusive scan of the tiles' sums, a scan inside the tile: a record's place is a prefix sum over the frame.
+ * How the device writes it: cells are numbered row-major, a TILE is TRT_DELTA_TILE consecutive cells, a lane owns TRT_DELTA_LANE_CELLS
+ * consecutive cells of it.  Lengths per cell, sums per tile, an exclusive scan of the tiles' sums, a scan inside the tile: a record's
+ * place is a prefix sum over the frame.  The LANE'S WALK is here, trt_delta_lane_cells: which bytes of the two frames lane `thread` of
+ * tile `tile` loads, its cells' rows and columns across the end of a row, its records' lengths; trt_delta_lane_byte gives the bytes.
+ * The kernels of trt_ansi_delta.hpp call the two for (blockIdx.x, threadIdx.x) and add the tile scheme, the sums and scans over the
+ * lanes; tests/ansi_delta_check.c calls the same two for every tile and every thread 0 .. TRT_DELTA_BLOCK - 1 on the host, under the
+ * address sanitizer, with frames allocated to the byte.
  */
 #ifndef TRT_ANSI_DELTA_H
 #define TRT_ANSI_DELTA_H
 
 #include "trt_ansi.h"
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#define TRT_DELTA_UNROLL _Pragma("unroll")
+#else
+#define TRT_DELTA_UNROLL /* the host compiler is left to itself */
+#endif
 
 #define TRT_DELTA_CURSOR 14 /* strlen("\033[00001;00001H") */
 #define TRT_DELTA_COLOUR 19 /* strlen("\033[48;2;000;000;000m") */
@@ -97,5 +107,74 @@ TRT_ANSI_HD unsigned trt_delta_record_byte(unsigned k, int r, int c, unsigned rg
 
 /* tiles of a frame of `cells` cells */
 TRT_ANSI_HD unsigned long long trt_delta_tiles(unsigned long long cells) { return (cells + TRT_DELTA_TILE - 1) / TRT_DELTA_TILE; }
+
+/* a lane's cells: their new colours, what their records depend on, the records' lengths and their sum, and where the cells lie */
+typedef struct
+{
+    unsigned rgb[TRT_DELTA_LANE_CELLS], bytes[TRT_DELTA_LANE_CELLS];
+    trt_delta_flags flags[TRT_DELTA_LANE_CELLS];
+    int row[TRT_DELTA_LANE_CELLS], col[TRT_DELTA_LANE_CELLS];
+    unsigned total;
+} trt_delta_lane;
+
+/* pixel p of a frame as r | g << 8 | b << 16, by bytes */
+TRT_ANSI_HD unsigned trt_delta_rgb(const unsigned char *frame, unsigned long long p)
+{
+    const unsigned char *px = frame + 3 * p;
+    return (unsigned)px[0] | (unsigned)px[1] << 8 | (unsigned)px[2] << 16;
+}
+
+/* The cells tile * TRT_DELTA_TILE + TRT_DELTA_LANE_CELLS * thread + j of a frame of width x rows cells; those behind the frame have no
+ * record and are not loaded.  One 64-bit division per workgroup (where the tile starts), one 32-bit division per lane. */
+TRT_ANSI_HD trt_delta_lane trt_delta_lane_cells(const unsigned char *shown, const unsigned char *next, int width, int rows, unsigned long long tile, unsigned thread)
+{
+    const unsigned long long cells = (unsigned long long)(unsigned)width * (unsigned)rows;
+    const unsigned long long tile_first = tile * TRT_DELTA_TILE;
+    const unsigned long long tile_row = tile_first / (unsigned)width;
+    const unsigned x = (unsigned)(tile_first - tile_row * (unsigned)width) + TRT_DELTA_LANE_CELLS * thread; /* < 49 999 + 1024 */
+    const unsigned q = x / (unsigned)width;
+    const unsigned long long p0 = tile_first + TRT_DELTA_LANE_CELLS * thread;
+    int row = (int)(tile_row + q), col = (int)(x - q * (unsigned)width);
+    /* the lane's cells and a neighbour either side: [j + 1] is cell p0 + j */
+    unsigned now[TRT_DELTA_LANE_CELLS + 2];
+    int changed[TRT_DELTA_LANE_CELLS + 2];
+    trt_delta_lane c;
+    /* where the cells lie, in front of the loads: the device compiler then issues the two divisions before and among the loads, whose
+     * latency covers them; with the rows and columns formed behind the loads it sinks the divisions behind the last wait */
+    TRT_DELTA_UNROLL
+    for (int j = 0; j < TRT_DELTA_LANE_CELLS; j++)
+    {
+        c.row[j] = row;
+        c.col[j] = col;
+        if (++col == width)
+            col = 0, row++;
+    }
+    TRT_DELTA_UNROLL
+    for (int j = -1; j <= TRT_DELTA_LANE_CELLS; j++)
+    {
+        const int there = (j >= 0 || p0 > 0) && p0 + j < cells; /* p0 + j wraps to a huge number only where p0 == 0, j == -1 */
+        now[j + 1] = there ? trt_delta_rgb(next, p0 + j) : 0u;
+        changed[j + 1] = there && now[j + 1] != trt_delta_rgb(shown, p0 + j);
+    }
+    c.total = 0;
+    TRT_DELTA_UNROLL
+    for (int j = 0; j < TRT_DELTA_LANE_CELLS; j++)
+    {
+        c.rgb[j] = now[j + 1];
+        c.flags[j].changed = changed[j + 1];
+        c.flags[j].changed_left = c.col[j] > 0 && changed[j];
+        c.flags[j].changed_right = c.col[j] + 1 < width && changed[j + 2];
+        c.flags[j].same_as_left = now[j + 1] == now[j];
+        c.bytes[j] = trt_delta_record_bytes(&c.flags[j]);
+        c.total += c.bytes[j];
+    }
+    return c;
+}
+
+/* byte k < c->bytes[j] of the record of the lane's j-th cell */
+TRT_ANSI_HD unsigned trt_delta_lane_byte(const trt_delta_lane *c, int j, unsigned k)
+{
+    return trt_delta_record_byte(k, c->row[j], c->col[j], c->rgb[j], &c->flags[j]);
+}
 
 #endif /* TRT_ANSI_DELTA_H */

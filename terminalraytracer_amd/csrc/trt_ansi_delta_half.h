@@ -31,10 +31,12 @@
  *
  * The limits.  Five decimal digits for t + 1 and for c + 1: width <= 99999, T <= 99999 (rows <= 199998).
  *
- * How the device writes it (trt_ansi_delta_half.hpp; tests/ansi_delta_half_check.c walks the same steps on the host): the scheme of
- * trt_ansi_delta.h -- cells numbered row-major over the TEXT rows, tiles of TRT_DELTA_TILE cells, TRT_DELTA_LANE_CELLS consecutive
- * cells per lane, lengths per cell, sums per tile (at most 1024 x 57 = 58 368 bytes: 32 bits), an exclusive scan of the tiles' sums,
- * a scan inside the tile.
+ * How the device writes it: the scheme of trt_ansi_delta.h -- cells numbered row-major over the TEXT rows, tiles of TRT_DELTA_TILE
+ * cells, TRT_DELTA_LANE_CELLS consecutive cells per lane, lengths per cell, sums per tile (at most 1024 x 57 = 58 368 bytes: 32 bits),
+ * an exclusive scan of the tiles' sums, a scan inside the tile.  The LANE'S WALK is here, trt_delta_half_lane_cells: which bytes of
+ * the two frames lane `thread` of tile `tile` loads -- never the pixel row behind an odd frame -- its cells' text rows and columns
+ * across the end of a row, its records' lengths; trt_delta_half_lane_byte gives the bytes.  The kernels of trt_ansi_delta.hpp and
+ * tests/ansi_delta_half_check.c call the two as they call those of trt_ansi_delta.h.
  */
 #ifndef TRT_ANSI_DELTA_HALF_H
 #define TRT_ANSI_DELTA_HALF_H
@@ -129,6 +131,73 @@ TRT_ANSI_HD unsigned trt_delta_half_record_byte(unsigned k, int t, int c, unsign
     else
         at = k < 2 ? k : k + (TRT_DELTA_HALF_BOTH - TRT_DELTA_HALF_SINGLE);
     return trt_ansi_half_cell_byte((int)at, upper, lower);
+}
+
+/* a lane's cells: their new colours, what their records depend on, the records' lengths and their sum, and where the cells lie */
+typedef struct
+{
+    unsigned upper[TRT_DELTA_LANE_CELLS], lower[TRT_DELTA_LANE_CELLS], bytes[TRT_DELTA_LANE_CELLS];
+    trt_delta_half_flags flags[TRT_DELTA_LANE_CELLS];
+    int trow[TRT_DELTA_LANE_CELLS], col[TRT_DELTA_LANE_CELLS];
+    unsigned total;
+} trt_delta_half_lane;
+
+/* The cells tile * TRT_DELTA_TILE + TRT_DELTA_LANE_CELLS * thread + j of a frame of width x rows pixels, (rows + 1) / 2 text rows; those
+ * behind the frame have no record and are not loaded.  One 64-bit division per workgroup (where the tile starts), one 32-bit division
+ * per lane.  Cell (t, col) has its upper pixel at pixel 2 t width + col of a frame and its lower one `width` pixels on, which exists,
+ * and is loaded, when 2 t + 1 < rows. */
+TRT_ANSI_HD trt_delta_half_lane trt_delta_half_lane_cells(const unsigned char *shown, const unsigned char *next, int width, int rows, unsigned long long tile,
+                                                          unsigned thread)
+{
+    const unsigned trows = ((unsigned)rows + 1u) / 2u;
+    const unsigned long long tile_first = tile * TRT_DELTA_TILE;
+    const unsigned long long tile_row = tile_first / (unsigned)width;
+    const unsigned x = (unsigned)(tile_first - tile_row * (unsigned)width) + TRT_DELTA_LANE_CELLS * thread; /* < 99 999 + 1024 */
+    const unsigned q = x / (unsigned)width;
+    /* the lane's cells and a neighbour either side, [j + 1] the j-th: cell -1 only matters inside a row, so it is read only there */
+    unsigned long long t = tile_row + q;
+    int col = (int)(x - q * (unsigned)width) - 1;
+    unsigned up[TRT_DELTA_LANE_CELLS + 2], low[TRT_DELTA_LANE_CELLS + 2];
+    int changed[TRT_DELTA_LANE_CELLS + 2];
+    trt_delta_half_lane c;
+    TRT_DELTA_UNROLL
+    for (int j = -1; j <= TRT_DELTA_LANE_CELLS; j++)
+    {
+        const int there = col >= 0 && t < trows;
+        const int has_lower = there && 2 * t + 1 < (unsigned long long)(unsigned)rows;
+        const unsigned long long p = 2 * t * (unsigned)width + (unsigned)col; /* used only where `there` */
+        up[j + 1] = there ? trt_delta_rgb(next, p) : 0u;
+        low[j + 1] = has_lower ? trt_delta_rgb(next, p + (unsigned)width) : 0u;
+        changed[j + 1] = there && (up[j + 1] != trt_delta_rgb(shown, p) || (has_lower && low[j + 1] != trt_delta_rgb(shown, p + (unsigned)width)));
+        if (j >= 0 && j < TRT_DELTA_LANE_CELLS)
+        {
+            c.trow[j] = (int)t;
+            c.col[j] = col;
+        }
+        if (++col == width)
+            col = 0, t++;
+    }
+    c.total = 0;
+    TRT_DELTA_UNROLL
+    for (int j = 0; j < TRT_DELTA_LANE_CELLS; j++)
+    {
+        c.upper[j] = up[j + 1];
+        c.lower[j] = low[j + 1];
+        c.flags[j].changed = changed[j + 1];
+        c.flags[j].changed_left = c.col[j] > 0 && changed[j];
+        c.flags[j].changed_right = c.col[j] + 1 < width && changed[j + 2];
+        c.flags[j].same_upper = up[j + 1] == up[j];
+        c.flags[j].same_lower = low[j + 1] == low[j];
+        c.bytes[j] = trt_delta_half_record_bytes(&c.flags[j]);
+        c.total += c.bytes[j];
+    }
+    return c;
+}
+
+/* byte k < c->bytes[j] of the record of the lane's j-th cell */
+TRT_ANSI_HD unsigned trt_delta_half_lane_byte(const trt_delta_half_lane *c, int j, unsigned k)
+{
+    return trt_delta_half_record_byte(k, c->trow[j], c->col[j], c->upper[j], c->lower[j], &c->flags[j]);
 }
 
 #endif /* TRT_ANSI_DELTA_HALF_H */

@@ -209,7 +209,7 @@ struct trt_context
     DeviceBuffer<unsigned char> d_shown[2];
     int shown_at = 0;
     bool shown_valid = false; // false: the next delta call sends a keyframe
-    bool shown_half = false;  // the text the shown frame was sent as: half-block cells (trt_ansi_delta_half.hpp) or the full text's;
+    bool shown_half = false;  // the text the shown frame was sent as: half-block cells (trt_ansi_delta_half.h) or the full text's;
                               // a delta call of the other kind sends a keyframe
     trt_rowset shown_rows{};
     DeviceBuffer<unsigned> d_delta_tile_bytes;         // per tile of cells: the bytes of its records

@@ -207,33 +207,33 @@ extern "C" int trt_render_frame_ansi_half(const Scene *scene, int width, int hei
     });
 }
 
-// the shown frame is the default context's: trt_shutdown forgets it with the context
-extern "C" int trt_render_frame_ansi_delta(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text, size_t capacity_bytes,
-                                           size_t *bytes)
+// the shown frame is the default context's: trt_shutdown forgets it with the context.  `capacity` and `render`: those of the kind
+static int render_frame_delta(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text, size_t capacity_bytes, size_t *bytes,
+                              size_t (*capacity)(int, int),
+                              int (*render)(trt_context *, const Camera *, const trt_rowset *, int, int, char *, size_t, size_t *))
 {
     if (!scene || !text || !bytes)
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (width <= 0 || height <= 0 || trt_ansi_delta_capacity(width, height) == 0)
+    if (width <= 0 || height <= 0 || capacity(width, height) == 0)
         return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, height);
-    if (capacity_bytes < trt_ansi_delta_capacity(width, height))
-        return fail(TRT_ERR_CAPACITY, "the text of %d x %d needs room for %zu B, %zu given", width, height, trt_ansi_delta_capacity(width, height), capacity_bytes);
+    if (capacity_bytes < capacity(width, height))
+        return fail(TRT_ERR_CAPACITY, "the text of %d x %d needs room for %zu B, %zu given", width, height, capacity(width, height), capacity_bytes);
     return render_default_frame(scene, width, height, [&](trt_context *ctx, const trt_rowset *whole) {
-        return trt_render_host_ansi_delta(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes);
+        return render(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes);
     });
+}
+
+extern "C" int trt_render_frame_ansi_delta(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text, size_t capacity_bytes,
+                                           size_t *bytes)
+{
+    return render_frame_delta(scene, width, height, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, trt_ansi_delta_capacity, trt_render_host_ansi_delta);
 }
 
 extern "C" int trt_render_frame_ansi_delta_half(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text, size_t capacity_bytes,
                                                 size_t *bytes)
 {
-    if (!scene || !text || !bytes)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (width <= 0 || height <= 0 || trt_ansi_delta_half_capacity(width, height) == 0)
-        return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, height);
-    if (capacity_bytes < trt_ansi_delta_half_capacity(width, height))
-        return fail(TRT_ERR_CAPACITY, "the text of %d x %d needs room for %zu B, %zu given", width, height, trt_ansi_delta_half_capacity(width, height), capacity_bytes);
-    return render_default_frame(scene, width, height, [&](trt_context *ctx, const trt_rowset *whole) {
-        return trt_render_host_ansi_delta_half(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes);
-    });
+    return render_frame_delta(scene, width, height, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, trt_ansi_delta_half_capacity,
+                              trt_render_host_ansi_delta_half);
 }
 
 extern "C" void project_scene(Scene *scene, Screen *screen)

@@ -10,7 +10,6 @@
 #include "trt_simple.hpp"
 #include "trt_ansi.hpp"
 #include "trt_ansi_delta.hpp"
-#include "trt_ansi_delta_half.hpp"
 #include "trt_ansi_half.hpp"
 
 using namespace trt_impl;
@@ -1206,7 +1205,7 @@ extern "C" int trt_kernel_info(trt_context *ctx, int *vgprs, int *sgprs, int *st
     return TRT_OK;
 }
 
-// ---- the delta texts (trt_ansi_delta.h, trt_ansi_delta.hpp: the full text's cells; trt_ansi_delta_half.h, trt_ansi_delta_half.hpp: half-block cells) ----
+// ---- the delta texts (trt_ansi_delta.h: the full text's cells; trt_ansi_delta_half.h: half-block cells; trt_ansi_delta.hpp: the kernels of both) ----
 
 extern "C" size_t trt_ansi_delta_capacity(int width, int rows)
 {
@@ -1230,6 +1229,11 @@ static size_t delta_capacity(bool half, int width, int rows) { return half ? trt
 static int launch_ansi_delta(trt_context *ctx, hipStream_t stream, bool half, const unsigned char *d_shown, const unsigned char *d_next, int width, int rows, void *d_text,
                              size_t capacity_bytes, unsigned long long *d_bytes, const Event *marks = nullptr)
 {
+    static const struct
+    {
+        void (*measure)(const unsigned char *, const unsigned char *, int, int, unsigned *);
+        void (*write)(const unsigned char *, const unsigned char *, int, int, const unsigned long long *, unsigned char *, unsigned long long);
+    } kernels[2] = {{trt::ansi_delta_measure_kernel, trt::ansi_delta_write_kernel}, {trt::ansi_delta_half_measure_kernel, trt::ansi_delta_half_write_kernel}};
     const unsigned long long cells = (unsigned long long)width * (unsigned long long)(half ? trt_ansi_half_text_rows(rows) : rows), tiles = trt_delta_tiles(cells);
     if (ctx->d_delta_tile_bytes.capacity < tiles || ctx->d_delta_tile_at.capacity < tiles)
         HIP_TRY(hipStreamSynchronize(stream)); // a text in flight may still use the old sums
@@ -1237,22 +1241,15 @@ static int launch_ansi_delta(trt_context *ctx, hipStream_t stream, bool half, co
     HIP_TRY(ctx->d_delta_tile_at.reserve((size_t)tiles));
     if (marks)
         HIP_TRY(hipEventRecord(marks[0], stream));
-    if (half)
-        hipLaunchKernelGGL(trt::ansi_delta_half_measure_kernel, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, rows, ctx->d_delta_tile_bytes.ptr);
-    else
-        hipLaunchKernelGGL(trt::ansi_delta_measure_kernel, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, cells, ctx->d_delta_tile_bytes.ptr);
+    hipLaunchKernelGGL(kernels[half].measure, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, rows, ctx->d_delta_tile_bytes.ptr);
     if (marks)
         HIP_TRY(hipEventRecord(marks[1], stream));
     hipLaunchKernelGGL(trt::ansi_delta_offsets_kernel, dim3(1), dim3(TRT_DELTA_SCAN_BLOCK), 0, stream, (const unsigned *)ctx->d_delta_tile_bytes.ptr, tiles,
                        ctx->d_delta_tile_at.ptr, d_bytes);
     if (marks)
         HIP_TRY(hipEventRecord(marks[2], stream));
-    if (half)
-        hipLaunchKernelGGL(trt::ansi_delta_half_write_kernel, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, rows,
-                           (const unsigned long long *)ctx->d_delta_tile_at.ptr, (unsigned char *)d_text, (unsigned long long)capacity_bytes);
-    else
-        hipLaunchKernelGGL(trt::ansi_delta_write_kernel, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, cells,
-                           (const unsigned long long *)ctx->d_delta_tile_at.ptr, (unsigned char *)d_text, (unsigned long long)capacity_bytes);
+    hipLaunchKernelGGL(kernels[half].write, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, rows,
+                       (const unsigned long long *)ctx->d_delta_tile_at.ptr, (unsigned char *)d_text, (unsigned long long)capacity_bytes);
     if (marks)
         HIP_TRY(hipEventRecord(marks[3], stream));
     HIP_TRY(hipGetLastError());

@@ -470,33 +470,46 @@ class Context:
         """the half-block text of a width x rows frame of RGB8 bytes in device memory, at text_ptr (trt_ansi_half_from_rgb8_device)"""
         _check(lib().trt_ansi_half_from_rgb8_device(self._h, _VP(rgb_ptr), width, rows, _VP(text_ptr)))
 
+    # the delta entries come in two kinds of cell, the full text's and half-block cells: each pair goes through one helper that takes the entry's name
+
+    def _delta_from_rgb8(self, entry, shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr):
+        _check(getattr(lib(), entry)(self._h, _VP(shown_ptr), _VP(next_ptr), width, rows, _VP(text_ptr), capacity_bytes, _VP(bytes_ptr)))
+
+    def _delta_kernel_times(self, entry, shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr):
+        ms = (C.c_float * 3)()
+        _check(getattr(lib(), entry)(self._h, _VP(shown_ptr), _VP(next_ptr), width, rows, _VP(text_ptr), capacity_bytes, _VP(bytes_ptr), ms))
+        return tuple(ms)
+
+    def _render_device_delta(self, entry, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr):
+        cam = camera_struct(camera_array)
+        _check(getattr(lib(), entry)(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, _VP(device_ptr), capacity_bytes, _VP(bytes_ptr)))
+
+    def _render_host_delta(self, entry, capacity, camera_array, rows, bounce_limit, rays_per_pixel, out):
+        if out is None:
+            out = np.empty(capacity(rows.width, lib().trt_rowset_rows(C.byref(rows))), dtype=np.uint8)
+        n = _SZ(0)
+        cam = camera_struct(camera_array)
+        _check(getattr(lib(), entry)(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data, out.size, C.byref(n)))
+        return out[:n.value]
+
     def ansi_delta_from_rgb8(self, shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr):
         """the delta text between two width x rows frames of RGB8 bytes in device memory, at text_ptr, its length (a uint64) at the device
         address bytes_ptr (trt_ansi_delta_from_rgb8_device)"""
-        _check(lib().trt_ansi_delta_from_rgb8_device(self._h, _VP(shown_ptr), _VP(next_ptr), width, rows, _VP(text_ptr), capacity_bytes, _VP(bytes_ptr)))
+        self._delta_from_rgb8("trt_ansi_delta_from_rgb8_device", shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr)
 
     def ansi_delta_kernel_times(self, shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr):
         """the same, synchronous: ms of the (measure, offsets, write) kernels by HIP events (trt_ansi_delta_kernel_times)"""
-        ms = (C.c_float * 3)()
-        _check(lib().trt_ansi_delta_kernel_times(self._h, _VP(shown_ptr), _VP(next_ptr), width, rows, _VP(text_ptr), capacity_bytes, _VP(bytes_ptr), ms))
-        return tuple(ms)
+        return self._delta_kernel_times("trt_ansi_delta_kernel_times", shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr)
 
     def render_device_ansi_delta(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr):
         """the frame as the delta text against the context's shown frame (a keyframe when there is none for this rowset) in device memory,
         its length (a uint64) at the device address bytes_ptr (trt_render_device_ansi_delta)"""
-        cam = camera_struct(camera_array)
-        _check(lib().trt_render_device_ansi_delta(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, _VP(device_ptr), capacity_bytes,
-                                                  _VP(bytes_ptr)))
+        self._render_device_delta("trt_render_device_ansi_delta", camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr)
 
     def render_host_ansi_delta(self, camera_array, rows, bounce_limit, rays_per_pixel, out=None):
         """the same into host memory: the uint8 text, exactly as long as the host is to write it (trt_render_host_ansi_delta); `out`: a
         uint8 buffer of ansi_delta_capacity bytes to reuse"""
-        if out is None:
-            out = np.empty(ansi_delta_capacity(rows.width, lib().trt_rowset_rows(C.byref(rows))), dtype=np.uint8)
-        n = _SZ(0)
-        cam = camera_struct(camera_array)
-        _check(lib().trt_render_host_ansi_delta(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data, out.size, C.byref(n)))
-        return out[:n.value]
+        return self._render_host_delta("trt_render_host_ansi_delta", ansi_delta_capacity, camera_array, rows, bounce_limit, rays_per_pixel, out)
 
     def ansi_delta_reset(self):
         """forget the shown frame: the next delta text, of either kind, is a keyframe (trt_ansi_delta_reset)"""
@@ -505,31 +518,22 @@ class Context:
     def ansi_delta_half_from_rgb8(self, shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr):
         """the delta text in half-block cells between two width x rows frames of RGB8 bytes in device memory, at text_ptr, its length (a
         uint64) at the device address bytes_ptr (trt_ansi_delta_half_from_rgb8_device)"""
-        _check(lib().trt_ansi_delta_half_from_rgb8_device(self._h, _VP(shown_ptr), _VP(next_ptr), width, rows, _VP(text_ptr), capacity_bytes, _VP(bytes_ptr)))
+        self._delta_from_rgb8("trt_ansi_delta_half_from_rgb8_device", shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr)
 
     def ansi_delta_half_kernel_times(self, shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr):
         """the same, synchronous: ms of the (measure, offsets, write) kernels by HIP events (trt_ansi_delta_half_kernel_times)"""
-        ms = (C.c_float * 3)()
-        _check(lib().trt_ansi_delta_half_kernel_times(self._h, _VP(shown_ptr), _VP(next_ptr), width, rows, _VP(text_ptr), capacity_bytes, _VP(bytes_ptr), ms))
-        return tuple(ms)
+        return self._delta_kernel_times("trt_ansi_delta_half_kernel_times", shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr)
 
     def render_device_ansi_delta_half(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr):
         """the frame as the half-block delta text against the context's shown frame (a keyframe, the half-block text, when there is none
         for this rowset and this kind) in device memory, its length (a uint64) at the device address bytes_ptr
         (trt_render_device_ansi_delta_half)"""
-        cam = camera_struct(camera_array)
-        _check(lib().trt_render_device_ansi_delta_half(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, _VP(device_ptr), capacity_bytes,
-                                                       _VP(bytes_ptr)))
+        self._render_device_delta("trt_render_device_ansi_delta_half", camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr)
 
     def render_host_ansi_delta_half(self, camera_array, rows, bounce_limit, rays_per_pixel, out=None):
         """the same into host memory: the uint8 text, exactly as long as the host is to write it (trt_render_host_ansi_delta_half); `out`:
         a uint8 buffer of ansi_delta_half_capacity bytes to reuse"""
-        if out is None:
-            out = np.empty(ansi_delta_half_capacity(rows.width, lib().trt_rowset_rows(C.byref(rows))), dtype=np.uint8)
-        n = _SZ(0)
-        cam = camera_struct(camera_array)
-        _check(lib().trt_render_host_ansi_delta_half(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data, out.size, C.byref(n)))
-        return out[:n.value]
+        return self._render_host_delta("trt_render_host_ansi_delta_half", ansi_delta_half_capacity, camera_array, rows, bounce_limit, rays_per_pixel, out)
 
     @staticmethod
     def _camera_batch(cameras):
@@ -733,36 +737,40 @@ def _header_constant(header, name):
 ANSI_HALF_WAVE_WORDS = _header_constant("trt_ansi_half.h", "TRT_ANSI_HALF_WAVE_WORDS")
 
 
+def _delta_capacity(entry, width, rows):
+    return int(getattr(lib(), entry)(width, rows))
+
+
+def _render_frame_delta(entry, capacity, scene_data, width, height, bounce_limit, rays_per_pixel):
+    scene = scene_data.as_scene()
+    out = np.empty(capacity(width, height), dtype=np.uint8)
+    n = _SZ(0)
+    _check(getattr(lib(), entry)(C.byref(scene), width, height, bounce_limit, rays_per_pixel, out.ctypes.data, out.size, C.byref(n)))
+    return out[:n.value]
+
+
 def ansi_delta_capacity(width, rows):
     """room for any text the delta entries write: max(ansi_bytes, rows * (21 * width + 18)); 0 when a size is not positive or above the
     format's limits (trt_ansi_delta_capacity)"""
-    return int(lib().trt_ansi_delta_capacity(width, rows))
+    return _delta_capacity("trt_ansi_delta_capacity", width, rows)
 
 
 def render_frame_ansi_delta(scene_data, width, height, bounce_limit=10, rays_per_pixel=10):
     """Host-in frame as the delta text against the frame this entry returned before (a keyframe the first time): the uint8 text, as
     long as the host is to write it (trt_render_frame_ansi_delta)."""
-    scene = scene_data.as_scene()
-    out = np.empty(ansi_delta_capacity(width, height), dtype=np.uint8)
-    n = _SZ(0)
-    _check(lib().trt_render_frame_ansi_delta(C.byref(scene), width, height, bounce_limit, rays_per_pixel, out.ctypes.data, out.size, C.byref(n)))
-    return out[:n.value]
+    return _render_frame_delta("trt_render_frame_ansi_delta", ansi_delta_capacity, scene_data, width, height, bounce_limit, rays_per_pixel)
 
 
 def ansi_delta_half_capacity(width, rows):
     """room for any text the half-block delta entries write: max(ansi_half_bytes, ((rows + 1) // 2) * (39 * width + 18)); 0 when a size
     is not positive or above the format's limits (trt_ansi_delta_half_capacity)"""
-    return int(lib().trt_ansi_delta_half_capacity(width, rows))
+    return _delta_capacity("trt_ansi_delta_half_capacity", width, rows)
 
 
 def render_frame_ansi_delta_half(scene_data, width, height, bounce_limit=10, rays_per_pixel=10):
     """Host-in frame as the half-block delta text against the frame this entry returned before (a keyframe the first time): the uint8
     text, as long as the host is to write it (trt_render_frame_ansi_delta_half)."""
-    scene = scene_data.as_scene()
-    out = np.empty(ansi_delta_half_capacity(width, height), dtype=np.uint8)
-    n = _SZ(0)
-    _check(lib().trt_render_frame_ansi_delta_half(C.byref(scene), width, height, bounce_limit, rays_per_pixel, out.ctypes.data, out.size, C.byref(n)))
-    return out[:n.value]
+    return _render_frame_delta("trt_render_frame_ansi_delta_half", ansi_delta_half_capacity, scene_data, width, height, bounce_limit, rays_per_pixel)
 
 
 def render_frame_ansi(scene_data, width, height, bounce_limit=10, rays_per_pixel=10):

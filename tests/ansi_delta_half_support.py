@@ -7,7 +7,7 @@ import re
 import numpy as np
 
 import ansi_delta_support as D
-from terminalraytracer_amd import host
+from terminalraytracer_amd import hip, host
 
 DEFAULT = -2   # after "\033[0m": the terminal's own colour
 NEVER = -1     # a half cell nothing was painted on
@@ -127,3 +127,10 @@ def pair(family, w, rows, seed=0):
 def expected(shown, nxt):
     """the sequential emitter's text of the pair, as bytes"""
     return host.emitter_delta_half_rgb8(shown, nxt).tobytes()
+
+
+def render_half(ctx, cam, rows, offset=0, what=""):
+    return D.render_text(ctx, hip.Context.render_device_ansi_delta_half, hip.ansi_delta_half_capacity, cam, rows, offset, what)
+
+
+HALF = D.Kind(host.emitter_half_rgb8, host.emitter_delta_half_rgb8, Terminal, render_half)

@@ -1,7 +1,10 @@
-"""What the delta-text tests share (test_ansi_delta_host.py without a GPU, test_ansi_delta_text.py with one): a small model of a terminal, the
-families of frame pairs the format is exercised with, and the oracle's frames of the demo orbit.  Expected texts never come from the
-library's device route: they are host.emitter_delta_rgb8 (the sequential C statement) of T.oracle_rgb8 frames, and what the model shows is
-held against those frames themselves."""
+"""What the delta-text tests share (test_ansi_delta_host.py without a GPU, test_ansi_delta_text.py and test_ansi_delta_half_text.py with
+one): a small model of a terminal, the families of frame pairs the format is exercised with, the oracle's frames of the demo orbit, and
+the harness of the GPU tests of both kinds of cell -- guarded device buffers, frames at odd addresses with trap bytes behind them, the
+keyframe-then-deltas sequence.  Expected texts never come from the library's device route: they are host.emitter_delta_rgb8 (the
+sequential C statement) of T.oracle_rgb8 frames, and what the model shows is held against those frames themselves."""
+import collections
+import ctypes as C
 import functools
 import os
 import re
@@ -9,7 +12,7 @@ import re
 import numpy as np
 
 import support as T
-from terminalraytracer_amd import host
+from terminalraytracer_amd import hip, host
 from terminalraytracer_amd import scenes as S
 
 DEFAULT = -2   # a cell painted after "\033[0m": the terminal's own background
@@ -174,3 +177,138 @@ def moved_scene(sc):
     spheres = sc.spheres.copy()
     spheres[0, 1] += 0.5
     return sc.with_spheres(spheres)
+
+
+# ---- the GPU tests' harness, for both kinds of cell ----
+
+GUARD = 64
+SENTINEL = 0x5A5A5A5A5A5A5A5A
+W, HEIGHT, B, SPP = 160, 48, 4, 10
+
+
+def fresh_context():
+    """the body of a test module's `ctx` fixture"""
+    c = hip.Context(0)
+    yield c
+    c.close()
+
+
+def restore_defaults(request):
+    """the body of a test module's autouse fixture: after a test that used `ctx`, the production kernel and no shown frame"""
+    yield
+    if "ctx" in request.fixturenames:
+        c = request.getfixturevalue("ctx")
+        c.set_kernel(hip.Context.PRODUCTION)
+        c.ansi_delta_reset()
+
+
+class Room:
+    """`capacity` bytes of device memory `offset` bytes behind an 8-aligned address, filled with 0xA5 and with GUARD such bytes either side, and a
+    uint64 on the device for the text's length"""
+
+    def __init__(self, capacity, offset=0):
+        import torch
+        self.capacity, self.start = capacity, GUARD + offset
+        self.buf = torch.full((GUARD + 8 + capacity + GUARD,), 0xA5, dtype=torch.uint8, device="cuda:0")
+        self.length = torch.full((1,), SENTINEL, dtype=torch.int64, device="cuda:0")
+        assert self.buf.data_ptr() % 8 == 0 and self.length.data_ptr() % 8 == 0
+        torch.cuda.synchronize()  # the fills are on torch's stream, the kernels on the context's
+
+    @property
+    def ptr(self):
+        return self.buf.data_ptr() + self.start
+
+    @property
+    def length_ptr(self):
+        return self.length.data_ptr()
+
+    def untouched(self, ctx):
+        ctx.synchronize()
+        return int(self.length.cpu()[0]) == SENTINEL and bool((self.buf == 0xA5).all().cpu())
+
+    def text(self, ctx, what=""):
+        """the text, once every byte in front of it, behind its length and behind its room has been seen unchanged"""
+        ctx.synchronize()
+        n = int(self.length.cpu()[0])
+        assert 0 <= n <= self.capacity, f"{what}: a length of {n} in a room of {self.capacity}"
+        got = self.buf.cpu().numpy()
+        outside = np.concatenate([got[:self.start], got[self.start + n:]])
+        assert (outside == 0xA5).all(), f"{what}: {int((outside != 0xA5).sum())} bytes outside the text's {n} were written"
+        return got[self.start:self.start + n].copy()
+
+
+def same_text(got, want, what):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.dtype == np.uint8 and got.size == want.size, f"{what}: {got.size} bytes for {want.size}"
+    wrong = got != want
+    if wrong.any():
+        at = int(np.argmax(wrong))
+        raise AssertionError(f"{what}: {int(wrong.sum())} of {wrong.size} bytes differ from the host's, the first at {at}: "
+                             f"{bytes(got[max(at - 8, 0):at + 8])!r} for {bytes(want[max(at - 8, 0):at + 8])!r}")
+
+
+def at_odd_address(frame, behind=None):
+    """the frame's bytes on the device, one byte behind an aligned address, followed directly by the bytes `behind` where given: (the
+    tensor that owns them, the frame's address)"""
+    import torch
+    tail = 0 if behind is None else behind.size
+    t = torch.zeros(frame.size + 1 + tail, dtype=torch.uint8, device="cuda:0")
+    t[1:1 + frame.size] = torch.from_numpy(np.ascontiguousarray(frame).reshape(-1)).to("cuda:0")
+    if tail:
+        t[1 + frame.size:] = torch.from_numpy(behind).to("cuda:0")
+    torch.cuda.synchronize()
+    return t, t.data_ptr() + 1
+
+
+def device_delta(ctx, from_rgb8, capacity, shown, nxt, offset=0, what="", trap=False):
+    """the text the formatting entry `from_rgb8` (a method of hip.Context) writes for the pair, both frames at odd addresses.  trap: a further
+    pixel row behind each frame, 0x00 behind `shown` and 0xFF behind `next` -- changed cells to a kernel that loaded it"""
+    rows, w, _ = shown.shape
+    a, pa = at_odd_address(shown, np.full(w * 3, 0x00, dtype=np.uint8) if trap else None)
+    b, pb = at_odd_address(nxt, np.full(w * 3, 0xFF, dtype=np.uint8) if trap else None)
+    room = Room(capacity(w, rows), offset)
+    from_rgb8(ctx, pa, pb, w, rows, room.ptr, room.capacity, room.length_ptr)
+    return room.text(ctx, what)
+
+
+def owned_rows(rows):
+    return hip.lib().trt_rowset_rows(C.byref(rows))
+
+
+def frames_of(scene_kind, indices, rows=None, b=B, h=HEIGHT):
+    out = [oracle_rgb(scene_kind, "synth", W, h, k, b, SPP) for k in indices]
+    if rows is not None:
+        owned = [hip.lib().trt_rowset_frame_row(C.byref(rows), i) for i in range(owned_rows(rows))]
+        out = [np.ascontiguousarray(f[owned]) for f in out]
+    return out
+
+
+def render_text(ctx, render, capacity, cam, rows, offset=0, what=""):
+    """the text the render entry `render` (a method of hip.Context) writes for the camera"""
+    room = Room(capacity(rows.width, owned_rows(rows)), offset)
+    render(ctx, cam, rows, B, SPP, room.ptr, room.capacity, room.length_ptr)
+    return room.text(ctx, what)
+
+
+def render_full(ctx, cam, rows, offset=0, what=""):
+    return render_text(ctx, hip.Context.render_device_ansi_delta, hip.ansi_delta_capacity, cam, rows, offset, what)
+
+
+# what a kind of cell supplies to check_sequence: the keyframe's text of a frame, the delta emitter of two, the terminal model, the render entry
+Kind = collections.namedtuple("Kind", "keyframe delta terminal render")
+FULL = Kind(full_text, host.emitter_delta_rgb8, Terminal, render_full)
+
+
+def check_sequence(kind, ctx, scene_kind, rows, indices=(0, 1, 2, 3), between=None, what="", h=HEIGHT):
+    """a keyframe, then deltas, of the Kind `kind` of cell over the scene `scene_kind`: the texts are the host's of the oracle's frames, and
+    the terminal shows every frame"""
+    cams = anim_cameras(indices, W, h)
+    frames = frames_of(scene_kind, indices, rows, h=h)
+    term = kind.terminal(W, frames[0].shape[0])
+    for k in range(len(indices)):
+        got = kind.render(ctx, cams[k], rows, offset=k % 4, what=f"{what} call {k}")
+        want = kind.keyframe(frames[0]) if k == 0 else kind.delta(frames[k - 1], frames[k])
+        same_text(got, want, f"{what} call {k}")
+        term.feed(got).shows(frames[k], f"{what} call {k}")
+        if between:
+            between(k)

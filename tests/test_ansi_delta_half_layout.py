@@ -1,7 +1,8 @@
 """The format of the delta text in half-block cells and the arithmetic the device kernels place its records by
 (csrc/trt_ansi_delta_half.h), without a GPU: the header the kernels compile is compiled for the host in tests/ansi_delta_half_check.c -- a
-program of its own, which assembles the text through the header the way the kernels go about it (a length per cell, a sum per tile, the
-exclusive scan of the tiles, the scan within a tile, the records' bytes by index) for every width 1..70 x rows 1..5, 160 x 47, 160 x 48 and
+program of its own, which assembles the text by calling the kernels' own lane walk (trt_delta_half_lane_cells, trt_delta_half_lane_byte)
+for every tile and every thread (the lanes' totals summed per tile, the exclusive scan of the tiles, each lane behind the lanes before
+it; tests/ansi_delta_check.h) for every width 1..70 x rows 1..5, 160 x 47, 160 x 48 and
 480 x 280 over eighteen families of frame pairs, and holds it against the sequential emitter trt_emitter_delta_half_rgb8
 (csrc/host/trt_emit.c), which does not use the header -- run plain and under the address and undefined-behaviour sanitizers.  The frames
 are allocated to the byte, so a read behind an odd frame's last row is the sanitizer's to report.  Nothing is loaded into Python."""

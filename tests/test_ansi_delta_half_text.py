@@ -1,5 +1,5 @@
 """The delta text in half-block cells written on the device (trt_ansi_delta_half_from_rgb8_device, trt_render_device_ansi_delta_half,
-trt_render_host_ansi_delta_half, trt_render_frame_ansi_delta_half; csrc/trt_ansi_delta_half.h, trt_ansi_delta_half.hpp): three kernels place
+trt_render_host_ansi_delta_half, trt_render_frame_ansi_delta_half; csrc/trt_ansi_delta_half.h, trt_ansi_delta.hpp): three kernels place
 every changed cell's record by a prefix sum over the text rows' cells.  The expected bytes never come from the device route: they are the
 sequential host statement host.emitter_delta_half_rgb8 of pattern frames or of consecutive T.oracle_rgb8 frames, keyframes
 host.emitter_half_rgb8's text, and a model of a terminal (ansi_delta_half_support.Terminal) must show every oracle frame after its text.
@@ -12,97 +12,26 @@ import pytest
 import ansi_delta_half_support as H
 import ansi_delta_support as D
 import support as T
+from ansi_delta_support import B, SPP, W, Room, at_odd_address, frames_of, same_text
+from ansi_delta_support import HEIGHT as H_
 from terminalraytracer_amd import hip, host
 
 pytestmark = pytest.mark.gpu
 ARGUMENT, NO_SCENE, CAPACITY = -2, -3, -4
-GUARD = 64
-SENTINEL = 0x5A5A5A5A5A5A5A5A
-W, H_, B, SPP = 160, 48, 4, 10
 
 
 @pytest.fixture(scope="module")
 def ctx():
-    c = hip.Context(0)
-    yield c
-    c.close()
+    yield from D.fresh_context()
 
 
 @pytest.fixture(autouse=True)
 def _defaults(request):
-    yield
-    if "ctx" in request.fixturenames:
-        c = request.getfixturevalue("ctx")
-        c.set_kernel(hip.Context.PRODUCTION)
-        c.ansi_delta_reset()
-
-
-class Room:
-    """`capacity` bytes of device memory `offset` bytes behind an 8-aligned address, filled with 0xA5 and with GUARD such bytes either side, and a
-    uint64 on the device for the text's length"""
-
-    def __init__(self, capacity, offset=0):
-        import torch
-        self.capacity, self.start = capacity, GUARD + offset
-        self.buf = torch.full((GUARD + 8 + capacity + GUARD,), 0xA5, dtype=torch.uint8, device="cuda:0")
-        self.length = torch.full((1,), SENTINEL, dtype=torch.int64, device="cuda:0")
-        assert self.buf.data_ptr() % 8 == 0 and self.length.data_ptr() % 8 == 0
-        torch.cuda.synchronize()  # the fills are on torch's stream, the kernels on the context's
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + self.start
-
-    @property
-    def length_ptr(self):
-        return self.length.data_ptr()
-
-    def untouched(self, ctx):
-        ctx.synchronize()
-        return int(self.length.cpu()[0]) == SENTINEL and bool((self.buf == 0xA5).all().cpu())
-
-    def text(self, ctx, what=""):
-        """the text, once every byte in front of it, behind its length and behind its room has been seen unchanged"""
-        ctx.synchronize()
-        n = int(self.length.cpu()[0])
-        assert 0 <= n <= self.capacity, f"{what}: a length of {n} in a room of {self.capacity}"
-        got = self.buf.cpu().numpy()
-        outside = np.concatenate([got[:self.start], got[self.start + n:]])
-        assert (outside == 0xA5).all(), f"{what}: {int((outside != 0xA5).sum())} bytes outside the text's {n} were written"
-        return got[self.start:self.start + n].copy()
-
-
-def same_text(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == np.uint8 and got.size == want.size, f"{what}: {got.size} bytes for {want.size}"
-    wrong = got != want
-    if wrong.any():
-        at = int(np.argmax(wrong))
-        raise AssertionError(f"{what}: {int(wrong.sum())} of {wrong.size} bytes differ from the host's, the first at {at}: "
-                             f"{bytes(got[max(at - 8, 0):at + 8])!r} for {bytes(want[max(at - 8, 0):at + 8])!r}")
-
-
-def at_odd_address(frame, behind=None):
-    """the frame's bytes on the device, one byte behind an aligned address, followed directly by the bytes `behind` where given: (the
-    tensor that owns them, the frame's address)"""
-    import torch
-    tail = 0 if behind is None else behind.size
-    t = torch.zeros(frame.size + 1 + tail, dtype=torch.uint8, device="cuda:0")
-    t[1:1 + frame.size] = torch.from_numpy(np.ascontiguousarray(frame).reshape(-1)).to("cuda:0")
-    if tail:
-        t[1 + frame.size:] = torch.from_numpy(behind).to("cuda:0")
-    torch.cuda.synchronize()
-    return t, t.data_ptr() + 1
+    yield from D.restore_defaults(request)
 
 
 def device_delta(ctx, shown, nxt, offset=0, what="", trap=False):
-    """trap: a further pixel row behind each frame, 0x00 behind `shown` and 0xFF behind `next` -- changed cells to a kernel that loaded it"""
-    rows, w, _ = shown.shape
-    a, pa = at_odd_address(shown, np.full(w * 3, 0x00, dtype=np.uint8) if trap else None)
-    b, pb = at_odd_address(nxt, np.full(w * 3, 0xFF, dtype=np.uint8) if trap else None)
-    room = Room(hip.ansi_delta_half_capacity(w, rows), offset)
-    ctx.ansi_delta_half_from_rgb8(pa, pb, w, rows, room.ptr, room.capacity, room.length_ptr)
-    return room.text(ctx, what)
+    return D.device_delta(ctx, hip.Context.ansi_delta_half_from_rgb8, hip.ansi_delta_half_capacity, shown, nxt, offset, what, trap)
 
 
 # ---- 1. the formatting alone ----
@@ -179,42 +108,11 @@ def test_the_formatting_entry_refuses_before_it_enqueues(ctx):
 
 # ---- 2. the render entries ----
 
-def frames_of(kind, indices, rows=None, b=B, h=H_):
-    out = [D.oracle_rgb(kind, "synth", W, h, k, b, SPP) for k in indices]
-    if rows is not None:
-        owned = [hip.lib().trt_rowset_frame_row(C.byref(rows), i) for i in range(hip.lib().trt_rowset_rows(C.byref(rows)))]
-        out = [np.ascontiguousarray(f[owned]) for f in out]
-    return out
+render_half, render_full = H.render_half, D.render_full
 
 
-def owned_rows(rows):
-    return hip.lib().trt_rowset_rows(C.byref(rows))
-
-
-def render_half(ctx, cam, rows, offset=0, what=""):
-    room = Room(hip.ansi_delta_half_capacity(rows.width, owned_rows(rows)), offset)
-    ctx.render_device_ansi_delta_half(cam, rows, B, SPP, room.ptr, room.capacity, room.length_ptr)
-    return room.text(ctx, what)
-
-
-def render_full(ctx, cam, rows, offset=0, what=""):
-    room = Room(hip.ansi_delta_capacity(rows.width, owned_rows(rows)), offset)
-    ctx.render_device_ansi_delta(cam, rows, B, SPP, room.ptr, room.capacity, room.length_ptr)
-    return room.text(ctx, what)
-
-
-def check_sequence(ctx, kind, rows, indices=(0, 1, 2, 3), between=None, what="", h=H_):
-    """a keyframe, then deltas: the texts are the host's of the oracle's frames, and the terminal shows every frame"""
-    cams = D.anim_cameras(indices, W, h)
-    frames = frames_of(kind, indices, rows, h=h)
-    term = H.Terminal(W, frames[0].shape[0])
-    for k in range(len(indices)):
-        got = render_half(ctx, cams[k], rows, offset=k % 4, what=f"{what} call {k}")
-        want = host.emitter_half_rgb8(frames[0]) if k == 0 else host.emitter_delta_half_rgb8(frames[k - 1], frames[k])
-        same_text(got, want, f"{what} call {k}")
-        term.feed(got).shows(frames[k], f"{what} call {k}")
-        if between:
-            between(k)
+def check_sequence(ctx, scene_kind, rows, **more):
+    D.check_sequence(H.HALF, ctx, scene_kind, rows, **more)
 
 
 @pytest.mark.parametrize("kind", ["demo", "synth64"])
