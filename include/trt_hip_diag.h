@@ -50,6 +50,19 @@ int trt_path_family_code(trt_context *ctx, int kind, int sphere, const double *p
 long trt_read_path_tables(trt_context *ctx, const Camera *camera, unsigned long long *cells, size_t capacity_cells,
                           unsigned long long *pool, size_t capacity_pool, long info[8]);
 
+/* LEAN TWINS of the spheres' own families (csrc/trt_raygrid.h): a path ray that leaves sphere i outwards, (o - c_i).d >= 0 as the
+ * exact test itself forms it, reads its cell's list without entry i -- that test would answer "miss".  mode 1: on (the twins are
+ * built if the scene has none; not on tables shared with other contexts), 0: every look-up reads the full tables, exactly as
+ * without twins, -1 (default): on where tables and twins together stay within the budget that chooses the patches
+ * (trt_set_path_patches), and not for a scene that changes from call to call.  Frames and ray counts do not depend on it.
+ * Environment TRT_PATH_LEAN sets the default.  The getter: whether the next frame reads twins, and the bytes they take (part of
+ * trt_scene_info's table_bytes). */
+int trt_set_path_lean_lists(trt_context *ctx, int mode);
+int trt_get_path_lean_lists(trt_context *ctx, int *in_use, unsigned long long *twin_bytes);
+/* The twins' cells (N P * 6 * sphere_cells^2, in the order of the non-mirrored tables of trt_read_path_tables, whose pool their
+ * long lists point into).  Returns the number of cells copied, 0 when the scene has no twins, or a negative TRT_ERR_*. */
+long trt_read_path_lean_tables(trt_context *ctx, unsigned long long *cells, size_t capacity_cells);
+
 /* After trt_read_counters: the number of wave-level traces of the last counted frame in which some ray failed its table's
  * membership / range test and the whole wave swept the culling table instead (the slow path). */
 int trt_read_sweep_fallbacks(trt_context *ctx, unsigned long long *swept_traces);

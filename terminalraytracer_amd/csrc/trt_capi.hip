@@ -129,6 +129,7 @@ int upload_primitives(trt_context *ctx, const Scene *scene, bool per_call)
                       ctx->T->grids_built_for[2] == ctx->dirgrid_slabs && ctx->T->grids_built_for[3] == ctx->pointgrid_shells &&
                       ctx->T->path_built_for[0] == ctx->path_g_eye && ctx->T->path_built_for[1] == ctx->path_g_sph &&
                       ctx->T->path_built_for[2] == ctx->path_min_spheres && ctx->T->path_built_for[3] == ctx->path_patches &&
+                      ctx->T->path_built_for[4] == lean_lists_wanted(ctx) &&
                       !memcmp(ctx->T->ground_built, &scene->ground, sizeof ctx->T->ground_built);
     if (!same)
     {
@@ -227,6 +228,12 @@ static int init_context(trt_context *ctx)
         int mode = -1;
         if (sscanf(e, "%d", &mode) == 1 && mode >= -1 && mode <= 1)
             ctx->compaction = mode;
+    }
+    if (const char *e = getenv("TRT_PATH_LEAN"))
+    {
+        int mode = -1;
+        if (sscanf(e, "%d", &mode) == 1 && mode >= -1 && mode <= 1)
+            ctx->path_lean = mode;
     }
     HIP_TRY(ctx->own_stream.create());
     ctx->stream = ctx->own_stream;
@@ -365,7 +372,7 @@ extern "C" int trt_share_scene(trt_context *dst, trt_context *src)
     dst->dirgrid_cells = src->dirgrid_cells, dst->pointgrid_cells = src->pointgrid_cells;
     dst->dirgrid_slabs = src->dirgrid_slabs, dst->pointgrid_shells = src->pointgrid_shells;
     dst->path_g_eye = src->path_g_eye, dst->path_g_sph = src->path_g_sph, dst->path_min_spheres = src->path_min_spheres;
-    dst->path_patches = src->path_patches, dst->list_pool_cap = src->list_pool_cap;
+    dst->path_patches = src->path_patches, dst->list_pool_cap = src->list_pool_cap, dst->path_lean = src->path_lean;
     memcpy(dst->sky_faces, src->sky_faces, sizeof dst->sky_faces);
     dst->sky_dim = src->sky_dim;
     dst->sky_stamp = src->sky_stamp;
@@ -518,6 +525,51 @@ extern "C" int trt_set_path_patches(trt_context *ctx, int m)
     trt_cull_build(ctx->T->h_spheres.data(), n, trt::kCullGroup, table.data(), &cs);
     const int rc = build_tables(ctx, cs, ctx->scene.ground);
     return rc ? rc : refresh_occupancy(ctx);
+}
+
+extern "C" int trt_set_path_lean_lists(trt_context *ctx, int mode)
+{
+    if (!ctx || mode < -1 || mode > 1)
+        return fail(TRT_ERR_ARGUMENT, "lean lists %d", mode);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream)); // a frame in flight may still read the tables
+    const int before = ctx->path_lean;
+    ctx->path_lean = mode;
+    if (!ctx->have_scene)
+        return TRT_OK;
+    const int level = lean_lists_wanted(ctx);
+    if (level > ctx->T->path_built_for[4] && !ctx->T->lean_at)
+    { // the scene's tables were built without twins, and not because a setting as strong as this one found no room: build again
+        if (const int shared = refuse_if_shared(ctx, "trt_set_path_lean_lists"))
+        {
+            ctx->path_lean = before;
+            return shared;
+        }
+        const int n = (int)(ctx->T->h_spheres.size() / 9);
+        std::vector<float> table((size_t)trt_cull_padded(n, trt::kCullGroup) * 4 + 4);
+        trt_cull_scene cs;
+        trt_cull_build(ctx->T->h_spheres.data(), n, trt::kCullGroup, table.data(), &cs);
+        const int rc = build_tables(ctx, cs, ctx->scene.ground);
+        return rc ? rc : refresh_occupancy(ctx);
+    }
+    if (level > ctx->T->path_built_for[4])
+        ctx->T->path_built_for[4] = level; // the twins in place are what this setting would have built
+    apply_lean_lists(ctx); // which tables the look-up reads: nothing is built or freed
+    return TRT_OK;
+}
+
+extern "C" int trt_get_path_lean_lists(trt_context *ctx, int *in_use, unsigned long long *twin_bytes)
+{
+    if (!ctx)
+        return fail(TRT_ERR_ARGUMENT, "ctx is NULL");
+    const trt::GridView &g = ctx->grids;
+    if (in_use)
+        *in_use = g.path_enabled && g.lean_off != 0;
+    if (twin_bytes)
+        *twin_bytes = g.path_enabled && ctx->T->lean_at ? 8ull * (unsigned long long)ctx->T->h_spheres.size() / 9 * (unsigned long long)g.patch_count * 6ull *
+                                                              (unsigned long long)g.g_sph * (unsigned long long)g.g_sph
+                                                        : 0ull;
+    return TRT_OK;
 }
 
 extern "C" int trt_get_path_patches(trt_context *ctx, int *m, int *patches_per_sphere)

@@ -141,7 +141,8 @@ struct SceneTables
     DeviceBuffer<double> d_sphere_fam;         // per sphere {mirror centre, |r|}: what the render kernel keeps in LDS
     DeviceBuffer<double> d_patch_rec;          // per patch {t, rho, mirrored t, rho}: likewise
     DeviceBuffer<uint32_t> d_sky;
-    int path_built_for[4] = {-1, -1, -1, -2};
+    int path_built_for[5] = {-1, -1, -1, -2, -1}; // [4]: lean_lists_wanted() at the time
+    size_t lean_at = 0;                            // cell of d_path_lists at which the lean twins of the own families start; 0: there are none
     int grids_built_for[4] = {-1, -1, -1, -1};
     size_t pool_scene_words = 0, pool_eye_words = 0; // capacities: the scene's part of d_pool, then kEyeSlots parts of pool_eye_words
     trt_cull_scene cull_scene{};                      // of the spheres the tables were built from
@@ -175,6 +176,7 @@ struct trt_context
     int path_g_eye = TRT_PATHGRID_EYE, path_g_sph = TRT_PATHGRID_SPHERE; // 0 = no path tables (every path ray sweeps)
     int path_min_spheres = TRT_PATHGRID_MIN_SPHERES;                      // scenes with fewer spheres sweep
     int path_patches = TRT_PATHGRID_PATCHES;                              // m of the spheres' sub-families; -1: by the number of spheres
+    int path_lean = -1;                                                   // trt_set_path_lean_lists: 0 off, 1 on, -1 (default) on within the tables' budget
     size_t list_pool_cap = 0;                                             // trt_set_list_pool_words: cap on the scene's part of the pool (0 = automatic)
     // project_scene is a pure function of *scene (TRT.c:966): a caller of the drop-in entries may move a sphere before every call.
     // The drop-in layer counts consecutive calls whose primitives differ from the call before; from the second on the scene
@@ -330,6 +332,8 @@ int refuse_if_shared(const trt_context *ctx, const char *what);
 extern int g_moving_after, g_still_after; // trt_set_scene_policy
 // ---- defined in trt_tables.hip
 int patches_for(const trt_context *ctx, int n);
+int lean_lists_wanted(const trt_context *ctx);
+void apply_lean_lists(trt_context *ctx);
 int build_tables(trt_context *ctx, const trt_cull_scene &cs, const double *ground);
 // the tables of `camera`'s eye in eye slot `slot` (-1: the context's own, eye_slot) and the slot's families, built on `stream` unless they hold
 int ensure_eye_tables(trt_context *ctx, const Camera *camera, hipStream_t stream, int slot = -1);

@@ -117,6 +117,25 @@ extern "C" long trt_read_path_tables(trt_context *ctx, const Camera *camera, uns
     return (long)total;
 }
 
+extern "C" long trt_read_path_lean_tables(trt_context *ctx, unsigned long long *cells, size_t capacity_cells)
+{
+    if (!ctx || !cells)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (!ctx->have_scene)
+        return fail(TRT_ERR_NO_SCENE, "no scene");
+    const trt::GridView &g = ctx->grids;
+    if (!g.path_enabled || !ctx->T->lean_at)
+        return 0;
+    const size_t total = ctx->T->h_spheres.size() / 9 * (size_t)g.patch_count * 6 * (size_t)g.g_sph * g.g_sph;
+    if (capacity_cells < total)
+        return fail(TRT_ERR_CAPACITY, "the twins have %zu cells", total);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (total)
+        HIP_TRY(hipMemcpy(cells, ctx->T->d_path_lists.ptr + ctx->T->lean_at, total * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return (long)total;
+}
+
 extern "C" long trt_read_light_grid(trt_context *ctx, int point_light, int index, unsigned long long *masks, size_t capacity_words)
 {
     if (!ctx || !masks || index < 0)

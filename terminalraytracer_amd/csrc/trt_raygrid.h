@@ -417,6 +417,61 @@ TRT_HD int trt_list_entry(unsigned long long cell, const unsigned long long *poo
     return (int)((cell >> (bits * k)) & emask);
 }
 
+/* ---- LEAN TWINS of a sphere's own families ----
+ * A path ray that starts on sphere i is looked up in a family of sphere i, and sphere i sits in every cell of its own families
+ * (s >= 0.7 above).  Its exact test is decided beforehand whenever the ray leaves the surface outwards: the test forms
+ * b = 2 (o - c_i).d and answers "miss" for every b >= 0 (TRT.c:657-659).  The kernel forms that very dot product from the very
+ * operands of the exact test, and a lane whose value is >= 0 reads the LEAN TWIN of its cell instead: the same list without
+ * entry i.  Nothing is estimated: the sign that sends a lane to the twin is the sign that makes the exact test a miss.  Every
+ * other lane (a negative dot: probe rays aimed inwards, rays inside a refractor; NaN) reads the full table, which stays what
+ * it was.  Only the n P non-mirrored families have a twin: in a mirror family, or a family of the eye, no sphere is special.
+ *
+ * pool words a cell's twin takes: 0 when the twin is the cell itself (no list, `own` not in it) or fits inline */
+TRT_HD unsigned trt_list_lean_words(unsigned long long cell, const unsigned long long *pool, int own, int bits)
+{
+    const int count = trt_list_entries(cell);
+    for (int k = 0; k < count; k++)
+        if (trt_list_entry(cell, pool, k, bits) == own)
+            return trt_list_pool_words(count - 1, bits);
+    return 0u;
+}
+
+/* The twin of `cell`: its entries without `own`, ascending as they were, in the same width; inline when they fit, otherwise
+ * in trt_list_lean_words() words of `pool` from pool_offset on (the caller reserved them; has_room == 0: there were none, and
+ * the twin is the cell itself -- a longer list, still conservative).  A cell without a list or without `own` is its own twin. */
+TRT_HD unsigned long long trt_list_lean(unsigned long long cell, unsigned long long *pool, int own, int bits, int has_room, unsigned pool_offset)
+{
+    const int per = 64 / bits, inline_max = 56 / bits;
+    const int count = trt_list_entries(cell);
+    int at = -1;
+    for (int k = 0; k < count && at < 0; k++)
+        if (trt_list_entry(cell, pool, k, bits) == own)
+            at = k;
+    if (at < 0)
+        return cell;
+    const int left = count - 1;
+    if (left > inline_max && !has_room)
+        return cell;
+    unsigned long long cur = left <= inline_max ? (unsigned long long)left << 56 : 0ull;
+    int k = 0;
+    for (int j = 0; j < count; j++)
+    {
+        if (j == at)
+            continue;
+        cur |= (unsigned long long)(unsigned)trt_list_entry(cell, pool, j, bits) << (bits * (k % per));
+        if (++k % per == 0 && left > inline_max)
+        {
+            pool[pool_offset + (unsigned)(k / per) - 1u] = cur;
+            cur = 0;
+        }
+    }
+    if (left <= inline_max)
+        return cur;
+    if (k % per)
+        pool[pool_offset + (unsigned)(k / per)] = cur;
+    return ((unsigned long long)TRT_LIST_POOLED << 56) | ((unsigned long long)(unsigned)left << 32) | pool_offset;
+}
+
 /* ---- marking the cells ----
  * bit (cell, sphere) of a family's table = the cone / cell predicate of trt_lightgrid.h for the cell AND, when the table's side
  * is a multiple of TRT_FAMILY_TILE, the same predicate for the TILE the cell lies in -- cell (c / TILE, j / TILE) of the grid of

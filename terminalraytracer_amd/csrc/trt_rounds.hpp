@@ -79,6 +79,9 @@ struct GridView
     int g_eye, g_sph;
     int patch_m, patch_count; // cells per face side of the origin's cube map (0: one family per sphere), P
     unsigned eye_at, sph_at;
+    unsigned lean_off; // LEAN TWINS of the n P non-mirrored tables (trt_raygrid.h), in the same order, from cell sph_at + lean_off; 0: there are
+                       // none, or they are switched off (an offset, not a second base: a select between two kernel arguments is a load from a
+                       // private copy of them all)
     const unsigned long long *path_lists;
     const unsigned long long *pool;
     const double *sphere_fam; // per sphere: mirror image of the centre (3), then r_chk of the sphere's family (patch_m == 0) or |r|
@@ -586,7 +589,7 @@ TRT_DEV void point_light_search(const LdsImage &L, int n, d3 o, d3 d, bool activ
 // BATCH: the ray belongs to frame `frame` of a batch launch, whose eye families and tables it reads (0 and unused otherwise)
 template <bool BATCH = false>
 TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n, int fam, d3 o, d3 d, bool active, unsigned long long active_lanes,
-                                     unsigned long long &fallback_lanes, int frame = 0)
+                                     unsigned long long &fallback_lanes, int frame = 0, int inside = -1)
 {
     const bool in_family = fam >= 0;
     const unsigned long long family_lanes = lanes_with(in_family); // next to its compare: a vote on a compare of another block is a select and a compare again
@@ -608,14 +611,21 @@ TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n
     // trt_rayfamily_member, operation for operation (all four conditions evaluated: no branches between them)
     const d3 w = sub(o, apex);
     const d3 c = d3{w.y * d.z - w.z * d.y, w.z * d.x - w.x * d.z, w.x * d.y - w.y * d.x};
-    const bool near_line = dot(c, c) <= r_chk * r_chk, ahead = dot(w, d) >= -r_chk, in_range = dot(w, w) <= rg2;
+    const double along = dot(w, d);
+    const bool near_line = dot(c, c) <= r_chk * r_chk, ahead = along >= -r_chk, in_range = dot(w, w) <= rg2;
     const bool unit_dir = __builtin_fabs(dot(d, d) - 1.0) <= 9.094947017729282e-13;
     const bool member = near_line & ahead & in_range & unit_dir;
     const unsigned long long member_lanes = family_lanes & lanes_with(near_line) & lanes_with(ahead) & lanes_with(in_range) & lanes_with(unit_dir);
     const int g = of_eye ? G.g_eye : G.g_sph;
     const int at = trt_cubemap_cell((float)d.x, (float)d.y, (float)d.z, 0.5f * (float)g, (float)(g - 1), g);
     const unsigned eye_cells = 6u * (unsigned)G.g_eye * (unsigned)G.g_eye, sph_cells = 6u * (unsigned)G.g_sph * (unsigned)G.g_sph;
-    const unsigned base = of_eye ? G.eye_at + (BATCH ? 2u * (unsigned)frame + (unsigned)f : (unsigned)f) * eye_cells : G.sph_at + (unsigned)s * sph_cells;
+    // A ray of sphere i's own family that leaves the surface outwards reads the LEAN TWIN of its cell, the list without i
+    // (trt_raygrid.h): `along` is then dot(sub(o, c_i), d) of the very operands exact_step reads -- the same LDS record -- so
+    // b = 2 along there, and b >= 0 is that test's own "miss".  (The sphere a refracted ray travels inside of is met at the far
+    // root whatever b is: such a ray keeps the full list.)  NaN, a negative dot, every other family: the full table.
+    const bool outwards = f >= 2 && !mirrored && along >= 0.0 && i != inside;
+    const unsigned base = of_eye ? G.eye_at + (BATCH ? 2u * (unsigned)frame + (unsigned)f : (unsigned)f) * eye_cells
+                                 : G.sph_at + (outwards ? G.lean_off : 0u) + (unsigned)s * sph_cells;
     unsigned long long cell = 0;
     if (has && member)
         cell = G.path_lists[base + (unsigned)at];
@@ -633,7 +643,7 @@ TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n
 // range; a unit direction) or whose cell has no list: the caller then sweeps.
 template <bool BATCH = false>
 TRT_DEV unsigned long long path_cell_patches(const LdsImage &L, const GridView &G, int n, int &fam, d3 o, d3 d, bool active, unsigned long long active_lanes,
-                                             unsigned long long &fallback_lanes, int frame = 0)
+                                             unsigned long long &fallback_lanes, int frame = 0, int inside = -1)
 {
     const bool in_family = fam >= 0;
     const unsigned long long family_lanes = lanes_with(in_family); // next to its compare: a vote on a compare of another block is a select and a compare again
@@ -649,8 +659,8 @@ TRT_DEV unsigned long long path_cell_patches(const LdsImage &L, const GridView &
     const double *src = of_eye ? L.eye + (BATCH ? frame * (2 * TRT_RAYFAMILY_DOUBLES) : 0) + TRT_RAYFAMILY_DOUBLES * (f & 1) : (mirrored ? at_mirror : at_sphere);
     const d3 base_at = load3(src);
     // which patch of its sphere the ray starts on (FP32: the membership test below is what counts)
-    const int here = trt_cubemap_cell((float)(o.x - base_at.x), (float)(o.y - base_at.y), (float)(o.z - base_at.z), 0.5f * (float)G.patch_m,
-                                      (float)(G.patch_m - 1), G.patch_m);
+    const d3 from_base = sub(o, base_at);
+    const int here = trt_cubemap_cell((float)from_base.x, (float)from_base.y, (float)from_base.z, 0.5f * (float)G.patch_m, (float)(G.patch_m - 1), G.patch_m);
     const int k = mirrored ? code & ((1 << TRT_PATCH_SHIFT) - 1) : (of_eye ? 0 : here);
     fam = !has ? -1 : (f == 0 ? 1 : (!of_eye && !mirrored ? 2 + n + (((f - 2) << TRT_PATCH_SHIFT) | k) : -1)); // a ray without a family has no successor family either
     const double r_abs = of_eye ? 0.0 : at_mirror[3];
@@ -676,7 +686,11 @@ TRT_DEV unsigned long long path_cell_patches(const LdsImage &L, const GridView &
     const int at = trt_cubemap_cell((float)d.x, (float)d.y, (float)d.z, 0.5f * (float)g, (float)(g - 1), g);
     const unsigned eye_cells = 6u * (unsigned)G.g_eye * (unsigned)G.g_eye, sph_cells = 6u * (unsigned)G.g_sph * (unsigned)G.g_sph;
     const unsigned table = ((mirrored ? (unsigned)n : 0u) + (unsigned)i) * (unsigned)G.patch_count + (unsigned)k;
-    const unsigned base = of_eye ? G.eye_at + (BATCH ? 2u * (unsigned)frame + (unsigned)f : (unsigned)f) * eye_cells : G.sph_at + table * sph_cells;
+    // the LEAN TWIN for a ray that leaves its sphere outwards, as in path_cell: there the base point is the centre, from_base the
+    // exact test's o - c_i from the same LDS record, and the dot half its b
+    const bool outwards = !of_eye && !mirrored && dot(from_base, d) >= 0.0 && i != inside;
+    const unsigned base = of_eye ? G.eye_at + (BATCH ? 2u * (unsigned)frame + (unsigned)f : (unsigned)f) * eye_cells
+                                 : G.sph_at + (outwards ? G.lean_off : 0u) + table * sph_cells;
     unsigned long long cell = 0;
     if (has && member)
         cell = G.path_lists[base + (unsigned)at];
@@ -726,9 +740,9 @@ TRT_DEV PathHit path_stage(const LdsImage &L, const CullView &cull, const GridVi
     {
         unsigned long long fallback_lanes;
         if constexpr (PATCHES)
-            p_cell = path_cell_patches<BATCH>(L, grids, n, fam, o, d, alive, alive_lanes, fallback_lanes, frame); // fam: now what a reflection by the ground belongs to
+            p_cell = path_cell_patches<BATCH>(L, grids, n, fam, o, d, alive, alive_lanes, fallback_lanes, frame, REFRACT ? inside : -1); // fam: now what a reflection by the ground belongs to
         else
-            p_cell = path_cell<BATCH>(L, grids, n, fam, o, d, alive, alive_lanes, fallback_lanes, frame);
+            p_cell = path_cell<BATCH>(L, grids, n, fam, o, d, alive, alive_lanes, fallback_lanes, frame, REFRACT ? inside : -1);
         p_list = fallback_lanes == 0;
     }
     if (COUNT && !p_list)

@@ -41,19 +41,12 @@ __global__ void build_pointgrid_kernel(const trt_pointgrid_cone *cones, int n, i
     }
 }
 
-// Mask words of a table -> list cells (trt_raygrid.h).  Lists longer than seven entries take words from the pool; when
-// the pool's part is exhausted the cell says TRT_LIST_NONE and its rays sweep.
-// The counter has 64 bits: it keeps counting after the pool is exhausted (exhaustion is a normal mode: the cell then says "no
-// list" and its rays sweep), and a 32-bit one would wrap after 2^32 words' worth of requests and hand out words that earlier
-// cells already point to.
+// Where this lane's `need` words of the pool start.
 // Called by EVERY lane of a wave (`valid`: the lane has a cell): the lanes' requests are summed and the wave takes its words
 // with ONE atomic -- a request per cell on the one counter serialises in L2 (the eye's tables at 256 spheres: 49 152 cells
 // with pooled lists, ~0.1 ms of nothing but that).
-__device__ unsigned long long pack_cell(const unsigned long long *mask, int words, unsigned long long *pool, unsigned long long *pool_used,
-                                        unsigned pool_limit, int bits, bool valid = true)
+__device__ unsigned long long take_pool_words(unsigned need, unsigned long long *pool_used)
 {
-    const int count = valid ? trt_list_count(mask, words) : 0;
-    const unsigned need = valid ? trt_list_pool_words(count, bits) : 0u;
     const int lane = (int)(threadIdx.x & 63);
     unsigned upto = need; // inclusive prefix sum over the wave
 #pragma unroll
@@ -70,14 +63,44 @@ __device__ unsigned long long pack_cell(const unsigned long long *mask, int word
             base = atomicAdd(pool_used, (unsigned long long)total);
         base = __shfl(base, 63);
     }
+    return base + (upto - need);
+}
+
+// Mask words of a table -> list cells (trt_raygrid.h).  Lists longer than seven entries take words from the pool; when
+// the pool's part is exhausted the cell says TRT_LIST_NONE and its rays sweep.
+// The counter has 64 bits: it keeps counting after the pool is exhausted (exhaustion is a normal mode: the cell then says "no
+// list" and its rays sweep), and a 32-bit one would wrap after 2^32 words' worth of requests and hand out words that earlier
+// cells already point to.
+__device__ unsigned long long pack_cell(const unsigned long long *mask, int words, unsigned long long *pool, unsigned long long *pool_used,
+                                        unsigned pool_limit, int bits, bool valid = true)
+{
+    const int count = valid ? trt_list_count(mask, words) : 0;
+    const unsigned need = valid ? trt_list_pool_words(count, bits) : 0u;
+    const unsigned long long at = take_pool_words(need, pool_used);
     if (!valid)
         return 0ull;
     if (need == 0)
         return trt_list_pack(mask, words, count, nullptr, 0u, bits);
-    const unsigned long long at = base + (upto - need);
     if (count > 0xffff || at + need > (unsigned long long)pool_limit)
         return (unsigned long long)TRT_LIST_NONE << 56;
     return trt_list_pack(mask, words, count, pool, (unsigned)at, bits);
+}
+
+// Lean twins of the spheres' own families (trt_raygrid.h): a thread per cell of the n P non-mirrored tables, which start at `full`
+// (P tables per sphere, `table_cells` cells each); the twins go to `lean` in the same order.  A twin that is still a long list takes
+// its words from the scene's part of the pool like any list; without room it is a copy of the full cell.
+__global__ __launch_bounds__(256) void build_lean_lists_kernel(const unsigned long long *full, unsigned long long *lean, unsigned long long cells,
+                                                               unsigned table_cells, unsigned tables_per_sphere, unsigned long long *pool,
+                                                               unsigned long long *pool_used, unsigned pool_limit, int bits)
+{
+    const unsigned long long at_cell = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool valid = at_cell < cells;
+    const unsigned long long cell = valid ? full[at_cell] : 0ull;
+    const int own = (int)(at_cell / table_cells / tables_per_sphere);
+    const unsigned need = valid ? trt_list_lean_words(cell, pool, own, bits) : 0u;
+    const unsigned long long at = take_pool_words(need, pool_used);
+    if (valid)
+        lean[at_cell] = trt_list_lean(cell, pool, own, bits, at + need <= (unsigned long long)pool_limit, (unsigned)at);
 }
 
 __global__ void set_pool_counter_kernel(unsigned long long *counter, unsigned long long value) { *counter = value; }
@@ -319,6 +342,29 @@ int patches_for(const trt_context *ctx, int n)
     return m;
 }
 
+// Does the scene get lean twins of its own families' tables (trt_raygrid.h; trt_set_path_lean_lists)?  0: no.  2: yes (mode 1).  1 (mode -1,
+// the default): yes where tables and twins together stay within the budget that chooses the patches -- twins are half as many cells
+// again -- and the scene does not change from call to call (patches_for): twins of tables that live for one frame cost more than they save.
+int lean_lists_wanted(const trt_context *ctx) { return ctx->path_lean > 0 ? 2 : (ctx->path_lean < 0 && !ctx->moving_scene ? 1 : 0); }
+
+// ... and is there room: where the twins would pass the 2^32 cells a look-up can address the scene goes without, by default also
+// where they outgrow the budget.  `families`: 2 n P tables of `sph_cells` cells behind the `eye_part` cells of the eye's tables.
+static bool builds_lean_lists(const trt_context *ctx, size_t families, size_t sph_cells, size_t eye_part)
+{
+    const size_t with_twins = (families + families / 2) * sph_cells;
+    return lean_lists_wanted(ctx) && eye_part + with_twins < 0xffffffffull &&
+           (lean_lists_wanted(ctx) > 1 || (unsigned long long)with_twins * 12ull <= kAutoPatchBudgetBytes);
+}
+
+// Which tables a lane that leaves its sphere outwards reads: the twins if the scene has them and the switch is on, else the
+// full tables (the look-up knows no difference: an offset that is zero or not).
+void apply_lean_lists(trt_context *ctx)
+{
+    trt::GridView &g = ctx->grids;
+    const bool on = ctx->T->lean_at != 0 && ctx->path_lean != 0;
+    g.lean_off = on ? (unsigned)ctx->T->lean_at - g.sph_at : 0u;
+}
+
 // Direction tables of the 2NP families of the spheres of the path rays (trt_raygrid.h: P patches per sphere and their mirror
 // images); the two families of the eye follow per camera (ensure_eye_tables).  The host places the families (O(NP)), the
 // device forms the cones and marks and packs the cells.
@@ -333,6 +379,9 @@ static int build_path_tables(trt_context *ctx, const trt_cull_scene &cs, const d
     ctx->T->path_built_for[1] = ctx->path_g_sph;
     ctx->T->path_built_for[2] = ctx->path_min_spheres;
     ctx->T->path_built_for[3] = ctx->path_patches;
+    ctx->T->path_built_for[4] = lean_lists_wanted(ctx);
+    ctx->T->lean_at = 0;
+    g.lean_off = 0;
     ctx->T->cull_scene = cs;
     memcpy(ctx->T->ground_built, ground, sizeof ctx->T->ground_built);
     const int ge = ctx->path_g_eye, gs = ctx->path_g_sph;
@@ -343,13 +392,16 @@ static int build_path_tables(trt_context *ctx, const trt_cull_scene &cs, const d
     const size_t P = (size_t)patches.count, families = 2 * (size_t)n * P;
     const size_t eye_cells = 6 * (size_t)ge * ge, sph_cells = 6 * (size_t)gs * gs;
     const size_t eye_part = (size_t)kEyeSlots * 2 * eye_cells; // the eye's two tables of every slot first
+    // the lean twins of the n P non-mirrored families (trt_raygrid.h) follow the 2 n P tables; they are no part of what trt_read_path_tables reports
+    const bool lean = builds_lean_lists(ctx, families, sph_cells, eye_part);
+    const size_t lean_cells = lean ? families / 2 * sph_cells : 0;
     if (eye_part + families * sph_cells >= 0xffffffffull)
         return fail(TRT_ERR_CAPACITY, "path tables of %zu families x %zu cells", families, sph_cells);
-    HIP_TRY(ctx->T->d_path_lists.reserve(eye_part + families * sph_cells));
+    HIP_TRY(ctx->T->d_path_lists.reserve(eye_part + families * sph_cells + lean_cells));
     // A cell that no builder has written must not look like a list: 0xFF.. is TRT_LIST_NONE ("no list": the ray's wave sweeps),
     // whereas the bytes hipMalloc hands out could read as a pooled list at any offset of the pool -- a wild read in the render
     // kernel (round 4's "nopack" experiment).  Every cell IS written before a kernel reads it; this is the belt.
-    HIP_TRY(hipMemsetAsync(ctx->T->d_path_lists.ptr, 0xFF, (eye_part + families * sph_cells) * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->T->d_path_lists.ptr, 0xFF, (eye_part + families * sph_cells + lean_cells) * sizeof(unsigned long long), ctx->stream));
     HIP_TRY(ctx->T->d_families.reserve(std::max<size_t>(families, 1)));
     HIP_TRY(ctx->T->d_sphere_fam.reserve(4 * (size_t)std::max(n, 1)));
     HIP_TRY(ctx->T->d_patch_rec.reserve(P * TRT_PATCH_RECORD));
@@ -371,6 +423,14 @@ static int build_path_tables(trt_context *ctx, const trt_cull_scene &cs, const d
                                   ctx->T->d_path_lists.ptr + eye_part + first * sph_cells, ctx->T->d_pool.ptr, ctx->T->d_pool_used.ptr, (unsigned)ctx->T->pool_scene_words,
                                   kSceneTilesPerBlock);
         }
+        if (lean_cells)
+        {
+            unsigned long long *const full = ctx->T->d_path_lists.ptr + eye_part;
+            hipLaunchKernelGGL(build_lean_lists_kernel, dim3((unsigned)((lean_cells + 255) / 256)), dim3(256), 0, ctx->stream, full, full + families * sph_cells,
+                               (unsigned long long)lean_cells, (unsigned)sph_cells, (unsigned)P, ctx->T->d_pool.ptr, ctx->T->d_pool_used.ptr,
+                               (unsigned)ctx->T->pool_scene_words, g.list_bits);
+            ctx->T->lean_at = eye_part + families * sph_cells;
+        }
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
@@ -387,6 +447,7 @@ static int build_path_tables(trt_context *ctx, const trt_cull_scene &cs, const d
     g.g_eye = ge;
     g.g_sph = gs;
     g.path_enabled = 1;
+    apply_lean_lists(ctx);
     return TRT_OK;
 }
 
@@ -403,7 +464,10 @@ int build_tables(trt_context *ctx, const trt_cull_scene &cs, const double *groun
     const int m = patches_for(ctx, (int)n);
     const size_t sphere_cells = 2 * n * (m ? 6 * (size_t)m * m : 1) * 6 * gs * gs;
     // (scenes of more than 256 spheres: 16-bit entries, a long list takes twice the words; beyond TRT_PATH_MAX_SPHERES no sphere families)
-    const size_t wide = n > TRT_LIST_MAX_SPHERES ? 2 : 1, sphere_part = n > TRT_PATH_MAX_SPHERES ? 0 : (m ? sphere_cells / 2 : sphere_cells);
+    // (the lean twins of the non-mirrored half, where they are built, are sized like the tables they thin)
+    const bool twins = builds_lean_lists(ctx, 2 * n * (m ? 6 * (size_t)m * m : 1), 6 * gs * gs, (size_t)kEyeSlots * 2 * 6 * ge * ge);
+    const size_t with_twins = twins ? sphere_cells + sphere_cells / 2 : sphere_cells;
+    const size_t wide = n > TRT_LIST_MAX_SPHERES ? 2 : 1, sphere_part = n > TRT_PATH_MAX_SPHERES ? 0 : (m ? with_twins / 2 : with_twins);
     ctx->T->pool_scene_words = std::max<size_t>(1024, wide * (nd * sd * gd * gd + np * 6 * sp * gp * gp + sphere_part));
     // The eye's two tables are rebuilt for every camera, on the frame's stream: nobody can look at their counter and grow their part
     // afterwards, so it holds the longest lists there can be -- every sphere in every cell, up to 64 words (512 / 256 entries) a cell.

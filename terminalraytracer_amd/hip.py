@@ -122,6 +122,9 @@ SYMBOLS = {
     "trt_set_scratch_fill": (_I, [_VP, _I]),
     "trt_default_context": (_VP, []),
     "trt_build_counts": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "trt_set_path_lean_lists": (_I, [_VP, _I]),
+    "trt_get_path_lean_lists": (_I, [_VP, C.POINTER(_I), C.POINTER(C.c_ulonglong)]),
+    "trt_read_path_lean_tables": (C.c_long, [_VP, _VP, C.c_size_t]),
     "trt_read_path_tables": (C.c_long, [_VP, C.POINTER(L.Camera), _VP, C.c_size_t, _VP, C.c_size_t, C.POINTER(C.c_long)]),
     "trt_read_sweep_fallbacks": (_I, [_VP, C.POINTER(C.c_ulonglong)]),
     "trt_read_shading_passes": (_I, [_VP, C.POINTER(C.c_ulonglong)]),
@@ -345,6 +348,26 @@ class Context:
             _check(int(got))
         keys = ("enabled", "eye_cells", "sphere_cells", "spheres", "cells", "pool_used_scene", "pool_used_eye", "pool_capacity")
         return dict(zip(keys, [int(x) for x in info])), cells[:got], pool
+
+    def set_path_lean_lists(self, mode):
+        """lean twins of the spheres' own families: 1 on, 0 off (the full tables, as without twins), -1 the default: on within the tables' budget
+        (trt_set_path_lean_lists)"""
+        _check(lib().trt_set_path_lean_lists(self._h, mode))
+
+    def path_lean_lists(self):
+        """{"in_use": bool, "twin_bytes": int} (trt_get_path_lean_lists)"""
+        u, b = _I(), C.c_ulonglong()
+        _check(lib().trt_get_path_lean_lists(self._h, C.byref(u), C.byref(b)))
+        return {"in_use": bool(u.value), "twin_bytes": b.value}
+
+    def read_path_lean_tables(self):
+        """the twins' list cells uint64[] (empty: the scene has none); their long lists are in read_path_tables()'s pool"""
+        n = self.path_lean_lists()["twin_bytes"] // 8
+        cells = np.zeros(max(1, n), dtype=np.uint64)
+        got = lib().trt_read_path_lean_tables(self._h, cells.ctypes.data, cells.size)
+        if got < 0:
+            _check(int(got))
+        return cells[:got]
 
     def set_refraction(self, ior=None):
         """EXTENSION, parity unpinned: per-sphere indices of refraction (0 = opaque); None turns it off (trt_set_refraction)"""
