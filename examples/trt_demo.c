@@ -3,6 +3,7 @@
  * the drop-in project_scene(), and the ANSI emitter stays on the host.
  *
  *   trt_demo <skybox-directory> [frames=0 (until Ctrl-C)] [width=160] [height=48] [--no-draw] [--rgb8] [--ansi] [--half] [--delta] [--step=SECONDS]
+ *            [--batch=N]
  *
  * --rgb8: the frame crosses PCIe as the 3 bytes per pixel the emitter makes of it (trt_render_frame_rgb8: the (int)(c*255) of
  * TRT.c:1157-1163 done on the device) instead of as 24-byte doubles; what reaches the terminal is the same.
@@ -17,6 +18,9 @@
  * --half --delta: the same in half-block cells (trt_render_frame_ansi_delta_half): frame 0 arrives as --half's whole text, every later frame
  * as the records of the one-column cells either of whose two pixels changed.
  * --step=SECONDS: frame k is rendered at orbit time k * SECONDS instead of at the wall clock's (a replay: the same frames every run).
+ * --batch=N, with --delta (or --half --delta) and --step=: the replay rendered ahead, N cameras per call, through a context of the program's
+ * own (trt_render_host_batch_ansi_delta, trt_render_host_batch_ansi_delta_half): one render and three text kernels per N frames, two
+ * transfers for their N texts, which are written frame by frame.  What reaches the terminal is byte for byte what --delta alone sends.
  *
  * The scene literals are the reference's (TRT.c:1256-1288). */
 #include <signal.h>
@@ -45,12 +49,12 @@ int main(int argc, char **argv)
 {
     if (argc < 2)
     {
-        fprintf(stderr, "usage: %s <skybox-directory> [frames] [width] [height] [--no-draw] [--rgb8] [--ansi] [--half] [--delta] [--step=SECONDS]\n", argv[0]);
+        fprintf(stderr, "usage: %s <skybox-directory> [frames] [width] [height] [--no-draw] [--rgb8] [--ansi] [--half] [--delta] [--step=SECONDS] [--batch=N]\n", argv[0]);
         return 2;
     }
     const long frames = argc > 2 ? atol(argv[2]) : 0;
     const int width = argc > 3 ? atoi(argv[3]) : 160, height = argc > 4 ? atoi(argv[4]) : 48;
-    int draw = 1, bytes_only = 0, text_only = 0, delta = 0, half = 0;
+    int draw = 1, bytes_only = 0, text_only = 0, delta = 0, half = 0, batch = 0;
     double step = -1.0;
     for (int i = 5; i < argc; i++)
     {
@@ -66,6 +70,13 @@ int main(int argc, char **argv)
             text_only = delta = 1;
         else if (strncmp(argv[i], "--step=", 7) == 0)
             step = atof(argv[i] + 7);
+        else if (strncmp(argv[i], "--batch=", 8) == 0)
+            batch = atoi(argv[i] + 8);
+    }
+    if (batch && (batch < 1 || batch > TRT_BATCH_MAX || !delta || step < 0.0))
+    {
+        fprintf(stderr, "--batch=N renders a replay ahead: 1 <= N <= %d, with --delta and --step=SECONDS\n", TRT_BATCH_MAX);
+        return 2;
     }
 
     Skybox sky;
@@ -101,7 +112,7 @@ int main(int argc, char **argv)
 
     Screen screen = {(Vector *)malloc(sizeof(Vector) * (size_t)width * height), width, height};
     unsigned char *rgb = (unsigned char *)malloc((size_t)width * height * 3);
-    const size_t text_room = delta  ? (half ? trt_ansi_delta_half_capacity(width, height) : trt_ansi_delta_capacity(width, height))
+    const size_t text_room = delta  ? (size_t)(batch ? batch : 1) * (half ? trt_ansi_delta_half_capacity(width, height) : trt_ansi_delta_capacity(width, height))
                              : half ? trt_ansi_half_bytes(width, height)
                                     : trt_ansi_bytes(width, height);
     size_t text_bytes = text_room, written_bytes = 0;
@@ -110,12 +121,52 @@ int main(int argc, char **argv)
     if (!screen.pixels || !rgb || !text || (!text_only && trt_emitter_create(width, height, &emitter) != TRT_HOST_OK))
         return 1;
 
+    /* --batch: a context of the program's own, the scene handed over once; the cameras of a batch and the lengths of their texts */
+    trt_context *ctx = NULL;
+    const trt_rowset whole = {width, height, height, 0, 1};
+    Camera cameras[TRT_BATCH_MAX];
+    size_t batch_bytes[TRT_BATCH_MAX];
+    if (batch && (trt_create(0, &ctx) != TRT_OK || trt_set_scene(ctx, &scene) != TRT_OK))
+    {
+        fprintf(stderr, "trt_create / trt_set_scene: %s\n", trt_last_error());
+        return 1;
+    }
+
     signal(SIGINT, on_sigint);
     struct timespec start;
     timespec_get(&start, TIME_UTC);
     double producer_seconds = 0.0, first_call_seconds = 0.0;
     long frame = 0;
-    for (; !stop_requested && (frames == 0 || frame < frames); frame++)
+    while (batch && !stop_requested && (frames == 0 || frame < frames))
+    { /* the next `n` frames of the replay in one call, their texts back to back */
+        const int n = frames == 0 || frames - frame > batch ? batch : (int)(frames - frame);
+        for (int b = 0; b < n; b++)
+        {
+            trt_orbit_camera(&scene.camera, step * (double)(frame + b));
+            cameras[b] = scene.camera;
+        }
+        const double before = seconds_since(&start);
+        if ((half ? trt_render_host_batch_ansi_delta_half : trt_render_host_batch_ansi_delta)(ctx, cameras, n, &whole, TRT_REF_BOUNCE_LIMIT, TRT_REF_RAYS_PER_PIXEL, text,
+                                                                                           text_room, batch_bytes) != TRT_OK)
+        {
+            fprintf(stderr, "trt_render_host_batch_ansi_delta%s: %s\n", half ? "_half" : "", trt_last_error());
+            return 1;
+        }
+        if (frame == 0) /* as below: initialisation is in the first call, which here is a whole batch */
+            first_call_seconds = seconds_since(&start) - before;
+        else
+            producer_seconds += seconds_since(&start) - before;
+        size_t at = 0;
+        for (int b = 0; b < n; at += batch_bytes[b], b++)
+            if (draw)
+            {
+                written_bytes += fwrite(text + at, 1, batch_bytes[b], stdout);
+                fflush(stdout);
+            }
+        frame += n;
+    }
+    const long first_batch = batch && frame ? (frame < batch ? frame : batch) : 1; /* frames of the first call, which producer_seconds leaves out */
+    for (; !batch && !stop_requested && (frames == 0 || frame < frames); frame++)
     {
         const double t = seconds_since(&start);
         trt_orbit_camera(&scene.camera, step >= 0.0 ? step * (double)frame : t);
@@ -191,7 +242,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "\033[%d;1H\n%.02f fps, %zu bytes of text for %ld frames (%zu each as whole texts)\n", half ? (height + 1) / 2 : height,
                 (double)frame / seconds_since(&start), written_bytes, frame, half ? trt_ansi_half_bytes(width, height) : trt_ansi_bytes(width, height));
     fprintf(stderr, "%ld frames %dx%d, frame producer %.3f ms/frame after a first call of %.1f ms (host-in/host-out%s, 10 bounces, 10 rays per pixel)\n",
-            frame, width, height, frame > 1 ? 1e3 * producer_seconds / (frame - 1) : 0.0, 1e3 * first_call_seconds,
+            frame, width, height, frame > first_batch ? 1e3 * producer_seconds / (frame - first_batch) : 0.0, 1e3 * first_call_seconds,
             delta && half ? " as half-block delta text" : delta ? " as delta text" : half ? " as half-block text" : text_only ? " as text" : bytes_only ? " as RGB8" : "");
 
     trt_emitter_destroy(emitter);
@@ -199,6 +250,8 @@ int main(int argc, char **argv)
     free(rgb);
     free(text);
     trt_free_skybox(&sky);
+    if (ctx)
+        trt_destroy(ctx);
     trt_shutdown();
     return 0;
 }

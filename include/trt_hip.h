@@ -254,8 +254,9 @@ int trt_ansi_half_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int wid
  *   - it writes exactly the `bytes` bytes it is given, not the capacity;
  *   - a text it drops instead of writing is a frame the terminal never showed: call trt_ansi_delta_reset, the next text is a keyframe;
  *   - nothing else may be printed over the picture (a status line belongs on stderr or below the last row);
- *   - the refraction extension and the batch entries have no delta form; of a trt_dist_render_rgb8 gather rank 0 formats the
- *     assembled bytes with trt_ansi_delta_from_rgb8_device;
+ *   - the refraction extension has no delta form; the batch entries have one (trt_render_device_batch_ansi_delta, below the batch
+ *     entries); of a trt_dist_render_rgb8 gather rank 0 formats the assembled bytes with trt_ansi_delta_from_rgb8_device, several
+ *     gathered frames at once with trt_ansi_delta_chain_from_rgb8_device;
  *   - the records here are of two-column cells of the full text; the half-block text has a delta form of its own, below, and a
  *     context remembers which of the two its shown frame was sent as: changing over is a keyframe. */
 
@@ -312,7 +313,8 @@ int trt_ansi_delta_reset(trt_context *ctx);
  * T * (39 * width + 18) bytes, reached when every cell changed and both colours differ from the left neighbour's everywhere.  Limits:
  * width <= 99999, T <= 99999 (rows <= 199998).  csrc/trt_ansi_delta_half.h is the format in code, trt_emitter_delta_half_rgb8
  * (trt_host.h) its sequential statement on the host; the measured bytes and times are in profiles/r15/a_delta_half.md.  The rules for
- * the host are those of the delta text above.  There is no batch form and no refraction form. */
+ * the host are those of the delta text above.  The batch form stands with the full kind's, below the batch entries; there is no
+ * refraction form. */
 
 /* Room for any text the half-block delta entries write: max(trt_ansi_half_bytes, ((rows + 1) / 2) * (39 * width + 18)), the keyframe or
  * the longest delta; 0 when either size is not positive or above the limits. */
@@ -402,6 +404,53 @@ int trt_render_device_batch_ansi_half(trt_context *ctx, const Camera *cameras, i
 /* The same into HOST memory: text[b * trt_ansi_half_bytes(width, owned rows) ...] (synchronous; one copy-out through pinned staging). */
 int trt_render_host_batch_ansi_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
                                     int rays_per_pixel, char *text);
+
+/* ---- delta texts for a batch: n texts back to back, one prefix sum over all frames --------------------------------------------------
+ * A CHAIN is a shown frame and n frames of RGB8 bytes (rows x width x 3 each), 1 <= n <= TRT_BATCH_MAX.  Text b takes a terminal from
+ * frame b - 1 to frame b, for b = 0 from the shown frame; each is byte for byte the delta text of its two frames (above).  The texts
+ * stand back to back: text b starts at the sum of the lengths before it, a text of 0 bytes where the next one starts.  The per-frame
+ * cost of the one-frame entries -- three launches, two round trips -- is paid once per chain (csrc/trt_ansi_delta_chain.h states the
+ * chain in code; profiles/r18/a_delta_batch.md has the measurement). */
+
+/* The formatting alone: the shown frame at d_shown_rgb8, the n frames back to back at d_frames_rgb8 (frame stride rows * width * 3, no
+ * padding, any alignment), the n texts back to back at d_text (any alignment), their n lengths at d_bytes[0..n) -- a DEVICE address,
+ * 8-byte aligned.  THREE launches whatever n is: measure and write over the tiles of all n pairs of frames, one workgroup's scan
+ * over all their sums between them.  Every byte below the sum of the lengths is stored once, none at or behind it.  It neither reads nor
+ * changes the context's shown frame; it is what rank 0 applies to several gathered trt_dist_render_rgb8 frames.  capacity_bytes >=
+ * n * trt_ansi_delta_capacity(width, rows), else TRT_ERR_CAPACITY; NULL, n out of range or a size above the limits: TRT_ERR_ARGUMENT.
+ * Asynchronous on the context's stream. */
+int trt_ansi_delta_chain_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows,
+                                          void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+/* The same in half-block cells; capacity_bytes >= n * trt_ansi_delta_half_capacity(width, rows).  Behind an odd frame's last pixel row
+ * lies the next frame of the chain: it is not read as a lower row, the last text row's lower halves are black in every text. */
+int trt_ansi_delta_half_chain_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows,
+                                               void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+
+/* trt_render_device_batch_rgb8 into a buffer of the context -- one launch, a split for LDS or one launch per camera, as it decides;
+ * trt_batch_info reports the batch, trt_kernel_times counts one entry -- and the n frames' delta texts as one chain.  Text 0 is against
+ * the context's SHOWN frame, which the context has for exactly this rowset and this kind under the rules of
+ * trt_render_device_ansi_delta; if it has none, text 0 is the KEYFRAME, byte for byte trt_render_device_ansi's text, d_bytes[0] its
+ * length, and the chain of the other frames starts behind it.  Texts 1..n-1 are against the previous frame of the batch.  Afterwards
+ * frame n - 1 is the shown frame, of this rowset and this kind (one frame's bytes are copied): a later trt_render_*_ansi_delta call
+ * continues from it, and a batch continues from theirs.
+ * Errors before anything is enqueued, the shown frame kept: those of trt_render_device_batch_rgb8 (n > 1 on shared tables:
+ * TRT_ERR_CAPACITY) and of trt_render_device_ansi_delta, with capacity_bytes >= n * trt_ansi_delta_capacity(width, owned rows).  A
+ * failure behind that point forgets the shown frame.  Asynchronous on the context's stream; d_bytes: n lengths at a DEVICE address,
+ * 8-byte aligned. */
+int trt_render_device_batch_ansi_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                       int rays_per_pixel, void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+/* The same in half-block cells: the keyframe is trt_render_device_ansi_half's text, capacity_bytes >= n *
+ * trt_ansi_delta_half_capacity(width, owned rows). */
+int trt_render_device_batch_ansi_delta_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                            int rays_per_pixel, void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+/* Into HOST memory, synchronous: one transfer of the n lengths, then one of exactly their sum through the pinned staging.  bytes[b] is
+ * text b's length, the texts stand back to back at text; capacity_bytes counts the bytes at text, checked as above.  If a copy fails
+ * the shown frame is forgotten. */
+int trt_render_host_batch_ansi_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                     int rays_per_pixel, char *text, size_t capacity_bytes, size_t *bytes);
+int trt_render_host_batch_ansi_delta_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                          int rays_per_pixel, char *text, size_t capacity_bytes, size_t *bytes);
+
 /* The most recent batch call of this context: its frames, and how many render-kernel launches served them
  * (1 = one launch over all frames; n = one launch per camera; between: the batch was split for LDS). */
 int trt_batch_info(trt_context *ctx, int *frames, int *render_launches);

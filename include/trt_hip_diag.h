@@ -188,6 +188,13 @@ int trt_ansi_delta_kernel_times(trt_context *ctx, const void *d_shown_rgb8, cons
  * (tools/ansi_delta_half_bench.py). */
 int trt_ansi_delta_half_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
                                      size_t capacity_bytes, unsigned long long *d_bytes, float *ms);
+/* The same of trt_ansi_delta_chain_from_rgb8_device and trt_ansi_delta_half_chain_from_rgb8_device: ms[0] the measure kernel over the
+ * tiles of all n pairs of frames, ms[1] the one workgroup's scan of all their sums and the n lengths, ms[2] the write kernel.  Same
+ * arguments, same texts, same errors (tools/ansi_delta_batch_bench.py). */
+int trt_ansi_delta_chain_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows,
+                                      void *d_text, size_t capacity_bytes, unsigned long long *d_bytes, float *ms);
+int trt_ansi_delta_half_chain_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows,
+                                           void *d_text, size_t capacity_bytes, unsigned long long *d_bytes, float *ms);
 
 #ifdef __cplusplus
 }

@@ -15,9 +15,14 @@
 // Every byte below the length is stored once and none behind it.  The frames and the text may have any alignment: everything is
 // read and stored by bytes; the lower row of an odd frame's last half-block text row is NOT loaded -- behind the frame is somebody
 // else's memory.  LDS: the waves' sums, nothing else.
+//
+// A CHAIN of n texts (trt_ansi_delta_chain.h: a shown frame, n frames back to back, text b between frames b - 1 and b) is the same three
+// launches: measure and write on a grid of tiles x n, the pair in blockIdx.y, and one scan over all n * tiles sums, which also stores the n
+// lengths.  The texts stand back to back; the walks and the bodies are the ones above.
 #pragma once
 
 #include "trt_ansi_delta.h"
+#include "trt_ansi_delta_chain.h"
 #include "trt_ansi_delta_half.h"
 #include "trt_common.hpp"
 
@@ -125,16 +130,16 @@ __global__ __launch_bounds__(TRT_DELTA_BLOCK) void ansi_delta_half_write_kernel(
     delta_write<DeltaHalf>(shown, next, width, rows, tile_at, out, capacity);
 }
 
-// launched as ONE workgroup of TRT_DELTA_SCAN_BLOCK threads
-__global__ __launch_bounds__(TRT_DELTA_SCAN_BLOCK) void ansi_delta_offsets_kernel(const unsigned *tile_bytes, unsigned long long tiles, unsigned long long *tile_at,
-                                                                                 unsigned long long *text_bytes)
+// The exclusive scan of `count` sums into 64-bit offsets that start at `base`, by ONE workgroup of TRT_DELTA_SCAN_BLOCK threads:
+// TRT_DELTA_SCAN_BLOCK sums per turn with a running total, which every thread returns: base + all sums
+__device__ __forceinline__ unsigned long long delta_scan(const unsigned *tile_bytes, unsigned long long count, unsigned long long base, unsigned long long *tile_at)
 {
     __shared__ unsigned long long wave_bytes[TRT_DELTA_SCAN_BLOCK / 64];
     const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long running = 0;
-    for (unsigned long long first = 0; first < tiles; first += TRT_DELTA_SCAN_BLOCK)
+    unsigned long long running = base;
+    for (unsigned long long first = 0; first < count; first += TRT_DELTA_SCAN_BLOCK)
     {
-        const unsigned long long i = first + threadIdx.x, mine = i < tiles ? tile_bytes[i] : 0ull;
+        const unsigned long long i = first + threadIdx.x, mine = i < count ? tile_bytes[i] : 0ull;
         unsigned long long through = mine; // inclusive over the wave
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1)
@@ -153,13 +158,73 @@ __global__ __launch_bounds__(TRT_DELTA_SCAN_BLOCK) void ansi_delta_offsets_kerne
             before += w < wave ? wave_bytes[w] : 0ull;
             all += wave_bytes[w];
         }
-        if (i < tiles)
+        if (i < count)
             tile_at[i] = running + before + through - mine;
         running += all;
         __syncthreads(); // the next turn overwrites the waves' sums
     }
+    return running;
+}
+
+// launched as ONE workgroup of TRT_DELTA_SCAN_BLOCK threads
+__global__ __launch_bounds__(TRT_DELTA_SCAN_BLOCK) void ansi_delta_offsets_kernel(const unsigned *tile_bytes, unsigned long long tiles, unsigned long long *tile_at,
+                                                                                 unsigned long long *text_bytes)
+{
+    const unsigned long long running = delta_scan(tile_bytes, tiles, 0, tile_at);
     if (threadIdx.x == 0)
         *text_bytes = running;
+}
+
+// ---- a chain of n texts (trt_ansi_delta_chain.h): grids of dim3(tiles, n), blockIdx.y the pair; the bodies above, given the pair's two
+// frames and the pair's slice of the tile arrays.  `out` and `capacity` are the whole buffer's: the offsets are the chain's ----
+
+template <class Kind>
+__device__ __forceinline__ void delta_chain_measure(const unsigned char *shown, const unsigned char *frames, int width, int rows, unsigned *tile_bytes)
+{
+    const trt_delta_chain_pair pair = trt_delta_chain_frames(shown, frames, width, rows, blockIdx.y);
+    delta_measure<Kind>(pair.shown, pair.next, width, rows, tile_bytes + trt_delta_chain_tile(gridDim.x, blockIdx.y, 0));
+}
+
+template <class Kind>
+__device__ __forceinline__ void delta_chain_write(const unsigned char *shown, const unsigned char *frames, int width, int rows, const unsigned long long *tile_at,
+                                                  unsigned char *out, unsigned long long capacity)
+{
+    const trt_delta_chain_pair pair = trt_delta_chain_frames(shown, frames, width, rows, blockIdx.y);
+    delta_write<Kind>(pair.shown, pair.next, width, rows, tile_at + trt_delta_chain_tile(gridDim.x, blockIdx.y, 0), out, capacity);
+}
+
+__global__ __launch_bounds__(TRT_DELTA_BLOCK) void ansi_delta_chain_measure_kernel(const unsigned char *shown, const unsigned char *frames, int width, int rows,
+                                                                                  unsigned *tile_bytes)
+{
+    delta_chain_measure<DeltaFull>(shown, frames, width, rows, tile_bytes);
+}
+
+__global__ __launch_bounds__(TRT_DELTA_BLOCK) void ansi_delta_half_chain_measure_kernel(const unsigned char *shown, const unsigned char *frames, int width, int rows,
+                                                                                       unsigned *tile_bytes)
+{
+    delta_chain_measure<DeltaHalf>(shown, frames, width, rows, tile_bytes);
+}
+
+__global__ __launch_bounds__(TRT_DELTA_BLOCK) void ansi_delta_chain_write_kernel(const unsigned char *shown, const unsigned char *frames, int width, int rows,
+                                                                                const unsigned long long *tile_at, unsigned char *out, unsigned long long capacity)
+{
+    delta_chain_write<DeltaFull>(shown, frames, width, rows, tile_at, out, capacity);
+}
+
+__global__ __launch_bounds__(TRT_DELTA_BLOCK) void ansi_delta_half_chain_write_kernel(const unsigned char *shown, const unsigned char *frames, int width, int rows,
+                                                                                     const unsigned long long *tile_at, unsigned char *out, unsigned long long capacity)
+{
+    delta_chain_write<DeltaHalf>(shown, frames, width, rows, tile_at, out, capacity);
+}
+
+// ONE workgroup of TRT_DELTA_SCAN_BLOCK threads: the scan over all n * tiles sums from `base`, a frame's first tile anywhere in a turn,
+// then the n lengths, read from the offsets the workgroup itself has just stored
+__global__ __launch_bounds__(TRT_DELTA_SCAN_BLOCK) void ansi_delta_chain_offsets_kernel(const unsigned *tile_bytes, unsigned long long tiles, unsigned n, unsigned long long base,
+                                                                                       unsigned long long *tile_at, unsigned long long *text_bytes)
+{
+    const unsigned long long total = delta_scan(tile_bytes, n * tiles, base, tile_at);
+    if (threadIdx.x < n) // the barrier that closes the scan's last turn stands between the other threads' stores and these loads
+        text_bytes[threadIdx.x] = trt_delta_chain_text_bytes(tile_at, tiles, n, threadIdx.x, total);
 }
 
 // the length of a keyframe's text, which the host knows, to where the delta's length goes

@@ -217,6 +217,7 @@ struct trt_context
     DeviceBuffer<unsigned> d_delta_tile_bytes;         // per tile of cells: the bytes of its records
     DeviceBuffer<unsigned long long> d_delta_tile_at;  // ... and where they start in the text
     DeviceBuffer<unsigned long long> d_delta_bytes;    // trt_render_host_ansi_delta: the text's length before it crosses PCIe
+    DeviceBuffer<unsigned char> d_chain;               // trt_render_device_batch_ansi_delta: the batch's frames as RGB8 bytes, back to back
     int ior_count = 0;          // 0 = off (the reference's path)
     DeviceBuffer<unsigned long long> d_counters;
     DeviceBuffer<unsigned int> d_queue;

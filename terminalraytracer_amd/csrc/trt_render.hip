@@ -895,6 +895,15 @@ static int fit_batch(trt_context *ctx, long units_per_frame, int spp, int remain
     }
 }
 
+// a batch of more than one camera builds its eye tables in the slots of the context's own tables: shared tables have none to spare
+static int check_batch_tables(const trt_context *ctx, int n)
+{
+    if (n > 1 && ctx->T.use_count() > 1)
+        return fail(TRT_ERR_CAPACITY, "this context's scene tables are shared with %ld other context(s) (trt_share_scene): their eye slots are the sharers', "
+                                      "a batch of %d cameras has none to build its tables in (one camera per call works)", ctx->T.use_count() - 1, n);
+    return TRT_OK;
+}
+
 // frame b in `kind` at d_pixels + b * frame_bytes(kind, width, owned rows)
 static int render_device_batch(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_pixels,
                                size_t capacity_bytes, Output kind)
@@ -905,9 +914,9 @@ static int render_device_batch(trt_context *ctx, const Camera *cameras, int n, c
     const long pixels = (long)trt_rowset_rows(rows) * rows->width, units = pixels * rays_per_pixel;
     const size_t each = frame_bytes(kind, rows->width, trt_rowset_rows(rows));
     const bool shared = ctx->T.use_count() > 1;
-    if (n > 1 && shared)
-        return fail(TRT_ERR_CAPACITY, "this context's scene tables are shared with %ld other context(s) (trt_share_scene): their eye slots are the sharers', "
-                                      "a batch of %d cameras has none to build its tables in (one camera per call works)", ctx->T.use_count() - 1, n);
+    rc = check_batch_tables(ctx, n);
+    if (rc)
+        return rc;
     ctx->batch_frames = n;
     ctx->batch_launches = 0;
     if (pixels == 0)
@@ -1329,6 +1338,112 @@ extern "C" int trt_ansi_delta_half_kernel_times(trt_context *ctx, const void *d_
     return delta_kernel_times(ctx, true, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes, ms);
 }
 
+// ---- a chain of delta texts (trt_ansi_delta_chain.h): n texts back to back, three launches whatever n is ----
+
+static_assert(TRT_DELTA_CHAIN_MAX == TRT_BATCH_MAX, "a chain holds a batch's frames");
+
+// measure, offsets, write on `stream` for the pairs (d_shown, frame 0), (frame 0, frame 1) ... of the n frames at d_frames: text b at d_text +
+// base + the lengths before it, its length at d_bytes[b]; capacity_bytes: the bytes at d_text; marks as in launch_ansi_delta
+static int launch_ansi_delta_chain(trt_context *ctx, hipStream_t stream, bool half, const unsigned char *d_shown, const unsigned char *d_frames, int n, int width, int rows,
+                                   void *d_text, size_t capacity_bytes, unsigned long long base, unsigned long long *d_bytes, const Event *marks = nullptr)
+{
+    static const struct
+    {
+        void (*measure)(const unsigned char *, const unsigned char *, int, int, unsigned *);
+        void (*write)(const unsigned char *, const unsigned char *, int, int, const unsigned long long *, unsigned char *, unsigned long long);
+    } kernels[2] = {{trt::ansi_delta_chain_measure_kernel, trt::ansi_delta_chain_write_kernel}, {trt::ansi_delta_half_chain_measure_kernel, trt::ansi_delta_half_chain_write_kernel}};
+    const unsigned long long cells = (unsigned long long)width * (unsigned long long)(half ? trt_ansi_half_text_rows(rows) : rows), tiles = trt_delta_tiles(cells);
+    const size_t all = (size_t)tiles * (size_t)n;
+    if (ctx->d_delta_tile_bytes.capacity < all || ctx->d_delta_tile_at.capacity < all)
+        HIP_TRY(hipStreamSynchronize(stream)); // a text in flight may still use the old sums
+    HIP_TRY(ctx->d_delta_tile_bytes.reserve(all));
+    HIP_TRY(ctx->d_delta_tile_at.reserve(all));
+    const dim3 grid((unsigned)tiles, (unsigned)n);
+    if (marks)
+        HIP_TRY(hipEventRecord(marks[0], stream));
+    hipLaunchKernelGGL(kernels[half].measure, grid, dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_frames, width, rows, ctx->d_delta_tile_bytes.ptr);
+    if (marks)
+        HIP_TRY(hipEventRecord(marks[1], stream));
+    hipLaunchKernelGGL(trt::ansi_delta_chain_offsets_kernel, dim3(1), dim3(TRT_DELTA_SCAN_BLOCK), 0, stream, (const unsigned *)ctx->d_delta_tile_bytes.ptr, tiles, (unsigned)n,
+                       base, ctx->d_delta_tile_at.ptr, d_bytes);
+    if (marks)
+        HIP_TRY(hipEventRecord(marks[2], stream));
+    hipLaunchKernelGGL(kernels[half].write, grid, dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_frames, width, rows, (const unsigned long long *)ctx->d_delta_tile_at.ptr,
+                       (unsigned char *)d_text, (unsigned long long)capacity_bytes);
+    if (marks)
+        HIP_TRY(hipEventRecord(marks[3], stream));
+    HIP_TRY(hipGetLastError());
+    return TRT_OK;
+}
+
+static int check_delta_chain_from_rgb8(const trt_context *ctx, bool half, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, const void *d_text,
+                                       size_t capacity_bytes, const unsigned long long *d_bytes)
+{
+    if (n < 1 || n > TRT_BATCH_MAX)
+        return fail(TRT_ERR_ARGUMENT, "a chain has 1 to %d frames, %d given", TRT_BATCH_MAX, n);
+    // one text's checks, then room for n of them
+    const int rc = check_delta_from_rgb8(ctx, half, d_shown_rgb8, d_frames_rgb8, width, rows, d_text, (size_t)-1, d_bytes);
+    if (rc)
+        return rc;
+    const size_t need = (size_t)n * delta_capacity(half, width, rows);
+    if (capacity_bytes < need)
+        return fail(TRT_ERR_CAPACITY, "%d delta texts of %d x %d need room for %zu B, %zu given", n, width, rows, need, capacity_bytes);
+    return TRT_OK;
+}
+
+// trt_ansi_delta_chain_from_rgb8_device and trt_ansi_delta_half_chain_from_rgb8_device; ms: trt_ansi_delta_chain_kernel_times and
+// trt_ansi_delta_half_chain_kernel_times, which are synchronous
+static int delta_chain_from_rgb8(trt_context *ctx, bool half, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
+                                 size_t capacity_bytes, unsigned long long *d_bytes, float *ms = nullptr)
+{
+    int rc = check_delta_chain_from_rgb8(ctx, half, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes);
+    if (rc)
+        return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ms)
+        return launch_ansi_delta_chain(ctx, ctx->stream, half, (const unsigned char *)d_shown_rgb8, (const unsigned char *)d_frames_rgb8, n, width, rows, d_text,
+                                       capacity_bytes, 0, d_bytes);
+    Event marks[4];
+    for (Event &e : marks)
+        HIP_TRY(e.create());
+    rc = launch_ansi_delta_chain(ctx, ctx->stream, half, (const unsigned char *)d_shown_rgb8, (const unsigned char *)d_frames_rgb8, n, width, rows, d_text, capacity_bytes, 0,
+                                 d_bytes, marks);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (rc)
+        return rc;
+    for (int k = 0; k < 3; k++)
+        HIP_TRY(hipEventElapsedTime(&ms[k], marks[k], marks[k + 1]));
+    return TRT_OK;
+}
+
+extern "C" int trt_ansi_delta_chain_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
+                                                     size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return delta_chain_from_rgb8(ctx, false, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes);
+}
+
+extern "C" int trt_ansi_delta_half_chain_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
+                                                          size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return delta_chain_from_rgb8(ctx, true, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes);
+}
+
+extern "C" int trt_ansi_delta_chain_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
+                                                 size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
+{
+    if (!ms)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    return delta_chain_from_rgb8(ctx, false, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes, ms);
+}
+
+extern "C" int trt_ansi_delta_half_chain_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
+                                                      size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
+{
+    if (!ms)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    return delta_chain_from_rgb8(ctx, true, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes, ms);
+}
+
 // ---- the render entries of both delta texts: one shown frame, which remembers the kind of text it was sent as ----
 
 extern "C" int trt_ansi_delta_reset(trt_context *ctx)
@@ -1339,9 +1454,10 @@ extern "C" int trt_ansi_delta_reset(trt_context *ctx)
     return TRT_OK;
 }
 
-// what the render entries refuse before anything is enqueued; `text`: the caller's buffer, on the device or on the host
+// what the render entries refuse before anything is enqueued; `text`: the caller's buffer, on the device or on the host, with room for
+// the texts of `frames` cameras (the batch entries: what trt_render_device_batch_rgb8 refuses, and room for every text)
 static int check_render_delta(const trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, const void *text,
-                              size_t capacity_bytes, const void *bytes, bool half)
+                              size_t capacity_bytes, const void *bytes, bool half, int frames = 1)
 {
     if (!bytes)
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
@@ -1352,13 +1468,13 @@ static int check_render_delta(const trt_context *ctx, const Camera *camera, cons
         return fail(TRT_ERR_ARGUMENT, "%d x %d owned rows: a half-block delta text has 1 to %d cells per row and 1 to %d text rows", rows->width, trt_rowset_rows(rows),
                     TRT_DELTA_HALF_MAX_WIDTH, TRT_DELTA_HALF_MAX_TEXT_ROWS);
     // the rest as the RGB8 entry checks it, whose frame these sizes let fit
-    const int rc = check_render_arguments(ctx, camera, 1, rows, bounce_limit, rays_per_pixel, text, (size_t)-1, kBytes);
+    const int rc = check_render_arguments(ctx, camera, frames, rows, bounce_limit, rays_per_pixel, text, (size_t)-1, kBytes);
     if (rc)
         return rc;
-    const size_t need = delta_capacity(half, rows->width, trt_rowset_rows(rows));
+    const size_t need = (size_t)frames * delta_capacity(half, rows->width, trt_rowset_rows(rows));
     if (capacity_bytes < need)
-        return fail(TRT_ERR_CAPACITY, "the text of %d x %d owned rows needs room for %zu B, %zu given", rows->width, trt_rowset_rows(rows), need, capacity_bytes);
-    return TRT_OK;
+        return fail(TRT_ERR_CAPACITY, "%d text(s) of %d x %d owned rows need room for %zu B, %zu given", frames, rows->width, trt_rowset_rows(rows), need, capacity_bytes);
+    return check_batch_tables(ctx, frames);
 }
 
 static bool same_rowset(const trt_rowset &a, const trt_rowset &b)
@@ -1479,4 +1595,131 @@ extern "C" int trt_render_host_ansi_delta_half(trt_context *ctx, const Camera *c
                                                size_t capacity_bytes, size_t *bytes)
 {
     return render_host_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, true);
+}
+
+// ---- the batch forms: n cameras in one render, their n delta texts back to back as one chain ----
+
+// trt_render_device_batch_ansi_delta and trt_render_device_batch_ansi_delta_half
+static int render_device_batch_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                                     size_t capacity_bytes, unsigned long long *d_bytes, bool half)
+{
+    int rc = check_render_delta(ctx, cameras, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, half, n);
+    if (rc)
+        return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int width = rows->width, owned = trt_rowset_rows(rows);
+    const size_t frame = (size_t)owned * width * 3;
+    const bool keyframe = !(ctx->shown_valid && ctx->shown_half == half && same_rowset(ctx->shown_rows, *rows));
+    const int into = ctx->shown_at ^ 1;
+    if (ctx->d_shown[0].capacity < frame || ctx->d_shown[1].capacity < frame || ctx->d_chain.capacity < frame * n)
+    { // nothing in flight may use a buffer that grows; shown frames that grow are of another size: a keyframe, which reads neither's contents
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx->d_shown[0].reserve(frame));
+        HIP_TRY(ctx->d_shown[1].reserve(frame));
+        HIP_TRY(ctx->d_chain.reserve(frame * n));
+    }
+    ctx->shown_valid = false; // a call that fails from here on has forgotten the shown frame
+    // the batch's frames as bytes, back to back: one launch, a split for LDS or one launch per camera, as trt_render_device_batch_rgb8 decides
+    rc = render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, ctx->d_chain.ptr, frame * n, kBytes);
+    if (rc)
+        return rc;
+    const unsigned char *const frames = ctx->d_chain.ptr;
+    if (keyframe)
+    { // text 0 is the whole text of frame 0; the chain of the pairs behind it starts where that text ends
+        const unsigned long long whole = half ? trt_ansi_half_text_bytes(width, owned) : trt_ansi_text_bytes(width, owned);
+        if (half)
+            launch_ansi_half_from_rgb8(ctx->stream, frames, width, owned, d_text);
+        else
+            launch_ansi_from_rgb8(ctx->stream, frames, width, owned, d_text);
+        hipLaunchKernelGGL(trt::ansi_delta_keyframe_bytes_kernel, dim3(1), dim3(1), 0, ctx->stream, d_bytes, whole);
+        HIP_TRY(hipGetLastError());
+        if (n > 1)
+            rc = launch_ansi_delta_chain(ctx, ctx->stream, half, frames, frames + frame, n - 1, width, owned, d_text, capacity_bytes, whole, d_bytes + 1);
+    }
+    else
+        rc = launch_ansi_delta_chain(ctx, ctx->stream, half, ctx->d_shown[ctx->shown_at].ptr, frames, n, width, owned, d_text, capacity_bytes, 0, d_bytes);
+    if (rc)
+        return rc;
+    // the last frame is the shown one from here on: the one copy of a frame's bytes
+    HIP_TRY(hipMemcpyAsync(ctx->d_shown[into].ptr, frames + (size_t)(n - 1) * frame, frame, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->shown_at = into;
+    ctx->shown_rows = *rows;
+    ctx->shown_half = half;
+    ctx->shown_valid = true;
+    return TRT_OK;
+}
+
+extern "C" int trt_render_device_batch_ansi_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                                                  size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return render_device_batch_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, false);
+}
+
+extern "C" int trt_render_device_batch_ansi_delta_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                                       void *d_text, size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return render_device_batch_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, true);
+}
+
+// trt_render_host_batch_ansi_delta and trt_render_host_batch_ansi_delta_half
+static int render_host_batch_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
+                                   size_t capacity_bytes, size_t *bytes, bool half)
+{
+    int rc = check_render_delta(ctx, cameras, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, half, n);
+    if (rc)
+        return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t room = (size_t)n * delta_capacity(half, rows->width, trt_rowset_rows(rows));
+    if (ctx->d_text.capacity < room || ctx->d_delta_bytes.capacity < (size_t)n)
+        HIP_TRY(hipStreamSynchronize(ctx->stream)); // a text in flight may still be written to the old buffers
+    HIP_TRY(ctx->d_text.reserve(room));
+    HIP_TRY(ctx->d_delta_bytes.reserve((size_t)n));
+    HIP_TRY(ctx->h_staging.reserve(sizeof(unsigned long long) * TRT_BATCH_MAX));
+    const double t_begin = host_now_ms();
+    rc = render_device_batch_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, room, ctx->d_delta_bytes.ptr, half);
+    if (rc)
+        return rc;
+    // two transfers for the batch: the n lengths, then exactly their sum, the staging grown to what the texts need
+    unsigned long long length[TRT_BATCH_MAX] = {}, sum = 0;
+    rc = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_delta_bytes.ptr, sizeof length[0] * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        memcpy(length, ctx->h_staging.ptr, sizeof length[0] * n);
+        for (int b = 0; b < n; b++)
+        {
+            if (length[b] > room - sum)
+                return fail(TRT_ERR_CAPACITY, "texts of more than %zu B", room);
+            sum += length[b];
+        }
+        if (sum)
+        {
+            HIP_TRY(ctx->h_staging.reserve((size_t)sum));
+            HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_text.ptr, (size_t)sum, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            memcpy(text, ctx->h_staging.ptr, (size_t)sum);
+        }
+        return TRT_OK;
+    }();
+    if (rc)
+    { // the host did not get the texts: the terminal does not show these frames
+        ctx->shown_valid = false;
+        return rc;
+    }
+    for (int b = 0; b < n; b++)
+        bytes[b] = (size_t)length[b];
+    if (print_host_times())
+        fprintf(stderr, "trt_render_host_batch_ansi_delta%s: %.3f ms for %d texts of %llu bytes\n", half ? "_half" : "", host_now_ms() - t_begin, n, sum);
+    return TRT_OK;
+}
+
+extern "C" int trt_render_host_batch_ansi_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
+                                                size_t capacity_bytes, size_t *bytes)
+{
+    return render_host_batch_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, false);
+}
+
+extern "C" int trt_render_host_batch_ansi_delta_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
+                                                     size_t capacity_bytes, size_t *bytes)
+{
+    return render_host_batch_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, true);
 }

@@ -96,6 +96,14 @@ SYMBOLS = {
     "trt_render_device_batch_ansi": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ]),
     "trt_render_host_batch_ansi": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP]),
     "trt_batch_info": (_I, [_VP, C.POINTER(_I), C.POINTER(_I)]),
+    "trt_ansi_delta_chain_from_rgb8_device": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP]),
+    "trt_ansi_delta_half_chain_from_rgb8_device": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP]),
+    "trt_ansi_delta_chain_kernel_times": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP, C.POINTER(C.c_float)]),
+    "trt_ansi_delta_half_chain_kernel_times": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP, C.POINTER(C.c_float)]),
+    "trt_render_device_batch_ansi_delta": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ, _VP]),
+    "trt_render_device_batch_ansi_delta_half": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ, _VP]),
+    "trt_render_host_batch_ansi_delta": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
+    "trt_render_host_batch_ansi_delta_half": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
     "trt_synchronize": (_I, [_VP]),
     "trt_kernel_times": (_I, [_VP, C.POINTER(C.c_float), _I]),
     "trt_render_kernel_times": (_I, [_VP, C.POINTER(C.c_float), C.POINTER(C.c_float), _I]),
@@ -622,6 +630,67 @@ class Context:
         _check(lib().trt_render_host_batch_ansi_half(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
                                                      out.ctypes.data))
         return out
+
+    # the batch forms of the delta entries, of both kinds of cell: n texts back to back, one helper per pair of entries
+
+    def _delta_chain_from_rgb8(self, entry, shown_ptr, frames_ptr, n, width, rows, text_ptr, capacity_bytes, bytes_ptr):
+        _check(getattr(lib(), entry)(self._h, _VP(shown_ptr), _VP(frames_ptr), n, width, rows, _VP(text_ptr), capacity_bytes, _VP(bytes_ptr)))
+
+    def _delta_chain_kernel_times(self, entry, shown_ptr, frames_ptr, n, width, rows, text_ptr, capacity_bytes, bytes_ptr):
+        ms = (C.c_float * 3)()
+        _check(getattr(lib(), entry)(self._h, _VP(shown_ptr), _VP(frames_ptr), n, width, rows, _VP(text_ptr), capacity_bytes, _VP(bytes_ptr), ms))
+        return tuple(ms)
+
+    def _render_device_batch_delta(self, entry, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr):
+        cams = self._camera_batch(cameras)
+        _check(getattr(lib(), entry)(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel, _VP(device_ptr), capacity_bytes,
+                                     _VP(bytes_ptr)))
+
+    def _render_host_batch_delta(self, entry, capacity, cameras, rows, bounce_limit, rays_per_pixel, out):
+        cams = self._camera_batch(cameras)
+        if out is None:
+            out = np.empty(cams.shape[0] * capacity(rows.width, lib().trt_rowset_rows(C.byref(rows))), dtype=np.uint8)
+        lengths = (_SZ * max(cams.shape[0], 1))()
+        _check(getattr(lib(), entry)(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data, out.size, lengths))
+        ends = np.cumsum([int(k) for k in lengths])
+        return [out[end - int(k):end] for k, end in zip(lengths, ends)]
+
+    def ansi_delta_chain_from_rgb8(self, shown_ptr, frames_ptr, n, width, rows, text_ptr, capacity_bytes, bytes_ptr):
+        """the n delta texts of a chain -- the shown frame at shown_ptr, n frames of RGB8 bytes back to back at frames_ptr, text b between
+        frames b - 1 and b -- back to back at text_ptr, their lengths (n uint64) at the device address bytes_ptr
+        (trt_ansi_delta_chain_from_rgb8_device)"""
+        self._delta_chain_from_rgb8("trt_ansi_delta_chain_from_rgb8_device", shown_ptr, frames_ptr, n, width, rows, text_ptr, capacity_bytes, bytes_ptr)
+
+    def ansi_delta_half_chain_from_rgb8(self, shown_ptr, frames_ptr, n, width, rows, text_ptr, capacity_bytes, bytes_ptr):
+        """the same in half-block cells (trt_ansi_delta_half_chain_from_rgb8_device)"""
+        self._delta_chain_from_rgb8("trt_ansi_delta_half_chain_from_rgb8_device", shown_ptr, frames_ptr, n, width, rows, text_ptr, capacity_bytes, bytes_ptr)
+
+    def ansi_delta_chain_kernel_times(self, shown_ptr, frames_ptr, n, width, rows, text_ptr, capacity_bytes, bytes_ptr):
+        """ansi_delta_chain_from_rgb8, synchronous: ms of the (measure, offsets, write) kernels by HIP events (trt_ansi_delta_chain_kernel_times)"""
+        return self._delta_chain_kernel_times("trt_ansi_delta_chain_kernel_times", shown_ptr, frames_ptr, n, width, rows, text_ptr, capacity_bytes, bytes_ptr)
+
+    def ansi_delta_half_chain_kernel_times(self, shown_ptr, frames_ptr, n, width, rows, text_ptr, capacity_bytes, bytes_ptr):
+        """the same in half-block cells (trt_ansi_delta_half_chain_kernel_times)"""
+        return self._delta_chain_kernel_times("trt_ansi_delta_half_chain_kernel_times", shown_ptr, frames_ptr, n, width, rows, text_ptr, capacity_bytes, bytes_ptr)
+
+    def render_device_batch_ansi_delta(self, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr):
+        """cameras[n, 15] as n delta texts back to back in device memory: text 0 against the context's shown frame (the keyframe when there
+        is none), text b against frame b - 1 of the batch; their lengths (n uint64) at the device address bytes_ptr
+        (trt_render_device_batch_ansi_delta)"""
+        self._render_device_batch_delta("trt_render_device_batch_ansi_delta", cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr)
+
+    def render_device_batch_ansi_delta_half(self, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr):
+        """the same in half-block cells (trt_render_device_batch_ansi_delta_half)"""
+        self._render_device_batch_delta("trt_render_device_batch_ansi_delta_half", cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr)
+
+    def render_host_batch_ansi_delta(self, cameras, rows, bounce_limit, rays_per_pixel, out=None):
+        """the same into host memory: a list of n uint8 texts, each as long as the host is to write it (trt_render_host_batch_ansi_delta);
+        `out`: a uint8 buffer of n * ansi_delta_capacity bytes to reuse, of which the texts are views"""
+        return self._render_host_batch_delta("trt_render_host_batch_ansi_delta", ansi_delta_capacity, cameras, rows, bounce_limit, rays_per_pixel, out)
+
+    def render_host_batch_ansi_delta_half(self, cameras, rows, bounce_limit, rays_per_pixel, out=None):
+        """the same in half-block cells (trt_render_host_batch_ansi_delta_half); `out`: n * ansi_delta_half_capacity bytes"""
+        return self._render_host_batch_delta("trt_render_host_batch_ansi_delta_half", ansi_delta_half_capacity, cameras, rows, bounce_limit, rays_per_pixel, out)
 
     def batch_info(self):
         """(frames, render-kernel launches) of this context's most recent batch call (trt_batch_info)"""
