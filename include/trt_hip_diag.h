@@ -7,6 +7,7 @@
  *   read-backs    the candidate tables the device built, for comparison with the host reference builders
  *   self-tests    device division / square root / normalisation / cube instructions / skybox estimate against their references
  *   probes        single rays through the reference-order kernel and through the production kernel's stages
+ *   look-ups      where the kernels' own table look-ups and the FP32 filter look, for the host's conservativeness checks
  *   scene image   where the kernels read the scene from: LDS or device memory
  *   drop-in       a borrowed handle to the default context; how many table builds and skybox uploads a context has performed
  *   test hooks    the pool cap of the long candidate lists; a NaN fill of a launch's scratch and output; a stand-in for RCCL so that several ranks can share one GPU
@@ -130,6 +131,37 @@ int trt_probe_rays(trt_context *ctx, const Ray *rays, size_t n, int *obj, double
  * camera: its origin is the eye the tables of families 0 and 1 are built for. */
 int trt_probe_rays_production(trt_context *ctx, const Camera *camera, const Ray *rays, const int *families, size_t n, int *obj,
                               double *point, double *normal, double *material, double *lit);
+
+/* WHERE THE DEVICE LOOKS (tests/test_device_lookups.py).  The candidate tables are proven conservative on the host, for the cell the
+ * host headers look up; the three entries below make the device report its own choice, so that the host's proofs can be run on it.
+ * Host arrays in and out, the context's stream, nothing on the product path.
+ *
+ * trt_probe_path_lookups: one lane per ray runs the render kernels' own look-up of a path ray's list cell (csrc/trt_rounds.hpp: path_cell, or
+ * path_cell_patches when the scene has patches) on the scene image as the render kernel stages it -- for one camera, or, n_cameras = 2 ..
+ * TRT_BATCH_MAX, as a batch launch stages it, frame b's eye tables in eye slot b; frames[i] < n_cameras is the frame of ray i (NULL: 0).
+ * families[i]: the ray's family code as in trt_probe_rays_production (a code the kernel cannot decode counts as none).  Per ray:
+ *   fallback   1: the ray's wave would sweep (no family, not a member of the family's table, or a cell without a list)
+ *   cell_word  the list cell that was read, 0 if none was
+ *   successor  with patches: the code path_cell_patches leaves for the ray's reflection by the ground; without: the code as it was looked up
+ *   read_at    the index into the path rays' list cells that was read, -1: nothing was read (the ray failed the membership test)
+ *   place      {region, table, cell} of read_at, split by the address ranges of the context's tables alone: region 0 the eye's tables (table =
+ *              2 slot + family), 1 the 2 N P tables of the spheres (patch k of sphere i at i P + k, then the mirror images), 2 the lean twins
+ *              (N P), -1 nothing read, -2 an index outside every table */
+int trt_probe_path_lookups(trt_context *ctx, const Camera *cameras, int n_cameras, const Ray *rays, const int *families, const int *frames, size_t n,
+                           int *fallback, unsigned long long *cell_word, int *successor, long long *read_at, int *place);
+
+/* The look-up lines of the shading stage (csrc/trt_rounds.hpp: shadow_stage) for ONE light, in the kernel's light order (the directional
+ * lights, then the point lights), on the headers the render kernel stages: per origin (3 doubles) far != 0 (the origin is not looked up),
+ * the cell index trt_dirgrid_cell / trt_pointgrid_cell gives, the list cell read there (0 when far) and, for a point light, the bounds of
+ * the any-hit search (trt_point_shadow_bounds of |light - o|^2 and of the unit direction's d.d; lo and hi may be NULL for a directional light). */
+int trt_probe_shadow_lookups(trt_context *ctx, const double *origins, size_t n, int light, int *far, int *cell, unsigned long long *cell_word,
+                             double *lo, double *hi);
+
+/* trt_filter_setup on the device with the context's culling constants, then trt_filter_sign of every sphere of the staged culling table and,
+ * if the scene has a directional light and sign_fixed != NULL, trt_filter_sign_fixed_dir with the staged row of directional light 0.
+ * fields: the nine members of trt_ray_filter per ray as 32-bit words (the floats' bits, then ok); sign, sign_fixed: sphere-major,
+ * [sphere * n + ray].  All IEEE operations: the host's must agree bit for bit. */
+int trt_selftest_filter(trt_context *ctx, const Ray *rays, size_t n, unsigned *fields, unsigned *sign, unsigned *sign_fixed);
 
 /* Measurement: the number of frames a context has launched so far (launch numbers count from 0), and the DEVICE time in ms from the
  * start of launch `first_launch` of context `first` to the end -- render kernel and ordered mean -- of launch `last_launch` of

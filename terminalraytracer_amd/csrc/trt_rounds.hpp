@@ -587,9 +587,10 @@ TRT_DEV void point_light_search(const LdsImage &L, int n, d3 o, d3 d, bool activ
 // behind it, within the table's range; a unit direction) or whose cell has no list: the caller then sweeps.  `active_lanes`:
 // lanes_with(active) (trt_device.hpp).
 // BATCH: the ray belongs to frame `frame` of a batch launch, whose eye families and tables it reads (0 and unused otherwise)
-template <bool BATCH = false>
+// DIAG (trt_probe_path_lookups only; the render kernels never set it): *read_at = the index into G.path_lists the lane read, -1: none
+template <bool BATCH = false, bool DIAG = false>
 TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n, int fam, d3 o, d3 d, bool active, unsigned long long active_lanes,
-                                     unsigned long long &fallback_lanes, int frame = 0, int inside = -1)
+                                     unsigned long long &fallback_lanes, int frame = 0, int inside = -1, long long *read_at = nullptr)
 {
     const bool in_family = fam >= 0;
     const unsigned long long family_lanes = lanes_with(in_family); // next to its compare: a vote on a compare of another block is a select and a compare again
@@ -629,6 +630,8 @@ TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n
     unsigned long long cell = 0;
     if (has && member)
         cell = G.path_lists[base + (unsigned)at];
+    if constexpr (DIAG)
+        *read_at = has && member ? (long long)(base + (unsigned)at) : -1;
     fallback_lanes = active_lanes & (~member_lanes | lanes_with((unsigned)(cell >> 56) == TRT_LIST_NONE)); // active && (!has || !member || no list)
     return cell;
 }
@@ -641,9 +644,10 @@ TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n
 // from the ground cannot hit the ground again).  `fallback_lanes` holds the active lanes whose ray fails the family's
 // membership test (its line must pass within r_chk of the apex, its origin not more than r_chk behind it, within the table's
 // range; a unit direction) or whose cell has no list: the caller then sweeps.
-template <bool BATCH = false>
+// DIAG: as in path_cell.
+template <bool BATCH = false, bool DIAG = false>
 TRT_DEV unsigned long long path_cell_patches(const LdsImage &L, const GridView &G, int n, int &fam, d3 o, d3 d, bool active, unsigned long long active_lanes,
-                                             unsigned long long &fallback_lanes, int frame = 0, int inside = -1)
+                                             unsigned long long &fallback_lanes, int frame = 0, int inside = -1, long long *read_at = nullptr)
 {
     const bool in_family = fam >= 0;
     const unsigned long long family_lanes = lanes_with(in_family); // next to its compare: a vote on a compare of another block is a select and a compare again
@@ -694,6 +698,8 @@ TRT_DEV unsigned long long path_cell_patches(const LdsImage &L, const GridView &
     unsigned long long cell = 0;
     if (has && member)
         cell = G.path_lists[base + (unsigned)at];
+    if constexpr (DIAG)
+        *read_at = has && member ? (long long)(base + (unsigned)at) : -1;
     fallback_lanes = active_lanes & (~member_lanes | lanes_with((unsigned)(cell >> 56) == TRT_LIST_NONE)); // active && (!has || !member || no list)
     return cell;
 }

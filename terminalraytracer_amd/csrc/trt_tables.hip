@@ -484,7 +484,12 @@ int build_tables(trt_context *ctx, const trt_cull_scene &cs, const double *groun
     // The scene's part is sized by a guess (a word per cell) and GROWN to what the builders asked for if that was more: the
     // counter keeps counting after the part is exhausted (pack_cell), so one more pass with a part of that size has room for
     // every list.  Dense scenes of many spheres need it (700 spheres: ~7 words a cell); the BASELINE configs never do.
-    for (int pass = 0; pass < 2 && !rc; pass++)
+    // The lean twins can ask for it a second time: the twin of a cell that found no room for its list asks for nothing, so the first pass does
+    // not count the words of those twins; the pass that has room for every full list does.  The part never becomes larger than the pool that
+    // was reserved for it: the eye slots' parts lie behind it, and a part that was only grown on paper put the last slots' lists behind the end of
+    // the allocation (a batch of 8 cameras at 300 spheres with twins: an illegal access in the eye slots' builder).
+    const int passes = 3;
+    for (int pass = 0; pass < passes && !rc; pass++)
     {
         if (ctx->T->pool_scene_words + kEyeSlots * ctx->T->pool_eye_words >= 0xffffffffull)
             return fail(TRT_ERR_CAPACITY, "candidate tables too large");
@@ -503,7 +508,7 @@ int build_tables(trt_context *ctx, const trt_cull_scene &cs, const double *groun
         // synchronised it, and a copy on the null stream does not wait for a non-blocking one (it then read what hipMalloc handed out)
         HIP_TRY(hipMemcpyAsync(&asked, ctx->T->d_pool_used.ptr, sizeof asked, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (asked <= ctx->T->pool_scene_words)
+        if (asked <= ctx->T->pool_scene_words || pass == passes - 1) // the last pass: lists without room leave their cells without one (twins: a copy)
             break;
         ctx->T->pool_scene_words = (size_t)asked + 1024;
     }

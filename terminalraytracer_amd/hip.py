@@ -149,6 +149,9 @@ SYMBOLS = {
     "trt_selftest_div_sqrt": (_I, [_VP, _VP, _VP, _SZ, _VP, _VP]),
     "trt_probe_rays": (_I, [_VP, _VP, _SZ, _VP, _VP, _VP, _VP, _VP]),
     "trt_probe_rays_production": (_I, [_VP, C.POINTER(L.Camera), _VP, _VP, _SZ, _VP, _VP, _VP, _VP, _VP]),
+    "trt_probe_path_lookups": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _SZ, _VP, _VP, _VP, _VP, _VP]),
+    "trt_probe_shadow_lookups": (_I, [_VP, _VP, _SZ, _I, _VP, _VP, _VP, _VP, _VP]),
+    "trt_selftest_filter": (_I, [_VP, _VP, _SZ, _VP, _VP, _VP]),
     "trt_launch_count": (C.c_long, [_VP]),
     "trt_launch_span_ms": (_I, [_VP, C.c_long, _VP, C.c_long, C.POINTER(C.c_float)]),
     "trt_dist_unique_id": (_I, [_VP]),
@@ -781,6 +784,45 @@ class Context:
         _check(lib().trt_probe_rays_production(self._h, C.byref(cam), rays.ctypes.data, None if fam is None else fam.ctypes.data, n,
                                                obj.ctypes.data, point.ctypes.data, normal.ctypes.data, material.ctypes.data, lit.ctypes.data))
         return obj, point, normal, material, lit
+
+    def probe_path_lookups(self, cameras, rays, families, frames=None):
+        """trt_probe_path_lookups: where the render kernels' own look-up reads a path ray's list cell.  cameras [15] or [n, 15] (2 to 8: the
+        batch form, frames[i] the frame of ray i).  Returns a dict of arrays: fallback, word, successor, read_at, region, table, cell."""
+        cams = np.ascontiguousarray(cameras, dtype=np.float64).reshape(-1, 15)
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        n = rays.shape[0]
+        fam = np.ascontiguousarray(families, dtype=np.int32)
+        frm = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32)
+        assert fam.shape == (n,) and (frm is None or frm.shape == (n,))
+        fallback, successor = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        word, read_at, place = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.int64), np.zeros((n, 3), dtype=np.int32)
+        _check(lib().trt_probe_path_lookups(self._h, cams.ctypes.data, cams.shape[0], rays.ctypes.data, fam.ctypes.data,
+                                            None if frm is None else frm.ctypes.data, n, fallback.ctypes.data, word.ctypes.data,
+                                            successor.ctypes.data, read_at.ctypes.data, place.ctypes.data))
+        return {"fallback": fallback, "word": word, "successor": successor, "read_at": read_at,
+                "region": place[:, 0].copy(), "table": place[:, 1].copy(), "cell": place[:, 2].copy()}
+
+    def probe_shadow_lookups(self, origins, light):
+        """trt_probe_shadow_lookups: the shading stage's look-up of one light (directional lights first) per origin.  Returns a dict of arrays:
+        far, cell, word and, for a point light, lo and hi."""
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        n = o.shape[0]
+        far, cell, word = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint64)
+        lo, hi = np.zeros(n), np.zeros(n)
+        _check(lib().trt_probe_shadow_lookups(self._h, o.ctypes.data, n, int(light), far.ctypes.data, cell.ctypes.data, word.ctypes.data,
+                                              lo.ctypes.data, hi.ctypes.data))
+        return {"far": far, "cell": cell, "word": word, "lo": lo, "hi": hi}
+
+    def selftest_filter(self, rays, num_spheres, fixed_dir=True):
+        """trt_selftest_filter: (fields uint32 [n, 9], sign uint32 [spheres, n], sign_fixed uint32 [spheres, n] or None) of the FP32 filter's
+        set-up and sign words as the device computes them for the current scene of num_spheres spheres"""
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        n = rays.shape[0]
+        fields, sign = np.zeros((n, 9), dtype=np.uint32), np.zeros((num_spheres, n), dtype=np.uint32)
+        fixed = np.zeros((num_spheres, n), dtype=np.uint32) if fixed_dir else None
+        _check(lib().trt_selftest_filter(self._h, rays.ctypes.data, n, fields.ctypes.data, sign.ctypes.data,
+                                         None if fixed is None else fixed.ctypes.data))
+        return fields, sign, fixed
 
 
 def default_context():

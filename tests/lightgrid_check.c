@@ -434,3 +434,311 @@ long lightgrid_pack(const unsigned long long *masks, long cells, int words, int 
     }
     return used;
 }
+
+/* ---- helpers of tests/test_device_lookups.py: the host's own look-up of many origins at once, and the checks above on a cell the CALLER names ----
+ * One light's table as the builders above make it: the same prepare, and per cell the same predicate the builders' loops evaluate -- a cell's
+ * mask is formed when it is first asked for, so that a table of a million cells costs what the cells that are looked up cost. */
+
+typedef struct
+{
+    int kind, n, g, depth, words; /* kind 0: directional light with to-light direction v, 1: point light at v */
+    long cells;
+    double v[3];
+    trt_dirgrid D;
+    trt_pointgrid P;
+    trt_dirgrid_disc *discs;
+    trt_pointgrid_cone *cones;
+    unsigned long long *masks;
+    unsigned char *have;
+    unsigned long long border_bits; /* directional: bits set in the border cells the clamp relies on being empty */
+} light_host;
+
+static const unsigned long long *cell_mask(light_host *H, long cell)
+{
+    unsigned long long *m = H->masks + cell * H->words;
+    if (H->have[cell])
+        return m;
+    const int g = H->g;
+    for (int i = 0; i < H->n; i++)
+    {
+        int in;
+        if (H->kind == 0) /* the body of trt_dirgrid_build's loop */
+            in = trt_dirgrid_in_slab(H->discs + i, (int)(cell / ((long)g * g))) && trt_dirgrid_reaches(H->discs + i, (int)(cell % g), (int)((cell / g) % g));
+        else /* of trt_pointgrid_build's */
+            in = trt_pointgrid_in_shell(H->cones + i, (int)(cell / (6L * g * g)), H->P.shells) &&
+                 trt_pointgrid_reaches(H->cones + i, (int)((cell / ((long)g * g)) % 6), (int)(cell % g), (int)((cell / g) % g), g);
+        if (in)
+            trt_lightgrid_set(m, i);
+    }
+    H->have[cell] = 1;
+    return m;
+}
+
+light_host *light_host_build(const double *spheres, int n, int kind, const double *v, int g, int depth)
+{
+    light_host *H = (light_host *)calloc(1, sizeof *H);
+    const int padded = trt_cull_padded(n, 8);
+    float *table = (float *)malloc(sizeof(float) * 4 * (size_t)(padded ? padded : 1));
+    trt_cull_scene cs;
+    trt_cull_build(spheres, n, 8, table, &cs);
+    free(table);
+    if (depth < 1)
+        depth = 1;
+    H->kind = kind, H->n = n, H->g = g, H->depth = depth, H->words = (n + 63) / 64 > 0 ? (n + 63) / 64 : 1;
+    H->cells = (long)depth * g * g * (kind ? 6 : 1);
+    memcpy(H->v, v, sizeof H->v);
+    H->discs = (trt_dirgrid_disc *)calloc((size_t)(n ? n : 1), sizeof(trt_dirgrid_disc));
+    H->cones = (trt_pointgrid_cone *)calloc((size_t)(n ? n : 1), sizeof(trt_pointgrid_cone));
+    if (kind == 0)
+        trt_dirgrid_prepare(spheres, n, &cs, v, g, depth, &H->D, H->discs);
+    else
+        trt_pointgrid_prepare(spheres, n, &cs, v, g, depth, &H->P, H->cones);
+    H->masks = (unsigned long long *)calloc((size_t)H->cells * H->words, sizeof(unsigned long long));
+    H->have = (unsigned char *)calloc((size_t)H->cells, 1);
+    if (kind == 0)
+        for (int s = 0; s < depth; s++)
+            for (int j = 0; j < g; j++)
+                for (int c = 0; c < g; c++)
+                    if (j == 0 || c == 0 || j == g - 1 || c == g - 1)
+                    {
+                        const unsigned long long *m = cell_mask(H, ((long)s * g + j) * g + c);
+                        for (int w = 0; w < H->words; w++)
+                            H->border_bits += (unsigned long long)__builtin_popcountll(m[w]);
+                    }
+    return H;
+}
+
+void light_host_free(light_host *H)
+{
+    free(H->discs), free(H->cones), free(H->masks), free(H->have);
+    free(H);
+}
+
+/* the header as the host prepared it (the device stages its own copy): sizeof(trt_dirgrid) resp. sizeof(trt_pointgrid) bytes */
+int light_host_header(const light_host *H, void *out)
+{
+    if (H->kind == 0)
+        memcpy(out, &H->D, sizeof H->D);
+    else
+        memcpy(out, &H->P, sizeof H->P);
+    return H->kind == 0 ? (int)sizeof H->D : (int)sizeof H->P;
+}
+
+/* normalize_vector of the reference (TRT.c:439-450): vectors not longer than 1e-4 are left alone */
+static void ref_unit(const double v[3], double out[3])
+{
+    const double len = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    out[0] = v[0], out[1] = v[1], out[2] = v[2];
+    if (len > 0.0001)
+        out[0] = v[0] / len, out[1] = v[1] / len, out[2] = v[2] / len;
+}
+
+/* the shadow ray the reference sends from o towards the light of H (TRT.c:903-907, :930-936) */
+static void shadow_ray(const light_host *H, const double *o, double ray[6], double *light_d2)
+{
+    double to_light[3] = {H->v[0], H->v[1], H->v[2]};
+    if (H->kind == 1)
+        for (int k = 0; k < 3; k++)
+            to_light[k] = H->v[k] - o[k];
+    *light_d2 = to_light[0] * to_light[0] + to_light[1] * to_light[1] + to_light[2] * to_light[2];
+    memcpy(ray, o, 3 * sizeof(double));
+    ref_unit(to_light, ray + 3);
+}
+
+/* THE HOST'S OWN LOOK-UP of the shadow ray from every origin (3 doubles), as the shading stage performs it: far[r] (the grid's, or a direction
+ * that is no unit vector), cell[r], and for a point light the bounds of the any-hit search; rays_out (6 doubles per origin, may be NULL): the
+ * shadow ray itself */
+void light_host_lookup(const light_host *H, const double *origins, size_t n_rays, int *far, int *cell, double *lo, double *hi, double *rays_out)
+{
+    for (size_t r = 0; r < n_rays; r++)
+    {
+        const double *o = origins + 3 * r;
+        double ray[6], light_d2;
+        shadow_ray(H, o, ray, &light_d2);
+        const double a = ray[3] * ray[3] + ray[4] * ray[4] + ray[5] * ray[5];
+        int f;
+        if (H->kind == 0)
+            cell[r] = trt_dirgrid_cell(&H->D, o[0], o[1], o[2], &f);
+        else
+        {
+            cell[r] = trt_pointgrid_cell(&H->P, o[0], o[1], o[2], &f);
+            f |= !(fabs(a - 1.0) <= 9.094947017729282e-13);
+            trt_point_shadow_bounds(&H->P, light_d2, a, lo + r, hi + r);
+        }
+        far[r] = f;
+        if (rays_out)
+            memcpy(rays_out + 6 * r, ray, sizeof ray);
+    }
+}
+
+/* dirgrid_check and pointgrid_check ON THE CALLER'S CELL: the shadow ray from origin r was looked up in cell[r] of the light's table (-1: not
+ * looked up; counted as far).  Everything else is those two functions': a sphere the exact test hits must be in the cell -- for a point light
+ * unless the hit is farther than the light + near / 2, rule (3) --, and the point light's lit / dark decision taken from the cell's spheres
+ * must be the one taken from all spheres. */
+void lightgrid_check_at(light_host *H, const double *spheres, const double *origins, const int *cell, size_t n_rays, grid_stats *st)
+{
+    memset(st, 0, sizeof *st);
+    const int n = H->n;
+    st->cells = (unsigned long long)H->cells;
+    st->violations += 1000000ull * H->border_bits; /* the clamp relies on an empty border */
+    const double near = 0.02 + 4e-6 * sqrt((double)H->P.rg2);
+    unsigned group_max = 0;
+    for (size_t r = 0; r < n_rays; r++)
+    {
+        double ray[6], light_d2;
+        shadow_ray(H, origins + 3 * r, ray, &light_d2);
+        const double *o = ray, *d = ray + 3;
+        const double a = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+        st->rays++;
+        if (cell[r] == -1 || !(fabs(a - 1.0) <= 9.094947017729282e-13))
+        {
+            st->far++;
+            continue;
+        }
+        if (cell[r] < 0 || cell[r] >= H->cells)
+        {
+            note(st, o, -1, cell[r]);
+            continue;
+        }
+        const unsigned long long *m = cell_mask(H, cell[r]);
+        const double light_d = sqrt(light_d2);
+        unsigned cand = 0;
+        for (int i = 0; i < n; i++)
+        {
+            double t;
+            const int hit = exact_hit(o, d, a, spheres + 9 * i, &t);
+            st->exact_hits += hit;
+            cand += in_cell(m, i);
+            if (hit && !in_cell(m, i) && (H->kind == 0 || t <= light_d + 0.5 * near))
+                note(st, o, i, cell[r]);
+        }
+        if (H->kind == 1 && decide_lit(spheres, n, NULL, o, d, a, light_d2) != decide_lit(spheres, n, m, o, d, a, light_d2))
+            st->decision_mismatches++;
+        tally(st, cand, &group_max, r, n_rays);
+    }
+}
+
+/* pointgrid_anyhit_check on the caller's cell: what the any-hit search decides from the spheres of cell[r] must be the reference's answer */
+void pointgrid_anyhit_check_at(light_host *H, const double *spheres, const double *ground, const double *origins, const int *cell, size_t n_rays,
+                               anyhit_stats *st)
+{
+    memset(st, 0, sizeof *st);
+    const int n = H->n;
+    for (size_t r = 0; r < n_rays; r++)
+    {
+        double ray[6], light_d2;
+        shadow_ray(H, origins + 3 * r, ray, &light_d2);
+        const double *o = ray, *d = ray + 3;
+        const double a = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+        st->rays++;
+        if (H->kind != 1 || !(fabs(a - 1.0) <= 9.094947017729282e-13) || cell[r] < 0 || cell[r] >= H->cells)
+        {
+            st->far++;
+            continue;
+        }
+        const unsigned long long *m = cell_mask(H, cell[r]);
+        double lo, hi;
+        trt_point_shadow_bounds(&H->P, light_d2, a, &lo, &hi);
+        const int cls = anyhit_class(spheres, n, m, ground, o, d, lo, hi, &st->tests);
+        for (int i = 0; i < n; i++)
+            st->tests_closest += (unsigned)in_cell(m, i);
+        st->dark += cls == 0, st->lit += cls == 1, st->unsure += cls == 2;
+        if (cls == 2)
+            continue;
+        const int ref = reference_lit(spheres, n, ground, o, d, a, light_d2);
+        if (ref != cls)
+        {
+            if (!st->wrong_dark && !st->wrong_lit)
+                memcpy(st->first_wrong, o, 6 * sizeof(double));
+            st->wrong_dark += cls == 0, st->wrong_lit += cls == 1;
+        }
+    }
+}
+
+/* do the list cells somebody else read at cell[r] (the device: words[r], long lists in `pool`, `bits` per entry) list exactly the spheres of the
+ * host's mask of that cell, in ascending order?  Returns how many differ; cell -1: skipped */
+long light_host_same_entries(light_host *H, const int *cell, const unsigned long long *words, const unsigned long long *pool, long pool_words, int bits,
+                             size_t n_rays)
+{
+    long differ = 0;
+    for (size_t r = 0; r < n_rays; r++)
+    {
+        if (cell[r] == -1)
+            continue;
+        if (cell[r] < 0 || cell[r] >= H->cells)
+        {
+            differ++;
+            continue;
+        }
+        const unsigned long long *m = cell_mask(H, cell[r]);
+        const int count = trt_list_count(m, H->words), e = trt_list_entries(words[r]);
+        int same = e == count;
+        if (same && ((unsigned)(words[r] >> 56) & TRT_LIST_POOLED) && (long)(unsigned)words[r] + (long)trt_list_pool_words(e, bits) > pool_words)
+            same = 0;
+        int k = 0;
+        for (int i = 0; same && i < H->n; i++)
+            if (in_cell(m, i))
+                same = trt_list_entry(words[r], pool, k++, bits) == i;
+        differ += !same;
+    }
+    return differ;
+}
+
+/* the FP32 filter (csrc/trt_filter.h) of many rays as the HOST evaluates it, for comparison with the device's (trt_selftest_filter): the nine
+ * members of trt_ray_filter as 32-bit words per ray, the sign word of every sphere of the culling table (sphere-major: sign[sphere * n_rays + r])
+ * and, dir_light != NULL, the fixed-direction sign words with the table of the directional light of that direction (TRT.c:903-904: the rays
+ * towards it run along the normalised negated direction), as the kernels' scene image forms it */
+void filter_host_words(const double *spheres, int n, const double *rays, size_t n_rays, const double *dir_light, unsigned *fields, unsigned *sign,
+                       unsigned *sign_fixed)
+{
+    const int padded = trt_cull_padded(n, 8);
+    float *table = (float *)malloc(sizeof(float) * 4 * (size_t)(padded ? padded : 1));
+    trt_cull_scene cs;
+    trt_cull_build(spheres, n, 8, table, &cs);
+    float *kk_fixed = (float *)malloc(sizeof(float) * (size_t)(n ? n : 1));
+    if (dir_light)
+    {
+        const double neg[3] = {dir_light[0] * -1.0, dir_light[1] * -1.0, dir_light[2] * -1.0};
+        double tl[3];
+        ref_unit(neg, tl);
+        for (int i = 0; i < n; i++)
+            kk_fixed[i] = trt_filter_fixed_dir_kk(table[4 * i], table[4 * i + 1], table[4 * i + 2], table[4 * i + 3], (float)tl[0], (float)tl[1], (float)tl[2]);
+    }
+    for (size_t r = 0; r < n_rays; r++)
+    {
+        const double *o = rays + 6 * r, *d = o + 3;
+        trt_ray_filter f;
+        trt_filter_setup(&f, o[0], o[1], o[2], d[0], d[1], d[2], d[0] * d[0] + d[1] * d[1] + d[2] * d[2], cs.c0[0], cs.c0[1], cs.c0[2], cs.cn, cs.rm);
+        const float members[8] = {f.dx, f.dy, f.dz, f.wx, f.wy, f.wz, f.neg_thr, f.cd_min};
+        memcpy(fields + 9 * r, members, sizeof members);
+        fields[9 * r + 8] = (unsigned)f.ok;
+        for (int i = 0; i < n; i++)
+        {
+            sign[(size_t)i * n_rays + r] = trt_filter_sign(&f, table[4 * i], table[4 * i + 1], table[4 * i + 2], table[4 * i + 3]);
+            if (dir_light)
+                sign_fixed[(size_t)i * n_rays + r] = trt_filter_sign_fixed_dir(&f, table[4 * i], table[4 * i + 1], table[4 * i + 2], kk_fixed[i]);
+        }
+    }
+    free(kk_fixed);
+    free(table);
+}
+
+/* centre (3) and admissible squared distance of a light's look-up: g0 and rg2 of a directional light's header, l and rg2 of a point light's */
+void light_host_range(const light_host *H, double out[4])
+{
+    const double *c = H->kind == 0 ? H->D.g0 : H->P.l;
+    out[0] = c[0], out[1] = c[1], out[2] = c[2], out[3] = (double)(H->kind == 0 ? H->D.rg2 : H->P.rg2);
+}
+
+/* (depth coordinate, face, row, column) of a cell index of the light's table (face 0 for a directional light) */
+void light_host_coords(const light_host *H, const int *cell, size_t count, int *out)
+{
+    const long g = H->g;
+    for (size_t r = 0; r < count; r++)
+    {
+        const long c = cell[r];
+        const long plane = c / (g * g);
+        out[4 * r] = (int)(H->kind ? plane / 6 : plane), out[4 * r + 1] = (int)(H->kind ? plane % 6 : 0);
+        out[4 * r + 2] = (int)((c / g) % g), out[4 * r + 3] = (int)(c % g);
+    }
+}

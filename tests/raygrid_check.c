@@ -120,6 +120,9 @@ static int table_of(const tables *T, const double *spheres, int code, const doub
     return 2 + (n + i) * P + k;
 }
 
+/* pool words per cell (per byte of an entry) that build() sets aside: 1 as the library's first guess; a caller that needs every list raises it */
+static size_t g_pool_words_factor = 1;
+
 static tables *build(const double *spheres, int n, const double *ground, const double *eye, int g_eye, int g_sph, int patch_m, ray_stats *st)
 {
     tables *T = (tables *)calloc(1, sizeof *T);
@@ -131,7 +134,7 @@ static tables *build(const double *spheres, int n, const double *ground, const d
     const size_t total = family_base(T, T->families);
     T->cells = (unsigned long long *)malloc(sizeof(unsigned long long) * total);
     T->bits = n > TRT_LIST_MAX_SPHERES ? 16 : 8;
-    T->pool_cap = total * (size_t)(T->bits / 8);
+    T->pool_cap = total * (size_t)(T->bits / 8) * g_pool_words_factor;
     T->pool = (unsigned long long *)malloc(sizeof(unsigned long long) * T->pool_cap);
     unsigned long long bits = 0;
 #pragma omp parallel for schedule(dynamic, 1) reduction(+ : bits)

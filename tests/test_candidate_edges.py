@@ -433,11 +433,12 @@ def test_the_lone_blocker_at_the_lights_distance_leaves_the_any_hit_search_unsur
 
 
 def test_checker_helpers_under_address_and_undefined_behaviour_sanitizers(tmp_path):
-    """the helpers this file adds to raygrid_check.c and lightgrid_check.c (cell look-ups, membership, prefilter, packing), with the host builders
+    """the helpers this file and test_device_lookups.py add to raygrid_check.c, lean_lists_check.c and lightgrid_check.c (cell look-ups, membership, prefilter,
+    packing; the host's look-up of many rays and the checks on a place the caller names), with the host builders
     they rest on, in a program of their own (tests/candidate_helpers_main.c) compiled with -fsanitize=address,undefined: a directed scene at
     either entry width must give the directed figures, and no report"""
     exe, inc = str(tmp_path / "candidate_helpers"), os.path.join(T.ROOT, "terminalraytracer_amd", "csrc")
-    src = [os.path.join(T.ROOT, "tests", f) for f in ("candidate_helpers_main.c", "raygrid_check.c", "lightgrid_check.c")]
+    src = [os.path.join(T.ROOT, "tests", f) for f in ("candidate_helpers_main.c", "lean_lists_check.c", "lightgrid_check.c")]  # lean_lists_check.c includes raygrid_check.c
     subprocess.check_call(["gcc", "-O1", "-g", "-ffp-contract=off", "-fno-fast-math", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                            "-fno-omit-frame-pointer", "-I" + inc, "-o", exe] + src + ["-lm"])
     run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
