@@ -431,7 +431,7 @@ int trt_ansi_delta_half_chain_from_rgb8_device(trt_context *ctx, const void *d_s
  * the context's SHOWN frame, which the context has for exactly this rowset and this kind under the rules of
  * trt_render_device_ansi_delta; if it has none, text 0 is the KEYFRAME, byte for byte trt_render_device_ansi's text, d_bytes[0] its
  * length, and the chain of the other frames starts behind it.  Texts 1..n-1 are against the previous frame of the batch.  Afterwards
- * frame n - 1 is the shown frame, of this rowset and this kind (one frame's bytes are copied): a later trt_render_*_ansi_delta call
+ * frame n - 1 is the shown frame, of this rowset and this kind (where it was rendered: no frame is copied): a later trt_render_*_ansi_delta call
  * continues from it, and a batch continues from theirs.
  * Errors before anything is enqueued, the shown frame kept: those of trt_render_device_batch_rgb8 (n > 1 on shared tables:
  * TRT_ERR_CAPACITY) and of trt_render_device_ansi_delta, with capacity_bytes >= n * trt_ansi_delta_capacity(width, owned rows).  A

@@ -1,24 +1,23 @@
-// trt_ansi_delta.hpp -- the delta text between two RGB8 frames, written on the device: three launches in stream order.  The text has
-// two KINDS of cell: the full text's, two columns wide (trt_ansi_delta.h), and half-block cells, two pixel rows a cell
-// (trt_ansi_delta_half.h).  Each header holds its format, the record lengths and bytes, and the LANE'S WALK: which bytes of the two
-// frames a lane loads for its cells.  This file holds the tile scheme, once for both kinds: the prefix sum that gives every record its place.
+// trt_ansi_delta.hpp -- the delta texts of a CHAIN of RGB8 frames (trt_ansi_delta_chain.h: a shown frame, n frames back to back, text b
+// between frames b - 1 and b), written on the device: three launches in stream order whatever n is.  The text between two frames is a
+// chain of one: there is no other set of kernels.  A text has one of two KINDS of cell: the full text's, two columns wide
+// (trt_ansi_delta.h), and half-block cells, two pixel rows a cell (trt_ansi_delta_half.h).  Each header holds its format, the record
+// lengths and bytes, and the LANE'S WALK: which bytes of the two frames a lane loads for its cells.  This file holds the tile scheme,
+// once for both kinds: the prefix sum that gives every record its place.
 //
-//   measure   a workgroup per tile of TRT_DELTA_TILE cells (row-major; over the TEXT rows for half-block cells), a lane per
-//             TRT_DELTA_LANE_CELLS consecutive cells: the kind's walk reads both frames and sums the lengths of the lane's records, the
-//             wave is reduced (__shfl_down), the waves' sums added through LDS: one 32-bit sum per tile (at most 1024 x 57 = 58 368)
-//   offsets   ONE workgroup scans the tiles' sums exclusively into 64-bit offsets, TRT_DELTA_SCAN_BLOCK sums per turn with a running
-//             total, and stores the text's length
-//   write     the walk again, an exclusive scan over the wave (__shfl_up), one over the waves' totals through LDS, and every lane
-//             stores its records at tile offset + wave offset + lane offset, a byte at a time
+//   measure   a grid of tiles x n, the pair in blockIdx.y: a workgroup per tile of TRT_DELTA_TILE cells (row-major; over the TEXT rows
+//             for half-block cells), a lane per TRT_DELTA_LANE_CELLS consecutive cells: the kind's walk reads the pair's two frames and
+//             sums the lengths of the lane's records, the wave is reduced (__shfl_down), the waves' sums added through LDS: one 32-bit
+//             sum per tile (at most 1024 x 57 = 58 368)
+//   offsets   ONE workgroup scans all n * tiles sums exclusively into 64-bit offsets, TRT_DELTA_SCAN_BLOCK sums per turn with a running
+//             total, and stores the n texts' lengths
+//   write     the grid and the walk again, an exclusive scan over the wave (__shfl_up), one over the waves' totals through LDS, and
+//             every lane stores its records at tile offset + wave offset + lane offset, a byte at a time
 //
-// No workgroup waits for another one -- the order is the stream's -- and there is no atomic: the text is a function of the two frames.
-// Every byte below the length is stored once and none behind it.  The frames and the text may have any alignment: everything is
-// read and stored by bytes; the lower row of an odd frame's last half-block text row is NOT loaded -- behind the frame is somebody
-// else's memory.  LDS: the waves' sums, nothing else.
-//
-// A CHAIN of n texts (trt_ansi_delta_chain.h: a shown frame, n frames back to back, text b between frames b - 1 and b) is the same three
-// launches: measure and write on a grid of tiles x n, the pair in blockIdx.y, and one scan over all n * tiles sums, which also stores the n
-// lengths.  The texts stand back to back; the walks and the bodies are the ones above.
+// No workgroup waits for another one -- the order is the stream's -- and there is no atomic: a text is a function of its two frames, and
+// the texts stand back to back.  Every byte below the lengths' sum is stored once and none behind it.  The frames and the texts may have
+// any alignment: everything is read and stored by bytes; the lower row of an odd frame's last half-block text row is NOT loaded -- behind
+// the shown frame is somebody else's memory, behind a frame of the chain the next one.  LDS: the waves' sums, nothing else.
 #pragma once
 
 #include "trt_ansi_delta.h"
@@ -107,29 +106,6 @@ __device__ __forceinline__ void delta_write(const unsigned char *shown, const un
     }
 }
 
-// the four kernels: the two bodies, of each kind
-__global__ __launch_bounds__(TRT_DELTA_BLOCK) void ansi_delta_measure_kernel(const unsigned char *shown, const unsigned char *next, int width, int rows, unsigned *tile_bytes)
-{
-    delta_measure<DeltaFull>(shown, next, width, rows, tile_bytes);
-}
-
-__global__ __launch_bounds__(TRT_DELTA_BLOCK) void ansi_delta_half_measure_kernel(const unsigned char *shown, const unsigned char *next, int width, int rows, unsigned *tile_bytes)
-{
-    delta_measure<DeltaHalf>(shown, next, width, rows, tile_bytes);
-}
-
-__global__ __launch_bounds__(TRT_DELTA_BLOCK) void ansi_delta_write_kernel(const unsigned char *shown, const unsigned char *next, int width, int rows, const unsigned long long *tile_at,
-                                                                          unsigned char *out, unsigned long long capacity)
-{
-    delta_write<DeltaFull>(shown, next, width, rows, tile_at, out, capacity);
-}
-
-__global__ __launch_bounds__(TRT_DELTA_BLOCK) void ansi_delta_half_write_kernel(const unsigned char *shown, const unsigned char *next, int width, int rows, const unsigned long long *tile_at,
-                                                                               unsigned char *out, unsigned long long capacity)
-{
-    delta_write<DeltaHalf>(shown, next, width, rows, tile_at, out, capacity);
-}
-
 // The exclusive scan of `count` sums into 64-bit offsets that start at `base`, by ONE workgroup of TRT_DELTA_SCAN_BLOCK threads:
 // TRT_DELTA_SCAN_BLOCK sums per turn with a running total, which every thread returns: base + all sums
 __device__ __forceinline__ unsigned long long delta_scan(const unsigned *tile_bytes, unsigned long long count, unsigned long long base, unsigned long long *tile_at)
@@ -166,17 +142,8 @@ __device__ __forceinline__ unsigned long long delta_scan(const unsigned *tile_by
     return running;
 }
 
-// launched as ONE workgroup of TRT_DELTA_SCAN_BLOCK threads
-__global__ __launch_bounds__(TRT_DELTA_SCAN_BLOCK) void ansi_delta_offsets_kernel(const unsigned *tile_bytes, unsigned long long tiles, unsigned long long *tile_at,
-                                                                                 unsigned long long *text_bytes)
-{
-    const unsigned long long running = delta_scan(tile_bytes, tiles, 0, tile_at);
-    if (threadIdx.x == 0)
-        *text_bytes = running;
-}
-
-// ---- a chain of n texts (trt_ansi_delta_chain.h): grids of dim3(tiles, n), blockIdx.y the pair; the bodies above, given the pair's two
-// frames and the pair's slice of the tile arrays.  `out` and `capacity` are the whole buffer's: the offsets are the chain's ----
+// ---- the kernels, on grids of dim3(tiles, n), blockIdx.y the pair (n = 1: the text between two frames): the bodies above, given the
+// pair's two frames and the pair's slice of the tile arrays.  `out` and `capacity` are the whole buffer's: the offsets are the chain's ----
 
 template <class Kind>
 __device__ __forceinline__ void delta_chain_measure(const unsigned char *shown, const unsigned char *frames, int width, int rows, unsigned *tile_bytes)

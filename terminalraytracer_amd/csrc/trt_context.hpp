@@ -206,18 +206,19 @@ struct trt_context
     DeviceBuffer<unsigned char> d_rgb8; // trt_render_host_rgb8: the quantised frame before it crosses PCIe
     DeviceBuffer<unsigned char> d_text; // trt_render_host_ansi: the terminal's text before it crosses PCIe
     DeviceBuffer<unsigned char> d_text_rgb8; // text frames of the reference-order kernel: the bytes the text is formatted from
-    // The delta text (trt_render_device_ansi_delta, trt_ansi_delta.hpp).  The SHOWN frame: the RGB8 bytes of the frame the terminal was
-    // last sent, in d_shown[shown_at], for the rowset shown_rows; the next frame is rendered into the other buffer and the two swap.
-    DeviceBuffer<unsigned char> d_shown[2];
-    int shown_at = 0;
+    // The delta texts (trt_render_device_ansi_delta, trt_render_device_batch_ansi_delta, trt_ansi_delta.hpp).  A call renders its n frames
+    // as RGB8 bytes, back to back, into d_delta_frames[shown_at ^ 1]; its texts are the chain against the SHOWN frame, the frame the
+    // terminal was last sent: frame shown_frame -- the last one of the call before -- of d_delta_frames[shown_at], for the rowset
+    // shown_rows.  Then the two flip.  Only the buffer being rendered into may grow: a buffer that grows loses its contents.
+    DeviceBuffer<unsigned char> d_delta_frames[2];
+    int shown_at = 0, shown_frame = 0;
     bool shown_valid = false; // false: the next delta call sends a keyframe
     bool shown_half = false;  // the text the shown frame was sent as: half-block cells (trt_ansi_delta_half.h) or the full text's;
                               // a delta call of the other kind sends a keyframe
     trt_rowset shown_rows{};
     DeviceBuffer<unsigned> d_delta_tile_bytes;         // per tile of cells: the bytes of its records
     DeviceBuffer<unsigned long long> d_delta_tile_at;  // ... and where they start in the text
-    DeviceBuffer<unsigned long long> d_delta_bytes;    // trt_render_host_ansi_delta: the text's length before it crosses PCIe
-    DeviceBuffer<unsigned char> d_chain;               // trt_render_device_batch_ansi_delta: the batch's frames as RGB8 bytes, back to back
+    DeviceBuffer<unsigned long long> d_delta_bytes;    // trt_render_host_ansi_delta: the texts' lengths before they cross PCIe
     int ior_count = 0;          // 0 = off (the reference's path)
     DeviceBuffer<unsigned long long> d_counters;
     DeviceBuffer<unsigned int> d_queue;

@@ -1214,7 +1214,10 @@ extern "C" int trt_kernel_info(trt_context *ctx, int *vgprs, int *sgprs, int *st
     return TRT_OK;
 }
 
-// ---- the delta texts (trt_ansi_delta.h: the full text's cells; trt_ansi_delta_half.h: half-block cells; trt_ansi_delta.hpp: the kernels of both) ----
+// ---- the delta texts (trt_ansi_delta.h: the full text's cells; trt_ansi_delta_half.h: half-block cells; trt_ansi_delta_chain.h: a chain of n
+// texts; trt_ansi_delta.hpp: the kernels).  ONE path: the text between two frames is a chain of one, a single frame a batch of one ----
+
+static_assert(TRT_DELTA_CHAIN_MAX == TRT_BATCH_MAX, "a chain holds a batch's frames");
 
 extern "C" size_t trt_ansi_delta_capacity(int width, int rows)
 {
@@ -1233,119 +1236,21 @@ extern "C" size_t trt_ansi_delta_half_capacity(int width, int rows)
 // room for any text of the kind: half-block cells or the full text's
 static size_t delta_capacity(bool half, int width, int rows) { return half ? trt_ansi_delta_half_capacity(width, rows) : trt_ansi_delta_capacity(width, rows); }
 
-// measure, offsets, write on `stream`, of the full text's cells or of half-block cells (the tiles are then of the text rows' cells; the
-// offsets kernel is the same); marks: four events, recorded around and between the launches (trt_ansi_delta_kernel_times)
-static int launch_ansi_delta(trt_context *ctx, hipStream_t stream, bool half, const unsigned char *d_shown, const unsigned char *d_next, int width, int rows, void *d_text,
-                             size_t capacity_bytes, unsigned long long *d_bytes, const Event *marks = nullptr)
+// the frames a delta text of the kind exists for: TRT_OK, or the refusal
+static int check_delta_size(bool half, int width, int rows)
 {
-    static const struct
-    {
-        void (*measure)(const unsigned char *, const unsigned char *, int, int, unsigned *);
-        void (*write)(const unsigned char *, const unsigned char *, int, int, const unsigned long long *, unsigned char *, unsigned long long);
-    } kernels[2] = {{trt::ansi_delta_measure_kernel, trt::ansi_delta_write_kernel}, {trt::ansi_delta_half_measure_kernel, trt::ansi_delta_half_write_kernel}};
-    const unsigned long long cells = (unsigned long long)width * (unsigned long long)(half ? trt_ansi_half_text_rows(rows) : rows), tiles = trt_delta_tiles(cells);
-    if (ctx->d_delta_tile_bytes.capacity < tiles || ctx->d_delta_tile_at.capacity < tiles)
-        HIP_TRY(hipStreamSynchronize(stream)); // a text in flight may still use the old sums
-    HIP_TRY(ctx->d_delta_tile_bytes.reserve((size_t)tiles));
-    HIP_TRY(ctx->d_delta_tile_at.reserve((size_t)tiles));
-    if (marks)
-        HIP_TRY(hipEventRecord(marks[0], stream));
-    hipLaunchKernelGGL(kernels[half].measure, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, rows, ctx->d_delta_tile_bytes.ptr);
-    if (marks)
-        HIP_TRY(hipEventRecord(marks[1], stream));
-    hipLaunchKernelGGL(trt::ansi_delta_offsets_kernel, dim3(1), dim3(TRT_DELTA_SCAN_BLOCK), 0, stream, (const unsigned *)ctx->d_delta_tile_bytes.ptr, tiles,
-                       ctx->d_delta_tile_at.ptr, d_bytes);
-    if (marks)
-        HIP_TRY(hipEventRecord(marks[2], stream));
-    hipLaunchKernelGGL(kernels[half].write, dim3((unsigned)tiles), dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_next, width, rows,
-                       (const unsigned long long *)ctx->d_delta_tile_at.ptr, (unsigned char *)d_text, (unsigned long long)capacity_bytes);
-    if (marks)
-        HIP_TRY(hipEventRecord(marks[3], stream));
-    HIP_TRY(hipGetLastError());
-    return TRT_OK;
+    if (half ? trt_delta_half_size_ok(width, rows) : trt_delta_size_ok(width, rows))
+        return TRT_OK;
+    return half ? fail(TRT_ERR_ARGUMENT, "%d x %d: a half-block delta text has 1 to %d cells per row and 1 to %d text rows", width, rows, TRT_DELTA_HALF_MAX_WIDTH,
+                       TRT_DELTA_HALF_MAX_TEXT_ROWS)
+                : fail(TRT_ERR_ARGUMENT, "%d x %d: a delta text has 1 to %d cells per row and 1 to %d rows", width, rows, TRT_DELTA_MAX_WIDTH, TRT_DELTA_MAX_ROWS);
 }
 
-static int check_delta_from_rgb8(const trt_context *ctx, bool half, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, const void *d_text,
-                                 size_t capacity_bytes, const unsigned long long *d_bytes)
-{
-    if (!ctx || !d_shown_rgb8 || !d_next_rgb8 || !d_text || !d_bytes)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (!half && !trt_delta_size_ok(width, rows))
-        return fail(TRT_ERR_ARGUMENT, "screen %d x %d: a delta text has 1 to %d cells per row and 1 to %d rows", width, rows, TRT_DELTA_MAX_WIDTH, TRT_DELTA_MAX_ROWS);
-    if (half && !trt_delta_half_size_ok(width, rows))
-        return fail(TRT_ERR_ARGUMENT, "screen %d x %d: a half-block delta text has 1 to %d cells per row and 1 to %d text rows", width, rows, TRT_DELTA_HALF_MAX_WIDTH,
-                    TRT_DELTA_HALF_MAX_TEXT_ROWS);
-    if (capacity_bytes < delta_capacity(half, width, rows))
-        return fail(TRT_ERR_CAPACITY, "the delta text of %d x %d needs room for %zu B, %zu given", width, rows, delta_capacity(half, width, rows), capacity_bytes);
-    return TRT_OK;
-}
-
-// trt_ansi_delta_from_rgb8_device and trt_ansi_delta_half_from_rgb8_device
-static int delta_from_rgb8(trt_context *ctx, bool half, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text, size_t capacity_bytes,
-                           unsigned long long *d_bytes)
-{
-    const int rc = check_delta_from_rgb8(ctx, half, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
-    if (rc)
-        return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    return launch_ansi_delta(ctx, ctx->stream, half, (const unsigned char *)d_shown_rgb8, (const unsigned char *)d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
-}
-
-extern "C" int trt_ansi_delta_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
-                                               size_t capacity_bytes, unsigned long long *d_bytes)
-{
-    return delta_from_rgb8(ctx, false, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
-}
-
-extern "C" int trt_ansi_delta_half_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
-                                                    size_t capacity_bytes, unsigned long long *d_bytes)
-{
-    return delta_from_rgb8(ctx, true, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
-}
-
-// trt_ansi_delta_kernel_times and trt_ansi_delta_half_kernel_times
-static int delta_kernel_times(trt_context *ctx, bool half, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text, size_t capacity_bytes,
-                              unsigned long long *d_bytes, float *ms)
-{
-    if (!ms)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    int rc = check_delta_from_rgb8(ctx, half, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes);
-    if (rc)
-        return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    Event marks[4];
-    for (Event &e : marks)
-        HIP_TRY(e.create());
-    rc = launch_ansi_delta(ctx, ctx->stream, half, (const unsigned char *)d_shown_rgb8, (const unsigned char *)d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes,
-                           marks);
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (rc)
-        return rc;
-    for (int k = 0; k < 3; k++)
-        HIP_TRY(hipEventElapsedTime(&ms[k], marks[k], marks[k + 1]));
-    return TRT_OK;
-}
-
-extern "C" int trt_ansi_delta_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
-                                           size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
-{
-    return delta_kernel_times(ctx, false, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes, ms);
-}
-
-extern "C" int trt_ansi_delta_half_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
-                                                size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
-{
-    return delta_kernel_times(ctx, true, d_shown_rgb8, d_next_rgb8, width, rows, d_text, capacity_bytes, d_bytes, ms);
-}
-
-// ---- a chain of delta texts (trt_ansi_delta_chain.h): n texts back to back, three launches whatever n is ----
-
-static_assert(TRT_DELTA_CHAIN_MAX == TRT_BATCH_MAX, "a chain holds a batch's frames");
-
-// measure, offsets, write on `stream` for the pairs (d_shown, frame 0), (frame 0, frame 1) ... of the n frames at d_frames: text b at d_text +
-// base + the lengths before it, its length at d_bytes[b]; capacity_bytes: the bytes at d_text; marks as in launch_ansi_delta
-static int launch_ansi_delta_chain(trt_context *ctx, hipStream_t stream, bool half, const unsigned char *d_shown, const unsigned char *d_frames, int n, int width, int rows,
-                                   void *d_text, size_t capacity_bytes, unsigned long long base, unsigned long long *d_bytes, const Event *marks = nullptr)
+// measure, offsets, write on `stream` for the pairs (d_shown, frame 0), (frame 0, frame 1) ... of the n frames at d_frames, of the full text's
+// cells or of half-block cells (the tiles are then of the text rows' cells): text b at d_text + base + the lengths before it, its length at
+// d_bytes[b]; capacity_bytes: the bytes at d_text; marks: four events, recorded around and between the launches (the ..._kernel_times entries)
+static int launch_ansi_delta(trt_context *ctx, hipStream_t stream, bool half, const unsigned char *d_shown, const unsigned char *d_frames, int n, int width, int rows,
+                             void *d_text, size_t capacity_bytes, unsigned long long base, unsigned long long *d_bytes, const Event *marks = nullptr)
 {
     static const struct
     {
@@ -1376,38 +1281,30 @@ static int launch_ansi_delta_chain(trt_context *ctx, hipStream_t stream, bool ha
     return TRT_OK;
 }
 
-static int check_delta_chain_from_rgb8(const trt_context *ctx, bool half, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, const void *d_text,
-                                       size_t capacity_bytes, const unsigned long long *d_bytes)
+// The formatting alone, all eight entries: trt_ansi_delta(_half)_from_rgb8_device with d_next as a chain of one frame,
+// trt_ansi_delta(_half)_chain_from_rgb8_device, and with `ms` their ..._kernel_times forms, which are synchronous
+static int delta_from_rgb8(trt_context *ctx, bool half, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text, size_t capacity_bytes,
+                           unsigned long long *d_bytes, float *ms = nullptr)
 {
+    if (!ctx || !d_shown_rgb8 || !d_frames_rgb8 || !d_text || !d_bytes)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
     if (n < 1 || n > TRT_BATCH_MAX)
         return fail(TRT_ERR_ARGUMENT, "a chain has 1 to %d frames, %d given", TRT_BATCH_MAX, n);
-    // one text's checks, then room for n of them
-    const int rc = check_delta_from_rgb8(ctx, half, d_shown_rgb8, d_frames_rgb8, width, rows, d_text, (size_t)-1, d_bytes);
+    int rc = check_delta_size(half, width, rows);
     if (rc)
         return rc;
     const size_t need = (size_t)n * delta_capacity(half, width, rows);
     if (capacity_bytes < need)
-        return fail(TRT_ERR_CAPACITY, "%d delta texts of %d x %d need room for %zu B, %zu given", n, width, rows, need, capacity_bytes);
-    return TRT_OK;
-}
-
-// trt_ansi_delta_chain_from_rgb8_device and trt_ansi_delta_half_chain_from_rgb8_device; ms: trt_ansi_delta_chain_kernel_times and
-// trt_ansi_delta_half_chain_kernel_times, which are synchronous
-static int delta_chain_from_rgb8(trt_context *ctx, bool half, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
-                                 size_t capacity_bytes, unsigned long long *d_bytes, float *ms = nullptr)
-{
-    int rc = check_delta_chain_from_rgb8(ctx, half, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes);
-    if (rc)
-        return rc;
+        return fail(TRT_ERR_CAPACITY, "%d delta text(s) of %d x %d need room for %zu B, %zu given", n, width, rows, need, capacity_bytes);
     HIP_TRY(hipSetDevice(ctx->device));
-    if (!ms)
-        return launch_ansi_delta_chain(ctx, ctx->stream, half, (const unsigned char *)d_shown_rgb8, (const unsigned char *)d_frames_rgb8, n, width, rows, d_text,
-                                       capacity_bytes, 0, d_bytes);
     Event marks[4];
-    for (Event &e : marks)
-        HIP_TRY(e.create());
-    rc = launch_ansi_delta_chain(ctx, ctx->stream, half, (const unsigned char *)d_shown_rgb8, (const unsigned char *)d_frames_rgb8, n, width, rows, d_text, capacity_bytes, 0,
-                                 d_bytes, marks);
+    if (ms)
+        for (Event &e : marks)
+            HIP_TRY(e.create());
+    rc = launch_ansi_delta(ctx, ctx->stream, half, (const unsigned char *)d_shown_rgb8, (const unsigned char *)d_frames_rgb8, n, width, rows, d_text, capacity_bytes, 0, d_bytes,
+                           ms ? marks : nullptr);
+    if (!ms)
+        return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (rc)
         return rc;
@@ -1416,32 +1313,52 @@ static int delta_chain_from_rgb8(trt_context *ctx, bool half, const void *d_show
     return TRT_OK;
 }
 
+extern "C" int trt_ansi_delta_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                               size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return delta_from_rgb8(ctx, false, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes);
+}
+
+extern "C" int trt_ansi_delta_half_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                                    size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return delta_from_rgb8(ctx, true, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes);
+}
+
+extern "C" int trt_ansi_delta_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                           size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
+{
+    return ms ? delta_from_rgb8(ctx, false, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
+}
+
+extern "C" int trt_ansi_delta_half_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                                size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
+{
+    return ms ? delta_from_rgb8(ctx, true, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
+}
+
 extern "C" int trt_ansi_delta_chain_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
                                                      size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    return delta_chain_from_rgb8(ctx, false, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes);
+    return delta_from_rgb8(ctx, false, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes);
 }
 
 extern "C" int trt_ansi_delta_half_chain_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
                                                           size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    return delta_chain_from_rgb8(ctx, true, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes);
+    return delta_from_rgb8(ctx, true, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes);
 }
 
 extern "C" int trt_ansi_delta_chain_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
                                                  size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
 {
-    if (!ms)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    return delta_chain_from_rgb8(ctx, false, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes, ms);
+    return ms ? delta_from_rgb8(ctx, false, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
 }
 
 extern "C" int trt_ansi_delta_half_chain_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
                                                       size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
 {
-    if (!ms)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    return delta_chain_from_rgb8(ctx, true, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes, ms);
+    return ms ? delta_from_rgb8(ctx, true, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
 }
 
 // ---- the render entries of both delta texts: one shown frame, which remembers the kind of text it was sent as ----
@@ -1454,27 +1371,24 @@ extern "C" int trt_ansi_delta_reset(trt_context *ctx)
     return TRT_OK;
 }
 
-// what the render entries refuse before anything is enqueued; `text`: the caller's buffer, on the device or on the host, with room for
-// the texts of `frames` cameras (the batch entries: what trt_render_device_batch_rgb8 refuses, and room for every text)
-static int check_render_delta(const trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, const void *text,
-                              size_t capacity_bytes, const void *bytes, bool half, int frames = 1)
+// what the render entries refuse before anything is enqueued: what trt_render_device_batch_rgb8 refuses for the n cameras, and a `text` --
+// the caller's buffer, on the device or on the host -- without room for n texts
+static int check_render_delta(const trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, const void *text,
+                              size_t capacity_bytes, const void *bytes, bool half)
 {
     if (!bytes)
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (!half && rowset_valid(rows) && !trt_delta_size_ok(rows->width, trt_rowset_rows(rows)))
-        return fail(TRT_ERR_ARGUMENT, "%d x %d owned rows: a delta text has 1 to %d cells per row and 1 to %d rows", rows->width, trt_rowset_rows(rows), TRT_DELTA_MAX_WIDTH,
-                    TRT_DELTA_MAX_ROWS);
-    if (half && rowset_valid(rows) && !trt_delta_half_size_ok(rows->width, trt_rowset_rows(rows)))
-        return fail(TRT_ERR_ARGUMENT, "%d x %d owned rows: a half-block delta text has 1 to %d cells per row and 1 to %d text rows", rows->width, trt_rowset_rows(rows),
-                    TRT_DELTA_HALF_MAX_WIDTH, TRT_DELTA_HALF_MAX_TEXT_ROWS);
-    // the rest as the RGB8 entry checks it, whose frame these sizes let fit
-    const int rc = check_render_arguments(ctx, camera, frames, rows, bounce_limit, rays_per_pixel, text, (size_t)-1, kBytes);
+    int rc = rowset_valid(rows) ? check_delta_size(half, rows->width, trt_rowset_rows(rows)) : TRT_OK;
     if (rc)
         return rc;
-    const size_t need = (size_t)frames * delta_capacity(half, rows->width, trt_rowset_rows(rows));
+    // the rest as the RGB8 entry checks it, whose frame these sizes let fit
+    rc = check_render_arguments(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, text, (size_t)-1, kBytes);
+    if (rc)
+        return rc;
+    const size_t need = (size_t)n * delta_capacity(half, rows->width, trt_rowset_rows(rows));
     if (capacity_bytes < need)
-        return fail(TRT_ERR_CAPACITY, "%d text(s) of %d x %d owned rows need room for %zu B, %zu given", frames, rows->width, trt_rowset_rows(rows), need, capacity_bytes);
-    return check_batch_tables(ctx, frames);
+        return fail(TRT_ERR_CAPACITY, "%d text(s) of %d x %d owned rows need room for %zu B, %zu given", n, rows->width, trt_rowset_rows(rows), need, capacity_bytes);
+    return check_batch_tables(ctx, n);
 }
 
 static bool same_rowset(const trt_rowset &a, const trt_rowset &b)
@@ -1482,11 +1396,13 @@ static bool same_rowset(const trt_rowset &a, const trt_rowset &b)
     return a.width == b.width && a.height == b.height && a.tile_rows == b.tile_rows && a.tile_first == b.tile_first && a.tile_step == b.tile_step;
 }
 
-// trt_render_device_ansi_delta and trt_render_device_ansi_delta_half
-static int render_device_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text, size_t capacity_bytes,
-                               unsigned long long *d_bytes, bool half)
+// trt_render_device_ansi_delta and trt_render_device_batch_ansi_delta, and their _half forms: n cameras as n texts back to back, text 0
+// against the shown frame.  `batch` as in render_host_as: the batch route, which picks the render kernel's BATCH form and counts for
+// trt_batch_info; otherwise n is 1 and the frame is the single frame's launch.
+static int render_device_delta(trt_context *ctx, const Camera *cameras, int n, bool batch, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                               size_t capacity_bytes, unsigned long long *d_bytes, bool half)
 {
-    int rc = check_render_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, half);
+    int rc = check_render_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, half);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1494,34 +1410,38 @@ static int render_device_delta(trt_context *ctx, const Camera *camera, const trt
     const size_t frame = (size_t)owned * width * 3;
     const bool keyframe = !(ctx->shown_valid && ctx->shown_half == half && same_rowset(ctx->shown_rows, *rows));
     const int into = ctx->shown_at ^ 1;
-    if (ctx->d_shown[0].capacity < frame || ctx->d_shown[1].capacity < frame)
-    { // another size: a keyframe, which reads neither buffer's contents
+    if (ctx->d_delta_frames[into].capacity < frame * n)
+    { // only the buffer rendered into grows, with nothing in flight that uses it: a buffer that grows loses its contents, and the other one holds the shown frame
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx->d_shown[0].reserve(frame));
-        HIP_TRY(ctx->d_shown[1].reserve(frame));
+        HIP_TRY(ctx->d_delta_frames[into].reserve(frame * n));
     }
+    unsigned char *const frames = ctx->d_delta_frames[into].ptr;
     ctx->shown_valid = false; // a call that fails from here on has forgotten the shown frame
-    // the new frame's bytes: the RGB8 form of the ordered mean (the reference-order kernel: its doubles through quantize_kernel)
-    rc = render_device_on(ctx, camera, rows, bounce_limit, rays_per_pixel, ctx->d_shown[into].ptr, frame, 0, kEntryWhole, kBytes);
+    // the new frames' bytes, back to back: the RGB8 form of the ordered mean (the reference-order kernel: its doubles through quantize_kernel); a
+    // batch in one launch, split for LDS or one launch per camera, as trt_render_device_batch_rgb8 decides
+    rc = batch ? render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, frames, frame * n, kBytes)
+               : render_device_on(ctx, cameras, rows, bounce_limit, rays_per_pixel, frames, frame, 0, kEntryWhole, kBytes);
     if (rc)
         return rc;
     if (keyframe)
-    { // the whole text, as trt_render_device_ansi or trt_render_device_ansi_half writes it
+    { // text 0 is the whole text of frame 0, as trt_render_device_ansi or trt_render_device_ansi_half writes it; the chain of the pairs behind it starts where that text ends
+        const unsigned long long whole = frame_bytes(half ? kHalfText : kText, width, owned);
         if (half)
-            launch_ansi_half_from_rgb8(ctx->stream, ctx->d_shown[into].ptr, width, owned, d_text);
+            launch_ansi_half_from_rgb8(ctx->stream, frames, width, owned, d_text);
         else
-            launch_ansi_from_rgb8(ctx->stream, ctx->d_shown[into].ptr, width, owned, d_text);
-        hipLaunchKernelGGL(trt::ansi_delta_keyframe_bytes_kernel, dim3(1), dim3(1), 0, ctx->stream, d_bytes,
-                           half ? trt_ansi_half_text_bytes(width, owned) : trt_ansi_text_bytes(width, owned));
+            launch_ansi_from_rgb8(ctx->stream, frames, width, owned, d_text);
+        hipLaunchKernelGGL(trt::ansi_delta_keyframe_bytes_kernel, dim3(1), dim3(1), 0, ctx->stream, d_bytes, whole);
         HIP_TRY(hipGetLastError());
+        if (n > 1)
+            rc = launch_ansi_delta(ctx, ctx->stream, half, frames, frames + frame, n - 1, width, owned, d_text, capacity_bytes, whole, d_bytes + 1);
     }
-    else
-    {
-        rc = launch_ansi_delta(ctx, ctx->stream, half, ctx->d_shown[ctx->shown_at].ptr, ctx->d_shown[into].ptr, width, owned, d_text, capacity_bytes, d_bytes);
-        if (rc)
-            return rc;
-    }
-    ctx->shown_at = into;
+    else // a shown frame of this size: the other buffer holds it, untouched since the call that rendered it
+        rc = launch_ansi_delta(ctx, ctx->stream, half, ctx->d_delta_frames[ctx->shown_at].ptr + (size_t)ctx->shown_frame * frame, frames, n, width, owned, d_text, capacity_bytes,
+                               0, d_bytes);
+    if (rc)
+        return rc;
+    ctx->shown_at = into; // the buffers flip: the last frame is the shown one from here on, where it was rendered
+    ctx->shown_frame = n - 1;
     ctx->shown_rows = *rows;
     ctx->shown_half = half;
     ctx->shown_valid = true;
@@ -1531,141 +1451,33 @@ static int render_device_delta(trt_context *ctx, const Camera *camera, const trt
 extern "C" int trt_render_device_ansi_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
                                             size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    return render_device_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, false);
+    return render_device_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, false);
 }
 
 extern "C" int trt_render_device_ansi_delta_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
                                                  size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    return render_device_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, true);
-}
-
-// trt_render_host_ansi_delta and trt_render_host_ansi_delta_half
-static int render_host_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text, size_t capacity_bytes,
-                             size_t *bytes, bool half)
-{
-    int rc = check_render_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, half);
-    if (rc)
-        return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t room = delta_capacity(half, rows->width, trt_rowset_rows(rows));
-    if (ctx->d_text.capacity < room)
-        HIP_TRY(hipStreamSynchronize(ctx->stream)); // a text in flight may still be written to the old buffer
-    HIP_TRY(ctx->d_text.reserve(room));
-    HIP_TRY(ctx->d_delta_bytes.reserve(1));
-    HIP_TRY(ctx->h_staging.reserve(room));
-    const double t_begin = host_now_ms();
-    rc = render_device_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, room, ctx->d_delta_bytes.ptr, half);
-    if (rc)
-        return rc;
-    // two small transfers instead of one large one: the length, then exactly that many bytes
-    unsigned long long length = 0;
-    rc = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_delta_bytes.ptr, sizeof length, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        memcpy(&length, ctx->h_staging.ptr, sizeof length);
-        if (length > room)
-            return fail(TRT_ERR_CAPACITY, "a text of %llu B where %zu are the most", length, room);
-        if (length)
-        {
-            HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_text.ptr, (size_t)length, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            memcpy(text, ctx->h_staging.ptr, (size_t)length);
-        }
-        return TRT_OK;
-    }();
-    if (rc)
-    { // the host did not get the text: the terminal does not show this frame
-        ctx->shown_valid = false;
-        return rc;
-    }
-    *bytes = (size_t)length;
-    if (print_host_times())
-        fprintf(stderr, "trt_render_host_ansi_delta%s: %.3f ms for %llu bytes of text\n", half ? "_half" : "", host_now_ms() - t_begin, length);
-    return TRT_OK;
-}
-
-extern "C" int trt_render_host_ansi_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
-                                          size_t capacity_bytes, size_t *bytes)
-{
-    return render_host_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, false);
-}
-
-extern "C" int trt_render_host_ansi_delta_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
-                                               size_t capacity_bytes, size_t *bytes)
-{
-    return render_host_delta(ctx, camera, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, true);
-}
-
-// ---- the batch forms: n cameras in one render, their n delta texts back to back as one chain ----
-
-// trt_render_device_batch_ansi_delta and trt_render_device_batch_ansi_delta_half
-static int render_device_batch_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
-                                     size_t capacity_bytes, unsigned long long *d_bytes, bool half)
-{
-    int rc = check_render_delta(ctx, cameras, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, half, n);
-    if (rc)
-        return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const int width = rows->width, owned = trt_rowset_rows(rows);
-    const size_t frame = (size_t)owned * width * 3;
-    const bool keyframe = !(ctx->shown_valid && ctx->shown_half == half && same_rowset(ctx->shown_rows, *rows));
-    const int into = ctx->shown_at ^ 1;
-    if (ctx->d_shown[0].capacity < frame || ctx->d_shown[1].capacity < frame || ctx->d_chain.capacity < frame * n)
-    { // nothing in flight may use a buffer that grows; shown frames that grow are of another size: a keyframe, which reads neither's contents
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx->d_shown[0].reserve(frame));
-        HIP_TRY(ctx->d_shown[1].reserve(frame));
-        HIP_TRY(ctx->d_chain.reserve(frame * n));
-    }
-    ctx->shown_valid = false; // a call that fails from here on has forgotten the shown frame
-    // the batch's frames as bytes, back to back: one launch, a split for LDS or one launch per camera, as trt_render_device_batch_rgb8 decides
-    rc = render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, ctx->d_chain.ptr, frame * n, kBytes);
-    if (rc)
-        return rc;
-    const unsigned char *const frames = ctx->d_chain.ptr;
-    if (keyframe)
-    { // text 0 is the whole text of frame 0; the chain of the pairs behind it starts where that text ends
-        const unsigned long long whole = half ? trt_ansi_half_text_bytes(width, owned) : trt_ansi_text_bytes(width, owned);
-        if (half)
-            launch_ansi_half_from_rgb8(ctx->stream, frames, width, owned, d_text);
-        else
-            launch_ansi_from_rgb8(ctx->stream, frames, width, owned, d_text);
-        hipLaunchKernelGGL(trt::ansi_delta_keyframe_bytes_kernel, dim3(1), dim3(1), 0, ctx->stream, d_bytes, whole);
-        HIP_TRY(hipGetLastError());
-        if (n > 1)
-            rc = launch_ansi_delta_chain(ctx, ctx->stream, half, frames, frames + frame, n - 1, width, owned, d_text, capacity_bytes, whole, d_bytes + 1);
-    }
-    else
-        rc = launch_ansi_delta_chain(ctx, ctx->stream, half, ctx->d_shown[ctx->shown_at].ptr, frames, n, width, owned, d_text, capacity_bytes, 0, d_bytes);
-    if (rc)
-        return rc;
-    // the last frame is the shown one from here on: the one copy of a frame's bytes
-    HIP_TRY(hipMemcpyAsync(ctx->d_shown[into].ptr, frames + (size_t)(n - 1) * frame, frame, hipMemcpyDeviceToDevice, ctx->stream));
-    ctx->shown_at = into;
-    ctx->shown_rows = *rows;
-    ctx->shown_half = half;
-    ctx->shown_valid = true;
-    return TRT_OK;
+    return render_device_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, true);
 }
 
 extern "C" int trt_render_device_batch_ansi_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
                                                   size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    return render_device_batch_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, false);
+    return render_device_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, false);
 }
 
 extern "C" int trt_render_device_batch_ansi_delta_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
                                                        void *d_text, size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    return render_device_batch_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, true);
+    return render_device_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, true);
 }
 
-// trt_render_host_batch_ansi_delta and trt_render_host_batch_ansi_delta_half
-static int render_host_batch_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
-                                   size_t capacity_bytes, size_t *bytes, bool half)
+// The copy-out of the four host entries, timed as `name` under print_host_times(): the n texts in the context's text buffer, their
+// lengths read back, then exactly their sum -- two transfers whatever n is.
+static int render_host_delta(trt_context *ctx, const Camera *cameras, int n, bool batch, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
+                             size_t capacity_bytes, size_t *bytes, bool half, const char *name)
 {
-    int rc = check_render_delta(ctx, cameras, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, half, n);
+    int rc = check_render_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, half);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1674,12 +1486,13 @@ static int render_host_batch_delta(trt_context *ctx, const Camera *cameras, int 
         HIP_TRY(hipStreamSynchronize(ctx->stream)); // a text in flight may still be written to the old buffers
     HIP_TRY(ctx->d_text.reserve(room));
     HIP_TRY(ctx->d_delta_bytes.reserve((size_t)n));
-    HIP_TRY(ctx->h_staging.reserve(sizeof(unsigned long long) * TRT_BATCH_MAX));
+    // Pinned staging.  A single frame: its text's capacity, once, so that a moving picture does not allocate pinned memory again and again as
+    // its texts grow.  A batch: the lengths now and the texts' sum when it is known -- n capacities are hundreds of MB at 1920x1080.
+    HIP_TRY(ctx->h_staging.reserve(batch ? sizeof(unsigned long long) * TRT_BATCH_MAX : room));
     const double t_begin = host_now_ms();
-    rc = render_device_batch_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, room, ctx->d_delta_bytes.ptr, half);
+    rc = render_device_delta(ctx, cameras, n, batch, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, room, ctx->d_delta_bytes.ptr, half);
     if (rc)
         return rc;
-    // two transfers for the batch: the n lengths, then exactly their sum, the staging grown to what the texts need
     unsigned long long length[TRT_BATCH_MAX] = {}, sum = 0;
     rc = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_delta_bytes.ptr, sizeof length[0] * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1688,7 +1501,7 @@ static int render_host_batch_delta(trt_context *ctx, const Camera *cameras, int 
         for (int b = 0; b < n; b++)
         {
             if (length[b] > room - sum)
-                return fail(TRT_ERR_CAPACITY, "texts of more than %zu B", room);
+                return fail(TRT_ERR_CAPACITY, "%d text(s) of more than %zu B", n, room);
             sum += length[b];
         }
         if (sum)
@@ -1708,18 +1521,30 @@ static int render_host_batch_delta(trt_context *ctx, const Camera *cameras, int 
     for (int b = 0; b < n; b++)
         bytes[b] = (size_t)length[b];
     if (print_host_times())
-        fprintf(stderr, "trt_render_host_batch_ansi_delta%s: %.3f ms for %d texts of %llu bytes\n", half ? "_half" : "", host_now_ms() - t_begin, n, sum);
+        fprintf(stderr, "%s: %.3f ms for %d text(s) of %llu bytes\n", name, host_now_ms() - t_begin, n, sum);
     return TRT_OK;
+}
+
+extern "C" int trt_render_host_ansi_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
+                                          size_t capacity_bytes, size_t *bytes)
+{
+    return render_host_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, false, "trt_render_host_ansi_delta");
+}
+
+extern "C" int trt_render_host_ansi_delta_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
+                                               size_t capacity_bytes, size_t *bytes)
+{
+    return render_host_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, true, "trt_render_host_ansi_delta_half");
 }
 
 extern "C" int trt_render_host_batch_ansi_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
                                                 size_t capacity_bytes, size_t *bytes)
 {
-    return render_host_batch_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, false);
+    return render_host_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, false, "trt_render_host_batch_ansi_delta");
 }
 
 extern "C" int trt_render_host_batch_ansi_delta_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
                                                      size_t capacity_bytes, size_t *bytes)
 {
-    return render_host_batch_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, true);
+    return render_host_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, true, "trt_render_host_batch_ansi_delta_half");
 }

@@ -3,7 +3,9 @@ and their _half forms; csrc/trt_ansi_delta_chain.h, trt_ansi_delta.hpp): the tex
 tiles of n pairs of frames -- three launches whatever n is.  The expected bytes never come from the device route: they are the sequential
 host statements host.emitter_delta_rgb8 / host.emitter_delta_half_rgb8 of consecutive pattern frames or of consecutive T.oracle_rgb8 frames,
 concatenated; keyframes are the host emitters' whole texts, and a model of a terminal must show every frame after its text.  Every device
-buffer stands between guard bytes of 0xA5, which also fill the unused room behind the last text: none of them may change."""
+buffer stands between guard bytes of 0xA5, which also fill the unused room behind the last text: none of them may change.  Section 3
+holds the ONE path behind all of these entries to what only it can break: the context's two frame buffers as they flip and grow under
+single-frame calls and batches, the single frame's render route behind a batch, the one-pair timing entries."""
 import ctypes as C
 import os
 import subprocess
@@ -242,7 +244,106 @@ def test_refusals_keep_the_shown_frame(ctx, kind):
     assert (text[lengths[0]:] == 0xA5).all() and list(lengths)[1:] == [77] * 8
 
 
-# ---- 3. the demo ----
+# ---- 3. one path: the context's two frame buffers flip under single-frame calls and batches alike; the one-pair entries are chains of one ----
+
+WHOLE, SHARD = hip.RowSet.whole(W, H_), hip.RowSet(W, H_, 8, 1, 3)
+HOST_SINGLE = {"full": hip.Context.render_host_ansi_delta, "half": hip.Context.render_host_ansi_delta_half}
+PAIR_TIMES = {"full": hip.Context.ansi_delta_kernel_times, "half": hip.Context.ansi_delta_half_kernel_times}
+# (rowset, a batch entry?, the orbit's cameras): the shown frame is the last frame of a buffer of eight while the other buffer, of one frame,
+# takes a batch of one, then lies in that buffer of one while the other takes eight; a shard's rows are a keyframe of another size
+FLIPS = [(WHOLE, False, [0]), (WHOLE, True, [1, 2, 3, 4, 5, 6, 7, 0]), (WHOLE, True, [1]), (WHOLE, True, [2, 3, 4, 5, 6, 7, 0, 1]), (WHOLE, False, [2]),
+         (SHARD, True, [0, 1]), (SHARD, False, [2])]
+# a fresh context's buffers are of one frame each after two single-frame calls: the batch's buffer GROWS from one frame to eight while the
+# shown frame lies in the other one, which a growing buffer's lost contents must not touch
+GROWS = [(WHOLE, False, [0]), (WHOLE, False, [1]), (WHOLE, True, [2, 3, 4, 5, 6, 7, 0, 1]), (WHOLE, False, [2])]
+
+
+def host_texts(ctx, kind, cams, rows, batch):
+    """the texts of the kind's host entry, single-frame or batch, written into a buffer between guard bytes that the room behind the texts continues"""
+    k = S.KINDS[kind]
+    capacity = len(cams) * k.capacity(rows.width, D.owned_rows(rows))
+    buf = np.full(D.GUARD + capacity + D.GUARD, 0xA5, dtype=np.uint8)
+    out = buf[D.GUARD:D.GUARD + capacity]
+    texts = k.render_host_batch(ctx, cams, rows, B, SPP, out) if batch else [HOST_SINGLE[kind](ctx, cams[0], rows, B, SPP, out)]
+    texts = [t.copy() for t in texts]
+    total = sum(t.size for t in texts)
+    assert (buf[:D.GUARD] == 0xA5).all() and (buf[D.GUARD + total:] == 0xA5).all(), "bytes outside the texts were written"
+    return texts
+
+
+@pytest.mark.parametrize("steps", [FLIPS, GROWS], ids=["flips", "grows"])
+@pytest.mark.parametrize("route", ["device", "host"])
+@pytest.mark.parametrize("kind", KIND_IDS)
+def test_the_shown_frame_stays_where_it_was_rendered(kind, route, steps):
+    """on a context of its own, whose buffers are as small as the calls so far made them: every text is the host's of the frame the terminal
+    shows and the next one, and the terminal, fed text by text, shows every frame"""
+    k = S.KINDS[kind]
+    with hip.Context(0) as ctx:
+        ctx.set_scene(D.scene("demo"))
+        shown_rows = last = term = None
+        for step, (rows, batch, indices) in enumerate(steps):
+            what = f"{kind} {route} step {step}"
+            cams, f = D.anim_cameras(indices, W, H_), frames_of("demo", indices, None if rows is WHOLE else rows)
+            if route == "host":
+                got = host_texts(ctx, kind, cams, rows, batch)
+            elif batch:
+                got = S.render_batch(ctx, k, cams, rows, step % 4, what)
+            else:
+                got = [k.render(ctx, cams[0], rows, offset=step % 4, what=what)]
+            if rows is not shown_rows:
+                shown_rows, term = rows, k.terminal(W, f[0].shape[0])
+                first = k.keyframe(f[0])
+            else:
+                first = k.delta(last, f[0])
+            S.same_texts(got, [first] + [k.delta(f[b - 1], f[b]) for b in range(1, len(f))], what)
+            fed(term, got, f, what)
+            last = f[-1]
+
+
+@pytest.mark.parametrize("kind", KIND_IDS)
+def test_a_single_frame_call_is_not_a_batch(ctx, kind):
+    """behind a batch of 3, a single-frame device call and a single-frame host call: trt_batch_info still tells of the batch, each is ONE
+    launch, and the kernel that ran is the one trt_render_device_rgb8 runs for the rowset -- the single frame's form"""
+    import torch
+    k = S.KINDS[kind]
+    ctx.set_scene(D.scene("demo"))
+    ctx.set_kernel(hip.Context.PRODUCTION)
+    cams, f = D.anim_cameras(range(5), W, H_), frames_of("demo", range(5))
+    S.same_texts(S.render_batch(ctx, k, cams[:3], WHOLE), [k.keyframe(f[0]), k.delta(f[0], f[1]), k.delta(f[1], f[2])], "a batch of 3")
+    info, launches = ctx.batch_info(), ctx.launch_count()
+    assert info[0] == 3
+    same_text(k.render(ctx, cams[3], WHOLE, offset=1), k.delta(f[2], f[3]), "a single-frame device call")
+    assert ctx.batch_info() == info and ctx.launch_count() == launches + 1
+    device_variant = ctx.render_variant()
+    same_text(host_texts(ctx, kind, cams[4:5], WHOLE, False)[0], k.delta(f[3], f[4]), "a single-frame host call")
+    assert ctx.batch_info() == info and ctx.launch_count() == launches + 2
+    host_variant = ctx.render_variant()
+    frame = torch.full((D.GUARD + f[4].size + D.GUARD,), 0xA5, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    ctx.render_device_rgb8(cams[4], WHOLE, B, SPP, frame.data_ptr() + D.GUARD, f[4].size)
+    ctx.synchronize()
+    assert device_variant == host_variant == ctx.render_variant()
+    got = frame.cpu().numpy()
+    assert (got[:D.GUARD] == 0xA5).all() and (got[-D.GUARD:] == 0xA5).all() and np.array_equal(got[D.GUARD:-D.GUARD], f[4].reshape(-1))
+
+
+@pytest.mark.parametrize("kind", KIND_IDS)
+def test_the_one_pair_timing_entry_writes_the_plain_entrys_text(ctx, kind):
+    """trt_ansi_delta(_half)_kernel_times, a chain of one with events: three times, and the text and the length at an odd address"""
+    k = S.KINDS[kind]
+    for w, rows in [(W, H_), (W, 47)]:
+        shown, frames = S.chain(w, rows, 1, 2)
+        a, pa = D.at_odd_address(np.array(shown))
+        b, pb = D.at_odd_address(np.array(frames[0]))
+        room = D.Room(k.capacity(w, rows), 1)
+        ms = PAIR_TIMES[kind](ctx, pa, pb, w, rows, room.ptr, room.capacity, room.length_ptr)
+        assert len(ms) == 3 and all(t >= 0 for t in ms)
+        timed = room.text(ctx, f"{kind} {w}x{rows}, the timing entry")
+        same_text(timed, k.delta(shown, frames[0]), f"{kind} {w}x{rows}, the timing entry")
+        same_text(timed, D.device_delta(ctx, k.single, k.capacity, np.array(shown), np.array(frames[0]), 1, f"{w}x{rows}"), f"{kind} {w}x{rows}, the plain entry")
+
+
+# ---- 4. the demo ----
 
 @pytest.mark.parametrize("frames", [4, 7])
 @pytest.mark.parametrize("flags", [["--half", "--delta", "--batch=4"], ["--delta", "--batch=3"]], ids=["half_batch4", "full_batch3"])
