@@ -1,13 +1,15 @@
-// trt_ansi.hpp -- the frame as the terminal's text, written on the device: the kernels that stand in the ordered mean's place when a
-// host asks for what buffered_draw_screen would fwrite (TRT.c:1142-1172), and the same formatting fed from RGB8 bytes.  trt_ansi.h
-// holds the layout and the lane map; this file the wave that carries them out.
+// trt_ansi.hpp -- the frame as the terminal's text, written on the device: the wave that writes a whole text of either format
+// (text_write), and for the full text the kernels that stand in the ordered mean's place when a host asks for what
+// buffered_draw_screen would fwrite (TRT.c:1142-1172), and the same formatting fed from RGB8 bytes.  trt_text_map.h holds the position
+// map and the lane map, trt_ansi.h the format; trt_ansi_half.hpp has the half-block text's kernels.
 //
-// A wave owns TRT_ANSI_WAVE_WORDS aligned words of the text and the up to 63 pixels they show.  Lane l forms pixel P0 + l -- the
-// ordered mean of its samples from 0.0 in sample order and the emitter's cast (rgb8_byte), or three bytes read from memory -- and keeps
-// it packed in ONE register.  Then, six times, every lane assembles one word: it finds the position of its word's first byte from the
-// wave's (32-bit arithmetic, trt_ansi_advance), walks the four bytes, fetches the one or two pixels they belong to from the lanes that
-// hold them (__shfl: ds_bpermute_b32, no LDS is allocated) and stores the word: 64 lanes, 256 consecutive aligned bytes.  No RGB8
-// frame and no frame of doubles is written on the way.  The only 64-bit division is trt_ansi_locate's, once per wave.
+// A wave owns wave_words aligned words of the text and the up to 63 cells they show.  Lane l forms what cell C0 + l shows -- the full
+// text's one pixel, the ordered mean of its samples from 0.0 in sample order and the emitter's cast (rgb8_byte), or three bytes read
+// from memory -- and keeps it packed in registers.  Then, wave_words / 64 times, every lane assembles one word: it finds the position
+// of its word's first byte from the wave's (32-bit arithmetic, trt_text_advance), fetches the colours its four bytes show from the
+// lanes that hold them (__shfl: ds_bpermute_b32, no LDS is allocated), walks the four bytes and stores the word: 64 lanes, 256
+// consecutive aligned bytes.  No RGB8 frame and no frame of doubles is written on the way.  The only 64-bit division is
+// trt_text_locate's, once per wave.
 #pragma once
 
 #include "trt_ansi.h"
@@ -18,46 +20,90 @@ namespace trt
 
 #ifdef TRT_UNIT_RENDER
 
-// One wave's share of a frame's text at `out` (any alignment).  `pixel_rgb(p)`: r | g << 8 | b << 16 of pixel p < width * rows.
-// Every lane of the wave calls it (the cross-lane reads need all of them); lanes store only what is theirs.
-template <class Fetch>
-__device__ __forceinline__ void ansi_write(unsigned char *out, int width, int rows, unsigned row_magic, unsigned long long wave, int lane, Fetch pixel_rgb)
+// One wave's share of a frame's text at `out` (any alignment).  Every lane of the wave calls it (the cross-lane reads need all of
+// them); lanes store only what is theirs.  The Format says what is its own:
+//   kind(), text_rows, text_bytes, lone_value      the format header's
+//   turns                                          kind().wave_words / 64, for the unrolling
+//   hold(from, lane, ..., fetch) -> held           what the lane keeps of cell trt_text_cell(from) + lane, formed through `fetch`
+//   colours(at, last, from, mine, width) -> seen   what the word from at to last shows, fetched from the lanes that hold it
+//   byte(at, rows, seen, other)                    what stands at *at; `other`: the walk has left the cell of the word's first byte
+template <class Format, class Fetch>
+__device__ __forceinline__ void text_write(unsigned char *out, int width, int rows, unsigned row_magic, unsigned width_magic, unsigned long long wave, int lane,
+                                           Fetch fetch)
 {
-    const trt_ansi_split split = trt_ansi_split_of((unsigned long long)out, trt_ansi_text_bytes(width, rows));
+    const trt_text_kind kind = Format::kind();
+    const long long trows = Format::text_rows(rows);
+    const unsigned long long bytes = Format::text_bytes(width, rows);
+    const trt_text_split split = trt_text_split_of((unsigned long long)out, bytes);
     if (wave == 0)
     {
-        const long long lone = trt_ansi_lone_byte(&split, lane);
+        const long long lone = trt_text_lone_byte(&split, lane);
         if (lone >= 0)
-            out[lone] = (unsigned char)trt_ansi_lone_value(lone);
+            out[lone] = (unsigned char)Format::lone_value(lone, bytes);
     }
-    const unsigned long long first = trt_ansi_lane_word(wave, 0, 0);
+    const unsigned long long first = trt_text_lane_word(kind, wave, 0, 0);
     if (first >= split.words) // the whole wave: a frame of a batch whose alignment needs a wave less than the grid has
         return;
-    const trt_ansi_at from = trt_ansi_locate(split.head + 4 * first, width, rows);
-    const long long pixels = (long long)width * rows, p0 = trt_ansi_pixel(&from, width);
-    const unsigned mine = p0 + lane < pixels ? pixel_rgb(p0 + lane) : 0u;
+    const trt_text_at from = trt_text_locate(kind, split.head + 4 * first, width, trows);
+    const typename Format::held mine = Format::hold(from, lane, width, rows, width_magic, fetch);
     unsigned char *const words = out + split.head;
 #pragma unroll
-    for (int j = 0; j < TRT_ANSI_WAVE_WORDS / 64; j++)
+    for (int j = 0; j < Format::turns; j++)
     {
-        const unsigned long long k = trt_ansi_lane_word(wave, lane, j);
-        trt_ansi_at at = trt_ansi_advance(&from, 4u * (unsigned)(64 * j + lane), width, rows, row_magic);
-        trt_ansi_at walk = at;
-        for (int b = 1; b < 4; b++)
-            (void)trt_ansi_step(&walk, width, rows);
-        // a word shows at most two pixels (a cell is longer than a word): that of its first byte and that of its last
-        const unsigned rgb_a = (unsigned)__shfl((int)mine, (int)(trt_ansi_pixel(&at, width) - p0) & 63);
-        const unsigned rgb_b = (unsigned)__shfl((int)mine, (int)(trt_ansi_pixel(&walk, width) - p0) & 63);
-        unsigned word = trt_ansi_byte(&at, rows, rgb_a), other = 0;
+        const unsigned long long k = trt_text_lane_word(kind, wave, lane, j);
+        trt_text_at at[4]; // the word's four bytes; other[b]: byte b stands in another cell than byte 0
+        unsigned other[4] = {0u};
+        at[0] = trt_text_advance(kind, &from, 4u * (unsigned)(64 * j + lane), width, trows, row_magic);
+#pragma unroll
         for (int b = 1; b < 4; b++)
         {
-            other |= (unsigned)trt_ansi_step(&at, width, rows);
-            word |= trt_ansi_byte(&at, rows, other ? rgb_b : rgb_a) << (8 * b);
+            at[b] = at[b - 1];
+            other[b] = other[b - 1] | (unsigned)trt_text_step(kind, &at[b], width, trows);
         }
+        const typename Format::seen shown = Format::colours(at[0], at[3], from, mine, width);
+        unsigned word = 0;
+#pragma unroll
+        for (int b = 0; b < 4; b++)
+            word |= Format::byte(at[b], rows, shown, other[b]) << (8 * b);
         if (k < split.words)
             *reinterpret_cast<unsigned *>(words + 4 * k) = word; // (out + head) is 4-aligned
     }
 }
+
+// The full text: a lane holds ONE pixel in one register, `pixel_rgb(p)`: r | g << 8 | b << 16 of pixel p < width * rows.  A word shows
+// at most two pixels (trt_ansi.h), that of its first byte and that of its last: two reads of the one register.
+struct ansi_text
+{
+    static constexpr int turns = TRT_ANSI_WAVE_WORDS / 64;
+    using held = unsigned;
+    struct seen
+    {
+        unsigned first, last;
+    };
+    static __device__ __forceinline__ trt_text_kind kind() { return trt_ansi_kind(); }
+    static __device__ __forceinline__ long long text_rows(int rows) { return trt_ansi_text_rows(rows); }
+    static __device__ __forceinline__ unsigned long long text_bytes(int width, int rows) { return trt_ansi_text_bytes(width, rows); }
+    static __device__ __forceinline__ unsigned lone_value(long long position, unsigned long long bytes) { return trt_ansi_lone_value(position, bytes); }
+
+    template <class Fetch>
+    static __device__ __forceinline__ held hold(const trt_text_at &from, int lane, int width, int rows, unsigned, Fetch pixel_rgb)
+    {
+        const long long pixels = (long long)width * rows, p0 = trt_text_cell(&from, width);
+        return p0 + lane < pixels ? pixel_rgb(p0 + lane) : 0u;
+    }
+    static __device__ __forceinline__ seen colours(const trt_text_at &at, const trt_text_at &last, const trt_text_at &from, held mine, int width)
+    {
+        const long long p0 = trt_text_cell(&from, width);
+        seen shown;
+        shown.first = (unsigned)__shfl((int)mine, (int)(trt_text_cell(&at, width) - p0) & 63);
+        shown.last = (unsigned)__shfl((int)mine, (int)(trt_text_cell(&last, width) - p0) & 63);
+        return shown;
+    }
+    static __device__ __forceinline__ unsigned byte(const trt_text_at &at, int rows, seen shown, unsigned other)
+    {
+        return trt_ansi_byte(&at, rows, other ? shown.last : shown.first);
+    }
+};
 
 // pixel p of a frame's scratch samples[(k * pixels + p) * 3 + channel]: TRT.c:1063-1065, then the emitter's cast
 __device__ __forceinline__ unsigned ansi_pixel_of_samples(const double *samples, long values, int spp, double inv_spp, long long p)
@@ -76,7 +122,7 @@ __device__ __forceinline__ unsigned ansi_pixel_of_samples(const double *samples,
 
 // The ordered mean, the emitter's cast and the terminal's text in ONE pass, as the last kernel of a launch in reduce_samples_kernel's
 // place: blockIdx.y is the frame, and it leaves the queue ready in the same way.  Frame b's text starts at out + b * trt_ansi_text_bytes,
-// aligned to nothing in general: every frame has a head and a tail of its own.  A single frame's grid has trt_ansi_waves(words of the
+// aligned to nothing in general: every frame has a head and a tail of its own.  A single frame's grid has trt_text_waves(words of the
 // text at `out`) waves; that of several frames the most waves an alignment needs (a frame's spare wave finds nothing to do).
 __global__ __launch_bounds__(256) void reduce_samples_ansi_kernel(const double *samples, unsigned char *out, int width, int rows, unsigned row_magic, int spp,
                                                                   double inv_spp, unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
@@ -85,8 +131,8 @@ __global__ __launch_bounds__(256) void reduce_samples_ansi_kernel(const double *
     const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long values = (long)width * rows * 3;
     const double *mine = samples + (size_t)blockIdx.y * (size_t)spp * (size_t)values;
-    ansi_write(out + (size_t)blockIdx.y * (size_t)trt_ansi_text_bytes(width, rows), width, rows, row_magic, t >> 6, (int)(t & 63),
-               [=](long long p) { return ansi_pixel_of_samples(mine, values, spp, inv_spp, p); });
+    text_write<ansi_text>(out + (size_t)blockIdx.y * (size_t)trt_ansi_text_bytes(width, rows), width, rows, row_magic, 0u, t >> 6, (int)(t & 63),
+                          [=](long long p) { return ansi_pixel_of_samples(mine, values, spp, inv_spp, p); });
 }
 
 // The formatting alone, of a frame that exists as RGB8 bytes rgb[p * 3 + channel] (trt_ansi_from_rgb8_device; the reference-order
@@ -94,7 +140,7 @@ __global__ __launch_bounds__(256) void reduce_samples_ansi_kernel(const double *
 __global__ __launch_bounds__(256) void ansi_from_rgb8_kernel(const unsigned char *rgb, unsigned char *out, int width, int rows, unsigned row_magic)
 {
     const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    ansi_write(out, width, rows, row_magic, t >> 6, (int)(t & 63), [=](long long p) {
+    text_write<ansi_text>(out, width, rows, row_magic, 0u, t >> 6, (int)(t & 63), [=](long long p) {
         const unsigned char *px = rgb + 3 * p;
         return (unsigned)px[0] | (unsigned)px[1] << 8 | (unsigned)px[2] << 16;
     });

@@ -454,21 +454,53 @@ static trt::FrameView frame_view(const trt_context *ctx, const Camera *camera, c
     return f;
 }
 
-// the text of a frame that exists as RGB8 bytes: the formatting alone (trt_ansi.hpp)
-static void launch_ansi_from_rgb8(hipStream_t stream, const unsigned char *d_rgb8, int width, int rows, void *d_text)
+// What the launches of a whole text need of its format (trt_ansi.h, trt_ansi_half.h): the length, the lane map's kind, and the two
+// kernels that write it.  The kernels' argument lists differ in one place: the half-block text's take the width's magic behind the
+// row length's.
+struct TextFormat
 {
-    const unsigned long long bytes = trt_ansi_text_bytes(width, rows), waves = trt_ansi_waves(trt_ansi_split_of((unsigned long long)d_text, bytes).words);
-    hipLaunchKernelGGL(trt::ansi_from_rgb8_kernel, dim3((unsigned)((waves * 64 + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK)), dim3(TRT_REDUCE_BLOCK), 0, stream, d_rgb8,
-                       (unsigned char *)d_text, width, rows, trt_ansi_row_magic(width));
+    trt_text_kind kind;
+    unsigned long long (*bytes)(int width, long long rows);
+    unsigned (*width_magic)(int width); // nullptr: the kernels take none
+    const void *reduce_kernel, *from_rgb8_kernel;
+};
+
+static const TextFormat &text_format(Output kind)
+{
+    static const TextFormat formats[2] = {
+        {trt_ansi_kind(), trt_ansi_text_bytes, nullptr, (const void *)trt::reduce_samples_ansi_kernel, (const void *)trt::ansi_from_rgb8_kernel},
+        {trt_ansi_half_kind(), trt_ansi_half_text_bytes, trt_ansi_half_width_magic, (const void *)trt::reduce_samples_ansi_half_kernel,
+         (const void *)trt::ansi_half_from_rgb8_kernel}};
+    return formats[kind == kHalfText];
 }
 
-// the half-block text of such a frame (trt_ansi_half.hpp)
-static void launch_ansi_half_from_rgb8(hipStream_t stream, const unsigned char *d_rgb8, int width, int rows, void *d_text)
+// One of a text's kernels over `frames` frames of width x rows at `out`, a wave per kind.wave_words aligned words: ONE frame's grid has
+// exactly the waves its output address needs, that of several the most an alignment needs.  `front`: the kernel's arguments in front of
+// (out, width, rows, row magic[, width magic]), `back`: those behind.
+static void launch_text_kernel(hipStream_t stream, const TextFormat &t, const void *kernel, unsigned frames, std::initializer_list<const void *> front,
+                               unsigned char *out, int width, int rows, std::initializer_list<const void *> back)
 {
-    const unsigned long long bytes = trt_ansi_half_text_bytes(width, rows),
-                             waves = trt_ansi_half_waves(trt_ansi_half_split_of((unsigned long long)d_text, bytes).words);
-    hipLaunchKernelGGL(trt::ansi_half_from_rgb8_kernel, dim3((unsigned)((waves * 64 + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK)), dim3(TRT_REDUCE_BLOCK), 0, stream, d_rgb8,
-                       (unsigned char *)d_text, width, rows, trt_ansi_half_row_magic(width), trt_ansi_half_width_magic(width));
+    const unsigned long long bytes = t.bytes(width, rows);
+    const unsigned long long waves = trt_text_waves(t.kind, frames > 1 ? bytes / 4 : trt_text_split_of((unsigned long long)out, bytes).words);
+    unsigned row_magic = trt_text_magic((unsigned long long)trt_text_row_bytes(t.kind, width)), width_magic = t.width_magic ? t.width_magic(width) : 0u;
+    void *args[16];
+    size_t n = 0;
+    for (const void *a : front)
+        args[n++] = const_cast<void *>(a);
+    for (void *a : {(void *)&out, (void *)&width, (void *)&rows, (void *)&row_magic})
+        args[n++] = a;
+    if (t.width_magic)
+        args[n++] = &width_magic;
+    for (const void *a : back)
+        args[n++] = const_cast<void *>(a);
+    (void)hipLaunchKernel(kernel, dim3((unsigned)((waves * 64 + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK), frames), dim3(TRT_REDUCE_BLOCK), args, 0, stream);
+}
+
+// the text of a frame that exists as RGB8 bytes: the formatting alone
+static void launch_text_from_rgb8(hipStream_t stream, Output kind, const unsigned char *d_rgb8, int width, int rows, void *d_text)
+{
+    const TextFormat &t = text_format(kind);
+    launch_text_kernel(stream, t, t.from_rgb8_kernel, 1, {&d_rgb8}, (unsigned char *)d_text, width, rows, {});
 }
 
 // `lane_set` 0: the context's stream, queue word 0, d_samples; 1: the alternate stream, its own queue word and scratch
@@ -509,10 +541,8 @@ static int launch_reference(trt_context *ctx, const RenderPlan &plan, trt::Frame
     if (kind != kDoubles)
         hipLaunchKernelGGL(trt::quantize_kernel, dim3((unsigned)((pixels * 3 + 255) / 256)), dim3(256), 0, stream, (const double *)f.out, pixels * 3,
                            is_text(kind) ? ctx->d_text_rgb8.ptr : (unsigned char *)out);
-    if (kind == kText)
-        launch_ansi_from_rgb8(stream, ctx->d_text_rgb8.ptr, f.width, f.local_rows, out);
-    if (kind == kHalfText)
-        launch_ansi_half_from_rgb8(stream, ctx->d_text_rgb8.ptr, f.width, f.local_rows, out);
+    if (is_text(kind))
+        launch_text_from_rgb8(stream, kind, ctx->d_text_rgb8.ptr, f.width, f.local_rows, out);
     if (entry & kEntryCloses)
         HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
     HIP_TRY(hipGetLastError());
@@ -522,7 +552,7 @@ static int launch_reference(trt_context *ctx, const RenderPlan &plan, trt::Frame
 // TRT.c:1063-1065: the mean over each pixel's samples, in sample order, of the `frames` frames of a launch whose scratch is `samples`,
 // into `out` as `kind`: one kernel per kind, the frame in blockIdx.y.  It starts the queue for the next launch of this shape.  ONE
 // frame's grid has exactly the lanes or waves its output address needs; the frames of several start at any alignment, so their grid is
-// sized for the most an alignment needs (trt_common.hpp, trt_ansi.h).
+// sized for the most an alignment needs (trt_common.hpp, trt_text_map.h).
 static void launch_ordered_mean(hipStream_t stream, const RenderPlan &plan, const trt::FrameView &f, const double *samples, void *out, Output kind, long pixels,
                                 unsigned frames)
 {
@@ -540,21 +570,13 @@ static void launch_ordered_mean(hipStream_t stream, const RenderPlan &plan, cons
                            blocks(frames > 1 ? values / trt::kRgb8Group + 6 : trt::rgb8_lanes(values, trt::rgb8_head((const unsigned char *)out, values))), block, 0,
                            stream, samples, (unsigned char *)out, values, f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
         break;
-    case kText: // a wave per TRT_ANSI_WAVE_WORDS aligned words
+    case kText:
+    case kHalfText: // a wave per kind.wave_words aligned words
     {
-        const unsigned long long bytes = trt_ansi_text_bytes(f.width, f.local_rows);
-        const unsigned long long waves = trt_ansi_waves(frames > 1 ? bytes / 4 : trt_ansi_split_of((unsigned long long)out, bytes).words);
-        hipLaunchKernelGGL(trt::reduce_samples_ansi_kernel, blocks(waves * 64), block, 0, stream, samples, (unsigned char *)out, f.width, f.local_rows,
-                           trt_ansi_row_magic(f.width), f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
-        break;
-    }
-    case kHalfText: // a wave per TRT_ANSI_HALF_WAVE_WORDS aligned words
-    {
-        const unsigned long long bytes = trt_ansi_half_text_bytes(f.width, f.local_rows);
-        const unsigned long long waves = trt_ansi_half_waves(frames > 1 ? bytes / 4 : trt_ansi_half_split_of((unsigned long long)out, bytes).words);
-        hipLaunchKernelGGL(trt::reduce_samples_ansi_half_kernel, blocks(waves * 64), block, 0, stream, samples, (unsigned char *)out, f.width, f.local_rows,
-                           trt_ansi_half_row_magic(f.width), trt_ansi_half_width_magic(f.width), f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64,
-                           f.queue_shift);
+        const TextFormat &t = text_format(kind);
+        const unsigned waves_per_group = plan.block / 64;
+        launch_text_kernel(stream, t, t.reduce_kernel, frames, {&samples}, (unsigned char *)out, f.width, f.local_rows,
+                           {&f.spp, &f.inv_spp, &f.queue, &plan.grid, &waves_per_group, &f.queue_shift});
         break;
     }
     }
@@ -715,28 +737,26 @@ extern "C" int trt_render_device_ansi_half(trt_context *ctx, const Camera *camer
     return render_device_on(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, 0, kEntryWhole, kHalfText);
 }
 
-extern "C" int trt_ansi_half_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text)
+static int text_from_rgb8_device(trt_context *ctx, Output kind, const void *d_rgb8, int width, int rows, void *d_text)
 {
     if (!ctx || !d_rgb8 || !d_text)
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
     if (width <= 0 || rows <= 0 || (unsigned long long)width * rows >= 0x7fffffffull)
         return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, rows);
     HIP_TRY(hipSetDevice(ctx->device));
-    launch_ansi_half_from_rgb8(ctx->stream, (const unsigned char *)d_rgb8, width, rows, d_text);
+    launch_text_from_rgb8(ctx->stream, kind, (const unsigned char *)d_rgb8, width, rows, d_text);
     HIP_TRY(hipGetLastError());
     return TRT_OK;
 }
 
+extern "C" int trt_ansi_half_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text)
+{
+    return text_from_rgb8_device(ctx, kHalfText, d_rgb8, width, rows, d_text);
+}
+
 extern "C" int trt_ansi_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text)
 {
-    if (!ctx || !d_rgb8 || !d_text)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (width <= 0 || rows <= 0 || (unsigned long long)width * rows >= 0x7fffffffull)
-        return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, rows);
-    HIP_TRY(hipSetDevice(ctx->device));
-    launch_ansi_from_rgb8(ctx->stream, (const unsigned char *)d_rgb8, width, rows, d_text);
-    HIP_TRY(hipGetLastError());
-    return TRT_OK;
+    return text_from_rgb8_device(ctx, kText, d_rgb8, width, rows, d_text);
 }
 
 extern "C" int trt_quantize_device(trt_context *ctx, const void *d_pixels, size_t num_pixels, void *d_rgb8)
@@ -1425,11 +1445,9 @@ static int render_device_delta(trt_context *ctx, const Camera *cameras, int n, b
         return rc;
     if (keyframe)
     { // text 0 is the whole text of frame 0, as trt_render_device_ansi or trt_render_device_ansi_half writes it; the chain of the pairs behind it starts where that text ends
-        const unsigned long long whole = frame_bytes(half ? kHalfText : kText, width, owned);
-        if (half)
-            launch_ansi_half_from_rgb8(ctx->stream, frames, width, owned, d_text);
-        else
-            launch_ansi_from_rgb8(ctx->stream, frames, width, owned, d_text);
+        const Output kind = half ? kHalfText : kText;
+        const unsigned long long whole = frame_bytes(kind, width, owned);
+        launch_text_from_rgb8(ctx->stream, kind, frames, width, owned, d_text);
         hipLaunchKernelGGL(trt::ansi_delta_keyframe_bytes_kernel, dim3(1), dim3(1), 0, ctx->stream, d_bytes, whole);
         HIP_TRY(hipGetLastError());
         if (n > 1)
