@@ -74,6 +74,12 @@ int trt_render_frame_ansi(const Scene *scene, int width, int height, int bounce_
  * bytes.  Lock and scene policy as above. */
 int trt_render_frame_ansi_half(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text);
 
+/* The same frame as a KITTY GRAPHICS-PROTOCOL image (trt_render_host_kitty below, on the default context: its format and its caveat -- no
+ * terminal has yet shown it): true pixels, four bytes of text each, for a terminal that takes them.  text holds trt_kitty_bytes(width,
+ * height) bytes, the whole of which the host writes with one fwrite: byte for byte trt_emitter_kitty_rgb8 (trt_host.h) of
+ * trt_render_frame_rgb8's bytes.  width and height are at most 99999.  Lock and scene policy as above. */
+int trt_render_frame_kitty(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text);
+
 /* The frame as the DELTA text against the frame this entry returned before (trt_render_host_ansi_delta below, on the default context: its
  * format, its rules for the host and its errors).  The first call, the first call of another size and the first call after trt_shutdown
  * return a keyframe: trt_render_frame_ansi's text.  text holds capacity_bytes >= trt_ansi_delta_capacity(width, height) bytes; the host
@@ -235,6 +241,42 @@ int trt_render_device_ansi_half(trt_context *ctx, const Camera *camera, const tr
  * trt_dist_render_rgb8 gather holds): trt_ansi_half_bytes(width, rows) bytes at d_text, any alignment.  Asynchronous. */
 int trt_ansi_half_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text);
 
+/* ---- the kitty graphics-protocol image: true pixels, four bytes of text each ----------------------------------------------------
+ * Both texts above paint a pixel with character cells, 25 and 19.5 bytes each.  Terminals that speak the kitty graphics protocol (kitty,
+ * WezTerm, Ghostty, Konsole) take true pixels, as base64 of RGB bytes inside APC escape sequences: three bytes are exactly four base64
+ * characters, so a pixel is one 32-bit word of text, a 1920 x 1080 frame 8.3 MB instead of 40 or 52, at full pixel resolution and
+ * lossless.  For a screen of `width` x `rows` owned rows, P = width * rows pixels in LOCAL row order (for a shard, v is the owned rows),
+ * K = ceil(P / 1024) chunks, in order:
+ *   "\033[0;0H"                                                        6 bytes
+ *   chunk 0:   "\033_Ga=T,f=24,i=1,p=1,q=2,C=1,s=WWWWW,v=RRRRR,m=M;"  48 bytes: WWWWW = width, RRRRR = rows, five zero-padded digits each
+ *              the payload of chunk 0, then "\033\\"
+ *   chunk c>0: "\033_Gm=0M;"                                           8 bytes
+ *              the payload of chunk c, then "\033\\"
+ * A payload holds the chunk's up to 1024 pixels, four characters each: RFC 4648 base64, standard alphabet, of the emitter's bytes R, G, B
+ * ((int)(c*255), trt_render_device_rgb8's); 4096 characters are the protocol's limit per escape.  M is 1 in every chunk but the last, 0
+ * in the last.  No '=', no newline, no NUL: 4 P + 10 K + 46 bytes.  a=T: transmit and display; f=24: RGB; i=1,p=1: image and placement
+ * id, so that re-sending replaces the picture in place; q=2: the terminal answers nothing; C=1: the cursor stays.
+ * NO TERMINAL HAS YET SHOWN THIS PICTURE: the key list is written from memory of the protocol, and the tests hold the text against a
+ * structural reader, not a terminal.  csrc/trt_kitty.h is the format in code -- the 48-byte header ONE literal there --
+ * trt_emitter_kitty_rgb8 (trt_host.h) its sequential statement on the host.  Limits: width <= 99999 and owned rows <= 99999; above them
+ * the length is 0 and the entries return TRT_ERR_ARGUMENT.  Checks, errors, stream behaviour and the trt_kernel_times accounting of every
+ * entry are otherwise those of the _ansi_half entry it mirrors; capacities count bytes of text, to the byte.  None of them reads or changes
+ * the delta entries' shown frame.  There is no delta or animation form (a=f), no compression (o=z), no shared-memory transmission, no
+ * refraction form and no tmux pass-through; of a trt_dist_render_rgb8 gather rank 0 formats the assembled bytes with
+ * trt_kitty_from_rgb8_device. */
+
+/* Length of the image text: 4 P + 10 ceil(P / 1024) + 46, P = width * rows; 0 unless both are positive and at most 99999. */
+size_t trt_kitty_bytes(int width, int rows);
+/* trt_render_device_ansi as the kitty image: trt_kitty_bytes(width, owned rows) bytes at d_text, any alignment, written by the pass that
+ * forms the ordered mean -- a lane forms a pixel once and keeps its four characters in a register; neither doubles nor RGB8 bytes are
+ * written on the way, every byte of the text is stored exactly once (d_text need not be initialised) and none outside it (the
+ * reference-order kernel goes through a framebuffer and bytes of the context's). */
+int trt_render_device_kitty(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,
+                            int rays_per_pixel, void *d_text, size_t capacity_bytes);
+/* The formatting alone, of a frame that exists as RGB8 bytes in device memory (as trt_ansi_from_rgb8_device; e.g. what rank 0 of a
+ * trt_dist_render_rgb8 gather holds): trt_kitty_bytes(width, rows) bytes at d_text, any alignment.  Asynchronous. */
+int trt_kitty_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text);
+
 /* ---- the delta text: only the cells that changed --------------------------------------------------------------------------------
  * A terminal keeps what it was sent.  The text above repaints every cell of every frame, 25 bytes each; the DELTA text between the frame
  * the terminal shows and the next one holds, for every CHANGED cell (its three RGB8 bytes differ), rows ascending, left to right:
@@ -358,6 +400,10 @@ int trt_render_host_ansi(trt_context *ctx, const Camera *camera, const trt_rowse
 int trt_render_host_ansi_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
                               char *text);
 
+/* trt_render_device_kitty into HOST memory: trt_kitty_bytes(width, owned rows) bytes (synchronous; one copy-out through pinned staging). */
+int trt_render_host_kitty(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                          char *text);
+
 /* Several cameras of the current scene in one call: an orbit, a replay, a stereo pair, the faces of an environment probe. */
 #define TRT_BATCH_MAX 8 /* = the eye-table slots a scene's tables have */
 
@@ -404,6 +450,15 @@ int trt_render_device_batch_ansi_half(trt_context *ctx, const Camera *cameras, i
 /* The same into HOST memory: text[b * trt_ansi_half_bytes(width, owned rows) ...] (synchronous; one copy-out through pinned staging). */
 int trt_render_host_batch_ansi_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
                                     int rays_per_pixel, char *text);
+
+/* trt_render_device_batch as the kitty image (trt_render_device_kitty): frame b at d_text + b * trt_kitty_bytes(width, owned rows), aligned
+ * to nothing in general; launches, splits, trt_batch_info and errors as trt_render_device_batch_ansi, the capacity counted in bytes of
+ * text for n frames. */
+int trt_render_device_batch_kitty(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                  int rays_per_pixel, void *d_text, size_t capacity_bytes);
+/* The same into HOST memory: text[b * trt_kitty_bytes(width, owned rows) ...] (synchronous; one copy-out through pinned staging). */
+int trt_render_host_batch_kitty(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                int rays_per_pixel, char *text);
 
 /* ---- delta texts for a batch: n texts back to back, one prefix sum over all frames --------------------------------------------------
  * A CHAIN is a shown frame and n frames of RGB8 bytes (rows x width x 3 each), 1 <= n <= TRT_BATCH_MAX.  Text b takes a terminal from

@@ -95,6 +95,15 @@ int trt_emitter_half_rgb8(const unsigned char *rgb, int width, int rows, char *t
  * positive or above the limits, a capacity below the bound. */
 int trt_emitter_delta_half_rgb8(const unsigned char *shown, const unsigned char *next, int width, int rows, char *text, size_t capacity,
                                 size_t *bytes);
+/* The frame of such bytes (rows x width x 3) as a KITTY GRAPHICS-PROTOCOL image, for terminals that take true pixels: base64 of the RGB
+ * bytes, four characters a pixel, in APC escape sequences of at most 4096 characters.  The format is the project's own statement of the
+ * protocol (csrc/trt_kitty.h) and NO TERMINAL HAS YET SHOWN IT.  "\033[0;0H"; then, P = width * rows pixels in row order cut
+ * into K = ceil(P / 1024) chunks, "\033_Ga=T,f=24,i=1,p=1,q=2,C=1,s=WWWWW,v=RRRRR,m=M;" (five zero-padded digits each) in front of the first
+ * chunk's characters and "\033_Gm=0M;" in front of every later chunk's, "\033\\" behind each; M is 1 but in the last chunk, where it is 0.
+ * No '=', no newline, no NUL: *bytes = 4 P + 10 K + 46, which `capacity` must hold; width <= 99999, rows <= 99999.  The sequential
+ * statement the device kernels (trt_render_device_kitty, trt_hip.h) are tested against, and the emitter of hosts that fetch RGB8 bytes.
+ * TRT_HOST_ERR_ARGUMENT: NULL, a size that is not positive or above the limits, a capacity below the length. */
+int trt_emitter_kitty_rgb8(const unsigned char *rgb, int width, int rows, char *text, size_t capacity, size_t *bytes);
 /* TRT.c:1171: one fwrite of the whole buffer (trailing NULs included, as the reference does) */
 int trt_emitter_write(const trt_emitter *e, FILE *stream);
 /* TRT.c:1084-1099: the unbuffered printf form */

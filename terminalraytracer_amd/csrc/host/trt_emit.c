@@ -301,6 +301,69 @@ int trt_emitter_delta_half_rgb8(const unsigned char *shown, const unsigned char 
     return TRT_HOST_OK;
 }
 
+/* The kitty graphics-protocol image (csrc/trt_kitty.h holds the format): base64 of the RGB bytes in APC escape sequences of at most 4096
+ * characters.  Plain loops and a table, on purpose without that header -- this is what the header's arithmetic and the device kernels are
+ * held against.  No terminal has yet shown this picture: the key list below is written from memory of the protocol. */
+static const char k_kitty_header[] = "\033_Ga=T,f=24,i=1,p=1,q=2,C=1,s=00000,v=00000,m=0;";
+static const char k_kitty_chunk[] = "\033_Gm=00;";
+static const char k_kitty_end[] = "\033\\";
+static const char k_base64[] = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
+enum
+{
+    KITTY_HEADER_LEN = sizeof(k_kitty_header) - 1, /* 48 */
+    KITTY_CHUNK_LEN = sizeof(k_kitty_chunk) - 1,   /* 8 */
+    KITTY_END_LEN = sizeof(k_kitty_end) - 1,       /* 2 */
+    KITTY_WIDTH_AT = 30,
+    KITTY_ROWS_AT = 38,
+    KITTY_MORE_AT = 46,
+    KITTY_CHUNK_MORE_AT = 6,
+    KITTY_CHUNK_PIXELS = 1024, /* 4096 characters, the protocol's limit per escape */
+    KITTY_MAX = 99999
+};
+
+int trt_emitter_kitty_rgb8(const unsigned char *rgb, int width, int rows, char *text, size_t capacity, size_t *bytes)
+{
+    if (!rgb || !text || !bytes || width <= 0 || rows <= 0 || width > KITTY_MAX || rows > KITTY_MAX)
+        return TRT_HOST_ERR_ARGUMENT;
+    const size_t pixels = (size_t)width * (size_t)rows, chunks = (pixels + KITTY_CHUNK_PIXELS - 1) / KITTY_CHUNK_PIXELS;
+    if (capacity < 4 * pixels + 10 * chunks + 46)
+        return TRT_HOST_ERR_ARGUMENT;
+    char *p = text;
+    memcpy(p, k_home, HOME_LEN);
+    p += HOME_LEN;
+    for (size_t chunk = 0; chunk < chunks; chunk++)
+    {
+        const size_t from = chunk * KITTY_CHUNK_PIXELS, to = from + KITTY_CHUNK_PIXELS < pixels ? from + KITTY_CHUNK_PIXELS : pixels;
+        const char more = (char)('0' + (chunk + 1 < chunks));
+        if (chunk == 0)
+        {
+            memcpy(p, k_kitty_header, KITTY_HEADER_LEN);
+            five_digits(p + KITTY_WIDTH_AT, width);
+            five_digits(p + KITTY_ROWS_AT, rows);
+            p[KITTY_MORE_AT] = more;
+            p += KITTY_HEADER_LEN;
+        }
+        else
+        {
+            memcpy(p, k_kitty_chunk, KITTY_CHUNK_LEN);
+            p[KITTY_CHUNK_MORE_AT] = more;
+            p += KITTY_CHUNK_LEN;
+        }
+        for (size_t px = from; px < to; px++, p += 4)
+        {
+            const unsigned n = (unsigned)rgb[3 * px] << 16 | (unsigned)rgb[3 * px + 1] << 8 | (unsigned)rgb[3 * px + 2];
+            p[0] = k_base64[n >> 18];
+            p[1] = k_base64[n >> 12 & 63];
+            p[2] = k_base64[n >> 6 & 63];
+            p[3] = k_base64[n & 63];
+        }
+        memcpy(p, k_kitty_end, KITTY_END_LEN);
+        p += KITTY_END_LEN;
+    }
+    *bytes = (size_t)(p - text);
+    return TRT_HOST_OK;
+}
+
 int trt_emitter_write(const trt_emitter *e, FILE *stream)
 {
     if (!e || !stream)

@@ -96,7 +96,7 @@ static int refresh_default_scene(trt_context *ctx, const Scene *scene)
     return TRT_OK;
 }
 
-// The drop-in entries (project_scene, trt_render_frame, trt_render_frame_rgb8, trt_render_frame_ansi, trt_render_frame_ansi_half) take the scene with every call.  A scene whose
+// The drop-in entries (project_scene, trt_render_frame, trt_render_frame_rgb8, trt_render_frame_ansi, trt_render_frame_ansi_half, trt_render_frame_kitty) take the scene with every call.  A scene whose
 // primitives differ from the previous call's on `moving_after` consecutive calls is treated as MOVING: its candidate tables are
 // rebuilt per call the cheap way (one family per sphere, no patches); after `still_after` consecutive unchanged calls the full
 // tables are built once.  moving_after = 0: never (every change builds the full tables).  Defaults 2 and 3.  Frames are
@@ -204,6 +204,17 @@ extern "C" int trt_render_frame_ansi_half(const Scene *scene, int width, int hei
         return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, height);
     return render_default_frame(scene, width, height, [&](trt_context *ctx, const trt_rowset *whole) {
         return trt_render_host_ansi_half(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, text);
+    });
+}
+
+extern "C" int trt_render_frame_kitty(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text)
+{
+    if (!scene || !text)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (width <= 0 || height <= 0 || trt_kitty_bytes(width, height) == 0)
+        return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, height);
+    return render_default_frame(scene, width, height, [&](trt_context *ctx, const trt_rowset *whole) {
+        return trt_render_host_kitty(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, text);
     });
 }
 

@@ -11,6 +11,7 @@
 #include "trt_ansi.hpp"
 #include "trt_ansi_delta.hpp"
 #include "trt_ansi_half.hpp"
+#include "trt_kitty.hpp"
 
 using namespace trt_impl;
 
@@ -372,10 +373,10 @@ extern "C" int trt_read_counters(trt_context *ctx, unsigned long long *path_rays
 
 // What a launch leaves of a frame: the Screen's pixels of three doubles (TRT.c:188-193), the emitter's three bytes per pixel
 // ((int)(c*255), TRT.c:1157-1163), the text the emitter makes of those bytes (TRT.c:1142-1172; trt_ansi.h), or the half-block text of
-// them, two owned rows per line of text (trt_ansi_half.h).
-enum Output : int { kDoubles, kBytes, kText, kHalfText };
+// them, two owned rows per line of text (trt_ansi_half.h), or those bytes as a kitty graphics-protocol image (trt_kitty.h).
+enum Output : int { kDoubles, kBytes, kText, kHalfText, kKittyText };
 
-static bool is_text(Output kind) { return kind == kText || kind == kHalfText; }
+static bool is_text(Output kind) { return kind == kText || kind == kHalfText || kind == kKittyText; }
 
 // bytes of one frame of `rows` rows of `width` pixels
 static size_t frame_bytes(Output kind, int width, int rows)
@@ -384,6 +385,8 @@ static size_t frame_bytes(Output kind, int width, int rows)
         return (size_t)trt_ansi_text_bytes(width, rows);
     if (kind == kHalfText)
         return (size_t)trt_ansi_half_text_bytes(width, rows);
+    if (kind == kKittyText)
+        return (size_t)trt_kitty_text_bytes(width, rows);
     return (size_t)rows * width * 3 * (kind == kBytes ? 1u : sizeof(double));
 }
 
@@ -406,6 +409,8 @@ static int check_render_arguments(const trt_context *ctx, const Camera *cameras,
     if (!ctx->have_scene)
         return fail(TRT_ERR_NO_SCENE, "trt_set_scene has not been called");
     const int local_rows = trt_rowset_rows(rows);
+    if (kind == kKittyText && (rows->width > TRT_KITTY_MAX || local_rows > TRT_KITTY_MAX)) // five digits each in the image's header
+        return fail(TRT_ERR_ARGUMENT, "a kitty image of %d x %d exceeds %d", rows->width, local_rows, TRT_KITTY_MAX);
     const size_t need = frame_bytes(kind, rows->width, local_rows) * frames;
     if (capacity_bytes < need)
         return fail(TRT_ERR_CAPACITY, "framebuffer of %d frame(s) needs %zu B, %zu given", frames, need, capacity_bytes);
@@ -496,9 +501,25 @@ static void launch_text_kernel(hipStream_t stream, const TextFormat &t, const vo
     (void)hipLaunchKernel(kernel, dim3((unsigned)((waves * 64 + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK), frames), dim3(TRT_REDUCE_BLOCK), args, 0, stream);
 }
 
+// The kitty image's kernels are a launch of their own (trt_kitty.h: another lane map, a wave per 64 word slots, the tail's among them; no
+// magics): over `frames` frames of width x rows at `out`, ONE frame's grid has exactly the waves its address needs, that of several the
+// most an alignment needs.
+static dim3 kitty_grid(const unsigned char *out, int width, int rows, unsigned frames)
+{
+    const unsigned long long bytes = trt_kitty_text_bytes(width, rows);
+    const unsigned long long waves = frames > 1 ? trt_kitty_waves_most(bytes) : trt_kitty_waves((unsigned long long)out, bytes);
+    return dim3((unsigned)((waves * 64 + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK), frames);
+}
+
 // the text of a frame that exists as RGB8 bytes: the formatting alone
 static void launch_text_from_rgb8(hipStream_t stream, Output kind, const unsigned char *d_rgb8, int width, int rows, void *d_text)
 {
+    if (kind == kKittyText)
+    {
+        hipLaunchKernelGGL(trt::kitty_from_rgb8_kernel, kitty_grid((const unsigned char *)d_text, width, rows, 1), dim3(TRT_REDUCE_BLOCK), 0, stream, d_rgb8,
+                           (unsigned char *)d_text, width, rows);
+        return;
+    }
     const TextFormat &t = text_format(kind);
     launch_text_kernel(stream, t, t.from_rgb8_kernel, 1, {&d_rgb8}, (unsigned char *)d_text, width, rows, {});
 }
@@ -511,7 +532,8 @@ static void launch_text_from_rgb8(hipStream_t stream, Output kind, const unsigne
 enum : int { kEntryOpens = 1, kEntryCloses = 2, kEntryWhole = kEntryOpens | kEntryCloses };
 
 // The reference-order kernel's launch: it has no scratch and no mean.  Its bytes are its doubles, rendered into the context's
-// framebuffer, through quantize_kernel, and its text is those bytes through ansi_from_rgb8_kernel or ansi_half_from_rgb8_kernel.
+// framebuffer, through quantize_kernel, and its text is those bytes through ansi_from_rgb8_kernel, ansi_half_from_rgb8_kernel or
+// kitty_from_rgb8_kernel.
 static int launch_reference(trt_context *ctx, const RenderPlan &plan, trt::FrameView f, void *out, Output kind, long pixels, hipStream_t stream, int entry)
 {
     const int slot = (int)(ctx->launches % kEventRing);
@@ -579,6 +601,10 @@ static void launch_ordered_mean(hipStream_t stream, const RenderPlan &plan, cons
                            {&f.spp, &f.inv_spp, &f.queue, &plan.grid, &waves_per_group, &f.queue_shift});
         break;
     }
+    case kKittyText: // a wave per 64 word slots
+        hipLaunchKernelGGL(trt::reduce_samples_kitty_kernel, kitty_grid((const unsigned char *)out, f.width, f.local_rows, frames), block, 0, stream, samples,
+                           (unsigned char *)out, f.width, f.local_rows, f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
+        break;
     }
 }
 
@@ -649,7 +675,7 @@ static int launch_production(trt_context *ctx, const RenderPlan &plan, trt::Fram
 }
 
 // Carries out a planned launch on the route its variant takes, into `out` as `kind`: doubles, (kBytes) cast to the emitter's bytes in
-// the ordered mean's pass, or (kText, kHalfText) cast and formatted as the terminal's text in the same pass.
+// the ordered mean's pass, or (kText, kHalfText, kKittyText) cast and formatted as the terminal's text in the same pass.
 static int launch_render(trt_context *ctx, const RenderPlan &plan, const trt::FrameView &f, const trt::GridView &grids, const trt::BatchView *batch, void *out,
                          Output kind, long pixels, int lane_set, int entry)
 {
@@ -757,6 +783,24 @@ extern "C" int trt_ansi_half_from_rgb8_device(trt_context *ctx, const void *d_rg
 extern "C" int trt_ansi_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text)
 {
     return text_from_rgb8_device(ctx, kText, d_rgb8, width, rows, d_text);
+}
+
+extern "C" size_t trt_kitty_bytes(int width, int rows)
+{
+    return (size_t)trt_kitty_text_bytes(width, rows);
+}
+
+extern "C" int trt_render_device_kitty(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                                       size_t capacity_bytes)
+{
+    return render_device_on(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, 0, kEntryWhole, kKittyText);
+}
+
+extern "C" int trt_kitty_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text)
+{
+    if (width > TRT_KITTY_MAX || rows > TRT_KITTY_MAX)
+        return fail(TRT_ERR_ARGUMENT, "a kitty image of %d x %d exceeds %d", width, rows, TRT_KITTY_MAX);
+    return text_from_rgb8_device(ctx, kKittyText, d_rgb8, width, rows, d_text);
 }
 
 extern "C" int trt_quantize_device(trt_context *ctx, const void *d_pixels, size_t num_pixels, void *d_rgb8)
@@ -1028,6 +1072,8 @@ static int render_host_as(trt_context *ctx, const Camera *cameras, int n, bool b
     if (!rowset_valid(rows))
         return fail(TRT_ERR_ARGUMENT, "invalid rowset");
     HIP_TRY(hipSetDevice(ctx->device));
+    if (kind == kKittyText && (rows->width > TRT_KITTY_MAX || trt_rowset_rows(rows) > TRT_KITTY_MAX))
+        return fail(TRT_ERR_ARGUMENT, "a kitty image of %d x %d exceeds %d", rows->width, trt_rowset_rows(rows), TRT_KITTY_MAX);
     const size_t bytes = (size_t)n * frame_bytes(kind, rows->width, trt_rowset_rows(rows));
     if (!batch && bytes == 0)
         return TRT_OK;
@@ -1095,6 +1141,22 @@ extern "C" int trt_render_host_batch_ansi_half(trt_context *ctx, const Camera *c
                                                char *text)
 {
     return render_host_as(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, kHalfText);
+}
+
+extern "C" int trt_render_device_batch_kitty(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                             void *d_text, size_t capacity_bytes)
+{
+    return render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, kKittyText);
+}
+
+extern "C" int trt_render_host_kitty(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text)
+{
+    return render_host_as(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, text, kKittyText, "trt_render_host_kitty");
+}
+
+extern "C" int trt_render_host_batch_kitty(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text)
+{
+    return render_host_as(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, kKittyText);
 }
 
 extern "C" int trt_batch_info(trt_context *ctx, int *frames, int *render_launches)

@@ -74,6 +74,13 @@ SYMBOLS = {
     "trt_render_host_ansi_half": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP]),
     "trt_render_device_batch_ansi_half": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ]),
     "trt_render_host_batch_ansi_half": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP]),
+    "trt_kitty_bytes": (_SZ, [_I, _I]),
+    "trt_render_device_kitty": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ]),
+    "trt_kitty_from_rgb8_device": (_I, [_VP, _VP, _I, _I, _VP]),
+    "trt_render_host_kitty": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP]),
+    "trt_render_device_batch_kitty": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ]),
+    "trt_render_host_batch_kitty": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP]),
+    "trt_render_frame_kitty": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP]),
     "trt_render_frame_ansi_delta_half": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
     "trt_ansi_delta_half_capacity": (_SZ, [_I, _I]),
     "trt_ansi_delta_half_from_rgb8_device": (_I, [_VP, _VP, _VP, _I, _I, _VP, _SZ, _VP]),
@@ -504,6 +511,38 @@ class Context:
         """the half-block text of a width x rows frame of RGB8 bytes in device memory, at text_ptr (trt_ansi_half_from_rgb8_device)"""
         _check(lib().trt_ansi_half_from_rgb8_device(self._h, _VP(rgb_ptr), width, rows, _VP(text_ptr)))
 
+    def render_device_kitty(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
+        """the frame as a kitty graphics-protocol image in device memory: kitty_bytes(width, owned rows) bytes at any alignment, formatted
+        by the ordered-mean pass itself (trt_render_device_kitty)"""
+        cam = camera_struct(camera_array)
+        _check(lib().trt_render_device_kitty(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, _VP(device_ptr), capacity_bytes))
+
+    def render_host_kitty(self, camera_array, rows, bounce_limit, rays_per_pixel):
+        """the same into host memory: uint8 [kitty_bytes(width, owned rows)] (trt_render_host_kitty)"""
+        out = np.zeros(kitty_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows))), dtype=np.uint8)
+        cam = camera_struct(camera_array)
+        _check(lib().trt_render_host_kitty(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data))
+        return out
+
+    def kitty_from_rgb8(self, rgb_ptr, width, rows, text_ptr):
+        """the kitty image of a width x rows frame of RGB8 bytes in device memory, at text_ptr (trt_kitty_from_rgb8_device)"""
+        _check(lib().trt_kitty_from_rgb8_device(self._h, _VP(rgb_ptr), width, rows, _VP(text_ptr)))
+
+    def render_batch_kitty(self, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
+        """cameras[n, 15] as kitty images in device memory; frame b at device_ptr + b * kitty_bytes(width, owned rows)
+        (trt_render_device_batch_kitty)"""
+        cams = self._camera_batch(cameras)
+        _check(lib().trt_render_device_batch_kitty(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
+                                                   _VP(device_ptr), capacity_bytes))
+
+    def render_host_batch_kitty(self, cameras, rows, bounce_limit, rays_per_pixel):
+        """the same into host memory: uint8 [n, kitty_bytes(width, owned rows)] (trt_render_host_batch_kitty)"""
+        cams = self._camera_batch(cameras)
+        out = np.zeros((cams.shape[0], kitty_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows)))), dtype=np.uint8)
+        _check(lib().trt_render_host_batch_kitty(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
+                                                 out.ctypes.data))
+        return out
+
     # the delta entries come in two kinds of cell, the full text's and half-block cells: each pair goes through one helper that takes the entry's name
 
     def _delta_from_rgb8(self, entry, shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr):
@@ -860,6 +899,12 @@ def ansi_half_bytes(width, rows):
     return int(lib().trt_ansi_half_bytes(width, rows))
 
 
+def kitty_bytes(width, rows):
+    """length of the kitty graphics-protocol image of a width x rows screen: 4 P + 10 ceil(P / 1024) + 46, P = width * rows; 0 unless both
+    are positive and at most 99999 (trt_kitty_bytes)"""
+    return int(lib().trt_kitty_bytes(width, rows))
+
+
 def _header_constant(header, name):
     """an integer #define of a header under csrc/: the layout headers are what the kernels compile, the binding reads them, it does not restate them"""
     import re
@@ -922,6 +967,15 @@ def render_frame_ansi_half(scene_data, width, height, bounce_limit=10, rays_per_
     scene = scene_data.as_scene()
     out = np.zeros(ansi_half_bytes(width, height), dtype=np.uint8)
     _check(lib().trt_render_frame_ansi_half(C.byref(scene), width, height, bounce_limit, rays_per_pixel, out.ctypes.data))
+    return out
+
+
+def render_frame_kitty(scene_data, width, height, bounce_limit=10, rays_per_pixel=10):
+    """Host-in, kitty-image-out frame: uint8 [kitty_bytes(width, height)], four bytes of text a pixel, formatted on the device
+    (trt_render_frame_kitty)."""
+    scene = scene_data.as_scene()
+    out = np.zeros(kitty_bytes(width, height), dtype=np.uint8)
+    _check(lib().trt_render_frame_kitty(C.byref(scene), width, height, bounce_limit, rays_per_pixel, out.ctypes.data))
     return out
 
 

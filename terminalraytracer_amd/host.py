@@ -29,6 +29,7 @@ HOST_SYMBOLS = {
     "trt_emitter_patch_rgb8": (C.c_int, [_VP, _VP]),
     "trt_emitter_delta_rgb8": (_I, [_VP, _VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_half_rgb8": (_I, [_VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "trt_emitter_kitty_rgb8": (_I, [_VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_delta_half_rgb8": (_I, [_VP, _VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_write": (_I, [_VP, _VP]),
     "trt_draw_screen": (_I, [C.POINTER(L.Screen), _VP]),
@@ -119,6 +120,20 @@ def emitter_delta_rgb8(shown, nxt):
     if rc != 0:
         raise ValueError(f"trt_emitter_delta_rgb8({width}, {rows}) failed with {rc}")
     return out[:n.value].copy()
+
+
+def emitter_kitty_rgb8(rgb):
+    """the kitty graphics-protocol image of a frame of bytes [rows, width, 3], formatted on the host: uint8
+    [4 P + 10 ceil(P / 1024) + 46], P = width rows (trt_emitter_kitty_rgb8)"""
+    a = np.ascontiguousarray(rgb, dtype=np.uint8)
+    rows, width, _ = a.shape
+    pixels = rows * width
+    out = np.empty(4 * pixels + 10 * ((pixels + 1023) // 1024) + 46, dtype=np.uint8)
+    n = C.c_size_t(0)
+    rc = lib().trt_emitter_kitty_rgb8(a.ctypes.data, width, rows, out.ctypes.data, out.size, C.byref(n))
+    if rc != 0 or n.value != out.size:
+        raise ValueError(f"trt_emitter_kitty_rgb8({width}, {rows}) failed with {rc}, {n.value} bytes")
+    return out
 
 
 def emitter_half_rgb8(rgb):
