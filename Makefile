@@ -23,7 +23,7 @@ all: lib demo oracle stub
 
 lib: $(LIB)
 
-$(BUILD)/host_%.o: $(CSRC)/host/%.c include/trt.h include/trt_host.h
+$(BUILD)/host_%.o: $(CSRC)/host/%.c include/trt.h include/trt_host.h $(CSRC)/trt_xterm256.h
 	@mkdir -p $(BUILD)
 	$(CC) $(HOSTFLAGS) -c -o $@ $<
 

@@ -80,6 +80,18 @@ int trt_render_frame_ansi_half(const Scene *scene, int width, int height, int bo
  * trt_render_frame_rgb8's bytes.  width and height are at most 99999.  Lock and scene policy as above. */
 int trt_render_frame_kitty(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text);
 
+/* The same frame as the text in the XTERM 256-COLOUR PALETTE, for terminals without 24-bit colour (trt_render_host_ansi256 below, on the
+ * default context: its format and its palette rule): two spaces a pixel, 13 bytes each.  text holds trt_ansi256_bytes(width, height)
+ * bytes, the whole of which the host writes with one fwrite: byte for byte trt_emitter_ansi256_rgb8 (trt_host.h) of
+ * trt_render_frame_rgb8's bytes.  Lock and scene policy as above. */
+int trt_render_frame_ansi256(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text);
+
+/* The same frame as the HALF-BLOCK text in the xterm 256-colour palette (trt_render_host_ansi256_half below, on the default context): two
+ * pixel rows per line of text, 23 bytes a cell.  text holds trt_ansi256_half_bytes(width, height) bytes: byte for byte
+ * trt_emitter_ansi256_half_rgb8 (trt_host.h) of trt_render_frame_rgb8's bytes.  The terminal must be in a UTF-8 locale.  Lock and scene
+ * policy as above. */
+int trt_render_frame_ansi256_half(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text);
+
 /* The frame as the DELTA text against the frame this entry returned before (trt_render_host_ansi_delta below, on the default context: its
  * format, its rules for the host and its errors).  The first call, the first call of another size and the first call after trt_shutdown
  * return a keyframe: trt_render_frame_ansi's text.  text holds capacity_bytes >= trt_ansi_delta_capacity(width, height) bytes; the host
@@ -277,6 +289,58 @@ int trt_render_device_kitty(trt_context *ctx, const Camera *camera, const trt_ro
  * trt_dist_render_rgb8 gather holds): trt_kitty_bytes(width, rows) bytes at d_text, any alignment.  Asynchronous. */
 int trt_kitty_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text);
 
+/* ---- the texts in the xterm 256-colour palette: for terminals without 24-bit colour ----------------------------------------------------
+ * The two texts above colour their cells with "48;2;R;G;B", 24-bit SGR colour, and the kitty image needs a terminal that speaks that
+ * protocol.  Terminal.app, older tmux and screen, PuTTY set-ups and many CI and serial consoles have only the palette of 256 colours:
+ * "48;5;N".  Entries 0..15 of it are the user's to theme and are never produced; the 240 others are fixed numbers -- 16 + 36 i + 6 j + k
+ * is the colour (L[i], L[j], L[k]), L = {0, 95, 135, 175, 215, 255}, and 232 + k is the grey 8 + 10 k, k = 0..23.  THE RULE: a pixel's
+ * index is the entry, of these 240, with the least squared Euclidean distance in RGB bytes to the emitter's bytes of the pixel
+ * ((int)(c*255), trt_render_device_rgb8's), ties to the lowest index.  trt_xterm256_index_search (trt_host.h) is that search;
+ * csrc/trt_xterm256.h is the closed form of it that the device computes, equal to it on all 2^24 colours.  An index depends on the
+ * pixel's three bytes alone: there is no dithering.
+ *
+ * The full 256-colour text.  For a screen of `width` x `rows` owned rows in LOCAL row order (for a shard, the owned rows), in order:
+ *   "\033[0;0H"                                    6 bytes
+ *   per owned row:  width cells "\033[48;5;NNNm  "  13 bytes each: NNN the pixel's index, three zero-padded digits
+ *                   "\033[0m\n"                     5 bytes
+ * 6 + (13 width + 5) rows bytes, no NUL.  It is not trt_ansi_bytes' text with other colours: rows end in a reset and no NULs follow.
+ *
+ * The half-block 256-colour text.  T = (rows + 1) / 2 text rows, in order:
+ *   "\033[0;0H"                                                          6 bytes
+ *   per text row t:  width cells "\033[38;5;UUU;48;5;LLLm" E2 96 80       23 bytes each: UUU the index of owned row 2 t, LLL that of owned
+ *                                                                         row 2 t + 1; 016, black, behind the last row of an odd frame
+ *                    "\033[0m\n"                                         5 bytes
+ * 6 + (23 width + 5) T bytes, no NUL.  The terminal must be in a UTF-8 locale.
+ *
+ * csrc/trt_ansi256.h and csrc/trt_ansi256_half.h are the formats in code, trt_emitter_ansi256_rgb8 and trt_emitter_ansi256_half_rgb8
+ * (trt_host.h) their sequential statements on the host.  Limits: those of the 24-bit texts (fewer than 2^31 - 1 pixels).  Checks,
+ * TRT_ERR_*, stream behaviour and the trt_kernel_times accounting of every entry are those of the _ansi_half entry it mirrors;
+ * capacities count bytes of text, to the byte.  OUT OF SCOPE: there is no delta form -- none of these entries reads or changes the delta
+ * entries' shown frame -- no refraction form, no dithering and no 16-colour text; of a trt_dist_render_rgb8 gather rank 0 formats the
+ * assembled bytes with the _from_rgb8_device entries.  No terminal was at hand to look at the picture: the tests hold the texts against
+ * the sequential emitters and a structural reader. */
+
+/* Lengths of the two texts: 6 + (13 width + 5) rows and 6 + (23 width + 5) ((rows + 1) / 2); 0 unless both arguments are positive. */
+size_t trt_ansi256_bytes(int width, int rows);
+size_t trt_ansi256_half_bytes(int width, int rows);
+/* trt_render_device_ansi as the 256-colour text: trt_ansi256_bytes(width, owned rows) bytes at d_text, any alignment, written by the pass
+ * that forms the ordered mean -- a lane forms a pixel once, maps it to the palette and keeps the index; neither doubles nor RGB8 bytes
+ * are written on the way, every byte of the text is stored exactly once (d_text need not be initialised) and none outside it (the
+ * reference-order kernel goes through a framebuffer and bytes of the context's). */
+int trt_render_device_ansi256(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,
+                              int rays_per_pixel, void *d_text, size_t capacity_bytes);
+/* The same as the half-block 256-colour text: trt_ansi256_half_bytes(width, owned rows) bytes; a lane forms both pixels of a cell. */
+int trt_render_device_ansi256_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,
+                                   int rays_per_pixel, void *d_text, size_t capacity_bytes);
+/* The formatting alone, of a frame that exists as RGB8 bytes in device memory (as trt_ansi_from_rgb8_device; e.g. what rank 0 of a
+ * trt_dist_render_rgb8 gather holds): trt_ansi256_bytes / trt_ansi256_half_bytes(width, rows) bytes at d_text, any alignment.
+ * Asynchronous. */
+int trt_ansi256_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text);
+int trt_ansi256_half_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text);
+/* The palette map alone, trt_quantize_device's analogue: d_index[p] = the palette index 16..255 of the pixel d_rgb8[3 p ...], a paletted
+ * frame at one byte a pixel, either pointer at any alignment.  Asynchronous on the context's stream; num_pixels 0 does nothing. */
+int trt_xterm256_from_rgb8_device(trt_context *ctx, const void *d_rgb8, size_t num_pixels, void *d_index);
+
 /* ---- the delta text: only the cells that changed --------------------------------------------------------------------------------
  * A terminal keeps what it was sent.  The text above repaints every cell of every frame, 25 bytes each; the DELTA text between the frame
  * the terminal shows and the next one holds, for every CHANGED cell (its three RGB8 bytes differ), rows ascending, left to right:
@@ -404,6 +468,13 @@ int trt_render_host_ansi_half(trt_context *ctx, const Camera *camera, const trt_
 int trt_render_host_kitty(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
                           char *text);
 
+/* trt_render_device_ansi256 and trt_render_device_ansi256_half into HOST memory: trt_ansi256_bytes / trt_ansi256_half_bytes(width, owned
+ * rows) bytes (synchronous; one copy-out through pinned staging). */
+int trt_render_host_ansi256(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                            char *text);
+int trt_render_host_ansi256_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                 char *text);
+
 /* Several cameras of the current scene in one call: an orbit, a replay, a stereo pair, the faces of an environment probe. */
 #define TRT_BATCH_MAX 8 /* = the eye-table slots a scene's tables have */
 
@@ -459,6 +530,20 @@ int trt_render_device_batch_kitty(trt_context *ctx, const Camera *cameras, int n
 /* The same into HOST memory: text[b * trt_kitty_bytes(width, owned rows) ...] (synchronous; one copy-out through pinned staging). */
 int trt_render_host_batch_kitty(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
                                 int rays_per_pixel, char *text);
+
+/* trt_render_device_batch as the 256-colour texts (trt_render_device_ansi256, trt_render_device_ansi256_half): frame b at d_text + b *
+ * trt_ansi256_bytes / trt_ansi256_half_bytes(width, owned rows), aligned to nothing in general; launches, splits, trt_batch_info and
+ * errors as trt_render_device_batch_ansi, the capacity counted in bytes of text for n frames. */
+int trt_render_device_batch_ansi256(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                    int rays_per_pixel, void *d_text, size_t capacity_bytes);
+int trt_render_device_batch_ansi256_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                         int rays_per_pixel, void *d_text, size_t capacity_bytes);
+/* The same into HOST memory: text[b * trt_ansi256_bytes / trt_ansi256_half_bytes(width, owned rows) ...] (synchronous; one copy-out
+ * through pinned staging). */
+int trt_render_host_batch_ansi256(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                  int rays_per_pixel, char *text);
+int trt_render_host_batch_ansi256_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                       int rays_per_pixel, char *text);
 
 /* ---- delta texts for a batch: n texts back to back, one prefix sum over all frames --------------------------------------------------
  * A CHAIN is a shown frame and n frames of RGB8 bytes (rows x width x 3 each), 1 <= n <= TRT_BATCH_MAX.  Text b takes a terminal from

@@ -104,6 +104,27 @@ int trt_emitter_delta_half_rgb8(const unsigned char *shown, const unsigned char 
  * statement the device kernels (trt_render_device_kitty, trt_hip.h) are tested against, and the emitter of hosts that fetch RGB8 bytes.
  * TRT_HOST_ERR_ARGUMENT: NULL, a size that is not positive or above the limits, a capacity below the length. */
 int trt_emitter_kitty_rgb8(const unsigned char *rgb, int width, int rows, char *text, size_t capacity, size_t *bytes);
+/* The xterm 256-colour palette, for terminals without 24-bit colour.  Entries 0..15 are the user's to theme and are never produced; of
+ * the 240 fixed ones -- 16 + 36 i + 6 j + k the colour (L[i], L[j], L[k]), L = {0, 95, 135, 175, 215, 255}, and 232 + k the grey 8 + 10 k
+ * -- a colour of three bytes has the entry with the least squared Euclidean distance in RGB bytes, ties to the lowest index.  No
+ * dithering: the index depends on the three bytes alone.  trt_xterm256_index_search IS that rule, a loop over the 240 entries;
+ * trt_xterm256_index is the closed form of csrc/trt_xterm256.h that the device kernels compute, compiled for the host: the two are equal
+ * on all 2^24 colours.  Both take bytes (the low 8 bits of each argument) and return 16..255.  (A program that compiles
+ * csrc/trt_xterm256.h itself, in front of this header, has trt_xterm256_index as that header's inline function.) */
+#ifndef TRT_XTERM256_H
+unsigned trt_xterm256_index(unsigned r, unsigned g, unsigned b);
+#endif
+unsigned trt_xterm256_index_search(unsigned r, unsigned g, unsigned b);
+/* The frame of such bytes (rows x width x 3) as text in that palette: "\033[0;0H"; per row, width cells "\033[48;5;NNNm" and two spaces,
+ * NNN the pixel's index by the SEARCH, three zero-padded digits; then "\033[0m\n".  No NUL: *bytes = 6 + (13 * width + 5) * rows, which
+ * `capacity` must hold.  The format is the project's own (csrc/trt_ansi256.h).  The sequential statement the device kernels
+ * (trt_render_device_ansi256, trt_hip.h) are tested against, and the emitter of hosts that fetch RGB8 bytes.  TRT_HOST_ERR_ARGUMENT: NULL,
+ * a size that is not positive, a capacity below the length. */
+int trt_emitter_ansi256_rgb8(const unsigned char *rgb, int width, int rows, char *text, size_t capacity, size_t *bytes);
+/* The same frame as HALF-BLOCK text in that palette (csrc/trt_ansi256_half.h): per text row t < (rows + 1) / 2, width cells
+ * "\033[38;5;UUU;48;5;LLLm" and the glyph U+2580 in UTF-8 (E2 96 80) -- UUU the index of row 2 t, LLL that of row 2 t + 1; 016, black, behind
+ * the last row of an odd frame -- then "\033[0m\n".  No NUL: *bytes = 6 + (23 * width + 5) * ((rows + 1) / 2).  Errors as above. */
+int trt_emitter_ansi256_half_rgb8(const unsigned char *rgb, int width, int rows, char *text, size_t capacity, size_t *bytes);
 /* TRT.c:1171: one fwrite of the whole buffer (trailing NULs included, as the reference does) */
 int trt_emitter_write(const trt_emitter *e, FILE *stream);
 /* TRT.c:1084-1099: the unbuffered printf form */

@@ -388,3 +388,111 @@ int trt_draw_screen(const Screen *screen, FILE *stream)
     }
     return TRT_HOST_OK;
 }
+
+/* ---- the xterm 256-colour palette (csrc/trt_xterm256.h holds the rule and its closed form) ---- */
+
+/* the closed form the device computes, compiled here from the header the kernels compile; the header's inline function has the name
+ * this library exports, so it is compiled under another */
+#define trt_xterm256_index trt_xterm256_index_closed_form
+#include "../trt_xterm256.h"
+#undef trt_xterm256_index
+
+unsigned trt_xterm256_index(unsigned r, unsigned g, unsigned b)
+{
+    return trt_xterm256_index_closed_form(r & 0xffu, g & 0xffu, b & 0xffu);
+}
+
+/* The rule itself: all 240 fixed entries in index order -- the cube's 16 + 36 i + 6 j + k, then the ramp's 232 + k -- the first of the
+ * nearest.  Plain loops, on purpose without the header's arithmetic -- this is what the closed form and the device kernels are held
+ * against. */
+unsigned trt_xterm256_index_search(unsigned r, unsigned g, unsigned b)
+{
+    static const int levels[6] = {0, 95, 135, 175, 215, 255};
+    const int pr = (int)(r & 0xffu), pg = (int)(g & 0xffu), pb = (int)(b & 0xffu);
+    unsigned best = 16, index = 16;
+    int best_distance = 3 * 255 * 255 + 1; /* above every distance */
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++)
+            for (int k = 0; k < 6; k++, index++)
+            {
+                const int distance = (pr - levels[i]) * (pr - levels[i]) + (pg - levels[j]) * (pg - levels[j]) + (pb - levels[k]) * (pb - levels[k]);
+                if (distance < best_distance) /* strictly nearer: ties stay with the lower index */
+                    best = index, best_distance = distance;
+            }
+    for (int k = 0; k < 24; k++, index++)
+    {
+        const int grey = 8 + 10 * k;
+        const int distance = (pr - grey) * (pr - grey) + (pg - grey) * (pg - grey) + (pb - grey) * (pb - grey);
+        if (distance < best_distance)
+            best = index, best_distance = distance;
+    }
+    return best;
+}
+
+/* The full text in the palette (csrc/trt_ansi256.h holds the format): two spaces a pixel on the background colour the search finds. */
+static const char k_cell256[] = "\033[48;5;000m  ";
+static const char k_end256[] = "\033[0m\n";
+static const char k_half_cell256[] = "\033[38;5;000;48;5;000m\xe2\x96\x80";
+enum
+{
+    CELL256_LEN = sizeof(k_cell256) - 1,           /* 13 */
+    END256_LEN = sizeof(k_end256) - 1,             /* 5 */
+    HALF_CELL256_LEN = sizeof(k_half_cell256) - 1, /* 23 */
+    INDEX256_AT = 7,                               /* "\033[48;5;" */
+    UPPER256_AT = 7,                               /* "\033[38;5;" */
+    LOWER256_AT = 16,                              /* ... "UUU;48;5;" */
+    BLACK256 = 16
+};
+
+int trt_emitter_ansi256_rgb8(const unsigned char *rgb, int width, int rows, char *text, size_t capacity, size_t *bytes)
+{
+    if (!rgb || !text || !bytes || width <= 0 || rows <= 0)
+        return TRT_HOST_ERR_ARGUMENT;
+    if (capacity < HOME_LEN + ((size_t)CELL256_LEN * width + END256_LEN) * (size_t)rows)
+        return TRT_HOST_ERR_ARGUMENT;
+    char *p = text;
+    memcpy(p, k_home, HOME_LEN);
+    p += HOME_LEN;
+    for (int row = 0; row < rows; row++)
+    {
+        const unsigned char *px = rgb + (size_t)row * width * 3;
+        for (int col = 0; col < width; col++, p += CELL256_LEN)
+        {
+            memcpy(p, k_cell256, CELL256_LEN);
+            three_digits(p + INDEX256_AT, (int)trt_xterm256_index_search(px[3 * col], px[3 * col + 1], px[3 * col + 2]));
+        }
+        memcpy(p, k_end256, END256_LEN);
+        p += END256_LEN;
+    }
+    *bytes = (size_t)(p - text);
+    return TRT_HOST_OK;
+}
+
+/* The half-block text in the palette (csrc/trt_ansi256_half.h holds the format): two owned rows per line of text, the upper one's index
+ * as the foreground and the lower one's as the background of an upper-half-block glyph; black, 016, behind an odd frame's last row. */
+int trt_emitter_ansi256_half_rgb8(const unsigned char *rgb, int width, int rows, char *text, size_t capacity, size_t *bytes)
+{
+    if (!rgb || !text || !bytes || width <= 0 || rows <= 0)
+        return TRT_HOST_ERR_ARGUMENT;
+    const size_t text_rows = ((size_t)rows + 1) / 2;
+    if (capacity < HOME_LEN + ((size_t)HALF_CELL256_LEN * width + END256_LEN) * text_rows)
+        return TRT_HOST_ERR_ARGUMENT;
+    char *p = text;
+    memcpy(p, k_home, HOME_LEN);
+    p += HOME_LEN;
+    for (int upper_row = 0; upper_row < rows; upper_row += 2)
+    {
+        const unsigned char *upper = rgb + (size_t)upper_row * width * 3;
+        const unsigned char *lower = upper_row + 1 < rows ? upper + (size_t)width * 3 : NULL;
+        for (int col = 0; col < width; col++, p += HALF_CELL256_LEN)
+        {
+            memcpy(p, k_half_cell256, HALF_CELL256_LEN);
+            three_digits(p + UPPER256_AT, (int)trt_xterm256_index_search(upper[3 * col], upper[3 * col + 1], upper[3 * col + 2]));
+            three_digits(p + LOWER256_AT, lower ? (int)trt_xterm256_index_search(lower[3 * col], lower[3 * col + 1], lower[3 * col + 2]) : BLACK256);
+        }
+        memcpy(p, k_end256, END256_LEN);
+        p += END256_LEN;
+    }
+    *bytes = (size_t)(p - text);
+    return TRT_HOST_OK;
+}

@@ -96,7 +96,7 @@ static int refresh_default_scene(trt_context *ctx, const Scene *scene)
     return TRT_OK;
 }
 
-// The drop-in entries (project_scene, trt_render_frame, trt_render_frame_rgb8, trt_render_frame_ansi, trt_render_frame_ansi_half, trt_render_frame_kitty) take the scene with every call.  A scene whose
+// The drop-in entries (project_scene, trt_render_frame, trt_render_frame_rgb8, trt_render_frame_ansi, trt_render_frame_ansi_half, trt_render_frame_kitty, trt_render_frame_ansi256, trt_render_frame_ansi256_half) take the scene with every call.  A scene whose
 // primitives differ from the previous call's on `moving_after` consecutive calls is treated as MOVING: its candidate tables are
 // rebuilt per call the cheap way (one family per sphere, no patches); after `still_after` consecutive unchanged calls the full
 // tables are built once.  moving_after = 0: never (every change builds the full tables).  Defaults 2 and 3.  Frames are
@@ -216,6 +216,29 @@ extern "C" int trt_render_frame_kitty(const Scene *scene, int width, int height,
     return render_default_frame(scene, width, height, [&](trt_context *ctx, const trt_rowset *whole) {
         return trt_render_host_kitty(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, text);
     });
+}
+
+// the two texts in the xterm 256-colour palette: `render` is the kind's host entry
+static int render_frame_ansi256(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text,
+                                int (*render)(trt_context *, const Camera *, const trt_rowset *, int, int, char *))
+{
+    if (!scene || !text)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (width <= 0 || height <= 0)
+        return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, height);
+    return render_default_frame(scene, width, height, [&](trt_context *ctx, const trt_rowset *whole) {
+        return render(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, text);
+    });
+}
+
+extern "C" int trt_render_frame_ansi256(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text)
+{
+    return render_frame_ansi256(scene, width, height, bounce_limit, rays_per_pixel, text, trt_render_host_ansi256);
+}
+
+extern "C" int trt_render_frame_ansi256_half(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text)
+{
+    return render_frame_ansi256(scene, width, height, bounce_limit, rays_per_pixel, text, trt_render_host_ansi256_half);
 }
 
 // the shown frame is the default context's: trt_shutdown forgets it with the context.  `capacity` and `render`: those of the kind

@@ -10,6 +10,7 @@
 #include "trt_simple.hpp"
 #include "trt_ansi.hpp"
 #include "trt_ansi_delta.hpp"
+#include "trt_ansi256.hpp"
 #include "trt_ansi_half.hpp"
 #include "trt_kitty.hpp"
 
@@ -373,10 +374,11 @@ extern "C" int trt_read_counters(trt_context *ctx, unsigned long long *path_rays
 
 // What a launch leaves of a frame: the Screen's pixels of three doubles (TRT.c:188-193), the emitter's three bytes per pixel
 // ((int)(c*255), TRT.c:1157-1163), the text the emitter makes of those bytes (TRT.c:1142-1172; trt_ansi.h), or the half-block text of
-// them, two owned rows per line of text (trt_ansi_half.h), or those bytes as a kitty graphics-protocol image (trt_kitty.h).
-enum Output : int { kDoubles, kBytes, kText, kHalfText, kKittyText };
+// them, two owned rows per line of text (trt_ansi_half.h), or those bytes as a kitty graphics-protocol image (trt_kitty.h), or either
+// text in the xterm 256-colour palette (trt_ansi256.h, trt_ansi256_half.h).
+enum Output : int { kDoubles, kBytes, kText, kHalfText, kKittyText, kText256, kHalfText256 };
 
-static bool is_text(Output kind) { return kind == kText || kind == kHalfText || kind == kKittyText; }
+static bool is_text(Output kind) { return kind >= kText; }
 
 // bytes of one frame of `rows` rows of `width` pixels
 static size_t frame_bytes(Output kind, int width, int rows)
@@ -387,6 +389,10 @@ static size_t frame_bytes(Output kind, int width, int rows)
         return (size_t)trt_ansi_half_text_bytes(width, rows);
     if (kind == kKittyText)
         return (size_t)trt_kitty_text_bytes(width, rows);
+    if (kind == kText256)
+        return (size_t)trt_ansi256_text_bytes(width, rows);
+    if (kind == kHalfText256)
+        return (size_t)trt_ansi256_half_text_bytes(width, rows);
     return (size_t)rows * width * 3 * (kind == kBytes ? 1u : sizeof(double));
 }
 
@@ -459,9 +465,9 @@ static trt::FrameView frame_view(const trt_context *ctx, const Camera *camera, c
     return f;
 }
 
-// What the launches of a whole text need of its format (trt_ansi.h, trt_ansi_half.h): the length, the lane map's kind, and the two
-// kernels that write it.  The kernels' argument lists differ in one place: the half-block text's take the width's magic behind the
-// row length's.
+// What the launches of a whole text need of its format (trt_ansi.h, trt_ansi_half.h, trt_ansi256.h, trt_ansi256_half.h): the length,
+// the lane map's kind, and the two kernels that write it.  The kernels' argument lists differ in one place: the half-block texts' take
+// the width's magic behind the row length's.
 struct TextFormat
 {
     trt_text_kind kind;
@@ -472,11 +478,14 @@ struct TextFormat
 
 static const TextFormat &text_format(Output kind)
 {
-    static const TextFormat formats[2] = {
+    static const TextFormat formats[4] = {
         {trt_ansi_kind(), trt_ansi_text_bytes, nullptr, (const void *)trt::reduce_samples_ansi_kernel, (const void *)trt::ansi_from_rgb8_kernel},
         {trt_ansi_half_kind(), trt_ansi_half_text_bytes, trt_ansi_half_width_magic, (const void *)trt::reduce_samples_ansi_half_kernel,
-         (const void *)trt::ansi_half_from_rgb8_kernel}};
-    return formats[kind == kHalfText];
+         (const void *)trt::ansi_half_from_rgb8_kernel},
+        {trt_ansi256_kind(), trt_ansi256_text_bytes, nullptr, (const void *)trt::reduce_samples_ansi256_kernel, (const void *)trt::ansi256_from_rgb8_kernel},
+        {trt_ansi256_half_kind(), trt_ansi256_half_text_bytes, trt_ansi256_half_width_magic, (const void *)trt::reduce_samples_ansi256_half_kernel,
+         (const void *)trt::ansi256_half_from_rgb8_kernel}};
+    return formats[kind == kText ? 0 : kind == kHalfText ? 1 : kind == kText256 ? 2 : 3];
 }
 
 // One of a text's kernels over `frames` frames of width x rows at `out`, a wave per kind.wave_words aligned words: ONE frame's grid has
@@ -532,8 +541,7 @@ static void launch_text_from_rgb8(hipStream_t stream, Output kind, const unsigne
 enum : int { kEntryOpens = 1, kEntryCloses = 2, kEntryWhole = kEntryOpens | kEntryCloses };
 
 // The reference-order kernel's launch: it has no scratch and no mean.  Its bytes are its doubles, rendered into the context's
-// framebuffer, through quantize_kernel, and its text is those bytes through ansi_from_rgb8_kernel, ansi_half_from_rgb8_kernel or
-// kitty_from_rgb8_kernel.
+// framebuffer, through quantize_kernel, and its text is those bytes through the kind's *_from_rgb8_kernel.
 static int launch_reference(trt_context *ctx, const RenderPlan &plan, trt::FrameView f, void *out, Output kind, long pixels, hipStream_t stream, int entry)
 {
     const int slot = (int)(ctx->launches % kEventRing);
@@ -593,7 +601,9 @@ static void launch_ordered_mean(hipStream_t stream, const RenderPlan &plan, cons
                            stream, samples, (unsigned char *)out, values, f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
         break;
     case kText:
-    case kHalfText: // a wave per kind.wave_words aligned words
+    case kHalfText:
+    case kText256:
+    case kHalfText256: // a wave per kind.wave_words aligned words
     {
         const TextFormat &t = text_format(kind);
         const unsigned waves_per_group = plan.block / 64;
@@ -675,7 +685,7 @@ static int launch_production(trt_context *ctx, const RenderPlan &plan, trt::Fram
 }
 
 // Carries out a planned launch on the route its variant takes, into `out` as `kind`: doubles, (kBytes) cast to the emitter's bytes in
-// the ordered mean's pass, or (kText, kHalfText, kKittyText) cast and formatted as the terminal's text in the same pass.
+// the ordered mean's pass, or (the texts) cast and formatted as the terminal's text in the same pass.
 static int launch_render(trt_context *ctx, const RenderPlan &plan, const trt::FrameView &f, const trt::GridView &grids, const trt::BatchView *batch, void *out,
                          Output kind, long pixels, int lane_set, int entry)
 {
@@ -801,6 +811,53 @@ extern "C" int trt_kitty_from_rgb8_device(trt_context *ctx, const void *d_rgb8, 
     if (width > TRT_KITTY_MAX || rows > TRT_KITTY_MAX)
         return fail(TRT_ERR_ARGUMENT, "a kitty image of %d x %d exceeds %d", width, rows, TRT_KITTY_MAX);
     return text_from_rgb8_device(ctx, kKittyText, d_rgb8, width, rows, d_text);
+}
+
+extern "C" size_t trt_ansi256_bytes(int width, int rows)
+{
+    return (size_t)trt_ansi256_text_bytes(width, rows);
+}
+
+extern "C" size_t trt_ansi256_half_bytes(int width, int rows)
+{
+    return (size_t)trt_ansi256_half_text_bytes(width, rows);
+}
+
+extern "C" int trt_render_device_ansi256(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                                         size_t capacity_bytes)
+{
+    return render_device_on(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, 0, kEntryWhole, kText256);
+}
+
+extern "C" int trt_render_device_ansi256_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                                              size_t capacity_bytes)
+{
+    return render_device_on(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, 0, kEntryWhole, kHalfText256);
+}
+
+extern "C" int trt_ansi256_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text)
+{
+    return text_from_rgb8_device(ctx, kText256, d_rgb8, width, rows, d_text);
+}
+
+extern "C" int trt_ansi256_half_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text)
+{
+    return text_from_rgb8_device(ctx, kHalfText256, d_rgb8, width, rows, d_text);
+}
+
+extern "C" int trt_xterm256_from_rgb8_device(trt_context *ctx, const void *d_rgb8, size_t num_pixels, void *d_index)
+{
+    if (!ctx || !d_rgb8 || !d_index)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    if (num_pixels == 0)
+        return TRT_OK;
+    if (num_pixels > 0x7fffffffull * 256) // a lane a pixel, 256 a block
+        return fail(TRT_ERR_ARGUMENT, "%zu pixels exceed one launch", num_pixels);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(trt::xterm256_from_rgb8_kernel, dim3((unsigned)((num_pixels + 255) / 256)), dim3(256), 0, ctx->stream, (const unsigned char *)d_rgb8,
+                       (unsigned char *)d_index, (unsigned long long)num_pixels);
+    HIP_TRY(hipGetLastError());
+    return TRT_OK;
 }
 
 extern "C" int trt_quantize_device(trt_context *ctx, const void *d_pixels, size_t num_pixels, void *d_rgb8)
@@ -1157,6 +1214,39 @@ extern "C" int trt_render_host_kitty(trt_context *ctx, const Camera *camera, con
 extern "C" int trt_render_host_batch_kitty(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text)
 {
     return render_host_as(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, kKittyText);
+}
+
+extern "C" int trt_render_host_ansi256(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text)
+{
+    return render_host_as(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, text, kText256, "trt_render_host_ansi256");
+}
+
+extern "C" int trt_render_host_ansi256_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text)
+{
+    return render_host_as(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, text, kHalfText256, "trt_render_host_ansi256_half");
+}
+
+extern "C" int trt_render_device_batch_ansi256(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                               void *d_text, size_t capacity_bytes)
+{
+    return render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, kText256);
+}
+
+extern "C" int trt_render_device_batch_ansi256_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                                    void *d_text, size_t capacity_bytes)
+{
+    return render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, kHalfText256);
+}
+
+extern "C" int trt_render_host_batch_ansi256(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text)
+{
+    return render_host_as(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, kText256);
+}
+
+extern "C" int trt_render_host_batch_ansi256_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                                  char *text)
+{
+    return render_host_as(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, kHalfText256);
 }
 
 extern "C" int trt_batch_info(trt_context *ctx, int *frames, int *render_launches)

@@ -81,6 +81,21 @@ SYMBOLS = {
     "trt_render_device_batch_kitty": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ]),
     "trt_render_host_batch_kitty": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP]),
     "trt_render_frame_kitty": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP]),
+    "trt_ansi256_bytes": (_SZ, [_I, _I]),
+    "trt_ansi256_half_bytes": (_SZ, [_I, _I]),
+    "trt_render_device_ansi256": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ]),
+    "trt_render_device_ansi256_half": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ]),
+    "trt_ansi256_from_rgb8_device": (_I, [_VP, _VP, _I, _I, _VP]),
+    "trt_ansi256_half_from_rgb8_device": (_I, [_VP, _VP, _I, _I, _VP]),
+    "trt_xterm256_from_rgb8_device": (_I, [_VP, _VP, _SZ, _VP]),
+    "trt_render_host_ansi256": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP]),
+    "trt_render_host_ansi256_half": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP]),
+    "trt_render_device_batch_ansi256": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ]),
+    "trt_render_device_batch_ansi256_half": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ]),
+    "trt_render_host_batch_ansi256": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP]),
+    "trt_render_host_batch_ansi256_half": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP]),
+    "trt_render_frame_ansi256": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP]),
+    "trt_render_frame_ansi256_half": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP]),
     "trt_render_frame_ansi_delta_half": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
     "trt_ansi_delta_half_capacity": (_SZ, [_I, _I]),
     "trt_ansi_delta_half_from_rgb8_device": (_I, [_VP, _VP, _VP, _I, _I, _VP, _SZ, _VP]),
@@ -543,6 +558,48 @@ class Context:
                                                  out.ctypes.data))
         return out
 
+    # the texts in the xterm 256-colour palette come in the same two kinds of cell; `half` chooses the half-block entry of each pair
+
+    def render_device_ansi256(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, half=False):
+        """the frame as the 256-colour text in device memory: ansi256_bytes(width, owned rows, half) bytes at any alignment, mapped to the
+        palette and formatted by the ordered-mean pass itself (trt_render_device_ansi256, trt_render_device_ansi256_half)"""
+        cam = camera_struct(camera_array)
+        _check(getattr(lib(), "trt_render_device_ansi256" + _half(half))(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, _VP(device_ptr),
+                                                                         capacity_bytes))
+
+    def render_host_ansi256(self, camera_array, rows, bounce_limit, rays_per_pixel, half=False):
+        """the same into host memory: uint8 [ansi256_bytes(width, owned rows, half)] (trt_render_host_ansi256, trt_render_host_ansi256_half)"""
+        out = np.zeros(ansi256_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows)), half), dtype=np.uint8)
+        cam = camera_struct(camera_array)
+        _check(getattr(lib(), "trt_render_host_ansi256" + _half(half))(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data))
+        return out
+
+    def ansi256_from_rgb8(self, rgb_ptr, width, rows, text_ptr, half=False):
+        """the 256-colour text of a width x rows frame of RGB8 bytes in device memory, at text_ptr (trt_ansi256_from_rgb8_device,
+        trt_ansi256_half_from_rgb8_device)"""
+        _check(getattr(lib(), "trt_ansi256" + _half(half) + "_from_rgb8_device")(self._h, _VP(rgb_ptr), width, rows, _VP(text_ptr)))
+
+    def xterm256_from_rgb8(self, rgb_ptr, num_pixels, index_ptr):
+        """the palette index 16..255 of each of num_pixels pixels of RGB8 bytes in device memory, a byte each at index_ptr
+        (trt_xterm256_from_rgb8_device)"""
+        _check(lib().trt_xterm256_from_rgb8_device(self._h, _VP(rgb_ptr), num_pixels, _VP(index_ptr)))
+
+    def render_batch_ansi256(self, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, half=False):
+        """cameras[n, 15] as 256-colour texts in device memory; frame b at device_ptr + b * ansi256_bytes(width, owned rows, half)
+        (trt_render_device_batch_ansi256, trt_render_device_batch_ansi256_half)"""
+        cams = self._camera_batch(cameras)
+        _check(getattr(lib(), "trt_render_device_batch_ansi256" + _half(half))(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit,
+                                                                               rays_per_pixel, _VP(device_ptr), capacity_bytes))
+
+    def render_host_batch_ansi256(self, cameras, rows, bounce_limit, rays_per_pixel, half=False):
+        """the same into host memory: uint8 [n, ansi256_bytes(width, owned rows, half)] (trt_render_host_batch_ansi256,
+        trt_render_host_batch_ansi256_half)"""
+        cams = self._camera_batch(cameras)
+        out = np.zeros((cams.shape[0], ansi256_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows)), half)), dtype=np.uint8)
+        _check(getattr(lib(), "trt_render_host_batch_ansi256" + _half(half))(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit,
+                                                                             rays_per_pixel, out.ctypes.data))
+        return out
+
     # the delta entries come in two kinds of cell, the full text's and half-block cells: each pair goes through one helper that takes the entry's name
 
     def _delta_from_rgb8(self, entry, shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr):
@@ -905,6 +962,16 @@ def kitty_bytes(width, rows):
     return int(lib().trt_kitty_bytes(width, rows))
 
 
+def _half(half):
+    return "_half" if half else ""
+
+
+def ansi256_bytes(width, rows, half=False):
+    """length of the text of a width x rows screen in the xterm 256-colour palette: 6 + (13 * width + 5) * rows, or for half-block cells
+    6 + (23 * width + 5) * ((rows + 1) // 2); 0 unless both are positive (trt_ansi256_bytes, trt_ansi256_half_bytes)"""
+    return int(getattr(lib(), "trt_ansi256" + _half(half) + "_bytes")(width, rows))
+
+
 def _header_constant(header, name):
     """an integer #define of a header under csrc/: the layout headers are what the kernels compile, the binding reads them, it does not restate them"""
     import re
@@ -976,6 +1043,15 @@ def render_frame_kitty(scene_data, width, height, bounce_limit=10, rays_per_pixe
     scene = scene_data.as_scene()
     out = np.zeros(kitty_bytes(width, height), dtype=np.uint8)
     _check(lib().trt_render_frame_kitty(C.byref(scene), width, height, bounce_limit, rays_per_pixel, out.ctypes.data))
+    return out
+
+
+def render_frame_ansi256(scene_data, width, height, bounce_limit=10, rays_per_pixel=10, half=False):
+    """Host-in, 256-colour-text-out frame: uint8 [ansi256_bytes(width, height, half)], mapped to the xterm palette and formatted on the
+    device (trt_render_frame_ansi256, trt_render_frame_ansi256_half)."""
+    scene = scene_data.as_scene()
+    out = np.zeros(ansi256_bytes(width, height, half), dtype=np.uint8)
+    _check(getattr(lib(), "trt_render_frame_ansi256" + _half(half))(C.byref(scene), width, height, bounce_limit, rays_per_pixel, out.ctypes.data))
     return out
 
 

@@ -30,6 +30,10 @@ HOST_SYMBOLS = {
     "trt_emitter_delta_rgb8": (_I, [_VP, _VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_half_rgb8": (_I, [_VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_kitty_rgb8": (_I, [_VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "trt_xterm256_index": (C.c_uint, [C.c_uint, C.c_uint, C.c_uint]),
+    "trt_xterm256_index_search": (C.c_uint, [C.c_uint, C.c_uint, C.c_uint]),
+    "trt_emitter_ansi256_rgb8": (_I, [_VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "trt_emitter_ansi256_half_rgb8": (_I, [_VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_delta_half_rgb8": (_I, [_VP, _VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_write": (_I, [_VP, _VP]),
     "trt_draw_screen": (_I, [C.POINTER(L.Screen), _VP]),
@@ -133,6 +137,31 @@ def emitter_kitty_rgb8(rgb):
     rc = lib().trt_emitter_kitty_rgb8(a.ctypes.data, width, rows, out.ctypes.data, out.size, C.byref(n))
     if rc != 0 or n.value != out.size:
         raise ValueError(f"trt_emitter_kitty_rgb8({width}, {rows}) failed with {rc}, {n.value} bytes")
+    return out
+
+
+def xterm256_index(r, g, b):
+    """the xterm palette entry 16..255 of a colour of three bytes, by the closed form the device computes (trt_xterm256_index)"""
+    return int(lib().trt_xterm256_index(r, g, b))
+
+
+def xterm256_index_search(r, g, b):
+    """the same by the rule itself: the nearest of the 240 fixed entries in RGB bytes, the lowest index of equals (trt_xterm256_index_search)"""
+    return int(lib().trt_xterm256_index_search(r, g, b))
+
+
+def emitter_ansi256_rgb8(rgb, half=False):
+    """the text of a frame of bytes [rows, width, 3] in the xterm 256-colour palette, formatted on the host: uint8
+    [6 + (13 width + 5) rows], or in half-block cells [6 + (23 width + 5) ((rows + 1) // 2)] (trt_emitter_ansi256_rgb8,
+    trt_emitter_ansi256_half_rgb8)"""
+    a = np.ascontiguousarray(rgb, dtype=np.uint8)
+    rows, width, _ = a.shape
+    name = "trt_emitter_ansi256_half_rgb8" if half else "trt_emitter_ansi256_rgb8"
+    out = np.empty(6 + (23 * width + 5) * ((rows + 1) // 2) if half else 6 + (13 * width + 5) * rows, dtype=np.uint8)
+    n = C.c_size_t(0)
+    rc = getattr(lib(), name)(a.ctypes.data, width, rows, out.ctypes.data, out.size, C.byref(n))
+    if rc != 0 or n.value != out.size:
+        raise ValueError(f"{name}({width}, {rows}) failed with {rc}, {n.value} bytes")
     return out
 
 
