@@ -131,6 +131,8 @@ int trt_oracle_skybox_lookup(const Scene *scene, const Vector *direction, int *f
             face = f;
         }
     }
+    if (face < 0) /* a NaN component makes every dot product NaN: the reference indexes face -1 (undefined); the build defines it as face 0 */
+        face = 0;
 
     /* scale the direction so that it touches the face plane (TRT.c:717-719) */
     v3 touching = mulc(dir, k_axes[face]);

@@ -343,7 +343,8 @@ TRT_DEV uint32_t sky_texel(const uint32_t *sky, int dim, d3 direction)
 // axis-table algebra of TRT.c:705-727 carried out symbolically: multiplying by +-1 or 0 and adding the
 // resulting zeros is exact, so t_f = +-component, scale_by = the winning t, and u, v are +-0.5 * a
 // component of dir*(1/scale_by).  Only the sign of a zero can differ from the table form, and no
-// later step (clamp, +0.5, *dim, truncation) can see it.  Assumes finite components.
+// later step (clamp, +0.5, *dim, truncation) can see it.  That holds for finite components; a direction
+// with a NaN component is given the table form's answer at the end.
 TRT_DEV long sky_index_unit(int dim, d3 dir, double dim_f)
 {
     int face = 0;
@@ -390,7 +391,10 @@ TRT_DEV long sky_index_unit(int dim, d3 dir, double dim_f)
     long idx = (long)ui + (long)vi * dim;
     const long last = (long)dim * dim - 1;
     idx = idx > last ? last : (idx < 0 ? 0 : idx);
-    return (long)face * dim * dim + idx;
+    // A NaN component: in the table form every dot product with an axis is NaN (0 * NaN), no face wins and the coordinates are NaN --
+    // sky_texel's face 0, texel 0 -- where the components picked out above would still choose a face by the ones that are numbers.
+    const bool number = !__builtin_isunordered(dir.x, dir.y) && dir.z == dir.z;
+    return number ? (long)face * dim * dim + idx : 0;
 }
 
 TRT_DEV uint32_t sky_texel_unit(const uint32_t *sky, int dim, d3 dir, double dim_f) { return sky[sky_index_unit(dim, dir, dim_f)]; }
@@ -426,7 +430,16 @@ TRT_DEV long sky_index_estimate(int dim, float dim_f, d3 dir, bool &ambiguous, u
     const float half = 0.5f * dim_f, e = 0x1p-20f * dim_f;
     const float U = __builtin_fmaf(un, dim_f, half), V = __builtin_fmaf(vn, dim_f, half);
     const float fu = __builtin_amdgcn_fractf(U), fv = __builtin_amdgcn_fractf(V);
-    const float lo = __builtin_fminf(__builtin_fminf(U, V), __builtin_fminf(fu, fv)), hi = __builtin_fmaxf(U - dim_f + 1.0f, __builtin_fmaxf(V - dim_f + 1.0f, __builtin_fmaxf(fu, fv)));
+    // The least and the largest of the four are taken of their BIT PATTERNS as signed integers (v_min_i32 / v_max_i32 where the float
+    // forms stood: no instruction more).  The float forms return the operand that is a number: a NaN component that is not the major
+    // one leaves `ma` a number and makes ONE of U, V a NaN, which they dropped, and the other coordinate alone vouched for the index.
+    // As integers a NaN with its sign bit clear is above every number, infinity included, and reaches `hi`; one with the bit set is
+    // negative and makes `lo` negative -- itself or a negative number that is below it.  Among numbers nothing changes: non-negative
+    // floats order as their patterns do, a negative operand of the maximum loses to fu or fv (fractions: never negative) either way,
+    // and a negative operand of the minimum makes it negative either way, which is all `above` asks.
+    const auto least = [](float a, float b) { const int i = __builtin_bit_cast(int, a), j = __builtin_bit_cast(int, b); return __builtin_bit_cast(float, i < j ? i : j); };
+    const auto largest = [](float a, float b) { const int i = __builtin_bit_cast(int, a), j = __builtin_bit_cast(int, b); return __builtin_bit_cast(float, i > j ? i : j); };
+    const float lo = least(least(U, V), least(fu, fv)), hi = largest(U - dim_f + 1.0f, largest(V - dim_f + 1.0f, largest(fu, fv)));
     // The cube instructions flush FP32 denormals: a direction whose LARGEST component is below 2^-100 (an un-normalised vector that
     // TRT.c:444 left alone) may have lost a smaller one altogether while the reference's FP64 ratio keeps it -- ambiguous.  With the
     // largest component above that, a component that flushes is below 2^-25 of it: inside E.

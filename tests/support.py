@@ -373,6 +373,150 @@ def non_finite_light_scene():
     return S.SceneData(base.spheres, base.ground, dl, pl, base.camera, base.sky)
 
 
+# ---- the camera family: the base scene of the value-domain family under cameras outside the domain every other scene stays in ----
+# (tests/test_camera_edges.py, tests/golden/make_golden_cameras.py; a family of its own, not part of edge_case_inputs)
+CAMERA_BASE = "base"
+CAMERA_WIDE = "twice the screen on twice the columns"
+CAMERA_TRIO = ("trio/rolled", "trio/sheared", "trio/left-handed x3")
+COS37, SIN37 = 0.7986355100472928, 0.6018150231520483  # literals: the recorded cameras do not hang on a libm
+
+
+def _basis_variants(cam):
+    """{name: basis[9]} of the camera family, from the orthonormal basis of `cam`"""
+    x, y, z = cam[0:3].copy(), cam[3:6].copy(), cam[6:9].copy()
+    cat = np.concatenate
+    return {"x3": cat([x * 3.0, y * 3.0, z * 3.0]), "sheared": cat([x + 0.5 * y, y, z + 0.3 * x]), "left-handed": cat([-x, y, z]),
+            "singular": cat([x, x, z]), "y = 0": cat([x, 0.0 * y, z]), "rolled 37 degrees": cat([COS37 * x + SIN37 * y, COS37 * y - SIN37 * x, z]),
+            "all zero": np.zeros(9), "x1e-200": cat([x, y, z]) * 1e-200, "x1e200": cat([x, y, z]) * 1e200,
+            "x = NaN": cat([np.full(3, np.nan), y, z]), "left-handed x3": cat([-x, y, z]) * 3.0}
+
+
+def screen_point(cam, w, h, row, column):
+    """the point of the screen that the first ray of pixel (row, column) goes through, in the operation order of TRT.c:987-1002 (numpy's
+    float64 arithmetic is the reference's, one rounding per operation); where triangle_wave(0) == 0 that ray has no jitter"""
+    sw, sh = np.float64(cam[13]), np.float64(cam[14])
+    sx = (np.float64(column) / np.float64(w)) * sw - sw / np.float64(2.0)
+    sy = -((np.float64(row) / np.float64(h)) * sh - sh / np.float64(2.0))
+    sz = -np.float64(cam[12])
+    p = np.zeros(3)
+    p = p + cam[0:3] * sx
+    p = p + cam[3:6] * sy
+    return p + cam[6:9] * sz
+
+
+def camera_scenes():
+    """[(name, scene, w, h, defined)]: the base scene of value_scenes() under cameras that leave bench_camera()'s domain -- screen
+    distances that are zero, negative, tiny, huge or not finite; screens that are empty, mirrored, tiny, huge or not finite; bases that
+    are scaled, sheared, left-handed, singular, zero or not finite; eyes at the origin, a denormal away from it, not finite, or on the
+    screen itself.  `defined`: every primary direction is finite and not of zero length, so the reference renders the camera (its two
+    builds agree bit for bit); otherwise a sky look-up of the reference indexes outside its tables and the compiled reference dies
+    (see non_finite_light_scene), and the library's own definitions apply (csrc/trt_device.hpp, sky_texel)."""
+    w, h = VALUE_SIZE
+    base = S.synth_scene(24, sky("synth"), bench_camera(w, h, 2.5), seed=3)
+    bases = _basis_variants(base.camera)
+    inf, nan = np.inf, np.nan
+    out = []
+
+    def case(name, defined, size=(w, h), **fields):
+        cam = base.camera.copy()
+        cam[13] = 5 * float(size[0]) / float(size[1])
+        for key, value in fields.items():
+            cam[{"basis": slice(0, 9), "eye": slice(9, 12), "sd": 12, "sw": 13, "sh": 14}[key]] = value
+        out.append((name, base.with_camera(cam), size[0], size[1], defined))
+        return cam
+
+    sw = base.camera[13]
+    case(CAMERA_BASE, True)
+    for v in (0.0, -0.0, -1.0, 1e-300, 0.05, 40.0):
+        case(f"screen_distance {v!r}", True, sd=v)
+    case("screen_width 0", True, sw=0.0)
+    case("screen_height 0", True, sh=0.0)
+    case("screen_width negated", True, sw=-sw)
+    case("screen_height -5", True, sh=-5.0)
+    case("screen 1e-9", True, sw=1e-9, sh=1e-9)
+    case("screen 1e9", True, sw=1e9, sh=1e9)
+    case("screen_width 5e-324, screen_height 1e-310", True, sw=5e-324, sh=1e-310)
+    for key in ("x3", "sheared", "left-handed", "singular", "y = 0", "rolled 37 degrees", "all zero", "x1e-200"):
+        case(f"basis {key}", True, basis=bases[key])
+    case("eye at the origin", True, eye=0.0)
+    case("eye at the origin, screen_distance 0", True, eye=0.0, sd=0.0)
+    case("eye at the origin, identity basis", True, eye=0.0, basis=np.eye(3).ravel())
+    case("eye a denormal from the origin", True, eye=[1e-300, -1e-300, 1e-310])
+    # the same pixel width as the base case (the jitter table is legitimately reused) on other axes
+    case(CAMERA_WIDE, True, size=(2 * w, h), sw=2.0 * sw)
+    # three cameras that share one odd screen, what a batch needs; a basis and an eye each
+    eye = base.camera[9:12]
+    for name, key, at in zip(CAMERA_TRIO, ("rolled 37 degrees", "sheared", "left-handed x3"),
+                             (eye, eye + np.array([0.4, 0.3, -0.2]), eye * np.array([-1.25, 0.5, 1.5]))):
+        case(name, True, sd=0.05, sw=-sw, sh=3.0, basis=bases[key], eye=at)
+    # ---- not defined by the reference ----
+    for v in (1e160, 1e300, inf, nan):
+        case(f"screen_distance {v!r}", False, sd=v)
+    case("screen_width inf", False, sw=inf)
+    case("screen_height NaN", False, sh=nan)
+    case("screen 1e308", False, sw=1e308, sh=1e308)
+    case("basis x1e200", False, basis=bases["x1e200"])
+    case("basis x = NaN", False, basis=bases["x = NaN"])
+    case("eye with a NaN component", False, eye=[eye[0], nan, eye[2]])
+    case("eye with an infinite component", False, eye=[-inf, eye[1], eye[2]])
+    case("eye 1e200 away", False, eye=[1e200, 1e200, -1e200])
+    # a primary ray of zero length, at 48x28, where triangle_wave(0) == 0 leaves the first ray of a pixel on the pixel's own point
+    tall = base.camera.copy()
+    tall[13] = 5 * 48.0 / 28.0
+    case("eye on the screen point of a pixel", False, size=(48, 28), eye=screen_point(tall, 48, 28, 9, 31))
+    case("identity basis, eye at the origin, screen_distance 0", False, size=(48, 28), basis=np.eye(3).ravel(), eye=0.0, sd=0.0)
+    assert len({n for n, *_ in out}) == len(out)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def camera_meta():
+    with open(os.path.join(GOLDEN, "golden_camera_edges.json")) as fh:
+        return json.load(fh)
+
+
+@functools.lru_cache(maxsize=None)
+def _camera_edges():
+    return dict(np.load(os.path.join(GOLDEN, "camera_edges.npz")))
+
+
+def camera_cases():
+    """the defined cases of the record, one per camera and shot: the keys of an edge case, and "camera": the camera's name"""
+    return camera_meta()["cases"]
+
+
+def camera_case_scene(case):
+    """the scene the reference rendered: the family's base scene and the camera's fifteen doubles, both from the record"""
+    a = _camera_edges()
+    scene = unpack_scene(a["scene"], case["spheres"], case["dir_lights"], case["point_lights"])
+    return scene.with_camera(a[case["scene"]])
+
+
+def camera_fb(case):
+    """the reference's double framebuffer [h, w, 3] (read-only), or None where only its hash is recorded"""
+    if case["fb"] is None:
+        return None
+    fb = _camera_edges()[case["fb"]]
+    fb.flags.writeable = False
+    return fb
+
+
+def assert_is_the_recorded_frame(got, case, want, positions_from, who):
+    """A frame equals the record when its NaNs sit in the same places, every other value has the same bits, the counts of NaN and
+    infinite values are the recorded ones and the FNV of the frame with its NaNs made one NaN is the recorded hash.  `want`: the
+    recorded frame, or None where the archive keeps the case's hash only; then `positions_from` -- the oracle's frame, which the CPU
+    test of the same case pins to that hash -- says where the NaNs and the values are."""
+    if want is None:
+        want = positions_from
+    assert got.shape == want.shape == (case["h"], case["w"], 3)
+    assert np.array_equal(np.isnan(got), np.isnan(want)), (case["name"], who, "NaNs in other places", int((np.isnan(got) != np.isnan(want)).sum()))
+    there = ~np.isnan(want)
+    differ = bits(got)[there] != bits(want)[there]
+    assert not differ.any(), (case["name"], who, "values differ", int(differ.sum()), np.argwhere(bits(got) != bits(want))[:4].tolist())
+    assert (int(np.isnan(got).sum()), int(np.isinf(got).sum())) == (case["nan"], case["inf"]), (case["name"], who)
+    assert fnv(canonical_nans(got)) == case["fb_fnv"], (case["name"], who)
+
+
 def fuzz_case(seed):
     """(scene, w, h, bounce limit, rays per pixel) of fuzz seed `seed`, with the draws test_fuzzed_scenes_match_the_oracle makes"""
     rng = np.random.default_rng(1000 + seed)

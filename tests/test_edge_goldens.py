@@ -37,16 +37,7 @@ def oracle_frame(name):
 
 def assert_is_the_recorded_frame(got, case, positions_from, who):
     """`positions_from`: the frame that says where the NaNs and the values are -- the record where the archive holds it, else the oracle's"""
-    want = T.edge_fb(case)
-    if want is None:
-        want = positions_from
-    assert got.shape == want.shape == (case["h"], case["w"], 3)
-    assert np.array_equal(np.isnan(got), np.isnan(want)), (case["name"], who, "NaNs in other places", int((np.isnan(got) != np.isnan(want)).sum()))
-    there = ~np.isnan(want)
-    differ = bits(got)[there] != bits(want)[there]
-    assert not differ.any(), (case["name"], who, "values differ", int(differ.sum()), np.argwhere(bits(got) != bits(want))[:4].tolist())
-    assert (int(np.isnan(got).sum()), int(np.isinf(got).sum())) == (case["nan"], case["inf"]), (case["name"], who)
-    assert T.fnv(T.canonical_nans(got)) == case["fb_fnv"], (case["name"], who)
+    T.assert_is_the_recorded_frame(got, case, T.edge_fb(case), positions_from, who)
 
 
 # ---- CPU: the fixture is what it claims, and the oracle equals it ----
