@@ -665,9 +665,25 @@ int trt_render_variant(trt_context *ctx, int *decoupled, int *workgroup_threads)
  * hits a refractor from outside is shaded like any hit (lighting, weight *= reflectivity, one bounce) and continues along
  * the refracted direction; inside, the sphere is met at its far root; leaving it adds no colour and no weight but costs a
  * bounce; total internal reflection mirrors the ray; shadow rays are the reference's.  count must equal the scene's
- * sphere count when a frame is rendered; count = 0 turns the extension off.  Frames are checked bit for bit against
- * oracle/trt_oracle.c's restatement of these very semantics -- not against the reference, which has none.  With the
- * extension off (the default) a different kernel instantiation runs and nothing of this is on the path. */
+ * sphere count when a frame is rendered; count = 0 turns the extension off.  Every ior[i] must lie in [0, 1e6): a call with
+ * any other value -- negative, huge, infinite, not a number -- fails with TRT_ERR_ARGUMENT and leaves the extension off.
+ *
+ * THE DECLARED RULES (what a path ray remembers; tests/refraction_model.py is written from these, not from the kernel):
+ *   - Only the sphere the ray most recently entered is remembered as the one it is `inside` of.
+ *   - A ray that leaves a refractor nested in, or overlapping, another forgets the outer one: it then meets the outer one
+ *     only at its near root, which lies behind it, so it passes that surface unbent.
+ *   - The same holds for an eye that starts inside a refractor.
+ *   - A ray inside a refractor that hits the ground or an opaque sphere reflects and stays inside.
+ *   - eta is 1 / ior on entering and ior on leaving, relative to vacuum, whatever surrounds the sphere.
+ *   - Total reflection, from inside or (ior < 1) from outside, keeps the side and the state.
+ *   With the facing unit normal nn, d_n = (d . nn) nn, d_t = d - d_n and s2 = eta^2 |d_t|^2: s2 > 1 mirrors the ray about nn, which
+ *   then starts 1e-6 BEFORE the surface like any reflected ray; otherwise the new direction is unit(eta d_t - sqrt(1 - s2) nn) from
+ *   1e-6 PAST the surface, and the state becomes the sphere's index on entering, none on leaving.
+ *
+ * The extension is still UNPINNED TO THE REFERENCE, which has no refraction.  Frames are checked bit for bit against
+ * oracle/trt_oracle.c's restatement of these very semantics, and that restatement is held, path ray by path ray, to an exact
+ * (60-digit) model of the rules above (tests/test_refraction_model.py).  With the extension off (the default) a different
+ * kernel instantiation runs and nothing of this is on the path. */
 int trt_set_refraction(trt_context *ctx, const double *ior, int count);
 
 /* Resource usage of the render kernel trt_render_variant describes (hipFuncGetAttributes / occupancy query; max_blocks_per_cu

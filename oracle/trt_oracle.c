@@ -593,6 +593,7 @@ static inline v3 shade_pixel_refractive(const Scene *scene, const double *ior, i
         while (going && bounces < bounce_limit && weight > 0.00001)
         {
             st->path_rays++;
+            log_ray(org, dir, 0);
             surface_ext h = closest_hit_ext(scene, org, dir, inside);
             const int leaving = h.s.what == SPHERE && h.sphere == inside;
             if (!leaving)

@@ -116,6 +116,27 @@ def oracle_render_refractive(scene_data, ior, width, height, bounce_limit, rays_
     return px, st
 
 
+class OracleRayLog(C.Structure):
+    _fields_ = [("rays", C.c_void_p), ("kinds", C.c_void_p), ("capacity", C.c_size_t), ("count", C.c_size_t)]
+
+
+def oracle_path_rays_refractive(scene_data, ior, width, height, bounce_limit, rays_per_pixel):
+    """(pixels, stats, path rays float64[n, 6]) of one single-threaded frame of the refraction restatement: every path ray it traces, in
+    trace order (trt_oracle_set_ray_log; the shadow rays between them are dropped)"""
+    cap = width * height * rays_per_pixel * bounce_limit * (1 + len(scene_data.dir_lights) + len(scene_data.point_lights)) + 1
+    rays, kinds = np.zeros((cap, 6)), np.zeros(cap, dtype=np.uint8)
+    log = OracleRayLog(rays.ctypes.data, kinds.ctypes.data, cap, 0)
+    lib = oracle()
+    lib.trt_oracle_set_ray_log.argtypes = [C.POINTER(OracleRayLog)]
+    lib.trt_oracle_set_ray_log(C.byref(log))
+    try:
+        px, st = oracle_render_refractive(scene_data, ior, width, height, bounce_limit, rays_per_pixel, threads=1)
+    finally:
+        lib.trt_oracle_set_ray_log(None)
+    assert log.count < cap
+    return px, st, rays[: log.count][kinds[: log.count] == 0].copy()
+
+
 def oracle_rgb8(pixels):
     px = np.ascontiguousarray(pixels, dtype=np.float64)
     out = np.empty(px.shape, dtype=np.uint8)

@@ -879,8 +879,9 @@ def test_refraction_extension_matches_its_cpu_restatement(ctx, tables):
     """EXTENSION, PARITY UNPINNED: the reference has no refraction (TRT.c:114-119, :657), so there is nothing of the reference's
     to compare with.  trt_set_refraction selects another instantiation of the production kernel; its frames must equal
     oracle/trt_oracle.c's restatement of the same semantics bit for bit (glass of index 1.5, an index below 1 with total
-    reflection from outside, index 1, nested and touching refractors, a refractor on the floor), the trace counts too;
-    with every index 0, and with the extension switched off again, the frame must be the reference path's."""
+    reflection from outside, index 1, an opaque sphere nested in a refractor, two touching refractors, a refractor on
+    the floor -- no refractor inside another: tests/test_refraction_gpu.py has those), the trace counts too; with every index 0, and
+    with the extension switched off again, the frame must be the reference path's."""
     base = S.synth_scene(24, T.sky("synth"), T.bench_camera(96, 54, 2.5), seed=3)
     sph = base.spheres.copy()
     sph[5, :3] = sph[4, :3]
