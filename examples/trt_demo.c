@@ -2,7 +2,7 @@
  * host C builds the demo scene and the orbiting camera, the MI355X produces the frame through
  * the drop-in project_scene(), and the ANSI emitter stays on the host.
  *
- *   trt_demo <skybox-directory> [frames=0 (until Ctrl-C)] [width=160] [height=48] [--no-draw] [--rgb8] [--ansi] [--half] [--kitty] [--256] [--delta] [--step=SECONDS]
+ *   trt_demo <skybox-directory> [frames=0 (until Ctrl-C)] [width=160] [height=48] [--no-draw] [--rgb8] [--ansi] [--half] [--kitty] [--sixel] [--256] [--delta] [--step=SECONDS]
  *            [--batch=N]
  *
  * --rgb8: the frame crosses PCIe as the 3 bytes per pixel the emitter makes of it (trt_render_frame_rgb8: the (int)(c*255) of
@@ -15,6 +15,10 @@
  * --kitty: true pixels for a terminal that speaks the kitty graphics protocol (trt_render_frame_kitty): base64 of the RGB bytes in APC escape
  * sequences, four bytes of text a pixel, trt_kitty_bytes(width, height) bytes, one fwrite per frame and nothing else on stdout; the image
  * replaces itself in place.  No terminal has yet shown this picture (csrc/trt_kitty.h).  It has no --delta form.
+ * --sixel: true pixels for a terminal that takes DEC sixel (trt_render_frame_sixel): the 240 fixed colours of the xterm palette as colour
+ * registers, the picture in bands of six rows; the length depends on the picture, so text has trt_sixel_capacity(width, height) bytes and
+ * each frame is one fwrite of what the call reports, nothing else on stdout.  The terminal needs 256 colour registers (xterm:
+ * numColorRegisters: 256).  No terminal has shown this picture (csrc/trt_sixel.h).  It has no --delta form.
  * --256: the text route for a terminal that has only the xterm 256-colour palette (trt_render_frame_ansi256; with --half
  * trt_render_frame_ansi256_half): "48;5;N" cells, N the entry of the palette's fixed part nearest to the pixel, no dithering;
  * trt_ansi256_bytes or trt_ansi256_half_bytes(width, height) bytes, one fwrite.  No terminal was at hand to look at this picture.  It has
@@ -56,12 +60,12 @@ int main(int argc, char **argv)
 {
     if (argc < 2)
     {
-        fprintf(stderr, "usage: %s <skybox-directory> [frames] [width] [height] [--no-draw] [--rgb8] [--ansi] [--half] [--kitty] [--256] [--delta] [--step=SECONDS] [--batch=N]\n", argv[0]);
+        fprintf(stderr, "usage: %s <skybox-directory> [frames] [width] [height] [--no-draw] [--rgb8] [--ansi] [--half] [--kitty] [--sixel] [--256] [--delta] [--step=SECONDS] [--batch=N]\n", argv[0]);
         return 2;
     }
     const long frames = argc > 2 ? atol(argv[2]) : 0;
     const int width = argc > 3 ? atoi(argv[3]) : 160, height = argc > 4 ? atoi(argv[4]) : 48;
-    int draw = 1, bytes_only = 0, text_only = 0, delta = 0, half = 0, kitty = 0, palette = 0, batch = 0;
+    int draw = 1, bytes_only = 0, text_only = 0, delta = 0, half = 0, kitty = 0, sixel = 0, palette = 0, batch = 0;
     double step = -1.0;
     for (int i = 5; i < argc; i++)
     {
@@ -75,6 +79,8 @@ int main(int argc, char **argv)
             text_only = half = 1;
         else if (strcmp(argv[i], "--kitty") == 0)
             text_only = kitty = 1;
+        else if (strcmp(argv[i], "--sixel") == 0)
+            text_only = sixel = 1;
         else if (strcmp(argv[i], "--256") == 0)
             text_only = palette = 1;
         else if (strcmp(argv[i], "--delta") == 0)
@@ -92,6 +98,11 @@ int main(int argc, char **argv)
     if (kitty && (delta || half || trt_kitty_bytes(width, height) == 0))
     {
         fprintf(stderr, "--kitty sends whole images of at most 99999 x 99999 pixels: it goes with neither --delta nor --half\n");
+        return 2;
+    }
+    if (sixel && (delta || half || kitty || palette || trt_sixel_capacity(width, height) == 0))
+    {
+        fprintf(stderr, "--sixel sends whole images of at most 99999 x 99999 pixels: it goes with none of --delta, --half, --kitty and --256\n");
         return 2;
     }
     if (palette && (delta || kitty))
@@ -137,6 +148,7 @@ int main(int argc, char **argv)
                              : palette ? (half ? trt_ansi256_half_bytes(width, height) : trt_ansi256_bytes(width, height))
                              : half  ? trt_ansi_half_bytes(width, height)
                              : kitty ? trt_kitty_bytes(width, height)
+                             : sixel ? trt_sixel_capacity(width, height)
                                     : trt_ansi_bytes(width, height);
     size_t text_bytes = text_room, written_bytes = 0;
     char *text = (char *)malloc(text_room ? text_room : 1);
@@ -235,6 +247,14 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        else if (sixel)
+        {
+            if (trt_render_frame_sixel(&scene, width, height, TRT_REF_BOUNCE_LIMIT, TRT_REF_RAYS_PER_PIXEL, text, text_room, &text_bytes) != TRT_OK)
+            {
+                fprintf(stderr, "trt_render_frame_sixel: %s\n", trt_last_error());
+                return 1;
+            }
+        }
         else if (text_only)
         {
             if (trt_render_frame_ansi(&scene, width, height, TRT_REF_BOUNCE_LIMIT, TRT_REF_RAYS_PER_PIXEL, text) != TRT_OK)
@@ -258,7 +278,7 @@ int main(int argc, char **argv)
         if (draw)
         {
             if (text_only)
-                written_bytes += fwrite(text, 1, text_bytes, stdout); /* --ansi: sizeof(screenbuffer), NULs included, as TRT.c:1171; --half, --kitty, --256: the whole text; --delta: what the call reported */
+                written_bytes += fwrite(text, 1, text_bytes, stdout); /* --ansi: sizeof(screenbuffer), NULs included, as TRT.c:1171; --half, --kitty, --256: the whole text; --delta, --sixel: what the call reported */
             else
             {
                 if (bytes_only)
@@ -267,7 +287,7 @@ int main(int argc, char **argv)
                     trt_emitter_patch(emitter, &screen);
                 trt_emitter_write(emitter, stdout);
             }
-            if (delta || kitty)
+            if (delta || kitty || sixel)
                 fflush(stdout); /* a delta text ends wherever its last record does: nothing of it may wait for the next frame; an image stands alone */
             else
             {
@@ -282,7 +302,7 @@ int main(int argc, char **argv)
                 (double)frame / seconds_since(&start), written_bytes, frame, half ? trt_ansi_half_bytes(width, height) : trt_ansi_bytes(width, height));
     fprintf(stderr, "%ld frames %dx%d, frame producer %.3f ms/frame after a first call of %.1f ms (host-in/host-out%s, 10 bounces, 10 rays per pixel)\n",
             frame, width, height, frame > first_batch ? 1e3 * producer_seconds / (frame - first_batch) : 0.0, 1e3 * first_call_seconds,
-            delta && half ? " as half-block delta text" : delta ? " as delta text" : palette && half ? " as half-block 256-colour text" : palette ? " as 256-colour text" : half ? " as half-block text" : kitty ? " as a kitty image" : text_only ? " as text" : bytes_only ? " as RGB8" : "");
+            delta && half ? " as half-block delta text" : delta ? " as delta text" : palette && half ? " as half-block 256-colour text" : palette ? " as 256-colour text" : half ? " as half-block text" : kitty ? " as a kitty image" : sixel ? " as a sixel image" : text_only ? " as text" : bytes_only ? " as RGB8" : "");
 
     trt_emitter_destroy(emitter);
     free(screen.pixels);

@@ -105,6 +105,14 @@ int trt_render_frame_ansi_delta(const Scene *scene, int width, int height, int b
 int trt_render_frame_ansi_delta_half(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text,
                                      size_t capacity_bytes, size_t *bytes);
 
+/* The frame as a DEC SIXEL image (trt_render_host_sixel below, on the default context: its format and its caveat -- no terminal has shown
+ * it): true pixels in the 240 fixed colours of the xterm palette, for the terminals that take sixel and not the kitty protocol.  The
+ * length depends on the picture: text holds capacity_bytes >= trt_sixel_capacity(width, height) bytes, the host writes *bytes of them
+ * with one fwrite: byte for byte trt_emitter_sixel_rgb8 (trt_host.h) of trt_render_frame_rgb8's bytes.  width and height are at most
+ * 99999.  It neither reads nor changes the delta entries' shown frame.  Lock and scene policy as above. */
+int trt_render_frame_sixel(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text,
+                           size_t capacity_bytes, size_t *bytes);
+
 /* project_scene is a pure function of *scene (TRT.c:966): a caller may move a sphere before every call.  The drop-in entries
  * compare the primitives with the previous call's; a scene that has changed on `moving_after` consecutive calls counts as MOVING
  * and its candidate tables are rebuilt per call the cheap way (one family per sphere instead of 24 patches: ~4 ms instead of ~100 ms
@@ -446,6 +454,61 @@ int trt_render_device_ansi_delta_half(trt_context *ctx, const Camera *camera, co
 /* The same into HOST memory, synchronous: the 8-byte length is read back, then exactly *bytes bytes cross PCIe. */
 int trt_render_host_ansi_delta_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
                                     char *text, size_t capacity_bytes, size_t *bytes);
+
+/* ---- the DEC sixel image: true pixels for the terminals that take sixel and nothing else -----------------------------------------------
+ * The kitty image above reaches kitty, WezTerm, Ghostty and Konsole.  xterm, foot, mlterm, Windows Terminal, VS Code's terminal, contour
+ * and tmux built with sixel take SIXEL: a picture in bands of six pixel rows, a band drawn one colour register at a time, a data
+ * character six pixels of one column.  For a screen of `width` x `rows` owned rows in LOCAL row order, in order:
+ *   "\033[0;0H"                       6 bytes   cursor home
+ *   "\033P0;1;0q"                     8 bytes   DCS, P2 = 1: a 0 bit leaves its pixel alone
+ *   "\"1;1;WWWWW;RRRRR"              16 bytes   raster attributes: width and rows, five zero-padded digits each
+ *   240 x "#NNN;2;PPP;PPP;PPP"     4320 bytes   colour register NNN = 016..255, ascending: the xterm palette's entry NNN (the 6 x 6 x 6 cube
+ *                                               and the grey ramp, trt_host.h) in RGB per cent, PPP = (100 v + 127) / 255 in integers
+ *   per band b of six pixel rows (the last has fewer), per palette index n, ASCENDING, that a pixel of the band has
+ *   (trt_xterm256_index of its emitter bytes), a colour row:
+ *     "#NNN"                          4 bytes
+ *     width data characters           63 + the sum over j of (the pixel of row 6 b + j in this column has index n) << j
+ *     T - 1 times "$", one more byte  "-" behind the LAST colour of every band but the last band, "$" everywhere else
+ *   "\033\\"                          2 bytes
+ * T = 1 + ((-(width + 1)) mod 4), so a colour row is L = 4 + width + T bytes, a multiple of 4 (a repeated "$" is a repeated graphics
+ * carriage return and changes nothing).  The text has 4352 + L * (the colour rows of all bands) bytes -- its length DEPENDS ON THE
+ * PICTURE, so every entry reports it, as the delta entries do.  No NUL, no newline.
+ * NO TERMINAL HAS SHOWN THIS PICTURE: the format is written from memory of DEC's description, and the tests hold the text against a
+ * structural reader (tests/sixel_support.py), not a terminal.  Registers up to 255 need a terminal with 256 colour registers: xterm as a
+ * VT340 defaults to 16 and needs `numColorRegisters: 256`.  A per-cent palette cannot say 95 or 135 exactly, so the colours are within
+ * 1/100 of the xterm palette's.  csrc/trt_sixel.h is the format in code, trt_emitter_sixel_rgb8 (trt_host.h) its sequential statement on
+ * the host.  Limits: width <= 99999 and owned rows <= 99999; above them the capacity is 0 and the entries return TRT_ERR_ARGUMENT.
+ * There are no "!" run-length repeats, no dithering, no palette other than the 240 fixed entries, no delta form, no batch forms, no
+ * refraction form and no tmux pass-through; of a trt_dist_render_rgb8 gather rank 0 formats the assembled bytes with
+ * trt_sixel_from_rgb8_device. */
+
+/* Room for any image of the size: 4352 + L * the sum over the bands of min(240, width * the band's rows); 0 unless both sizes are positive
+ * and at most 99999. */
+size_t trt_sixel_capacity(int width, int rows);
+
+/* The formatting alone, of a frame that exists as RGB8 bytes in device memory (rows x width x 3, any alignment): the image at d_text (any
+ * alignment, need not be initialised), its length at *d_bytes -- a DEVICE address, 8-byte aligned.  Three kernels in stream order
+ * (csrc/trt_sixel.hpp), no atomic on device memory and no workgroup that waits for another: a workgroup per band ORs its pixels' indices
+ * into a 240-bit mask; one workgroup scans the bands' colour counts into offsets, stores the length and writes the 4350 bytes in front of
+ * the first colour row and the 2 behind the last; a thread per four adjacent columns of a band keeps their 6 x 4 indices in registers,
+ * walks the band's mask and stores an aligned 32-bit word per colour.  Every byte below the length is stored once, none at or behind it.
+ * It neither reads nor changes the context's shown frame.  capacity_bytes >= trt_sixel_capacity(width, rows), else TRT_ERR_CAPACITY; NULL
+ * or a size that is not positive or above the limits: TRT_ERR_ARGUMENT.  Asynchronous on the context's stream. */
+int trt_sixel_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text, size_t capacity_bytes,
+                               unsigned long long *d_bytes);
+/* trt_render_device as the sixel image: the frame's bytes are written by the RGB8 form of the ordered-mean pass into a buffer of the
+ * context's that is NOT one of the delta entries' shown pair (the reference-order kernel goes through trt_quantize_device's kernel), then
+ * formatted by the three kernels above.  The delta entries' shown frame is neither read nor changed.  For a shard the raster's rows are
+ * the owned rows, in local order.  Errors, before anything is enqueued: NULL, an invalid rowset, a size above the limits ->
+ * TRT_ERR_ARGUMENT; no scene -> TRT_ERR_NO_SCENE; capacity_bytes < trt_sixel_capacity(width, owned rows) -> TRT_ERR_CAPACITY.
+ * Asynchronous on the context's stream; d_bytes as above.  One entry of trt_kernel_times (the render and the ordered mean; the image's
+ * kernels follow it). */
+int trt_render_device_sixel(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                            void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+/* The same into HOST memory, synchronous: the length is read back, then exactly *bytes bytes cross PCIe through the pinned staging.
+ * capacity_bytes counts the bytes at text, checked as above. */
+int trt_render_host_sixel(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                          char *text, size_t capacity_bytes, size_t *bytes);
 
 /* Same as trt_render_device but into HOST memory (synchronous; pinned staging inside). */
 int trt_render_host(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,

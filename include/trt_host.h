@@ -125,6 +125,18 @@ int trt_emitter_ansi256_rgb8(const unsigned char *rgb, int width, int rows, char
  * "\033[38;5;UUU;48;5;LLLm" and the glyph U+2580 in UTF-8 (E2 96 80) -- UUU the index of row 2 t, LLL that of row 2 t + 1; 016, black, behind
  * the last row of an odd frame -- then "\033[0m\n".  No NUL: *bytes = 6 + (23 * width + 5) * ((rows + 1) / 2).  Errors as above. */
 int trt_emitter_ansi256_half_rgb8(const unsigned char *rgb, int width, int rows, char *text, size_t capacity, size_t *bytes);
+/* The frame of such bytes (rows x width x 3) as a DEC SIXEL image, for the terminals that take sixel and not the kitty protocol (xterm,
+ * foot, mlterm, Windows Terminal, VS Code's terminal, contour, tmux built with sixel).  The format is the project's own statement
+ * (csrc/trt_sixel.h), written from memory of DEC's description, and NO TERMINAL HAS SHOWN IT.  "\033[0;0H"; "\033P0;1;0q";
+ * "\"1;1;WWWWW;RRRRR" (five zero-padded digits each); the 240 colour registers "#NNN;2;PPP;PPP;PPP", NNN = 016..255 the xterm palette's
+ * entry in RGB per cent, PPP = (100 v + 127) / 255; then per band of six rows, per index that a pixel of the band has BY THE SEARCH,
+ * ascending, a colour row "#NNN", width characters 63 + (bit j: the pixel of the band's row j in this column has the index), T - 1 times "$"
+ * and one more byte, "-" behind the last colour of every band but the last and "$" elsewhere, T = 1 + ((-(width + 1)) mod 4); then "\033\\".
+ * No NUL, no newline: *bytes = 4352 + (4 + width + T) * (the colour rows), which depends on the picture and which `capacity` must hold;
+ * width <= 99999, rows <= 99999.  The sequential statement the device kernels (trt_render_device_sixel, trt_hip.h) are tested against, and
+ * the emitter of hosts that fetch RGB8 bytes.  TRT_HOST_ERR_ARGUMENT: NULL, a size that is not positive or above the limits, a capacity
+ * below the length; a refused call writes nothing.  TRT_HOST_ERR_MEMORY: no room for the six rows of indices it works on. */
+int trt_emitter_sixel_rgb8(const unsigned char *rgb, int width, int rows, char *text, size_t capacity, size_t *bytes);
 /* TRT.c:1171: one fwrite of the whole buffer (trailing NULs included, as the reference does) */
 int trt_emitter_write(const trt_emitter *e, FILE *stream);
 /* TRT.c:1084-1099: the unbuffered printf form */

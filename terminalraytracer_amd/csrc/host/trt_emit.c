@@ -496,3 +496,125 @@ int trt_emitter_ansi256_half_rgb8(const unsigned char *rgb, int width, int rows,
     *bytes = (size_t)(p - text);
     return TRT_HOST_OK;
 }
+
+/* The DEC sixel image (csrc/trt_sixel.h holds the format): the 240 fixed palette entries as colour registers, then the picture in bands of
+ * six pixel rows, a band one colour row per index that occurs in it.  Plain loops over the search, on purpose without that header -- this is
+ * what the header's arithmetic and the device kernels are held against.  No terminal has shown this picture: the format is written from
+ * memory of DEC's description. */
+static const char k_sixel_dcs[] = "\033P0;1;0q";
+static const char k_sixel_raster[] = "\"1;1;00000;00000";
+static const char k_sixel_define[] = "#000;2;000;000;000";
+static const char k_sixel_end[] = "\033\\";
+enum
+{
+    SIXEL_DCS_LEN = sizeof(k_sixel_dcs) - 1,       /* 8 */
+    SIXEL_RASTER_LEN = sizeof(k_sixel_raster) - 1, /* 16 */
+    SIXEL_DEFINE_LEN = sizeof(k_sixel_define) - 1, /* 18 */
+    SIXEL_END_LEN = sizeof(k_sixel_end) - 1,       /* 2 */
+    SIXEL_WIDTH_AT = 5,
+    SIXEL_ROWS_AT = 11,
+    SIXEL_FIRST = 16,
+    SIXEL_COLOURS = 240,
+    SIXEL_BAND = 6,
+    SIXEL_FIXED = HOME_LEN + SIXEL_DCS_LEN + SIXEL_RASTER_LEN + SIXEL_COLOURS * SIXEL_DEFINE_LEN + SIXEL_END_LEN, /* 4352 */
+    SIXEL_MAX = 99999
+};
+
+/* the indices of band `band`'s pixels, band_rows x width, and which of the 240 occur; returns how many do */
+static int sixel_band(const unsigned char *rgb, int width, int band, int band_rows, unsigned char *index, unsigned char *occurs)
+{
+    int colours = 0;
+    memset(occurs, 0, SIXEL_COLOURS);
+    for (int j = 0; j < band_rows; j++)
+    {
+        const unsigned char *px = rgb + (size_t)(SIXEL_BAND * band + j) * width * 3;
+        for (int col = 0; col < width; col++)
+        {
+            const unsigned n = trt_xterm256_index_search(px[3 * col], px[3 * col + 1], px[3 * col + 2]);
+            index[(size_t)j * width + col] = (unsigned char)n;
+            colours += !occurs[n - SIXEL_FIRST];
+            occurs[n - SIXEL_FIRST] = 1;
+        }
+    }
+    return colours;
+}
+
+int trt_emitter_sixel_rgb8(const unsigned char *rgb, int width, int rows, char *text, size_t capacity, size_t *bytes)
+{
+    static const int levels[6] = {0, 95, 135, 175, 215, 255};
+    if (!rgb || !text || !bytes || width <= 0 || rows <= 0 || width > SIXEL_MAX || rows > SIXEL_MAX)
+        return TRT_HOST_ERR_ARGUMENT;
+    const int bands = (rows + SIXEL_BAND - 1) / SIXEL_BAND, pad = 1 + ((4 - (width + 1) % 4) % 4);
+    const size_t row_len = 4 + (size_t)width + (size_t)pad;
+    unsigned char occurs[SIXEL_COLOURS];
+    unsigned char *index = (unsigned char *)malloc((size_t)SIXEL_BAND * width);
+    if (!index)
+        return TRT_HOST_ERR_MEMORY;
+    /* a refused call writes nothing: where the capacity is below what any frame of the size fits into, the length first */
+    size_t most = 0, colour_rows = 0;
+    for (int band = 0; band < bands; band++)
+    {
+        const size_t pixels = (size_t)width * (size_t)(rows - SIXEL_BAND * band < SIXEL_BAND ? rows - SIXEL_BAND * band : SIXEL_BAND);
+        most += pixels < SIXEL_COLOURS ? pixels : SIXEL_COLOURS;
+    }
+    if (capacity < SIXEL_FIXED + row_len * most)
+    {
+        for (int band = 0; band < bands; band++)
+        {
+            const int band_rows = rows - SIXEL_BAND * band < SIXEL_BAND ? rows - SIXEL_BAND * band : SIXEL_BAND;
+            colour_rows += (size_t)sixel_band(rgb, width, band, band_rows, index, occurs);
+        }
+        if (capacity < SIXEL_FIXED + row_len * colour_rows)
+        {
+            free(index);
+            return TRT_HOST_ERR_ARGUMENT;
+        }
+    }
+    char *p = text;
+    memcpy(p, k_home, HOME_LEN);
+    p += HOME_LEN;
+    memcpy(p, k_sixel_dcs, SIXEL_DCS_LEN);
+    p += SIXEL_DCS_LEN;
+    memcpy(p, k_sixel_raster, SIXEL_RASTER_LEN);
+    five_digits(p + SIXEL_WIDTH_AT, width);
+    five_digits(p + SIXEL_ROWS_AT, rows);
+    p += SIXEL_RASTER_LEN;
+    for (int n = SIXEL_FIRST; n < SIXEL_FIRST + SIXEL_COLOURS; n++, p += SIXEL_DEFINE_LEN)
+    {
+        const int c = n - SIXEL_FIRST, grey = 8 + 10 * (n - 232);
+        const int value[3] = {n < 232 ? levels[c / 36] : grey, n < 232 ? levels[c / 6 % 6] : grey, n < 232 ? levels[c % 6] : grey};
+        memcpy(p, k_sixel_define, SIXEL_DEFINE_LEN);
+        three_digits(p + 1, n);
+        for (int ch = 0; ch < 3; ch++)
+            three_digits(p + 7 + 4 * ch, (100 * value[ch] + 127) / 255);
+    }
+    for (int band = 0; band < bands; band++)
+    {
+        const int band_rows = rows - SIXEL_BAND * band < SIXEL_BAND ? rows - SIXEL_BAND * band : SIXEL_BAND;
+        int left = sixel_band(rgb, width, band, band_rows, index, occurs);
+        for (int n = SIXEL_FIRST; n < SIXEL_FIRST + SIXEL_COLOURS; n++)
+        {
+            if (!occurs[n - SIXEL_FIRST])
+                continue;
+            left--;
+            *p++ = '#';
+            three_digits(p, n);
+            p += 3;
+            for (int col = 0; col < width; col++)
+            {
+                int six = 0;
+                for (int j = 0; j < band_rows; j++)
+                    six |= (index[(size_t)j * width + col] == n) << j;
+                *p++ = (char)(63 + six);
+            }
+            for (int k = 0; k < pad - 1; k++)
+                *p++ = '$';
+            *p++ = left == 0 && band + 1 < bands ? '-' : '$';
+        }
+    }
+    memcpy(p, k_sixel_end, SIXEL_END_LEN);
+    p += SIXEL_END_LEN;
+    free(index);
+    *bytes = (size_t)(p - text);
+    return TRT_HOST_OK;
+}

@@ -219,6 +219,11 @@ struct trt_context
     DeviceBuffer<unsigned> d_delta_tile_bytes;         // per tile of cells: the bytes of its records
     DeviceBuffer<unsigned long long> d_delta_tile_at;  // ... and where they start in the text
     DeviceBuffer<unsigned long long> d_delta_bytes;    // trt_render_host_ansi_delta: the texts' lengths before they cross PCIe
+    // The sixel image (trt_render_device_sixel, trt_sixel.hpp): the frame's RGB8 bytes -- a buffer of its own, never one of the delta
+    // entries' shown pair --, per band of six rows the 8 words of its colour mask and its colour rows, and where they start in the text
+    DeviceBuffer<unsigned char> d_sixel_frame;
+    DeviceBuffer<unsigned> d_sixel_masks, d_sixel_counts;
+    DeviceBuffer<unsigned long long> d_sixel_band_at;
     int ior_count = 0;          // 0 = off (the reference's path)
     DeviceBuffer<unsigned long long> d_counters;
     DeviceBuffer<unsigned int> d_queue;

@@ -13,6 +13,7 @@
 #include "trt_ansi256.hpp"
 #include "trt_ansi_half.hpp"
 #include "trt_kitty.hpp"
+#include "trt_sixel.hpp"
 
 using namespace trt_impl;
 
@@ -1717,4 +1718,132 @@ extern "C" int trt_render_host_batch_ansi_delta_half(trt_context *ctx, const Cam
                                                      size_t capacity_bytes, size_t *bytes)
 {
     return render_host_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, true, "trt_render_host_batch_ansi_delta_half");
+}
+
+// ---- the sixel image (trt_sixel.h: the format, its position map and its lane map; trt_sixel.hpp: the kernels).  Its length depends on the
+// picture, so it goes the delta texts' way: the frame's RGB8 bytes, then measure, offsets, write ----
+
+extern "C" size_t trt_sixel_capacity(int width, int rows)
+{
+    return (size_t)trt_sixel_capacity_bytes(width, rows);
+}
+
+// measure, offsets, write on `stream` for the frame of width x rows at d_rgb8: the text at d_text, any alignment, its length at *d_bytes
+static int launch_sixel(trt_context *ctx, hipStream_t stream, const unsigned char *d_rgb8, int width, int rows, void *d_text, unsigned long long *d_bytes)
+{
+    const size_t bands = (size_t)trt_sixel_bands(rows);
+    if (ctx->d_sixel_masks.capacity < bands * TRT_SIXEL_MASK_WORDS || ctx->d_sixel_counts.capacity < bands || ctx->d_sixel_band_at.capacity < bands)
+        HIP_TRY(hipStreamSynchronize(stream)); // an image in flight may still use the old masks
+    HIP_TRY(ctx->d_sixel_masks.reserve(bands * TRT_SIXEL_MASK_WORDS));
+    HIP_TRY(ctx->d_sixel_counts.reserve(bands));
+    HIP_TRY(ctx->d_sixel_band_at.reserve(bands));
+    const trt_text_split split = trt_sixel_row_split((unsigned long long)d_text, width);
+    const unsigned tiles = (trt_sixel_slots(&split) + TRT_SIXEL_BLOCK - 1) / TRT_SIXEL_BLOCK;
+    hipLaunchKernelGGL(trt::sixel_measure_kernel, dim3((unsigned)bands), dim3(TRT_SIXEL_BLOCK), 0, stream, d_rgb8, width, rows, ctx->d_sixel_masks.ptr, ctx->d_sixel_counts.ptr);
+    hipLaunchKernelGGL(trt::sixel_offsets_kernel, dim3(1), dim3(TRT_SIXEL_SCAN_BLOCK), 0, stream, (const unsigned *)ctx->d_sixel_counts.ptr, width, rows,
+                       ctx->d_sixel_band_at.ptr, (unsigned char *)d_text, d_bytes);
+    hipLaunchKernelGGL(trt::sixel_write_kernel, dim3(tiles, (unsigned)bands), dim3(TRT_SIXEL_BLOCK), 0, stream, d_rgb8, width, rows, (const unsigned *)ctx->d_sixel_masks.ptr,
+                       (const unsigned long long *)ctx->d_sixel_band_at.ptr, (unsigned char *)d_text);
+    HIP_TRY(hipGetLastError());
+    return TRT_OK;
+}
+
+static int check_sixel_size(int width, int rows)
+{
+    if (trt_sixel_size_ok(width, rows))
+        return TRT_OK;
+    return fail(TRT_ERR_ARGUMENT, "%d x %d: a sixel image has 1 to %d pixels a row and 1 to %d rows", width, rows, TRT_SIXEL_MAX, TRT_SIXEL_MAX);
+}
+
+extern "C" int trt_sixel_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text, size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    if (!ctx || !d_rgb8 || !d_text || !d_bytes)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    const int rc = check_sixel_size(width, rows);
+    if (rc)
+        return rc;
+    const size_t need = trt_sixel_capacity(width, rows);
+    if (capacity_bytes < need)
+        return fail(TRT_ERR_CAPACITY, "a sixel image of %d x %d needs room for %zu B, %zu given", width, rows, need, capacity_bytes);
+    HIP_TRY(hipSetDevice(ctx->device));
+    return launch_sixel(ctx, ctx->stream, (const unsigned char *)d_rgb8, width, rows, d_text, d_bytes);
+}
+
+// what the render entries refuse before anything is enqueued: what trt_render_device_rgb8 refuses, a size without an image, and a `text` --
+// the caller's buffer, on the device or on the host -- without room for any image of the size
+static int check_render_sixel(const trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, const void *text,
+                              size_t capacity_bytes, const void *bytes)
+{
+    if (!bytes)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    int rc = rowset_valid(rows) ? check_sixel_size(rows->width, trt_rowset_rows(rows)) : TRT_OK;
+    if (rc)
+        return rc;
+    rc = check_render_arguments(ctx, camera, 1, rows, bounce_limit, rays_per_pixel, text, (size_t)-1, kBytes);
+    if (rc)
+        return rc;
+    const size_t need = trt_sixel_capacity(rows->width, trt_rowset_rows(rows));
+    if (capacity_bytes < need)
+        return fail(TRT_ERR_CAPACITY, "a sixel image of %d x %d owned rows needs room for %zu B, %zu given", rows->width, trt_rowset_rows(rows), need, capacity_bytes);
+    return TRT_OK;
+}
+
+extern "C" int trt_render_device_sixel(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                                       size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    int rc = check_render_sixel(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes);
+    if (rc)
+        return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int width = rows->width, owned = trt_rowset_rows(rows);
+    const size_t frame = (size_t)owned * width * 3;
+    if (ctx->d_sixel_frame.capacity < frame)
+    {
+        HIP_TRY(hipStreamSynchronize(ctx->stream)); // an image in flight may still be formatted from the old bytes
+        HIP_TRY(ctx->d_sixel_frame.reserve(frame));
+    }
+    // the frame's bytes: the RGB8 form of the ordered mean (the reference-order kernel: its doubles through quantize_kernel)
+    rc = render_device_on(ctx, camera, rows, bounce_limit, rays_per_pixel, ctx->d_sixel_frame.ptr, frame, 0, kEntryWhole, kBytes);
+    if (rc)
+        return rc;
+    return launch_sixel(ctx, ctx->stream, ctx->d_sixel_frame.ptr, width, owned, d_text, d_bytes);
+}
+
+// the image in the context's text buffer, its length read back, then exactly that many bytes through the pinned staging
+extern "C" int trt_render_host_sixel(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
+                                     size_t capacity_bytes, size_t *bytes)
+{
+    int rc = check_render_sixel(ctx, camera, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes);
+    if (rc)
+        return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t room = trt_sixel_capacity(rows->width, trt_rowset_rows(rows));
+    if (ctx->d_text.capacity < room || ctx->d_delta_bytes.capacity < 1)
+        HIP_TRY(hipStreamSynchronize(ctx->stream)); // a text in flight may still be written to the old buffers
+    HIP_TRY(ctx->d_text.reserve(room));
+    HIP_TRY(ctx->d_delta_bytes.reserve(1));
+    HIP_TRY(ctx->h_staging.reserve(sizeof(unsigned long long)));
+    const double t_begin = host_now_ms();
+    rc = trt_render_device_sixel(ctx, camera, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, room, ctx->d_delta_bytes.ptr);
+    if (rc)
+        return rc;
+    unsigned long long length = 0;
+    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_delta_bytes.ptr, sizeof length, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(&length, ctx->h_staging.ptr, sizeof length);
+    if (length > room)
+        return fail(TRT_ERR_CAPACITY, "an image of more than %zu B", room);
+    // Pinned staging grows with the images' lengths, not to the capacity -- 240 colours in every band are 83 MB at 1920x1080 and rare -- and
+    // in steps of a power of two, so that a moving picture whose images grow does not allocate pinned memory frame after frame
+    size_t staged = 4096;
+    while (staged < (size_t)length)
+        staged *= 2;
+    HIP_TRY(ctx->h_staging.reserve(std::min(staged, std::max(room, sizeof length))));
+    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_text.ptr, (size_t)length, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(text, ctx->h_staging.ptr, (size_t)length);
+    *bytes = (size_t)length;
+    if (print_host_times())
+        fprintf(stderr, "trt_render_host_sixel: %.3f ms for an image of %llu bytes\n", host_now_ms() - t_begin, length);
+    return TRT_OK;
 }

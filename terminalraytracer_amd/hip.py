@@ -102,6 +102,11 @@ SYMBOLS = {
     "trt_ansi_delta_half_kernel_times": (_I, [_VP, _VP, _VP, _I, _I, _VP, _SZ, _VP, C.POINTER(C.c_float)]),
     "trt_render_device_ansi_delta_half": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ, _VP]),
     "trt_render_host_ansi_delta_half": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
+    "trt_sixel_capacity": (_SZ, [_I, _I]),
+    "trt_sixel_from_rgb8_device": (_I, [_VP, _VP, _I, _I, _VP, _SZ, _VP]),
+    "trt_render_device_sixel": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ, _VP]),
+    "trt_render_host_sixel": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
+    "trt_render_frame_sixel": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
     "trt_ansi_delta_capacity": (_SZ, [_I, _I]),
     "trt_ansi_delta_from_rgb8_device": (_I, [_VP, _VP, _VP, _I, _I, _VP, _SZ, _VP]),
     "trt_ansi_delta_kernel_times": (_I, [_VP, _VP, _VP, _I, _I, _VP, _SZ, _VP, C.POINTER(C.c_float)]),
@@ -665,6 +670,23 @@ class Context:
         a uint8 buffer of ansi_delta_half_capacity bytes to reuse"""
         return self._render_host_delta("trt_render_host_ansi_delta_half", ansi_delta_half_capacity, camera_array, rows, bounce_limit, rays_per_pixel, out)
 
+    # the sixel image: a text whose length depends on the picture, reported as the delta entries report theirs
+
+    def sixel_from_rgb8(self, rgb_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr):
+        """the DEC sixel image of a width x rows frame of RGB8 bytes in device memory, at text_ptr, its length (a uint64) at the device
+        address bytes_ptr (trt_sixel_from_rgb8_device)"""
+        _check(lib().trt_sixel_from_rgb8_device(self._h, _VP(rgb_ptr), width, rows, _VP(text_ptr), capacity_bytes, _VP(bytes_ptr)))
+
+    def render_device_sixel(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr):
+        """the frame as a DEC sixel image in device memory, at any alignment, its length (a uint64) at the device address bytes_ptr
+        (trt_render_device_sixel)"""
+        self._render_device_delta("trt_render_device_sixel", camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr)
+
+    def render_host_sixel(self, camera_array, rows, bounce_limit, rays_per_pixel, out=None):
+        """the same into host memory: the uint8 image, exactly as long as the host is to write it (trt_render_host_sixel); `out`: a uint8
+        buffer of sixel_capacity bytes to reuse"""
+        return self._render_host_delta("trt_render_host_sixel", sixel_capacity, camera_array, rows, bounce_limit, rays_per_pixel, out)
+
     @staticmethod
     def _camera_batch(cameras):
         cams = np.ascontiguousarray(cameras, dtype=np.float64)
@@ -1005,6 +1027,18 @@ def render_frame_ansi_delta(scene_data, width, height, bounce_limit=10, rays_per
     """Host-in frame as the delta text against the frame this entry returned before (a keyframe the first time): the uint8 text, as
     long as the host is to write it (trt_render_frame_ansi_delta)."""
     return _render_frame_delta("trt_render_frame_ansi_delta", ansi_delta_capacity, scene_data, width, height, bounce_limit, rays_per_pixel)
+
+
+def sixel_capacity(width, rows):
+    """room for any DEC sixel image of a width x rows screen: 4352 + L * the sum over the bands of six rows of min(240, the band's pixels),
+    L = 4 + width + T; 0 unless both sizes are positive and at most 99999 (trt_sixel_capacity)"""
+    return _delta_capacity("trt_sixel_capacity", width, rows)
+
+
+def render_frame_sixel(scene_data, width, height, bounce_limit=10, rays_per_pixel=10):
+    """Host-in frame as a DEC sixel image in the 240 fixed colours of the xterm palette, formatted on the device: the uint8 text, as long
+    as the host is to write it (trt_render_frame_sixel)."""
+    return _render_frame_delta("trt_render_frame_sixel", sixel_capacity, scene_data, width, height, bounce_limit, rays_per_pixel)
 
 
 def ansi_delta_half_capacity(width, rows):

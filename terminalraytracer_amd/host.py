@@ -34,6 +34,7 @@ HOST_SYMBOLS = {
     "trt_xterm256_index_search": (C.c_uint, [C.c_uint, C.c_uint, C.c_uint]),
     "trt_emitter_ansi256_rgb8": (_I, [_VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_ansi256_half_rgb8": (_I, [_VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "trt_emitter_sixel_rgb8": (_I, [_VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_delta_half_rgb8": (_I, [_VP, _VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_write": (_I, [_VP, _VP]),
     "trt_draw_screen": (_I, [C.POINTER(L.Screen), _VP]),
@@ -163,6 +164,21 @@ def emitter_ansi256_rgb8(rgb, half=False):
     if rc != 0 or n.value != out.size:
         raise ValueError(f"{name}({width}, {rows}) failed with {rc}, {n.value} bytes")
     return out
+
+
+def emitter_sixel_rgb8(rgb):
+    """the DEC sixel image of a frame of bytes [rows, width, 3], formatted on the host: uint8 [4352 + L * colour rows], L = 4 + width + T,
+    a length that depends on the picture (trt_emitter_sixel_rgb8)"""
+    a = np.ascontiguousarray(rgb, dtype=np.uint8)
+    rows, width, _ = a.shape
+    row_len = 4 + width + 1 + (-(width + 1)) % 4
+    most = sum(min(240, width * min(6, rows - first)) for first in range(0, rows, 6))
+    out = np.empty(4352 + row_len * most, dtype=np.uint8)
+    n = C.c_size_t(0)
+    rc = lib().trt_emitter_sixel_rgb8(a.ctypes.data, width, rows, out.ctypes.data, out.size, C.byref(n))
+    if rc != 0 or n.value > out.size:
+        raise ValueError(f"trt_emitter_sixel_rgb8({width}, {rows}) failed with {rc}, {n.value} bytes")
+    return out[:n.value].copy()
 
 
 def emitter_half_rgb8(rgb):
