@@ -137,6 +137,52 @@ def oracle_path_rays_refractive(scene_data, ior, width, height, bounce_limit, ra
     return px, st, rays[: log.count][kinds[: log.count] == 0].copy()
 
 
+ENDED_ON_SKY, ENDED_BY_LIMIT, ENDED_BY_WEIGHT = 0, 1, 2
+
+
+def oracle_hit_sequences(scene_data, width, height, bounce_limit, rays_per_pixel, cameras=None):
+    """What every sample of a small frame does, from one single-threaded oracle frame under the ray log: per work unit, in unit order
+    (unit = pixel * rays_per_pixel + k; `cameras`: a batch, frame-major), the number of path rays, the number of hits (a path ray that
+    shadow rays follow: the scene has a light) and how the sample ended (ENDED_*: the last ray met the sky; the last hit was the bounce
+    limit's; the weight fell to 1e-5 or below).  Returns {"paths", "hits", "ending": int arrays, "frames": [pixels], "counts": (path
+    rays, shadow rays) of all frames, "rays": per unit the float64[paths, 6] path rays}."""
+    lights = len(scene_data.dir_lights) + len(scene_data.point_lights)
+    assert lights >= 1 and bounce_limit >= 1
+    samples = width * height * rays_per_pixel
+    cap = samples * bounce_limit * (1 + lights) + 1
+    lib = oracle()
+    lib.trt_oracle_set_ray_log.argtypes = [C.POINTER(OracleRayLog)]
+    paths, hits, ending, rays_of, frames, counts = [], [], [], [], [], [0, 0]
+    for cam in ([scene_data.camera] if cameras is None else cameras):
+        scene = scene_data.with_camera(cam)
+        rays, kinds = np.zeros((cap, 6)), np.zeros(cap, dtype=np.uint8)
+        log = OracleRayLog(rays.ctypes.data, kinds.ctypes.data, cap, 0)
+        lib.trt_oracle_set_ray_log(C.byref(log))
+        try:
+            px, st = oracle_render(scene, width, height, bounce_limit, rays_per_pixel, threads=1)
+        finally:
+            lib.trt_oracle_set_ray_log(None)
+        assert log.count < cap, "the ray log overflowed"
+        rays, kinds = rays[: log.count], kinds[: log.count]
+        path_at = np.nonzero(kinds == 0)[0]
+        assert path_at.size == st.path_rays and log.count - path_at.size == st.shadow_rays
+        is_hit = np.append(path_at[1:], log.count) - path_at > 1  # shadow rays follow
+        # a sample's first path ray starts at the eye, bit for bit; no reflected ray does (it starts 1e-6 off a surface)
+        first = np.nonzero((bits(rays[path_at, :3]) == bits(scene.camera[9:12])[None, :]).all(axis=1))[0]
+        assert first.size == samples == st.samples, (first.size, samples, st.samples)
+        assert first[0] == 0
+        for a, b in zip(first, np.append(first[1:], path_at.size)):
+            p, h = int(b - a), int(is_hit[a:b].sum())
+            assert is_hit[a:a + h].all() and h in (p, p - 1) and 1 <= p <= bounce_limit  # hits, then at most one ray into the sky
+            paths.append(p), hits.append(h), rays_of.append(rays[path_at[a:b]].copy())
+            ending.append(ENDED_ON_SKY if h < p else ENDED_BY_LIMIT if h == bounce_limit else ENDED_BY_WEIGHT)
+        px.setflags(write=False)
+        frames.append(px)
+        counts[0] += int(st.path_rays)
+        counts[1] += int(st.shadow_rays)
+    return {"paths": np.array(paths), "hits": np.array(hits), "ending": np.array(ending), "frames": frames, "counts": tuple(counts), "rays": rays_of}
+
+
 def oracle_rgb8(pixels):
     px = np.ascontiguousarray(pixels, dtype=np.float64)
     out = np.empty(px.shape, dtype=np.uint8)
