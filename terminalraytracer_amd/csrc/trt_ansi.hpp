@@ -1,7 +1,8 @@
 // trt_ansi.hpp -- the frame as the terminal's text, written on the device: the wave that writes a whole text of either format
-// (text_write), and for the full text the kernels that stand in the ordered mean's place when a host asks for what
-// buffered_draw_screen would fwrite (TRT.c:1142-1172), and the same formatting fed from RGB8 bytes.  trt_text_map.h holds the position
-// map and the lane map, trt_ansi.h the format; trt_ansi_half.hpp has the half-block text's kernels.
+// (text_write), what it fetches a cell's pixels from (the scratch or RGB8 bytes), the two kernels every character-cell text is an
+// instantiation of -- the one that stands in the ordered mean's place when a host asks for what buffered_draw_screen would fwrite
+// (TRT.c:1142-1172), and the same formatting fed from RGB8 bytes -- and the full text's format.  trt_text_map.h holds the position map
+// and the lane map, trt_ansi.h the format; trt_ansi_half.hpp and trt_ansi256.hpp say what the other formats' lanes hold.
 //
 // A wave owns wave_words aligned words of the text and the up to 63 cells they show.  Lane l forms what cell C0 + l shows -- the full
 // text's one pixel, the ordered mean of its samples from 0.0 in sample order and the emitter's cast (rgb8_byte), or three bytes read
@@ -120,30 +121,89 @@ __device__ __forceinline__ unsigned ansi_pixel_of_samples(const double *samples,
     return rgb8_byte(m0, inv_spp) | rgb8_byte(m1, inv_spp) << 8 | rgb8_byte(m2, inv_spp) << 16;
 }
 
-// The ordered mean, the emitter's cast and the terminal's text in ONE pass, as the last kernel of a launch in reduce_samples_kernel's
-// place: blockIdx.y is the frame, and it leaves the queue ready in the same way.  Frame b's text starts at out + b * trt_ansi_text_bytes,
+// the two pixels of a half-block cell, formed TOGETHER (trt_ansi_half.hpp, trt_ansi256.hpp)
+struct ansi_half_pair
+{
+    unsigned upper, lower; // r | g << 8 | b << 16 each
+};
+
+// pixels p and q of a frame's scratch (as ansi_pixel_of_samples forms one): each sum from 0.0 in sample order, the two side by side
+__device__ __forceinline__ ansi_half_pair ansi_half_pixels_of_samples(const double *samples, long values, int spp, double inv_spp, long long p, long long q)
+{
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;
+#pragma unroll 2 // two samples of BOTH pixels in flight per lane, the sums in sample order (profiles/r13/a_half.md: one pixel after the other and four samples of both were slower)
+    for (int k = 0; k < spp; k++)
+    {
+        const double *s = samples + (long)k * values;
+        a0 += s[3 * p], a1 += s[3 * p + 1], a2 += s[3 * p + 2];
+        b0 += s[3 * q], b1 += s[3 * q + 1], b2 += s[3 * q + 2];
+    }
+    ansi_half_pair both;
+    both.upper = rgb8_byte(a0, inv_spp) | rgb8_byte(a1, inv_spp) << 8 | rgb8_byte(a2, inv_spp) << 16;
+    both.lower = rgb8_byte(b0, inv_spp) | rgb8_byte(b1, inv_spp) << 8 | rgb8_byte(b2, inv_spp) << 16;
+    return both;
+}
+
+// What a Format's hold() is given as `fetch`, from either source: (p) forms pixel p < width * rows as r | g << 8 | b << 16 for the formats
+// whose cell is one pixel, (p, q) the pixels p and q together for the half-block formats.
+// ... from ONE frame's scratch: the ordered mean and the emitter's cast
+struct pixels_of_samples
+{
+    const double *samples;
+    long values;
+    int spp;
+    double inv_spp;
+    __device__ __forceinline__ unsigned operator()(long long p) const { return ansi_pixel_of_samples(samples, values, spp, inv_spp, p); }
+    __device__ __forceinline__ ansi_half_pair operator()(long long p, long long q) const { return ansi_half_pixels_of_samples(samples, values, spp, inv_spp, p, q); }
+};
+
+// ... from a frame that exists as RGB8 bytes rgb[p * 3 + channel]
+struct pixels_of_rgb8
+{
+    const unsigned char *rgb;
+    __device__ __forceinline__ unsigned operator()(long long p) const
+    {
+        const unsigned char *px = rgb + 3 * p;
+        return (unsigned)px[0] | (unsigned)px[1] << 8 | (unsigned)px[2] << 16;
+    }
+    __device__ __forceinline__ ansi_half_pair operator()(long long p, long long q) const
+    {
+        ansi_half_pair both;
+        both.upper = (*this)(p);
+        both.lower = (*this)(q);
+        return both;
+    }
+};
+
+// Every kernel that writes a whole text has ONE of two argument lists, whatever its format reads of it (the full-cell formats ignore
+// width_magic, the kitty image, trt_kitty.hpp, both magics): the host launches them through these types (trt_render.hip).
+using TextMeanKernel = void (*)(const double *samples, unsigned char *out, int width, int rows, unsigned row_magic, unsigned width_magic, int spp, double inv_spp,
+                                unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift);
+using TextFromRgb8Kernel = void (*)(const unsigned char *rgb, unsigned char *out, int width, int rows, unsigned row_magic, unsigned width_magic);
+
+// The ordered mean, the emitter's cast and the Format's text in ONE pass, as the last kernel of a launch in reduce_samples_kernel's
+// place: blockIdx.y is the frame, and it leaves the queue ready in the same way.  Frame b's text starts at out + b * Format::text_bytes,
 // aligned to nothing in general: every frame has a head and a tail of its own.  A single frame's grid has trt_text_waves(words of the
 // text at `out`) waves; that of several frames the most waves an alignment needs (a frame's spare wave finds nothing to do).
-__global__ __launch_bounds__(256) void reduce_samples_ansi_kernel(const double *samples, unsigned char *out, int width, int rows, unsigned row_magic, int spp,
-                                                                  double inv_spp, unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
+template <class Format>
+__global__ __launch_bounds__(256) void reduce_samples_text_kernel(const double *samples, unsigned char *out, int width, int rows, unsigned row_magic,
+                                                                  unsigned width_magic, int spp, double inv_spp, unsigned int *queue, unsigned grid,
+                                                                  unsigned waves_per_group, unsigned shift)
 {
     arm_queue(queue, grid, waves_per_group, shift);
     const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long values = (long)width * rows * 3;
-    const double *mine = samples + (size_t)blockIdx.y * (size_t)spp * (size_t)values;
-    text_write<ansi_text>(out + (size_t)blockIdx.y * (size_t)trt_ansi_text_bytes(width, rows), width, rows, row_magic, 0u, t >> 6, (int)(t & 63),
-                          [=](long long p) { return ansi_pixel_of_samples(mine, values, spp, inv_spp, p); });
+    text_write<Format>(out + (size_t)blockIdx.y * (size_t)Format::text_bytes(width, rows), width, rows, row_magic, width_magic, t >> 6, (int)(t & 63),
+                       pixels_of_samples{samples + (size_t)blockIdx.y * (size_t)spp * (size_t)values, values, spp, inv_spp});
 }
 
-// The formatting alone, of a frame that exists as RGB8 bytes rgb[p * 3 + channel] (trt_ansi_from_rgb8_device; the reference-order
-// kernel's frames, which have no scratch)
-__global__ __launch_bounds__(256) void ansi_from_rgb8_kernel(const unsigned char *rgb, unsigned char *out, int width, int rows, unsigned row_magic)
+// The formatting alone, of a frame that exists as RGB8 bytes (the ..._from_rgb8_device entries; the reference-order kernel's frames,
+// which have no scratch)
+template <class Format>
+__global__ __launch_bounds__(256) void text_from_rgb8_kernel(const unsigned char *rgb, unsigned char *out, int width, int rows, unsigned row_magic, unsigned width_magic)
 {
     const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    text_write<ansi_text>(out, width, rows, row_magic, 0u, t >> 6, (int)(t & 63), [=](long long p) {
-        const unsigned char *px = rgb + 3 * p;
-        return (unsigned)px[0] | (unsigned)px[1] << 8 | (unsigned)px[2] << 16;
-    });
+    text_write<Format>(out, width, rows, row_magic, width_magic, t >> 6, (int)(t & 63), pixels_of_rgb8{rgb});
 }
 
 #endif // TRT_UNIT_RENDER

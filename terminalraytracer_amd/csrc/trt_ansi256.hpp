@@ -1,8 +1,8 @@
-// trt_ansi256.hpp -- the frame as the terminal's text in the xterm 256-colour palette, written on the device: for the full text (two
-// spaces a pixel) and the half-block text (two pixel rows a line) the kernels that stand in the ordered mean's place, the same
-// formatting fed from RGB8 bytes, and the palette map alone, a byte a pixel.  trt_xterm256.h holds the palette map, trt_text_map.h the
-// position map and the lane map, trt_ansi256.h and trt_ansi256_half.h the formats, trt_ansi.hpp the wave that carries them out
-// (text_write); this file says what a lane of that wave holds of a cell and how a word fetches it.
+// trt_ansi256.hpp -- the frame as the terminal's text in the xterm 256-colour palette, written on the device: the full text (two
+// spaces a pixel) and the half-block text (two pixel rows a line), and the palette map alone, a byte a pixel.  trt_xterm256.h holds the
+// palette map, trt_text_map.h the position map and the lane map, trt_ansi256.h and trt_ansi256_half.h the formats, trt_ansi.hpp the
+// wave that carries them out (text_write), the fetches and the two kernels (reduce_samples_text_kernel, text_from_rgb8_kernel); this
+// file says what a lane of that wave holds of a cell and how a word fetches it.
 //
 // A wave owns wave_words aligned words of the text (192: three a lane; 320: five a lane) and the up to 60 or 57 cells they show.  Lane
 // l forms what cell C0 + l shows -- its pixel or its two pixels as the 24-bit texts' lanes form theirs: the ordered mean of the samples
@@ -83,60 +83,6 @@ struct ansi256_half_text
     }
     static __device__ __forceinline__ unsigned byte(const trt_text_at &at, int, seen shown, unsigned) { return trt_ansi256_half_byte(&at, shown); }
 };
-
-// The ordered mean, the emitter's cast, the palette map and the 256-colour text in ONE pass, as the last kernel of a launch in
-// reduce_samples_kernel's place: blockIdx.y is the frame, and it leaves the queue ready in the same way.  Frame b's text starts at
-// out + b * trt_ansi256_text_bytes, aligned to nothing in general: every frame has a head and a tail of its own.  A single frame's grid
-// has trt_text_waves(words of the text at `out`) waves; that of several frames the most waves an alignment needs (a frame's spare wave
-// finds nothing to do).
-__global__ __launch_bounds__(256) void reduce_samples_ansi256_kernel(const double *samples, unsigned char *out, int width, int rows, unsigned row_magic, int spp,
-                                                                     double inv_spp, unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
-{
-    arm_queue(queue, grid, waves_per_group, shift);
-    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long values = (long)width * rows * 3;
-    const double *mine = samples + (size_t)blockIdx.y * (size_t)spp * (size_t)values;
-    text_write<ansi256_text>(out + (size_t)blockIdx.y * (size_t)trt_ansi256_text_bytes(width, rows), width, rows, row_magic, 0u, t >> 6, (int)(t & 63),
-                             [=](long long p) { return ansi_pixel_of_samples(mine, values, spp, inv_spp, p); });
-}
-
-// the same for the half-block text: frame b's starts at out + b * trt_ansi256_half_text_bytes
-__global__ __launch_bounds__(256) void reduce_samples_ansi256_half_kernel(const double *samples, unsigned char *out, int width, int rows, unsigned row_magic,
-                                                                          unsigned width_magic, int spp, double inv_spp, unsigned int *queue, unsigned grid,
-                                                                          unsigned waves_per_group, unsigned shift)
-{
-    arm_queue(queue, grid, waves_per_group, shift);
-    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long values = (long)width * rows * 3;
-    const double *mine = samples + (size_t)blockIdx.y * (size_t)spp * (size_t)values;
-    text_write<ansi256_half_text>(out + (size_t)blockIdx.y * (size_t)trt_ansi256_half_text_bytes(width, rows), width, rows, row_magic, width_magic, t >> 6,
-                                  (int)(t & 63), [=](long long p, long long q) { return ansi_half_pixels_of_samples(mine, values, spp, inv_spp, p, q); });
-}
-
-// The formatting alone, of a frame that exists as RGB8 bytes rgb[p * 3 + channel] (trt_ansi256_from_rgb8_device; the reference-order
-// kernel's frames, which have no scratch)
-__global__ __launch_bounds__(256) void ansi256_from_rgb8_kernel(const unsigned char *rgb, unsigned char *out, int width, int rows, unsigned row_magic)
-{
-    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    text_write<ansi256_text>(out, width, rows, row_magic, 0u, t >> 6, (int)(t & 63), [=](long long p) {
-        const unsigned char *px = rgb + 3 * p;
-        return (unsigned)px[0] | (unsigned)px[1] << 8 | (unsigned)px[2] << 16;
-    });
-}
-
-// the same for the half-block text (trt_ansi256_half_from_rgb8_device)
-__global__ __launch_bounds__(256) void ansi256_half_from_rgb8_kernel(const unsigned char *rgb, unsigned char *out, int width, int rows, unsigned row_magic,
-                                                                     unsigned width_magic)
-{
-    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    text_write<ansi256_half_text>(out, width, rows, row_magic, width_magic, t >> 6, (int)(t & 63), [=](long long p, long long q) {
-        const unsigned char *a = rgb + 3 * p, *b = rgb + 3 * q;
-        ansi_half_pair both;
-        both.upper = (unsigned)a[0] | (unsigned)a[1] << 8 | (unsigned)a[2] << 16;
-        both.lower = (unsigned)b[0] | (unsigned)b[1] << 8 | (unsigned)b[2] << 16;
-        return both;
-    });
-}
 
 // The palette map alone (trt_xterm256_from_rgb8_device): index[p] of the pixel rgb[3 p ...], a lane a pixel, any alignment of either
 __global__ __launch_bounds__(256) void xterm256_from_rgb8_kernel(const unsigned char *rgb, unsigned char *index, unsigned long long pixels)

@@ -174,71 +174,49 @@ extern "C" int render_frame(const Scene *scene, Screen *screen, int bounce_limit
     return trt_render_frame(scene, screen, bounce_limit, rays_per_pixel);
 }
 
-extern "C" int trt_render_frame_rgb8(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, unsigned char *rgb)
+// every kind whose length the size fixes -- the bytes, the four character-cell texts, the kitty image: `render` is the kind's host entry,
+// `has_size`: whether the kind exists at this size
+template <class T>
+static int render_frame_as(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, T *out,
+                           int (*render)(trt_context *, const Camera *, const trt_rowset *, int, int, T *), bool has_size = true)
 {
-    if (!scene || !rgb)
+    if (!scene || !out)
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (width <= 0 || height <= 0)
+    if (width <= 0 || height <= 0 || !has_size)
         return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, height);
     return render_default_frame(scene, width, height, [&](trt_context *ctx, const trt_rowset *whole) {
-        return trt_render_host_rgb8(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, rgb);
+        return render(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, out);
     });
+}
+
+extern "C" int trt_render_frame_rgb8(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, unsigned char *rgb)
+{
+    return render_frame_as(scene, width, height, bounce_limit, rays_per_pixel, rgb, trt_render_host_rgb8);
 }
 
 extern "C" int trt_render_frame_ansi(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text)
 {
-    if (!scene || !text)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (width <= 0 || height <= 0)
-        return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, height);
-    return render_default_frame(scene, width, height, [&](trt_context *ctx, const trt_rowset *whole) {
-        return trt_render_host_ansi(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, text);
-    });
+    return render_frame_as(scene, width, height, bounce_limit, rays_per_pixel, text, trt_render_host_ansi);
 }
 
 extern "C" int trt_render_frame_ansi_half(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text)
 {
-    if (!scene || !text)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (width <= 0 || height <= 0)
-        return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, height);
-    return render_default_frame(scene, width, height, [&](trt_context *ctx, const trt_rowset *whole) {
-        return trt_render_host_ansi_half(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, text);
-    });
+    return render_frame_as(scene, width, height, bounce_limit, rays_per_pixel, text, trt_render_host_ansi_half);
 }
 
 extern "C" int trt_render_frame_kitty(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text)
 {
-    if (!scene || !text)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (width <= 0 || height <= 0 || trt_kitty_bytes(width, height) == 0)
-        return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, height);
-    return render_default_frame(scene, width, height, [&](trt_context *ctx, const trt_rowset *whole) {
-        return trt_render_host_kitty(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, text);
-    });
-}
-
-// the two texts in the xterm 256-colour palette: `render` is the kind's host entry
-static int render_frame_ansi256(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text,
-                                int (*render)(trt_context *, const Camera *, const trt_rowset *, int, int, char *))
-{
-    if (!scene || !text)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    if (width <= 0 || height <= 0)
-        return fail(TRT_ERR_ARGUMENT, "screen %d x %d", width, height);
-    return render_default_frame(scene, width, height, [&](trt_context *ctx, const trt_rowset *whole) {
-        return render(ctx, &scene->camera, whole, bounce_limit, rays_per_pixel, text);
-    });
+    return render_frame_as(scene, width, height, bounce_limit, rays_per_pixel, text, trt_render_host_kitty, trt_kitty_bytes(width, height) != 0);
 }
 
 extern "C" int trt_render_frame_ansi256(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text)
 {
-    return render_frame_ansi256(scene, width, height, bounce_limit, rays_per_pixel, text, trt_render_host_ansi256);
+    return render_frame_as(scene, width, height, bounce_limit, rays_per_pixel, text, trt_render_host_ansi256);
 }
 
 extern "C" int trt_render_frame_ansi256_half(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text)
 {
-    return render_frame_ansi256(scene, width, height, bounce_limit, rays_per_pixel, text, trt_render_host_ansi256_half);
+    return render_frame_as(scene, width, height, bounce_limit, rays_per_pixel, text, trt_render_host_ansi256_half);
 }
 
 // the shown frame is the default context's: trt_shutdown forgets it with the context.  `capacity` and `render`: those of the kind

@@ -82,9 +82,10 @@ __device__ __forceinline__ unsigned kitty_pixel_of_samples(const double *samples
 // The ordered mean, the emitter's cast and the image text in ONE pass, as the last kernel of a launch in reduce_samples_kernel's place:
 // blockIdx.y is the frame, and it leaves the queue ready in the same way.  Frame b's text starts at out + b * trt_kitty_text_bytes,
 // aligned to nothing in general: every frame has a head and a tail of its own.  A single frame's grid has trt_kitty_waves(out, bytes)
-// waves; that of several frames trt_kitty_waves_most(bytes) (a frame's spare wave finds nothing to do).
-__global__ __launch_bounds__(256) void reduce_samples_kitty_kernel(const double *samples, unsigned char *out, int width, int rows, int spp, double inv_spp,
-                                                                   unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
+// waves; that of several frames trt_kitty_waves_most(bytes) (a frame's spare wave finds nothing to do).  The argument list is every
+// whole text's (TextMeanKernel, trt_ansi.hpp): the image has no use for the two magics.
+__global__ __launch_bounds__(256) void reduce_samples_kitty_kernel(const double *samples, unsigned char *out, int width, int rows, unsigned, unsigned, int spp,
+                                                                   double inv_spp, unsigned int *queue, unsigned grid, unsigned waves_per_group, unsigned shift)
 {
     arm_queue(queue, grid, waves_per_group, shift);
     const long values = (long)width * rows * 3;
@@ -94,13 +95,10 @@ __global__ __launch_bounds__(256) void reduce_samples_kitty_kernel(const double 
 }
 
 // The formatting alone, of a frame that exists as RGB8 bytes rgb[p * 3 + channel] (trt_kitty_from_rgb8_device; the reference-order
-// kernel's frames, which have no scratch)
-__global__ __launch_bounds__(256) void kitty_from_rgb8_kernel(const unsigned char *rgb, unsigned char *out, int width, int rows)
+// kernel's frames, which have no scratch; TextFromRgb8Kernel's argument list)
+__global__ __launch_bounds__(256) void kitty_from_rgb8_kernel(const unsigned char *rgb, unsigned char *out, int width, int rows, unsigned, unsigned)
 {
-    kitty_write(out, width, rows, kitty_wave_index(), (int)(threadIdx.x & 63), [=](int p) {
-        const unsigned char *px = rgb + 3 * (long long)p;
-        return (unsigned)px[0] | (unsigned)px[1] << 8 | (unsigned)px[2] << 16;
-    });
+    kitty_write(out, width, rows, kitty_wave_index(), (int)(threadIdx.x & 63), pixels_of_rgb8{rgb});
 }
 
 #endif // TRT_UNIT_RENDER

@@ -377,24 +377,93 @@ extern "C" int trt_read_counters(trt_context *ctx, unsigned long long *path_rays
 // ((int)(c*255), TRT.c:1157-1163), the text the emitter makes of those bytes (TRT.c:1142-1172; trt_ansi.h), or the half-block text of
 // them, two owned rows per line of text (trt_ansi_half.h), or those bytes as a kitty graphics-protocol image (trt_kitty.h), or either
 // text in the xterm 256-colour palette (trt_ansi256.h, trt_ansi256_half.h).
-enum Output : int { kDoubles, kBytes, kText, kHalfText, kKittyText, kText256, kHalfText256 };
+enum Output : int { kDoubles, kBytes, kText, kHalfText, kKittyText, kText256, kHalfText256, kOutputs };
 
-static bool is_text(Output kind) { return kind >= kText; }
-
-// bytes of one frame of `rows` rows of `width` pixels
-static size_t frame_bytes(Output kind, int width, int rows)
+// What the launches, the checks and the host entries need of a kind, once: how long a frame of it is, the side no frame of it exceeds,
+// where a host entry stages it and how it words its time; and of a text -- the kinds behind the ordered mean that are neither doubles
+// nor bytes, which keep reduce_samples_kernel and reduce_samples_rgb8_kernel (launch_ordered_mean) -- the two kernels that write it, how
+// many waves its lane map asks for, and the magics its kernels divide by (trt_text_map.h; trt_kitty.h has another lane map and no magics).
+struct OutputKind
 {
-    if (kind == kText)
-        return (size_t)trt_ansi_text_bytes(width, rows);
-    if (kind == kHalfText)
-        return (size_t)trt_ansi_half_text_bytes(width, rows);
-    if (kind == kKittyText)
-        return (size_t)trt_kitty_text_bytes(width, rows);
-    if (kind == kText256)
-        return (size_t)trt_ansi256_text_bytes(width, rows);
-    if (kind == kHalfText256)
-        return (size_t)trt_ansi256_half_text_bytes(width, rows);
-    return (size_t)rows * width * 3 * (kind == kBytes ? 1u : sizeof(double));
+    unsigned long long (*bytes)(int width, long long rows); // of one frame of `rows` rows of `width` pixels
+    int side_max;          // 0: any
+    const char *too_large; // the refusal of a width or a row count above side_max
+    int (*stage)(trt_context *ctx, size_t room, void **d_out); // the context's buffer with room for `room` bytes of it (render_host_as)
+    const char *counted; // print_host_times(): what a host entry says it took its time for, and how many bytes one of them is
+    size_t counted_bytes;
+    trt::TextMeanKernel mean; // null: not a text
+    trt::TextFromRgb8Kernel from_rgb8;
+    unsigned long long (*waves)(unsigned long long address, unsigned long long bytes, bool several);
+    unsigned (*row_magic)(int width), (*width_magic)(int width); // null: the kernels ignore the argument
+};
+
+static unsigned long long doubles_bytes(int width, long long rows) { return (unsigned long long)rows * width * 3 * sizeof(double); }
+static unsigned long long rgb8_bytes(int width, long long rows) { return (unsigned long long)rows * width * 3; }
+
+static int stage_in_framebuffer(trt_context *ctx, size_t room, void **d_out)
+{
+    HIP_TRY(ctx->d_fb.reserve((room + sizeof(double) - 1) / sizeof(double)));
+    *d_out = ctx->d_fb.ptr;
+    return TRT_OK;
+}
+
+template <DeviceBuffer<unsigned char> trt_context::*Buffer>
+static int stage_in(trt_context *ctx, size_t room, void **d_out)
+{
+    HIP_TRY((ctx->*Buffer).reserve(room));
+    *d_out = (ctx->*Buffer).ptr;
+    return TRT_OK;
+}
+
+// A character-cell text's lane map, a wave per Kind().wave_words aligned words: ONE frame has exactly the waves its output address needs,
+// the frames of several the most an alignment needs.  Its rows divide by their length.
+template <trt_text_kind (*Kind)()>
+static unsigned long long text_waves(unsigned long long address, unsigned long long bytes, bool several)
+{
+    return trt_text_waves(Kind(), several ? bytes / 4 : trt_text_split_of(address, bytes).words);
+}
+
+template <trt_text_kind (*Kind)()>
+static unsigned text_row_magic(int width)
+{
+    return trt_text_magic((unsigned long long)trt_text_row_bytes(Kind(), width));
+}
+
+// the kitty image's: a wave per 64 word slots, the tail's among them
+static unsigned long long kitty_waves(unsigned long long address, unsigned long long bytes, bool several)
+{
+    return several ? trt_kitty_waves_most(bytes) : trt_kitty_waves(address, bytes);
+}
+
+// a character-cell text's row: its Format (trt_ansi.hpp) for the kernels, its kind for the lane map and the rows' magic
+template <class Format, trt_text_kind (*Kind)()>
+static OutputKind character_cells(unsigned long long (*bytes)(int, long long), unsigned (*width_magic)(int))
+{
+    return {bytes, 0, nullptr, stage_in<&trt_context::d_text>, "bytes of text", 1, trt::reduce_samples_text_kernel<Format>, trt::text_from_rgb8_kernel<Format>,
+            text_waves<Kind>, text_row_magic<Kind>, width_magic};
+}
+
+static const OutputKind kOutput[kOutputs] = {
+    {doubles_bytes, 0, nullptr, stage_in_framebuffer, "bytes", 1},
+    {rgb8_bytes, 0, nullptr, stage_in<&trt_context::d_rgb8>, "pixels", 3},
+    character_cells<trt::ansi_text, trt_ansi_kind>(trt_ansi_text_bytes, nullptr),
+    character_cells<trt::ansi_half_text, trt_ansi_half_kind>(trt_ansi_half_text_bytes, trt_ansi_half_width_magic),
+    // five digits a side in the image's header
+    {trt_kitty_text_bytes, TRT_KITTY_MAX, "a kitty image of %d x %d exceeds %d", stage_in<&trt_context::d_text>, "bytes of text", 1, trt::reduce_samples_kitty_kernel,
+     trt::kitty_from_rgb8_kernel, kitty_waves, nullptr, nullptr},
+    character_cells<trt::ansi256_text, trt_ansi256_kind>(trt_ansi256_text_bytes, nullptr),
+    character_cells<trt::ansi256_half_text, trt_ansi256_half_kind>(trt_ansi256_half_text_bytes, trt_ansi256_half_width_magic),
+};
+
+static size_t frame_bytes(Output kind, int width, int rows) { return (size_t)kOutput[kind].bytes(width, rows); }
+
+// the kind's side limit on a frame of width x rows: TRT_OK, or the refusal
+static int check_side(Output kind, int width, int rows)
+{
+    const OutputKind &k = kOutput[kind];
+    if (k.side_max && (width > k.side_max || rows > k.side_max))
+        return fail(TRT_ERR_ARGUMENT, k.too_large, width, rows, k.side_max);
+    return TRT_OK;
 }
 
 // what the device entries refuse, for `frames` cameras into one framebuffer of `frames` frames of the rowset
@@ -416,8 +485,9 @@ static int check_render_arguments(const trt_context *ctx, const Camera *cameras,
     if (!ctx->have_scene)
         return fail(TRT_ERR_NO_SCENE, "trt_set_scene has not been called");
     const int local_rows = trt_rowset_rows(rows);
-    if (kind == kKittyText && (rows->width > TRT_KITTY_MAX || local_rows > TRT_KITTY_MAX)) // five digits each in the image's header
-        return fail(TRT_ERR_ARGUMENT, "a kitty image of %d x %d exceeds %d", rows->width, local_rows, TRT_KITTY_MAX);
+    const int rc = check_side(kind, rows->width, local_rows);
+    if (rc)
+        return rc;
     const size_t need = frame_bytes(kind, rows->width, local_rows) * frames;
     if (capacity_bytes < need)
         return fail(TRT_ERR_CAPACITY, "framebuffer of %d frame(s) needs %zu B, %zu given", frames, need, capacity_bytes);
@@ -466,72 +536,26 @@ static trt::FrameView frame_view(const trt_context *ctx, const Camera *camera, c
     return f;
 }
 
-// What the launches of a whole text need of its format (trt_ansi.h, trt_ansi_half.h, trt_ansi256.h, trt_ansi256_half.h): the length,
-// the lane map's kind, and the two kernels that write it.  The kernels' argument lists differ in one place: the half-block texts' take
-// the width's magic behind the row length's.
-struct TextFormat
+// The grid and the magics of one of a text's kernels over `frames` frames of width x rows at `out`: ONE frame's grid has exactly the waves
+// its output address needs, that of several the most an alignment needs.
+struct TextLaunch
 {
-    trt_text_kind kind;
-    unsigned long long (*bytes)(int width, long long rows);
-    unsigned (*width_magic)(int width); // nullptr: the kernels take none
-    const void *reduce_kernel, *from_rgb8_kernel;
+    dim3 grid;
+    unsigned row_magic, width_magic;
 };
 
-static const TextFormat &text_format(Output kind)
+static TextLaunch text_launch(const OutputKind &k, const unsigned char *out, int width, int rows, unsigned frames)
 {
-    static const TextFormat formats[4] = {
-        {trt_ansi_kind(), trt_ansi_text_bytes, nullptr, (const void *)trt::reduce_samples_ansi_kernel, (const void *)trt::ansi_from_rgb8_kernel},
-        {trt_ansi_half_kind(), trt_ansi_half_text_bytes, trt_ansi_half_width_magic, (const void *)trt::reduce_samples_ansi_half_kernel,
-         (const void *)trt::ansi_half_from_rgb8_kernel},
-        {trt_ansi256_kind(), trt_ansi256_text_bytes, nullptr, (const void *)trt::reduce_samples_ansi256_kernel, (const void *)trt::ansi256_from_rgb8_kernel},
-        {trt_ansi256_half_kind(), trt_ansi256_half_text_bytes, trt_ansi256_half_width_magic, (const void *)trt::reduce_samples_ansi256_half_kernel,
-         (const void *)trt::ansi256_half_from_rgb8_kernel}};
-    return formats[kind == kText ? 0 : kind == kHalfText ? 1 : kind == kText256 ? 2 : 3];
-}
-
-// One of a text's kernels over `frames` frames of width x rows at `out`, a wave per kind.wave_words aligned words: ONE frame's grid has
-// exactly the waves its output address needs, that of several the most an alignment needs.  `front`: the kernel's arguments in front of
-// (out, width, rows, row magic[, width magic]), `back`: those behind.
-static void launch_text_kernel(hipStream_t stream, const TextFormat &t, const void *kernel, unsigned frames, std::initializer_list<const void *> front,
-                               unsigned char *out, int width, int rows, std::initializer_list<const void *> back)
-{
-    const unsigned long long bytes = t.bytes(width, rows);
-    const unsigned long long waves = trt_text_waves(t.kind, frames > 1 ? bytes / 4 : trt_text_split_of((unsigned long long)out, bytes).words);
-    unsigned row_magic = trt_text_magic((unsigned long long)trt_text_row_bytes(t.kind, width)), width_magic = t.width_magic ? t.width_magic(width) : 0u;
-    void *args[16];
-    size_t n = 0;
-    for (const void *a : front)
-        args[n++] = const_cast<void *>(a);
-    for (void *a : {(void *)&out, (void *)&width, (void *)&rows, (void *)&row_magic})
-        args[n++] = a;
-    if (t.width_magic)
-        args[n++] = &width_magic;
-    for (const void *a : back)
-        args[n++] = const_cast<void *>(a);
-    (void)hipLaunchKernel(kernel, dim3((unsigned)((waves * 64 + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK), frames), dim3(TRT_REDUCE_BLOCK), args, 0, stream);
-}
-
-// The kitty image's kernels are a launch of their own (trt_kitty.h: another lane map, a wave per 64 word slots, the tail's among them; no
-// magics): over `frames` frames of width x rows at `out`, ONE frame's grid has exactly the waves its address needs, that of several the
-// most an alignment needs.
-static dim3 kitty_grid(const unsigned char *out, int width, int rows, unsigned frames)
-{
-    const unsigned long long bytes = trt_kitty_text_bytes(width, rows);
-    const unsigned long long waves = frames > 1 ? trt_kitty_waves_most(bytes) : trt_kitty_waves((unsigned long long)out, bytes);
-    return dim3((unsigned)((waves * 64 + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK), frames);
+    const unsigned long long waves = k.waves((unsigned long long)out, k.bytes(width, rows), frames > 1);
+    return {dim3((unsigned)((waves * 64 + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK), frames), k.row_magic ? k.row_magic(width) : 0u,
+            k.width_magic ? k.width_magic(width) : 0u};
 }
 
 // the text of a frame that exists as RGB8 bytes: the formatting alone
 static void launch_text_from_rgb8(hipStream_t stream, Output kind, const unsigned char *d_rgb8, int width, int rows, void *d_text)
 {
-    if (kind == kKittyText)
-    {
-        hipLaunchKernelGGL(trt::kitty_from_rgb8_kernel, kitty_grid((const unsigned char *)d_text, width, rows, 1), dim3(TRT_REDUCE_BLOCK), 0, stream, d_rgb8,
-                           (unsigned char *)d_text, width, rows);
-        return;
-    }
-    const TextFormat &t = text_format(kind);
-    launch_text_kernel(stream, t, t.from_rgb8_kernel, 1, {&d_rgb8}, (unsigned char *)d_text, width, rows, {});
+    const TextLaunch t = text_launch(kOutput[kind], (const unsigned char *)d_text, width, rows, 1);
+    hipLaunchKernelGGL(kOutput[kind].from_rgb8, t.grid, dim3(TRT_REDUCE_BLOCK), 0, stream, d_rgb8, (unsigned char *)d_text, width, rows, t.row_magic, t.width_magic);
 }
 
 // `lane_set` 0: the context's stream, queue word 0, d_samples; 1: the alternate stream, its own queue word and scratch
@@ -546,12 +570,13 @@ enum : int { kEntryOpens = 1, kEntryCloses = 2, kEntryWhole = kEntryOpens | kEnt
 static int launch_reference(trt_context *ctx, const RenderPlan &plan, trt::FrameView f, void *out, Output kind, long pixels, hipStream_t stream, int entry)
 {
     const int slot = (int)(ctx->launches % kEventRing);
+    const bool text = kOutput[kind].from_rgb8 != nullptr;
     if (kind != kDoubles)
     {
-        if (ctx->d_fb.capacity < (size_t)pixels * 3 || (is_text(kind) && ctx->d_text_rgb8.capacity < (size_t)pixels * 3))
+        if (ctx->d_fb.capacity < (size_t)pixels * 3 || (text && ctx->d_text_rgb8.capacity < (size_t)pixels * 3))
             HIP_TRY(hipStreamSynchronize(stream)); // a frame in flight may still use the old framebuffer
         HIP_TRY(ctx->d_fb.reserve((size_t)pixels * 3));
-        if (is_text(kind)) // text: the framebuffer's bytes first, in a buffer of the context's
+        if (text) // text: the framebuffer's bytes first, in a buffer of the context's
             HIP_TRY(ctx->d_text_rgb8.reserve((size_t)pixels * 3));
         f.out = ctx->d_fb.ptr;
     }
@@ -571,8 +596,8 @@ static int launch_reference(trt_context *ctx, const RenderPlan &plan, trt::Frame
         HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
     if (kind != kDoubles)
         hipLaunchKernelGGL(trt::quantize_kernel, dim3((unsigned)((pixels * 3 + 255) / 256)), dim3(256), 0, stream, (const double *)f.out, pixels * 3,
-                           is_text(kind) ? ctx->d_text_rgb8.ptr : (unsigned char *)out);
-    if (is_text(kind))
+                           text ? ctx->d_text_rgb8.ptr : (unsigned char *)out);
+    if (text)
         launch_text_from_rgb8(stream, kind, ctx->d_text_rgb8.ptr, f.width, f.local_rows, out);
     if (entry & kEntryCloses)
         HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
@@ -590,32 +615,18 @@ static void launch_ordered_mean(hipStream_t stream, const RenderPlan &plan, cons
     const long values = pixels * 3;
     const dim3 block(TRT_REDUCE_BLOCK);
     const auto blocks = [&](unsigned long long lanes) { return dim3((unsigned)((lanes + TRT_REDUCE_BLOCK - 1) / TRT_REDUCE_BLOCK), frames); };
-    switch (kind)
-    {
-    case kDoubles: // a lane per group of values and one per value the groups leave
+    if (kind == kDoubles) // a lane per group of values and one per value the groups leave
         hipLaunchKernelGGL(trt::reduce_samples_kernel, blocks((unsigned long long)trt_mean_lanes(values)), block, 0, stream, samples, (double *)out, values, f.spp, f.inv_spp, f.queue, plan.grid,
                            plan.block / 64, f.queue_shift);
-        break;
-    case kBytes: // a lane per group of four values and one per value of a frame's head and tail
+    else if (kind == kBytes) // a lane per group of four values and one per value of a frame's head and tail
         hipLaunchKernelGGL(trt::reduce_samples_rgb8_kernel,
                            blocks(frames > 1 ? values / trt::kRgb8Group + 6 : trt::rgb8_lanes(values, trt::rgb8_head((const unsigned char *)out, values))), block, 0,
                            stream, samples, (unsigned char *)out, values, f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
-        break;
-    case kText:
-    case kHalfText:
-    case kText256:
-    case kHalfText256: // a wave per kind.wave_words aligned words
+    else // a text: the waves its lane map asks for
     {
-        const TextFormat &t = text_format(kind);
-        const unsigned waves_per_group = plan.block / 64;
-        launch_text_kernel(stream, t, t.reduce_kernel, frames, {&samples}, (unsigned char *)out, f.width, f.local_rows,
-                           {&f.spp, &f.inv_spp, &f.queue, &plan.grid, &waves_per_group, &f.queue_shift});
-        break;
-    }
-    case kKittyText: // a wave per 64 word slots
-        hipLaunchKernelGGL(trt::reduce_samples_kitty_kernel, kitty_grid((const unsigned char *)out, f.width, f.local_rows, frames), block, 0, stream, samples,
-                           (unsigned char *)out, f.width, f.local_rows, f.spp, f.inv_spp, f.queue, plan.grid, plan.block / 64, f.queue_shift);
-        break;
+        const TextLaunch t = text_launch(kOutput[kind], (const unsigned char *)out, f.width, f.local_rows, frames);
+        hipLaunchKernelGGL(kOutput[kind].mean, t.grid, block, 0, stream, samples, (unsigned char *)out, f.width, f.local_rows, t.row_magic, t.width_magic, f.spp, f.inv_spp,
+                           f.queue, plan.grid, plan.block / 64, f.queue_shift);
     }
 }
 
@@ -809,9 +820,8 @@ extern "C" int trt_render_device_kitty(trt_context *ctx, const Camera *camera, c
 
 extern "C" int trt_kitty_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text)
 {
-    if (width > TRT_KITTY_MAX || rows > TRT_KITTY_MAX)
-        return fail(TRT_ERR_ARGUMENT, "a kitty image of %d x %d exceeds %d", width, rows, TRT_KITTY_MAX);
-    return text_from_rgb8_device(ctx, kKittyText, d_rgb8, width, rows, d_text);
+    const int rc = check_side(kKittyText, width, rows);
+    return rc ? rc : text_from_rgb8_device(ctx, kKittyText, d_rgb8, width, rows, d_text);
 }
 
 extern "C" size_t trt_ansi256_bytes(int width, int rows)
@@ -1130,29 +1140,28 @@ static int render_host_as(trt_context *ctx, const Camera *cameras, int n, bool b
     if (!rowset_valid(rows))
         return fail(TRT_ERR_ARGUMENT, "invalid rowset");
     HIP_TRY(hipSetDevice(ctx->device));
-    if (kind == kKittyText && (rows->width > TRT_KITTY_MAX || trt_rowset_rows(rows) > TRT_KITTY_MAX))
-        return fail(TRT_ERR_ARGUMENT, "a kitty image of %d x %d exceeds %d", rows->width, trt_rowset_rows(rows), TRT_KITTY_MAX);
+    int rc = check_side(kind, rows->width, trt_rowset_rows(rows));
+    if (rc)
+        return rc;
     const size_t bytes = (size_t)n * frame_bytes(kind, rows->width, trt_rowset_rows(rows));
     if (!batch && bytes == 0)
         return TRT_OK;
     const size_t room = std::max<size_t>(bytes, 1);
-    if (kind == kDoubles)
-        HIP_TRY(ctx->d_fb.reserve((room + sizeof(double) - 1) / sizeof(double)));
-    else
-        HIP_TRY((kind == kBytes ? ctx->d_rgb8 : ctx->d_text).reserve(room)); // either text in the context's text buffer
-    void *const d_out = kind == kDoubles ? (void *)ctx->d_fb.ptr : kind == kBytes ? (void *)ctx->d_rgb8.ptr : (void *)ctx->d_text.ptr;
+    void *d_out;
+    rc = kOutput[kind].stage(ctx, room, &d_out);
+    if (rc)
+        return rc;
     HIP_TRY(ctx->h_staging.reserve(room));
     const double t_begin = host_now_ms();
-    const int rc = batch ? render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_out, bytes, kind)
-                         : render_device_on(ctx, cameras, rows, bounce_limit, rays_per_pixel, d_out, bytes, 0, kEntryWhole, kind);
+    rc = batch ? render_device_batch(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_out, bytes, kind)
+               : render_device_on(ctx, cameras, rows, bounce_limit, rays_per_pixel, d_out, bytes, 0, kEntryWhole, kind);
     if (rc || bytes == 0)
         return rc;
     HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     memcpy(host, ctx->h_staging.ptr, bytes);
     if (name && print_host_times())
-        fprintf(stderr, kind == kBytes ? "%s: %.3f ms for %zu pixels\n" : "%s: %.3f ms for %zu bytes of text\n", name, host_now_ms() - t_begin,
-                kind == kBytes ? bytes / 3 : bytes);
+        fprintf(stderr, "%s: %.3f ms for %zu %s\n", name, host_now_ms() - t_begin, bytes / kOutput[kind].counted_bytes, kOutput[kind].counted);
     return TRT_OK;
 }
 
@@ -1406,17 +1415,77 @@ extern "C" size_t trt_ansi_delta_half_capacity(int width, int rows)
     return (size_t)std::max(trt_ansi_half_text_bytes(width, rows), trt_delta_half_bound(width, rows));
 }
 
-// room for any text of the kind: half-block cells or the full text's
-static size_t delta_capacity(bool half, int width, int rows) { return half ? trt_ansi_delta_half_capacity(width, rows) : trt_ansi_delta_capacity(width, rows); }
-
-// the frames a delta text of the kind exists for: TRT_OK, or the refusal
-static int check_delta_size(bool half, int width, int rows)
+// What a kind of MEASURED text -- one whose length depends on the picture, so that the device reports it: the two delta texts and the sixel
+// image (below) -- says of a frame size: whether it has such a text, the refusal where it has none, and the room any text of the size fits.
+struct MeasuredText
 {
-    if (half ? trt_delta_half_size_ok(width, rows) : trt_delta_size_ok(width, rows))
-        return TRT_OK;
-    return half ? fail(TRT_ERR_ARGUMENT, "%d x %d: a half-block delta text has 1 to %d cells per row and 1 to %d text rows", width, rows, TRT_DELTA_HALF_MAX_WIDTH,
-                       TRT_DELTA_HALF_MAX_TEXT_ROWS)
-                : fail(TRT_ERR_ARGUMENT, "%d x %d: a delta text has 1 to %d cells per row and 1 to %d rows", width, rows, TRT_DELTA_MAX_WIDTH, TRT_DELTA_MAX_ROWS);
+    int (*size_ok)(int width, long long rows);
+    const char *no_text; // with the width, the rows and the two limits
+    int max_width, max_rows;
+    size_t (*capacity)(int width, int rows);
+};
+static const MeasuredText kDeltaText[2] = { // by `half`: the full text's cells, half-block cells
+    {trt_delta_size_ok, "%d x %d: a delta text has 1 to %d cells per row and 1 to %d rows", TRT_DELTA_MAX_WIDTH, TRT_DELTA_MAX_ROWS, trt_ansi_delta_capacity},
+    {trt_delta_half_size_ok, "%d x %d: a half-block delta text has 1 to %d cells per row and 1 to %d text rows", TRT_DELTA_HALF_MAX_WIDTH, TRT_DELTA_HALF_MAX_TEXT_ROWS,
+     trt_ansi_delta_half_capacity}};
+static const MeasuredText kSixelText = {trt_sixel_size_ok, "%d x %d: a sixel image has 1 to %d pixels a row and 1 to %d rows", TRT_SIXEL_MAX, TRT_SIXEL_MAX,
+                                        trt_sixel_capacity};
+
+// the frames a text of the kind exists for: TRT_OK, or the refusal
+static int check_measured_size(const MeasuredText &k, int width, int rows)
+{
+    return k.size_ok(width, rows) ? TRT_OK : fail(TRT_ERR_ARGUMENT, k.no_text, width, rows, k.max_width, k.max_rows);
+}
+
+// What the render entries of a measured text refuse before anything is enqueued: what trt_render_device_batch_rgb8 refuses for the n cameras,
+// a size without a text, and a `text` -- the caller's buffer, on the device or on the host -- without room for n texts of the size, which
+// `no_room(need)` words.
+template <class NoRoom>
+static int check_render_measured(const trt_context *ctx, const MeasuredText &k, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                 const void *text, size_t capacity_bytes, const void *bytes, NoRoom no_room)
+{
+    if (!bytes)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    int rc = rowset_valid(rows) ? check_measured_size(k, rows->width, trt_rowset_rows(rows)) : TRT_OK;
+    if (rc)
+        return rc;
+    // the rest as the RGB8 entry checks it, whose frame these sizes let fit
+    rc = check_render_arguments(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, text, (size_t)-1, kBytes);
+    if (rc)
+        return rc;
+    const size_t need = (size_t)n * k.capacity(rows->width, trt_rowset_rows(rows));
+    if (capacity_bytes < need)
+        return no_room(need);
+    return check_batch_tables(ctx, n);
+}
+
+// The copy-out of a measured text's host entries: the n lengths at d_delta_bytes read back and held against `room`, the bytes at d_text
+// (`too_long()` words the refusal), then exactly their sum through pinned staging of `staged(sum)` bytes into `text` -- two transfers
+// whatever n is -- and the lengths into `bytes`.  *sum: what was copied.
+template <class Staged, class TooLong>
+static int copy_out_measured(trt_context *ctx, int n, size_t room, char *text, size_t *bytes, unsigned long long *sum, Staged staged, TooLong too_long)
+{
+    unsigned long long length[TRT_BATCH_MAX] = {};
+    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_delta_bytes.ptr, sizeof length[0] * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(length, ctx->h_staging.ptr, sizeof length[0] * n);
+    *sum = 0;
+    for (int b = 0; b < n; b++)
+    {
+        if (length[b] > room - *sum)
+            return too_long();
+        *sum += length[b];
+    }
+    if (*sum)
+    {
+        HIP_TRY(ctx->h_staging.reserve(staged((size_t)*sum)));
+        HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_text.ptr, (size_t)*sum, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        memcpy(text, ctx->h_staging.ptr, (size_t)*sum);
+    }
+    for (int b = 0; b < n; b++)
+        bytes[b] = (size_t)length[b];
+    return TRT_OK;
 }
 
 // measure, offsets, write on `stream` for the pairs (d_shown, frame 0), (frame 0, frame 1) ... of the n frames at d_frames, of the full text's
@@ -1463,10 +1532,10 @@ static int delta_from_rgb8(trt_context *ctx, bool half, const void *d_shown_rgb8
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
     if (n < 1 || n > TRT_BATCH_MAX)
         return fail(TRT_ERR_ARGUMENT, "a chain has 1 to %d frames, %d given", TRT_BATCH_MAX, n);
-    int rc = check_delta_size(half, width, rows);
+    int rc = check_measured_size(kDeltaText[half], width, rows);
     if (rc)
         return rc;
-    const size_t need = (size_t)n * delta_capacity(half, width, rows);
+    const size_t need = (size_t)n * kDeltaText[half].capacity(width, rows);
     if (capacity_bytes < need)
         return fail(TRT_ERR_CAPACITY, "%d delta text(s) of %d x %d need room for %zu B, %zu given", n, width, rows, need, capacity_bytes);
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1544,24 +1613,13 @@ extern "C" int trt_ansi_delta_reset(trt_context *ctx)
     return TRT_OK;
 }
 
-// what the render entries refuse before anything is enqueued: what trt_render_device_batch_rgb8 refuses for the n cameras, and a `text` --
-// the caller's buffer, on the device or on the host -- without room for n texts
+// check_render_measured for n delta texts of the kind
 static int check_render_delta(const trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, const void *text,
                               size_t capacity_bytes, const void *bytes, bool half)
 {
-    if (!bytes)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    int rc = rowset_valid(rows) ? check_delta_size(half, rows->width, trt_rowset_rows(rows)) : TRT_OK;
-    if (rc)
-        return rc;
-    // the rest as the RGB8 entry checks it, whose frame these sizes let fit
-    rc = check_render_arguments(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, text, (size_t)-1, kBytes);
-    if (rc)
-        return rc;
-    const size_t need = (size_t)n * delta_capacity(half, rows->width, trt_rowset_rows(rows));
-    if (capacity_bytes < need)
+    return check_render_measured(ctx, kDeltaText[half], cameras, n, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, [&](size_t need) {
         return fail(TRT_ERR_CAPACITY, "%d text(s) of %d x %d owned rows need room for %zu B, %zu given", n, rows->width, trt_rowset_rows(rows), need, capacity_bytes);
-    return check_batch_tables(ctx, n);
+    });
 }
 
 static bool same_rowset(const trt_rowset &a, const trt_rowset &b)
@@ -1652,7 +1710,7 @@ static int render_host_delta(trt_context *ctx, const Camera *cameras, int n, boo
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t room = (size_t)n * delta_capacity(half, rows->width, trt_rowset_rows(rows));
+    const size_t room = (size_t)n * kDeltaText[half].capacity(rows->width, trt_rowset_rows(rows));
     if (ctx->d_text.capacity < room || ctx->d_delta_bytes.capacity < (size_t)n)
         HIP_TRY(hipStreamSynchronize(ctx->stream)); // a text in flight may still be written to the old buffers
     HIP_TRY(ctx->d_text.reserve(room));
@@ -1664,33 +1722,14 @@ static int render_host_delta(trt_context *ctx, const Camera *cameras, int n, boo
     rc = render_device_delta(ctx, cameras, n, batch, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, room, ctx->d_delta_bytes.ptr, half);
     if (rc)
         return rc;
-    unsigned long long length[TRT_BATCH_MAX] = {}, sum = 0;
-    rc = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_delta_bytes.ptr, sizeof length[0] * n, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        memcpy(length, ctx->h_staging.ptr, sizeof length[0] * n);
-        for (int b = 0; b < n; b++)
-        {
-            if (length[b] > room - sum)
-                return fail(TRT_ERR_CAPACITY, "%d text(s) of more than %zu B", n, room);
-            sum += length[b];
-        }
-        if (sum)
-        {
-            HIP_TRY(ctx->h_staging.reserve((size_t)sum));
-            HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_text.ptr, (size_t)sum, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            memcpy(text, ctx->h_staging.ptr, (size_t)sum);
-        }
-        return TRT_OK;
-    }();
+    unsigned long long sum = 0;
+    rc = copy_out_measured(ctx, n, room, text, bytes, &sum, [](size_t copied) { return copied; },
+                           [&] { return fail(TRT_ERR_CAPACITY, "%d text(s) of more than %zu B", n, room); });
     if (rc)
     { // the host did not get the texts: the terminal does not show these frames
         ctx->shown_valid = false;
         return rc;
     }
-    for (int b = 0; b < n; b++)
-        bytes[b] = (size_t)length[b];
     if (print_host_times())
         fprintf(stderr, "%s: %.3f ms for %d text(s) of %llu bytes\n", name, host_now_ms() - t_begin, n, sum);
     return TRT_OK;
@@ -1748,18 +1787,11 @@ static int launch_sixel(trt_context *ctx, hipStream_t stream, const unsigned cha
     return TRT_OK;
 }
 
-static int check_sixel_size(int width, int rows)
-{
-    if (trt_sixel_size_ok(width, rows))
-        return TRT_OK;
-    return fail(TRT_ERR_ARGUMENT, "%d x %d: a sixel image has 1 to %d pixels a row and 1 to %d rows", width, rows, TRT_SIXEL_MAX, TRT_SIXEL_MAX);
-}
-
 extern "C" int trt_sixel_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, int rows, void *d_text, size_t capacity_bytes, unsigned long long *d_bytes)
 {
     if (!ctx || !d_rgb8 || !d_text || !d_bytes)
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    const int rc = check_sixel_size(width, rows);
+    const int rc = check_measured_size(kSixelText, width, rows);
     if (rc)
         return rc;
     const size_t need = trt_sixel_capacity(width, rows);
@@ -1769,29 +1801,19 @@ extern "C" int trt_sixel_from_rgb8_device(trt_context *ctx, const void *d_rgb8, 
     return launch_sixel(ctx, ctx->stream, (const unsigned char *)d_rgb8, width, rows, d_text, d_bytes);
 }
 
-// what the render entries refuse before anything is enqueued: what trt_render_device_rgb8 refuses, a size without an image, and a `text` --
-// the caller's buffer, on the device or on the host -- without room for any image of the size
-static int check_render_sixel(const trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, const void *text,
+// check_render_measured for the one image
+static int check_sixel_render(const trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, const void *text,
                               size_t capacity_bytes, const void *bytes)
 {
-    if (!bytes)
-        return fail(TRT_ERR_ARGUMENT, "NULL argument");
-    int rc = rowset_valid(rows) ? check_sixel_size(rows->width, trt_rowset_rows(rows)) : TRT_OK;
-    if (rc)
-        return rc;
-    rc = check_render_arguments(ctx, camera, 1, rows, bounce_limit, rays_per_pixel, text, (size_t)-1, kBytes);
-    if (rc)
-        return rc;
-    const size_t need = trt_sixel_capacity(rows->width, trt_rowset_rows(rows));
-    if (capacity_bytes < need)
+    return check_render_measured(ctx, kSixelText, camera, 1, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, [&](size_t need) {
         return fail(TRT_ERR_CAPACITY, "a sixel image of %d x %d owned rows needs room for %zu B, %zu given", rows->width, trt_rowset_rows(rows), need, capacity_bytes);
-    return TRT_OK;
+    });
 }
 
 extern "C" int trt_render_device_sixel(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
                                        size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    int rc = check_render_sixel(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes);
+    int rc = check_sixel_render(ctx, camera, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1813,7 +1835,7 @@ extern "C" int trt_render_device_sixel(trt_context *ctx, const Camera *camera, c
 extern "C" int trt_render_host_sixel(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
                                      size_t capacity_bytes, size_t *bytes)
 {
-    int rc = check_render_sixel(ctx, camera, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes);
+    int rc = check_sixel_render(ctx, camera, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1827,22 +1849,18 @@ extern "C" int trt_render_host_sixel(trt_context *ctx, const Camera *camera, con
     rc = trt_render_device_sixel(ctx, camera, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, room, ctx->d_delta_bytes.ptr);
     if (rc)
         return rc;
-    unsigned long long length = 0;
-    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_delta_bytes.ptr, sizeof length, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    memcpy(&length, ctx->h_staging.ptr, sizeof length);
-    if (length > room)
-        return fail(TRT_ERR_CAPACITY, "an image of more than %zu B", room);
     // Pinned staging grows with the images' lengths, not to the capacity -- 240 colours in every band are 83 MB at 1920x1080 and rare -- and
     // in steps of a power of two, so that a moving picture whose images grow does not allocate pinned memory frame after frame
-    size_t staged = 4096;
-    while (staged < (size_t)length)
-        staged *= 2;
-    HIP_TRY(ctx->h_staging.reserve(std::min(staged, std::max(room, sizeof length))));
-    HIP_TRY(hipMemcpyAsync(ctx->h_staging.ptr, ctx->d_text.ptr, (size_t)length, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    memcpy(text, ctx->h_staging.ptr, (size_t)length);
-    *bytes = (size_t)length;
+    const auto staged = [&](size_t length) {
+        size_t bytes = 4096;
+        while (bytes < length)
+            bytes *= 2;
+        return std::min(bytes, std::max(room, sizeof(unsigned long long)));
+    };
+    unsigned long long length = 0;
+    rc = copy_out_measured(ctx, 1, room, text, bytes, &length, staged, [&] { return fail(TRT_ERR_CAPACITY, "an image of more than %zu B", room); });
+    if (rc)
+        return rc;
     if (print_host_times())
         fprintf(stderr, "trt_render_host_sixel: %.3f ms for an image of %llu bytes\n", host_now_ms() - t_begin, length);
     return TRT_OK;

@@ -464,125 +464,121 @@ class Context:
             _check(int(got))
         return dict(zip(("cells", "list_bits", "pool_words", "enabled"), [int(x) for x in info])), cells[:got], pool
 
-    def render_device(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
+    # The entries of a kind whose length the frame's size fixes -- doubles, bytes, the character-cell texts, the kitty image -- have four call
+    # shapes and a fifth for the formatting alone: one helper each, which takes the entry's name.  `frame(width, owned rows)`: the shape of one
+    # frame of the kind in host memory.
+
+    @staticmethod
+    def _camera_batch(cameras):
+        cams = np.ascontiguousarray(cameras, dtype=np.float64)
+        if cams.ndim != 2 or cams.shape[1] != 15:
+            raise ValueError("cameras: float64 [n, 15] (Camera, TRT.c:178-184)")
+        return cams
+
+    def _render_device(self, entry, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
         cam = camera_struct(camera_array)
-        _check(lib().trt_render_device(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel,
-                                       _VP(device_ptr), capacity_bytes))
+        _check(getattr(lib(), entry)(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, _VP(device_ptr), capacity_bytes))
+
+    def _render_host(self, entry, frame, camera_array, rows, bounce_limit, rays_per_pixel, dtype=np.uint8):
+        out = np.zeros(frame(rows.width, lib().trt_rowset_rows(C.byref(rows))), dtype=dtype)
+        cam = camera_struct(camera_array)
+        _check(getattr(lib(), entry)(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data))
+        return out
+
+    def _render_device_batch(self, entry, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
+        cams = self._camera_batch(cameras)
+        _check(getattr(lib(), entry)(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel, _VP(device_ptr), capacity_bytes))
+
+    def _render_host_batch(self, entry, frame, cameras, rows, bounce_limit, rays_per_pixel, dtype=np.uint8):
+        cams = self._camera_batch(cameras)
+        out = np.zeros((cams.shape[0], *np.atleast_1d(frame(rows.width, lib().trt_rowset_rows(C.byref(rows))))), dtype=dtype)
+        _check(getattr(lib(), entry)(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data))
+        return out
+
+    def _text_from_rgb8(self, entry, rgb_ptr, width, rows, text_ptr):
+        _check(getattr(lib(), entry)(self._h, _VP(rgb_ptr), width, rows, _VP(text_ptr)))
+
+    def render_device(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
+        self._render_device("trt_render_device", camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes)
 
     def render_device_rgb8(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
         """the frame as the emitter's bytes in device memory, 3 per pixel at any alignment, written by the ordered-mean pass itself
         (trt_render_device_rgb8)"""
-        cam = camera_struct(camera_array)
-        _check(lib().trt_render_device_rgb8(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel,
-                                            _VP(device_ptr), capacity_bytes))
+        self._render_device("trt_render_device_rgb8", camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes)
 
     def quantize_device(self, device_ptr, num_pixels, rgb_ptr):
         _check(lib().trt_quantize_device(self._h, _VP(device_ptr), num_pixels, _VP(rgb_ptr)))
 
     def render_host(self, camera_array, rows, bounce_limit, rays_per_pixel):
-        n = lib().trt_rowset_rows(C.byref(rows))
-        out = np.zeros((n, rows.width, 3), dtype=np.float64)
-        cam = camera_struct(camera_array)
-        _check(lib().trt_render_host(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel,
-                                     out.ctypes.data))
-        return out
+        return self._render_host("trt_render_host", _pixels, camera_array, rows, bounce_limit, rays_per_pixel, dtype=np.float64)
 
     def render_host_rgb8(self, camera_array, rows, bounce_limit, rays_per_pixel):
         """the frame as the emitter's bytes, (int)(c*255) done on the device: uint8 [rows, width, 3] (trt_render_host_rgb8)"""
-        n = lib().trt_rowset_rows(C.byref(rows))
-        out = np.zeros((n, rows.width, 3), dtype=np.uint8)
-        cam = camera_struct(camera_array)
-        _check(lib().trt_render_host_rgb8(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data))
-        return out
+        return self._render_host("trt_render_host_rgb8", _pixels, camera_array, rows, bounce_limit, rays_per_pixel)
 
     def render_device_ansi(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
         """the frame as the terminal's text in device memory, ansi_bytes(width, owned rows) bytes at any alignment, formatted by the
         ordered-mean pass itself (trt_render_device_ansi)"""
-        cam = camera_struct(camera_array)
-        _check(lib().trt_render_device_ansi(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel,
-                                            _VP(device_ptr), capacity_bytes))
+        self._render_device("trt_render_device_ansi", camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes)
 
     def render_host_ansi(self, camera_array, rows, bounce_limit, rays_per_pixel):
         """the frame as the terminal's text, formatted on the device: uint8 [ansi_bytes(width, owned rows)] (trt_render_host_ansi)"""
-        out = np.zeros(ansi_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows))), dtype=np.uint8)
-        cam = camera_struct(camera_array)
-        _check(lib().trt_render_host_ansi(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data))
-        return out
+        return self._render_host("trt_render_host_ansi", ansi_bytes, camera_array, rows, bounce_limit, rays_per_pixel)
 
     def ansi_from_rgb8(self, rgb_ptr, width, rows, text_ptr):
         """the text of a width x rows frame of RGB8 bytes in device memory, at text_ptr (trt_ansi_from_rgb8_device)"""
-        _check(lib().trt_ansi_from_rgb8_device(self._h, _VP(rgb_ptr), width, rows, _VP(text_ptr)))
+        self._text_from_rgb8("trt_ansi_from_rgb8_device", rgb_ptr, width, rows, text_ptr)
 
     def render_device_ansi_half(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
         """the frame as the half-block text in device memory, two owned rows per line of text: ansi_half_bytes(width, owned rows) bytes at
         any alignment, formatted by the ordered-mean pass itself (trt_render_device_ansi_half)"""
-        cam = camera_struct(camera_array)
-        _check(lib().trt_render_device_ansi_half(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel,
-                                                 _VP(device_ptr), capacity_bytes))
+        self._render_device("trt_render_device_ansi_half", camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes)
 
     def render_host_ansi_half(self, camera_array, rows, bounce_limit, rays_per_pixel):
         """the same into host memory: uint8 [ansi_half_bytes(width, owned rows)] (trt_render_host_ansi_half)"""
-        out = np.zeros(ansi_half_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows))), dtype=np.uint8)
-        cam = camera_struct(camera_array)
-        _check(lib().trt_render_host_ansi_half(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data))
-        return out
+        return self._render_host("trt_render_host_ansi_half", ansi_half_bytes, camera_array, rows, bounce_limit, rays_per_pixel)
 
     def ansi_half_from_rgb8(self, rgb_ptr, width, rows, text_ptr):
         """the half-block text of a width x rows frame of RGB8 bytes in device memory, at text_ptr (trt_ansi_half_from_rgb8_device)"""
-        _check(lib().trt_ansi_half_from_rgb8_device(self._h, _VP(rgb_ptr), width, rows, _VP(text_ptr)))
+        self._text_from_rgb8("trt_ansi_half_from_rgb8_device", rgb_ptr, width, rows, text_ptr)
 
     def render_device_kitty(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
         """the frame as a kitty graphics-protocol image in device memory: kitty_bytes(width, owned rows) bytes at any alignment, formatted
         by the ordered-mean pass itself (trt_render_device_kitty)"""
-        cam = camera_struct(camera_array)
-        _check(lib().trt_render_device_kitty(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, _VP(device_ptr), capacity_bytes))
+        self._render_device("trt_render_device_kitty", camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes)
 
     def render_host_kitty(self, camera_array, rows, bounce_limit, rays_per_pixel):
         """the same into host memory: uint8 [kitty_bytes(width, owned rows)] (trt_render_host_kitty)"""
-        out = np.zeros(kitty_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows))), dtype=np.uint8)
-        cam = camera_struct(camera_array)
-        _check(lib().trt_render_host_kitty(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data))
-        return out
+        return self._render_host("trt_render_host_kitty", kitty_bytes, camera_array, rows, bounce_limit, rays_per_pixel)
 
     def kitty_from_rgb8(self, rgb_ptr, width, rows, text_ptr):
         """the kitty image of a width x rows frame of RGB8 bytes in device memory, at text_ptr (trt_kitty_from_rgb8_device)"""
-        _check(lib().trt_kitty_from_rgb8_device(self._h, _VP(rgb_ptr), width, rows, _VP(text_ptr)))
+        self._text_from_rgb8("trt_kitty_from_rgb8_device", rgb_ptr, width, rows, text_ptr)
 
     def render_batch_kitty(self, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
         """cameras[n, 15] as kitty images in device memory; frame b at device_ptr + b * kitty_bytes(width, owned rows)
         (trt_render_device_batch_kitty)"""
-        cams = self._camera_batch(cameras)
-        _check(lib().trt_render_device_batch_kitty(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
-                                                   _VP(device_ptr), capacity_bytes))
+        self._render_device_batch("trt_render_device_batch_kitty", cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes)
 
     def render_host_batch_kitty(self, cameras, rows, bounce_limit, rays_per_pixel):
         """the same into host memory: uint8 [n, kitty_bytes(width, owned rows)] (trt_render_host_batch_kitty)"""
-        cams = self._camera_batch(cameras)
-        out = np.zeros((cams.shape[0], kitty_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows)))), dtype=np.uint8)
-        _check(lib().trt_render_host_batch_kitty(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
-                                                 out.ctypes.data))
-        return out
+        return self._render_host_batch("trt_render_host_batch_kitty", kitty_bytes, cameras, rows, bounce_limit, rays_per_pixel)
 
     # the texts in the xterm 256-colour palette come in the same two kinds of cell; `half` chooses the half-block entry of each pair
 
     def render_device_ansi256(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, half=False):
         """the frame as the 256-colour text in device memory: ansi256_bytes(width, owned rows, half) bytes at any alignment, mapped to the
         palette and formatted by the ordered-mean pass itself (trt_render_device_ansi256, trt_render_device_ansi256_half)"""
-        cam = camera_struct(camera_array)
-        _check(getattr(lib(), "trt_render_device_ansi256" + _half(half))(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, _VP(device_ptr),
-                                                                         capacity_bytes))
+        self._render_device("trt_render_device_ansi256" + _half(half), camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes)
 
     def render_host_ansi256(self, camera_array, rows, bounce_limit, rays_per_pixel, half=False):
         """the same into host memory: uint8 [ansi256_bytes(width, owned rows, half)] (trt_render_host_ansi256, trt_render_host_ansi256_half)"""
-        out = np.zeros(ansi256_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows)), half), dtype=np.uint8)
-        cam = camera_struct(camera_array)
-        _check(getattr(lib(), "trt_render_host_ansi256" + _half(half))(self._h, C.byref(cam), C.byref(rows), bounce_limit, rays_per_pixel, out.ctypes.data))
-        return out
+        return self._render_host("trt_render_host_ansi256" + _half(half), functools.partial(ansi256_bytes, half=half), camera_array, rows, bounce_limit, rays_per_pixel)
 
     def ansi256_from_rgb8(self, rgb_ptr, width, rows, text_ptr, half=False):
         """the 256-colour text of a width x rows frame of RGB8 bytes in device memory, at text_ptr (trt_ansi256_from_rgb8_device,
         trt_ansi256_half_from_rgb8_device)"""
-        _check(getattr(lib(), "trt_ansi256" + _half(half) + "_from_rgb8_device")(self._h, _VP(rgb_ptr), width, rows, _VP(text_ptr)))
+        self._text_from_rgb8("trt_ansi256" + _half(half) + "_from_rgb8_device", rgb_ptr, width, rows, text_ptr)
 
     def xterm256_from_rgb8(self, rgb_ptr, num_pixels, index_ptr):
         """the palette index 16..255 of each of num_pixels pixels of RGB8 bytes in device memory, a byte each at index_ptr
@@ -592,18 +588,12 @@ class Context:
     def render_batch_ansi256(self, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, half=False):
         """cameras[n, 15] as 256-colour texts in device memory; frame b at device_ptr + b * ansi256_bytes(width, owned rows, half)
         (trt_render_device_batch_ansi256, trt_render_device_batch_ansi256_half)"""
-        cams = self._camera_batch(cameras)
-        _check(getattr(lib(), "trt_render_device_batch_ansi256" + _half(half))(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit,
-                                                                               rays_per_pixel, _VP(device_ptr), capacity_bytes))
+        self._render_device_batch("trt_render_device_batch_ansi256" + _half(half), cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes)
 
     def render_host_batch_ansi256(self, cameras, rows, bounce_limit, rays_per_pixel, half=False):
         """the same into host memory: uint8 [n, ansi256_bytes(width, owned rows, half)] (trt_render_host_batch_ansi256,
         trt_render_host_batch_ansi256_half)"""
-        cams = self._camera_batch(cameras)
-        out = np.zeros((cams.shape[0], ansi256_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows)), half)), dtype=np.uint8)
-        _check(getattr(lib(), "trt_render_host_batch_ansi256" + _half(half))(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit,
-                                                                             rays_per_pixel, out.ctypes.data))
-        return out
+        return self._render_host_batch("trt_render_host_batch_ansi256" + _half(half), functools.partial(ansi256_bytes, half=half), cameras, rows, bounce_limit, rays_per_pixel)
 
     # the delta entries come in two kinds of cell, the full text's and half-block cells: each pair goes through one helper that takes the entry's name
 
@@ -687,70 +677,39 @@ class Context:
         buffer of sixel_capacity bytes to reuse"""
         return self._render_host_delta("trt_render_host_sixel", sixel_capacity, camera_array, rows, bounce_limit, rays_per_pixel, out)
 
-    @staticmethod
-    def _camera_batch(cameras):
-        cams = np.ascontiguousarray(cameras, dtype=np.float64)
-        if cams.ndim != 2 or cams.shape[1] != 15:
-            raise ValueError("cameras: float64 [n, 15] (Camera, TRT.c:178-184)")
-        return cams
-
     def render_device_batch(self, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
         """cameras[n, 15] of the current scene in one call; frame b at device_ptr + b * rows * width * 24 (trt_render_device_batch)"""
-        cams = self._camera_batch(cameras)
-        _check(lib().trt_render_device_batch(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
-                                             _VP(device_ptr), capacity_bytes))
+        self._render_device_batch("trt_render_device_batch", cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes)
 
     def render_host_batch(self, cameras, rows, bounce_limit, rays_per_pixel):
         """the same into host memory: float64 [n, rows, width, 3] (trt_render_host_batch)"""
-        cams = self._camera_batch(cameras)
-        out = np.zeros((cams.shape[0], lib().trt_rowset_rows(C.byref(rows)), rows.width, 3), dtype=np.float64)
-        _check(lib().trt_render_host_batch(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
-                                           out.ctypes.data))
-        return out
+        return self._render_host_batch("trt_render_host_batch", _pixels, cameras, rows, bounce_limit, rays_per_pixel, dtype=np.float64)
 
     def render_batch_rgb8(self, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
         """cameras[n, 15] as the emitter's bytes in device memory; frame b at device_ptr + b * rows * width * 3 (trt_render_device_batch_rgb8)"""
-        cams = self._camera_batch(cameras)
-        _check(lib().trt_render_device_batch_rgb8(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
-                                                  _VP(device_ptr), capacity_bytes))
+        self._render_device_batch("trt_render_device_batch_rgb8", cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes)
 
     def render_host_batch_rgb8(self, cameras, rows, bounce_limit, rays_per_pixel):
         """the same into host memory: uint8 [n, rows, width, 3] (trt_render_host_batch_rgb8)"""
-        cams = self._camera_batch(cameras)
-        out = np.zeros((cams.shape[0], lib().trt_rowset_rows(C.byref(rows)), rows.width, 3), dtype=np.uint8)
-        _check(lib().trt_render_host_batch_rgb8(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
-                                                out.ctypes.data))
-        return out
+        return self._render_host_batch("trt_render_host_batch_rgb8", _pixels, cameras, rows, bounce_limit, rays_per_pixel)
 
     def render_batch_ansi(self, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
         """cameras[n, 15] as the terminal's text in device memory; frame b at device_ptr + b * ansi_bytes(width, owned rows)
         (trt_render_device_batch_ansi)"""
-        cams = self._camera_batch(cameras)
-        _check(lib().trt_render_device_batch_ansi(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
-                                                  _VP(device_ptr), capacity_bytes))
+        self._render_device_batch("trt_render_device_batch_ansi", cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes)
 
     def render_host_batch_ansi(self, cameras, rows, bounce_limit, rays_per_pixel):
         """the same into host memory: uint8 [n, ansi_bytes(width, owned rows)] (trt_render_host_batch_ansi)"""
-        cams = self._camera_batch(cameras)
-        out = np.zeros((cams.shape[0], ansi_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows)))), dtype=np.uint8)
-        _check(lib().trt_render_host_batch_ansi(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
-                                                out.ctypes.data))
-        return out
+        return self._render_host_batch("trt_render_host_batch_ansi", ansi_bytes, cameras, rows, bounce_limit, rays_per_pixel)
 
     def render_batch_ansi_half(self, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes):
         """cameras[n, 15] as the half-block text in device memory; frame b at device_ptr + b * ansi_half_bytes(width, owned rows)
         (trt_render_device_batch_ansi_half)"""
-        cams = self._camera_batch(cameras)
-        _check(lib().trt_render_device_batch_ansi_half(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
-                                                       _VP(device_ptr), capacity_bytes))
+        self._render_device_batch("trt_render_device_batch_ansi_half", cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes)
 
     def render_host_batch_ansi_half(self, cameras, rows, bounce_limit, rays_per_pixel):
         """the same into host memory: uint8 [n, ansi_half_bytes(width, owned rows)] (trt_render_host_batch_ansi_half)"""
-        cams = self._camera_batch(cameras)
-        out = np.zeros((cams.shape[0], ansi_half_bytes(rows.width, lib().trt_rowset_rows(C.byref(rows)))), dtype=np.uint8)
-        _check(lib().trt_render_host_batch_ansi_half(self._h, cams.ctypes.data, cams.shape[0], C.byref(rows), bounce_limit, rays_per_pixel,
-                                                     out.ctypes.data))
-        return out
+        return self._render_host_batch("trt_render_host_batch_ansi_half", ansi_half_bytes, cameras, rows, bounce_limit, rays_per_pixel)
 
     # the batch forms of the delta entries, of both kinds of cell: n texts back to back, one helper per pair of entries
 
@@ -986,6 +945,11 @@ def kitty_bytes(width, rows):
 
 def _half(half):
     return "_half" if half else ""
+
+
+def _pixels(width, rows):
+    """the shape of a frame of pixels in host memory, as doubles or as the emitter's bytes"""
+    return rows, width, 3
 
 
 def ansi256_bytes(width, rows, half=False):

@@ -6,6 +6,7 @@ import re
 
 import numpy as np
 
+from support import GUARD, STORE, DeviceBytes, same_text  # noqa: F401 -- the 256-colour tests take the scaffold from here
 from terminalraytracer_amd import host
 
 HOME, END = b"\033[0;0H", b"\033[0m\n"
@@ -13,7 +14,6 @@ CELL = {False: re.compile(rb"\033\[48;5;(\d{3})m  "), True: re.compile(rb"\033\[
 CELL_BYTES = {False: 13, True: 23}
 WIDTHS = (1, 2, 3, 5, 40, 55, 56, 57, 58, 59, 60, 61, 63, 64, 65, 67, 130)
 ROWS = (1, 2, 3, 13)
-GUARD, STORE = 64, 4
 
 
 def length(w, h, half):
@@ -89,36 +89,6 @@ def edge_frame(w, h, seed):
     return rgb
 
 
-class DeviceBytes:
-    """n bytes of device memory that start `offset` bytes behind a 4-aligned address, GUARD bytes of 0xA5 in front and behind; the n bytes
-    themselves hold 0xA5 too, or, `raw`, whatever the allocation held"""
-
-    def __init__(self, n, offset=0, raw=False):
-        import torch
-        self.n, self.start = n, GUARD + offset
-        size = GUARD + STORE + n + GUARD
-        if raw:
-            self.buf = torch.empty(size, dtype=torch.uint8, device="cuda:0")
-            self.buf[:self.start] = 0xA5
-            self.buf[self.start + n:] = 0xA5
-        else:
-            self.buf = torch.full((size,), 0xA5, dtype=torch.uint8, device="cuda:0")
-        assert self.buf.data_ptr() % STORE == 0
-        torch.cuda.synchronize()  # the fill is on torch's stream, the render on the context's
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + self.start
-
-    def read(self, ctx, what=""):
-        """the n bytes, once every byte outside them has been seen unchanged"""
-        ctx.synchronize()
-        got = self.buf.cpu().numpy()
-        outside = np.concatenate([got[:self.start], got[self.start + self.n:]])
-        assert outside.size >= 2 * GUARD and (outside == 0xA5).all(), f"{what}: {int((outside != 0xA5).sum())} bytes outside the text were written"
-        return got[self.start:self.start + self.n].copy()
-
-
 def upload_odd(rgb):
     """a frame's bytes in device memory one byte behind an aligned address: (tensor to keep alive, pointer)"""
     import torch
@@ -128,12 +98,3 @@ def upload_odd(rgb):
     torch.cuda.synchronize()
     return src, src.data_ptr() + 1
 
-
-def same_text(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == np.uint8 and got.shape == want.shape, (what, got.dtype, got.shape, want.shape)
-    wrong = got != want
-    if wrong.any():
-        at = int(np.argmax(wrong.reshape(-1)))
-        raise AssertionError(f"{what}: {int(wrong.sum())} of {wrong.size} bytes differ from the emitter's, the first at {at}: "
-                             f"{bytes(got.reshape(-1)[max(at - 8, 0):at + 8])!r} for {bytes(want.reshape(-1)[max(at - 8, 0):at + 8])!r}")

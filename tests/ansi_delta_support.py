@@ -12,6 +12,7 @@ import re
 import numpy as np
 
 import support as T
+from support import GUARD, anim_cameras, owned_rows  # noqa: F401 -- the delta tests take them from here
 from terminalraytracer_amd import hip, host
 from terminalraytracer_amd import scenes as S
 
@@ -146,13 +147,6 @@ def pair(family, w, rows, seed=0):
 
 # ---- the oracle's orbit ----
 
-def anim_cameras(indices, w, h):
-    d = np.load(os.path.join(T.GOLDEN, "cameras_anim.npz"))
-    cams = d["camera"][list(indices)].copy()
-    cams[:, 13] = 5 * float(w) / float(h)
-    return cams
-
-
 @functools.lru_cache(maxsize=None)
 def scene(kind, sky="synth"):
     cam = anim_cameras([0], 160, 48)[0]
@@ -181,7 +175,6 @@ def moved_scene(sc):
 
 # ---- the GPU tests' harness, for both kinds of cell ----
 
-GUARD = 64
 SENTINEL = 0x5A5A5A5A5A5A5A5A
 W, HEIGHT, B, SPP = 160, 48, 4, 10
 
@@ -237,14 +230,7 @@ class Room:
         return got[self.start:self.start + n].copy()
 
 
-def same_text(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == np.uint8 and got.size == want.size, f"{what}: {got.size} bytes for {want.size}"
-    wrong = got != want
-    if wrong.any():
-        at = int(np.argmax(wrong))
-        raise AssertionError(f"{what}: {int(wrong.sum())} of {wrong.size} bytes differ from the host's, the first at {at}: "
-                             f"{bytes(got[max(at - 8, 0):at + 8])!r} for {bytes(want[max(at - 8, 0):at + 8])!r}")
+same_text = functools.partial(T.same_text, whose="the host's")
 
 
 def at_odd_address(frame, behind=None):
@@ -269,10 +255,6 @@ def device_delta(ctx, from_rgb8, capacity, shown, nxt, offset=0, what="", trap=F
     room = Room(capacity(w, rows), offset)
     from_rgb8(ctx, pa, pb, w, rows, room.ptr, room.capacity, room.length_ptr)
     return room.text(ctx, what)
-
-
-def owned_rows(rows):
-    return hip.lib().trt_rowset_rows(C.byref(rows))
 
 
 def frames_of(scene_kind, indices, rows=None, b=B, h=HEIGHT):

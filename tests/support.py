@@ -976,3 +976,72 @@ def light_list_scene(kind, K, p, wide, unsure=False, total=None):
     scene = S.SceneData(directed_spheres(centres, radii), S.demo_ground(), dl, pl, bench_camera(24, 16), sky("synth"))
     rays = {k: np.array([v[0], gy + 0.05, v[2], 0.0, -1.0, 0.0]) for k, v in (("main", o), ("other", other), ("over", over))}
     return scene, rays, index[0]
+
+
+# ---- the scaffold of the tests of the whole-frame outputs: the orbit's cameras, device buffers with guards, byte-for-byte comparisons ----
+
+GUARD = 64   # bytes of 0xA5 either side of every device byte buffer
+STORE = 4    # the widest store a text pass uses: an aligned 32-bit word
+
+
+def anim_cameras(indices, w, h):
+    d = np.load(os.path.join(GOLDEN, "cameras_anim.npz"))
+    cams = d["camera"][list(indices)].copy()
+    cams[:, 13] = 5 * float(w) / float(h)
+    return cams
+
+
+def owned_rows(rows):
+    return hip.lib().trt_rowset_rows(C.byref(rows))
+
+
+class DeviceBytes:
+    """n bytes of device memory that start `offset` bytes behind a 4-aligned address, GUARD bytes of 0xA5 in front and behind; the n bytes
+    themselves hold 0xA5 too, or, `raw`, whatever the allocation held"""
+
+    def __init__(self, n, offset=0, raw=False):
+        import torch
+        self.n, self.start = n, GUARD + offset
+        size = GUARD + STORE + n + GUARD
+        if raw:
+            self.buf = torch.empty(size, dtype=torch.uint8, device="cuda:0")
+            self.buf[:self.start] = 0xA5
+            self.buf[self.start + n:] = 0xA5
+        else:
+            self.buf = torch.full((size,), 0xA5, dtype=torch.uint8, device="cuda:0")
+        assert self.buf.data_ptr() % STORE == 0 and GUARD % STORE == 0
+        torch.cuda.synchronize()  # the fill is on torch's stream, the render on the context's
+
+    @property
+    def ptr(self):
+        return self.buf.data_ptr() + self.start
+
+    def read(self, ctx, what=""):
+        """the n bytes, once every byte outside them has been seen unchanged"""
+        ctx.synchronize()
+        got = self.buf.cpu().numpy()
+        outside = np.concatenate([got[:self.start], got[self.start + self.n:]])
+        assert outside.size >= 2 * GUARD and (outside == 0xA5).all(), f"{what}: {int((outside != 0xA5).sum())} bytes outside the {self.n} were written"
+        return got[self.start:self.start + self.n].copy()
+
+    def untouched(self, ctx):
+        ctx.synchronize()
+        return bool((self.buf.cpu().numpy() == 0xA5).all())
+
+
+def same_text(got, want, what, whose="the emitter's"):
+    """uint8 arrays of one shape, byte for byte"""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.dtype == np.uint8 and got.shape == want.shape, (what, got.dtype, got.shape, want.shape)
+    wrong = got != want
+    if wrong.any():
+        at = int(np.argmax(wrong.reshape(-1)))
+        raise AssertionError(f"{what}: {int(wrong.sum())} of {wrong.size} bytes differ from {whose}, the first at {at}: "
+                             f"{bytes(got.reshape(-1)[max(at - 8, 0):at + 8])!r} for {bytes(want.reshape(-1)[max(at - 8, 0):at + 8])!r}")
+
+
+def same_bytes(got, want, what):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.dtype == np.uint8 and got.shape == want.shape, (what, got.dtype, got.shape, want.shape)
+    wrong = got != want
+    assert not wrong.any(), f"{what}: {int(wrong.sum())} of {wrong.size} bytes differ from the oracle's, the first at {int(np.argmax(wrong.reshape(-1)))}"

@@ -15,6 +15,7 @@ import pytest
 import ansi256_support as A
 import stream_order_support as O
 import support as T
+from support import owned_rows
 from ansi256_support import DeviceBytes, same_text
 from terminalraytracer_amd import hip, host
 
@@ -46,10 +47,6 @@ def text_of(rgb, half):
     text = host.emitter_ansi256_rgb8(rgb, half)
     assert text.size == hip.ansi256_bytes(w, rows, half) == A.length(w, rows, half)
     return text
-
-
-def owned_rows(rows):
-    return hip.lib().trt_rowset_rows(C.byref(rows))
 
 
 def device_text(ctx, cam, rows, b, half, offset=0, what=""):

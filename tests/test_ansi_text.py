@@ -14,13 +14,12 @@ import numpy as np
 import pytest
 
 import support as T
+from support import STORE, DeviceBytes, anim_cameras, owned_rows, same_bytes, same_text
 from terminalraytracer_amd import hip, host
 from terminalraytracer_amd import scenes as S
 
 pytestmark = pytest.mark.gpu
 ARGUMENT, NO_SCENE, CAPACITY = -2, -3, -4
-GUARD = 64   # bytes of 0xA5 either side of every device byte buffer
-STORE = 4    # the widest store the text pass uses: an aligned 32-bit word
 
 
 @pytest.fixture(scope="module")
@@ -41,13 +40,6 @@ def _defaults(request):
         c.set_scene_image(-1)
         c.set_path_patches(-1)
         c.set_compaction(-1)
-
-
-def anim_cameras(indices, w, h):
-    d = np.load(os.path.join(T.GOLDEN, "cameras_anim.npz"))
-    cams = d["camera"][list(indices)].copy()
-    cams[:, 13] = 5 * float(w) / float(h)
-    return cams
 
 
 @functools.lru_cache(maxsize=None)
@@ -82,33 +74,6 @@ def oracle(kind, w, h, index, b, spp):
     return px, rgb, text, (st.path_rays, st.shadow_rays)
 
 
-class DeviceBytes:
-    """n bytes of device memory that start `offset` bytes behind a 4-aligned address, GUARD bytes of 0xA5 in front and behind"""
-
-    def __init__(self, n, offset=0):
-        import torch
-        self.n, self.start = n, GUARD + offset
-        self.buf = torch.full((GUARD + STORE + n + GUARD,), 0xA5, dtype=torch.uint8, device="cuda:0")
-        assert self.buf.data_ptr() % STORE == 0 and GUARD % STORE == 0
-        torch.cuda.synchronize()  # the fill is on torch's stream, the render on the context's
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + self.start
-
-    def read(self, ctx, what=""):
-        """the n bytes, once every byte outside them has been seen unchanged"""
-        ctx.synchronize()
-        got = self.buf.cpu().numpy()
-        outside = np.concatenate([got[:self.start], got[self.start + self.n:]])
-        assert outside.size >= 2 * GUARD and (outside == 0xA5).all(), f"{what}: {int((outside != 0xA5).sum())} bytes outside the text were written"
-        return got[self.start:self.start + self.n].copy()
-
-
-def owned_rows(rows):
-    return hip.lib().trt_rowset_rows(C.byref(rows))
-
-
 def device_ansi(ctx, cam, w, h, b, spp, offset=0, rows=None, what=""):
     rows = rows or hip.RowSet.whole(w, h)
     n = hip.ansi_bytes(w, owned_rows(rows))
@@ -140,21 +105,6 @@ def text_of_device_rgb8(ctx, rgb, offset=0, what=""):
     mem = DeviceBytes(hip.ansi_bytes(w, rows), offset)
     ctx.ansi_from_rgb8(src.data_ptr() + 1, w, rows, mem.ptr)
     return mem.read(ctx, what)
-
-
-def same_text(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == np.uint8 and got.shape == want.shape, (what, got.dtype, got.shape, want.shape)
-    wrong = got != want
-    if wrong.any():
-        at = int(np.argmax(wrong.reshape(-1)))
-        raise AssertionError(f"{what}: {int(wrong.sum())} of {wrong.size} bytes differ from the emitter's, the first at {at}: "
-                             f"{bytes(got.reshape(-1)[max(at - 8, 0):at + 8])!r} for {bytes(want.reshape(-1)[max(at - 8, 0):at + 8])!r}")
-
-
-def same_bytes(got, want, what):
-    wrong = np.asarray(got) != np.asarray(want)
-    assert np.asarray(got).shape == np.asarray(want).shape and not wrong.any(), f"{what}: {int(wrong.sum())} of {wrong.size} bytes differ from the oracle's"
 
 
 # ---- 1. the reference's bytes ----

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import support as T
+from support import anim_cameras
 from terminalraytracer_amd import hip
 from terminalraytracer_amd import scenes as S
 
@@ -149,13 +150,6 @@ def _defaults(request):
 
 def bits(a):
     return np.ascontiguousarray(a).view(np.uint64)
-
-
-def anim_cameras(indices, w, h):
-    d = np.load(os.path.join(T.GOLDEN, "cameras_anim.npz"))
-    cams = d["camera"][list(indices)].copy()
-    cams[:, 13] = 5 * float(w) / float(h)
-    return cams
 
 
 def frame_rows(rows):

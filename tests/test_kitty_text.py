@@ -15,13 +15,12 @@ import pytest
 
 import kitty_support as K
 import support as T
+from support import STORE, DeviceBytes, anim_cameras, owned_rows
 from terminalraytracer_amd import hip, host
 from terminalraytracer_amd import scenes as S
 
 pytestmark = pytest.mark.gpu
 ARGUMENT, NO_SCENE, CAPACITY = -2, -3, -4
-GUARD = 64   # bytes of 0xA5 either side of every device byte buffer
-STORE = 4    # the widest store the text pass uses: an aligned 32-bit word
 # (width, rows, bounce limit, rays per pixel): P on the wave's and the chunk's edges -- 1, 63, 64, 65, 1023, 1024, 1025, 2049 -- and 160 x 48
 SHAPES = [(1, 1, 2, 3), (21, 3, 2, 3), (8, 8, 2, 3), (13, 5, 2, 3), (341, 3, 2, 3), (32, 32, 2, 3), (41, 25, 2, 3), (683, 3, 2, 3), (160, 48, 4, 10)]
 INDEX = 7    # the camera of the orbit every single frame is rendered from
@@ -41,13 +40,6 @@ def _defaults(request):
         c = request.getfixturevalue("ctx")
         c.set_kernel(hip.Context.PRODUCTION)
         c.set_scratch_fill(False)
-
-
-def anim_cameras(indices, w, h):
-    d = np.load(os.path.join(T.GOLDEN, "cameras_anim.npz"))
-    cams = d["camera"][list(indices)].copy()
-    cams[:, 13] = 5 * float(w) / float(h)
-    return cams
 
 
 @functools.lru_cache(maxsize=None)
@@ -71,37 +63,6 @@ def oracle(w, h, index, b, spp):
     text = kitty_text(rgb)
     px.flags.writeable = rgb.flags.writeable = text.flags.writeable = False
     return px, rgb, text
-
-
-class DeviceBytes:
-    """n bytes of device memory that start `offset` bytes behind a 4-aligned address, GUARD bytes of 0xA5 in front and behind"""
-
-    def __init__(self, n, offset=0):
-        import torch
-        self.n, self.start = n, GUARD + offset
-        self.buf = torch.full((GUARD + STORE + n + GUARD,), 0xA5, dtype=torch.uint8, device="cuda:0")
-        assert self.buf.data_ptr() % STORE == 0 and GUARD % STORE == 0
-        torch.cuda.synchronize()  # the fill is on torch's stream, the render on the context's
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + self.start
-
-    def read(self, ctx, what=""):
-        """the n bytes, once every byte outside them has been seen unchanged"""
-        ctx.synchronize()
-        got = self.buf.cpu().numpy()
-        outside = np.concatenate([got[:self.start], got[self.start + self.n:]])
-        assert outside.size >= 2 * GUARD and (outside == 0xA5).all(), f"{what}: {int((outside != 0xA5).sum())} bytes outside the text were written"
-        return got[self.start:self.start + self.n].copy()
-
-    def untouched(self, ctx):
-        ctx.synchronize()
-        return bool((self.buf.cpu().numpy() == 0xA5).all())
-
-
-def owned_rows(rows):
-    return hip.lib().trt_rowset_rows(C.byref(rows))
 
 
 def device_kitty(ctx, cam, w, h, b, spp, offset=0, rows=None, what=""):
@@ -133,15 +94,9 @@ def kitty_of_device_rgb8(ctx, rgb, offset=0, what=""):
 
 def same_text(got, want, what, rgb=None):
     """byte for byte the emitter's; and, where the frame is given, what the structural reader reads of it"""
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == np.uint8 and got.shape == want.shape, (what, got.dtype, got.shape, want.shape)
-    wrong = got != want
-    if wrong.any():
-        at = int(np.argmax(wrong.reshape(-1)))
-        raise AssertionError(f"{what}: {int(wrong.sum())} of {wrong.size} bytes differ from the emitter's, the first at {at}: "
-                             f"{bytes(got.reshape(-1)[max(at - 8, 0):at + 8])!r} for {bytes(want.reshape(-1)[max(at - 8, 0):at + 8])!r}")
+    T.same_text(got, want, what)
     if rgb is not None:
-        assert np.array_equal(K.read(got.tobytes()), rgb), what + ": the structural reader reads another frame"
+        assert np.array_equal(K.read(np.asarray(got).tobytes()), rgb), what + ": the structural reader reads another frame"
 
 
 # ---- 1. the wave's and the chunk's edges, at any alignment ----

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import support as T
+from support import anim_cameras
 from terminalraytracer_amd import hip
 from terminalraytracer_amd import scenes as S
 
@@ -41,13 +42,6 @@ def _defaults(request):
         c.set_scene_image(-1)
         c.set_path_patches(-1)
         c.set_compaction(-1)
-
-
-def anim_cameras(indices, w, h):
-    d = np.load(os.path.join(T.GOLDEN, "cameras_anim.npz"))
-    cams = d["camera"][list(indices)].copy()
-    cams[:, 13] = 5 * float(w) / float(h)
-    return cams
 
 
 @functools.lru_cache(maxsize=None)

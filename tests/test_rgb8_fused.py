@@ -11,12 +11,12 @@ import numpy as np
 import pytest
 
 import support as T
+from support import DeviceBytes, anim_cameras, same_bytes
 from terminalraytracer_amd import hip
 from terminalraytracer_amd import scenes as S
 
 pytestmark = pytest.mark.gpu
 ARGUMENT, NO_SCENE, CAPACITY = -2, -3, -4
-GUARD = 64  # bytes of 0xA5 either side of every device byte buffer
 
 
 @pytest.fixture(scope="module")
@@ -39,13 +39,6 @@ def _defaults(request):
         c.set_compaction(-1)
 
 
-def anim_cameras(indices, w, h):
-    d = np.load(os.path.join(T.GOLDEN, "cameras_anim.npz"))
-    cams = d["camera"][list(indices)].copy()
-    cams[:, 13] = 5 * float(w) / float(h)
-    return cams
-
-
 @functools.lru_cache(maxsize=None)
 def scene(kind):
     cam = anim_cameras([0], 160, 48)[0]
@@ -63,29 +56,6 @@ def oracle(kind, w, h, index, b, spp):
     return px, rgb, (st.path_rays, st.shadow_rays)
 
 
-class DeviceBytes:
-    """n bytes of device memory that start `offset` bytes behind a 4-aligned address, GUARD bytes of 0xA5 in front and behind"""
-
-    def __init__(self, n, offset=0):
-        import torch
-        self.n, self.start = n, GUARD + offset
-        self.buf = torch.full((GUARD + 4 + n + GUARD,), 0xA5, dtype=torch.uint8, device="cuda:0")
-        assert self.buf.data_ptr() % 4 == 0 and GUARD % 4 == 0
-        torch.cuda.synchronize()  # the fill is on torch's stream, the render on the context's
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + self.start
-
-    def read(self, ctx, what=""):
-        """the n bytes, once every byte outside them has been seen unchanged"""
-        ctx.synchronize()
-        host = self.buf.cpu().numpy()
-        outside = np.concatenate([host[:self.start], host[self.start + self.n:]])
-        assert outside.size >= 2 * GUARD and (outside == 0xA5).all(), f"{what}: {int((outside != 0xA5).sum())} bytes outside the frame were written"
-        return host[self.start:self.start + self.n].copy()
-
-
 def device_rgb8(ctx, cam, w, h, b, spp, offset=0, rows=None, what=""):
     rows = rows or hip.RowSet.whole(w, h)
     n = hip.lib().trt_rowset_rows(C.byref(rows)) * w * 3
@@ -99,13 +69,6 @@ def batch_rgb8(ctx, cams, w, h, b, spp, offset=0, what=""):
     mem = DeviceBytes(n, offset)
     ctx.render_batch_rgb8(cams, hip.RowSet.whole(w, h), b, spp, mem.ptr, n)
     return mem.read(ctx, what).reshape(len(cams), h, w, 3)
-
-
-def same_bytes(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == np.uint8 and got.shape == want.shape, (what, got.dtype, got.shape, want.shape)
-    wrong = got != want
-    assert not wrong.any(), f"{what}: {int(wrong.sum())} of {wrong.size} bytes differ from the oracle's, the first at {int(np.argmax(wrong.reshape(-1)))}"
 
 
 # ---- 1. the reference's bytes ----

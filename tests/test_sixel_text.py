@@ -15,13 +15,12 @@ import pytest
 
 import sixel_support as X
 import support as T
+from support import GUARD, STORE, anim_cameras
 from terminalraytracer_amd import hip, host
 from terminalraytracer_amd import scenes as S
 
 pytestmark = pytest.mark.gpu
 ARGUMENT, NO_SCENE, CAPACITY = -2, -3, -4
-GUARD = 64       # bytes of 0xA5 either side of every device byte buffer
-STORE = 4        # the widest store the write kernel uses: an aligned 32-bit word
 SENTINEL = 0x1111111111111111
 SCAN_BLOCK = hip._header_constant("trt_sixel.h", "TRT_SIXEL_SCAN_BLOCK")  # bands the offsets kernel scans per turn
 TILE = hip._header_constant("trt_sixel.h", "TRT_SIXEL_BLOCK")            # slots, four columns each, of a write workgroup
@@ -43,13 +42,6 @@ def _defaults(request):
     yield
     if "ctx" in request.fixturenames:
         request.getfixturevalue("ctx").set_kernel(hip.Context.PRODUCTION)
-
-
-def anim_cameras(indices, w, h):
-    d = np.load(os.path.join(T.GOLDEN, "cameras_anim.npz"))
-    cams = d["camera"][list(indices)].copy()
-    cams[:, 13] = 5 * float(w) / float(h)
-    return cams
 
 
 @functools.lru_cache(maxsize=None)
@@ -118,15 +110,9 @@ class DeviceText:
 
 def same_text(got, want, what, index=None):
     """byte for byte the emitter's, the length too; and, where the frame of indices is given, what the structural reader reads"""
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == np.uint8 and got.size == want.size, f"{what}: {got.size} bytes, the emitter's text has {want.size}"
-    wrong = got != want
-    if wrong.any():
-        at = int(np.argmax(wrong))
-        raise AssertionError(f"{what}: {int(wrong.sum())} of {wrong.size} bytes differ from the emitter's, the first at {at}: "
-                             f"{bytes(got[max(at - 8, 0):at + 8])!r} for {bytes(want[max(at - 8, 0):at + 8])!r}")
+    T.same_text(got, want, what)
     if index is not None:
-        assert np.array_equal(X.read(got.tobytes()), index), what + ": the structural reader reads another frame"
+        assert np.array_equal(X.read(np.asarray(got).tobytes()), index), what + ": the structural reader reads another frame"
 
 
 def upload(rgb):

@@ -11,7 +11,7 @@ Within one process the three routes take turns, orbit by orbit, `--rounds` times
 differences between them); per route and round the median, the least and the most over the orbit's frames 1..59 of bytes and of host-to-host
 ms per frame (frame 0, the keyframe of the delta routes, is listed by itself).  Then the three kernels by HIP events
 (trt_ansi_delta_half_kernel_times): on the orbit's frames 0 -> 1, and on a 1920x1080 pair whose every cell changed with all neighbours
-different -- the longest text there is -- beside ansi_half_from_rgb8_kernel (trt_ansi_half_from_rgb8_device) on the same frame.  Prints a
+different -- the longest text there is -- beside text_from_rgb8_kernel<ansi_half_text> (trt_ansi_half_from_rgb8_device) on the same frame.  Prints a
 markdown report (profiles/r15/a_delta_half.md holds one)."""
 import argparse
 import ctypes as C
@@ -77,7 +77,7 @@ class Orbit:
 
 
 def kernel_times(ctx, shown, nxt, repeats=20):
-    """(bytes of the delta text, [ms of measure, offsets, write] as medians over `repeats`, ms of ansi_half_from_rgb8_kernel on `nxt`: wall
+    """(bytes of the delta text, [ms of measure, offsets, write] as medians over `repeats`, ms of text_from_rgb8_kernel<ansi_half_text> on `nxt`: wall
     clock over `repeats` launches back to back between two synchronisations)"""
     import torch
     rows, w, _ = shown.shape
@@ -135,8 +135,8 @@ def main():
             nxt = shown ^ np.uint8(0x80)  # every cell changed; random colours: horizontal neighbours differ (but for one pair in 2^24)
             kernels.append((f"{w}x{h}, every cell changed, all neighbours different", kernel_times(o.ctx, shown, nxt)))
         o.close()
-    print("## the three kernels (HIP events, median (min, max) of 20) beside ansi_half_from_rgb8_kernel on the new frame (wall clock over 20 launches back to back)\n")
-    print("| frames | delta text bytes | measure ms | offsets ms | write ms | sum ms | ansi_half_from_rgb8_kernel ms (whole text) |")
+    print("## the three kernels (HIP events, median (min, max) of 20) beside text_from_rgb8_kernel<ansi_half_text> on the new frame (wall clock over 20 launches back to back)\n")
+    print("| frames | delta text bytes | measure ms | offsets ms | write ms | sum ms | text_from_rgb8_kernel<ansi_half_text> ms (whole text) |")
     print("|---|---|---|---|---|---|---|")
     for what, (n, ms, whole) in kernels:
         total = [sum(x) for x in zip(*ms)]
