@@ -32,6 +32,9 @@
  * --batch=N, with --delta (or --half --delta) and --step=: the replay rendered ahead, N cameras per call, through a context of the program's
  * own (trt_render_host_batch_ansi_delta, trt_render_host_batch_ansi_delta_half): one render and three text kernels per N frames, two
  * transfers for their N texts, which are written frame by frame.  What reaches the terminal is byte for byte what --delta alone sends.
+ * --specular: EXTENSION, parity unpinned (trt_set_default_specular; with --batch also trt_set_specular on the program's own context): the
+ * lights' Blinn-Phong highlights from the specularity of 100.0 that the reference's scene gives every material and never reads.  Goes with
+ * every other flag.
  *
  * The scene literals are the reference's (TRT.c:1256-1288). */
 #include <signal.h>
@@ -60,12 +63,12 @@ int main(int argc, char **argv)
 {
     if (argc < 2)
     {
-        fprintf(stderr, "usage: %s <skybox-directory> [frames] [width] [height] [--no-draw] [--rgb8] [--ansi] [--half] [--kitty] [--sixel] [--256] [--delta] [--step=SECONDS] [--batch=N]\n", argv[0]);
+        fprintf(stderr, "usage: %s <skybox-directory> [frames] [width] [height] [--no-draw] [--rgb8] [--ansi] [--half] [--kitty] [--sixel] [--256] [--delta] [--step=SECONDS] [--batch=N] [--specular]\n", argv[0]);
         return 2;
     }
     const long frames = argc > 2 ? atol(argv[2]) : 0;
     const int width = argc > 3 ? atoi(argv[3]) : 160, height = argc > 4 ? atoi(argv[4]) : 48;
-    int draw = 1, bytes_only = 0, text_only = 0, delta = 0, half = 0, kitty = 0, sixel = 0, palette = 0, batch = 0;
+    int draw = 1, bytes_only = 0, text_only = 0, delta = 0, half = 0, kitty = 0, sixel = 0, palette = 0, batch = 0, specular = 0;
     double step = -1.0;
     for (int i = 5; i < argc; i++)
     {
@@ -89,6 +92,8 @@ int main(int argc, char **argv)
             step = atof(argv[i] + 7);
         else if (strncmp(argv[i], "--batch=", 8) == 0)
             batch = atoi(argv[i] + 8);
+        else if (strcmp(argv[i], "--specular") == 0)
+            specular = 1; /* EXTENSION, parity unpinned: highlights from Material.specularity; goes with every other flag */
     }
     if (batch && (batch < 1 || batch > TRT_BATCH_MAX || !delta || step < 0.0))
     {
@@ -109,6 +114,11 @@ int main(int argc, char **argv)
     {
         fprintf(stderr, "--256 sends whole texts in the xterm palette: it goes with --half, with neither --delta nor --kitty\n");
         return 2;
+    }
+    if (specular && trt_set_default_specular(1) != TRT_OK)
+    {
+        fprintf(stderr, "trt_set_default_specular: %s\n", trt_last_error());
+        return 1;
     }
 
     Skybox sky;
@@ -161,9 +171,9 @@ int main(int argc, char **argv)
     const trt_rowset whole = {width, height, height, 0, 1};
     Camera cameras[TRT_BATCH_MAX];
     size_t batch_bytes[TRT_BATCH_MAX];
-    if (batch && (trt_create(0, &ctx) != TRT_OK || trt_set_scene(ctx, &scene) != TRT_OK))
+    if (batch && (trt_create(0, &ctx) != TRT_OK || trt_set_scene(ctx, &scene) != TRT_OK || trt_set_specular(ctx, specular) != TRT_OK))
     {
-        fprintf(stderr, "trt_create / trt_set_scene: %s\n", trt_last_error());
+        fprintf(stderr, "trt_create / trt_set_scene / trt_set_specular: %s\n", trt_last_error());
         return 1;
     }
 

@@ -749,6 +749,55 @@ int trt_render_variant(trt_context *ctx, int *decoupled, int *workgroup_threads)
  * kernel instantiation runs and nothing of this is on the path. */
 int trt_set_refraction(trt_context *ctx, const double *ior, int count);
 
+/* EXTENSION, PARITY UNPINNED.  Specular highlights from Material.specularity, which the reference carries through every
+ * Material and never reads: its author wrote the Blinn-Phong term into apply_lighting and left it commented out (TRT.c:913-916, :921,
+ * :947-950, :955), and project_scene still forms the `view` vector the term needs (TRT.c:1029).  on = 1 switches the term on for the
+ * frames this context renders, 0 (the default) off; anything else fails with TRT_ERR_ARGUMENT.
+ *
+ * THE DECLARED RULES (tests/specular_model.py is written from these, not from the kernel).  The lighting of a hit (TRT.c:894-962)
+ * changes for every light i that reaches the surface point -- the same shadow test, unchanged --:
+ *
+ *     view  = -d                                      d: the path ray's direction as the round holds it, that is after
+ *                                                     normalize_vector (TRT.c:1008 / :1055); TRT.c:1029
+ *     half  = normalize_vector(light_direction + view)  light_direction first; the reference's normalisation, which leaves a vector
+ *                                                     no longer than 1e-4 alone (TRT.c:444)
+ *     c     = clamp(dot(normal, half), 0.0, 1.0)      the reference's clamp: a NaN passes through
+ *     s     = powi(c, n)
+ *     spec  = light.color * s                         directional light (TRT.c:916)
+ *     spec  = light.color * (light_intensity * s)     point light (TRT.c:950): ONE product first, then the scale
+ *     output_color += diffuse * material.color;  output_color += spec       in this order (TRT.c:920-921, :954-955)
+ *
+ * The term enters before the clamp of TRT.c:960 and is not multiplied by the material's colour.  n comes from the specularity e of
+ * the hit material -- a sphere's, the even ground's or the odd ground's --: n = 0 if !(e >= 0), which covers negative values and NaN;
+ * n = 65535 if e >= 65535; otherwise n = (int)e.  A FRACTIONAL EXPONENT IS TRUNCATED.  powi is binary exponentiation, right to left,
+ * each product one rounded FP64 multiplication:
+ *
+ *     r = 1.0; b = c; while (n) { if (n & 1) r = r * b; n >>= 1; if (n) b = b * b; }
+ *
+ * so n = 0 gives 1.0, as pow(c, 0) does.  THIS IS THE ONE DEPARTURE from the commented-out lines, which call pow: pow is correctly
+ * rounded neither in glibc nor in the device library, the two disagree in the last bits, and frames could not be held bit for bit.
+ * powi is also the cheap form on the FP64 VALU: the demo's n = 100 is six squarings and two products.  Everything else -- shadow rays,
+ * the diffuse term, weights, bounces and reflection, the sky, the nudge -- stays the reference's.
+ *
+ * The extension runs on the plain rounds (256-thread workgroups, never decoupled, with or without patches) and on the reference-order
+ * kernel, as refraction does: a batch of cameras is served one launch per camera; a scene whose image outgrows LDS fails at render time
+ * with TRT_ERR_CAPACITY; a render with this and the refraction extension both on fails with TRT_ERR_ARGUMENT -- the two do not combine
+ * yet.  Every output kind (doubles, RGB8, the texts, kitty, sixel, the delta texts) works unchanged: they read the ordered mean.  The
+ * trt_dist_* entries are out of scope: trt_dist_create and trt_dist_set_scene switch the extension off on every frame slot's context,
+ * whatever TRT_SPECULAR says.  The switch is per context, like the refraction indices: trt_share_scene(dst, src) switches dst's OFF,
+ * also when dst had it on from trt_set_specular or from the environment; call trt_set_specular(dst, 1) after sharing.
+ * Environment: TRT_SPECULAR=0|1 sets the default of new contexts, until a trt_share_scene into them or a trt_set_specular.
+ *
+ * UNPINNED TO THE REFERENCE, whose live code has no such term.  Frames are checked bit for bit against tests/specular_restatement.c,
+ * which with the switch off equals the oracle bit for bit, and whose every (hit, light) term is held to an exact model of the rules
+ * above (tests/test_specular_model.py).  With the extension off other kernel instantiations run and nothing of this is on the path. */
+int trt_set_specular(trt_context *ctx, int on);
+int trt_get_specular(trt_context *ctx, int *on);
+/* ... for the default context behind project_scene and the trt_render_frame_* entries (section 1), which their callers cannot reach:
+ * holds for the default context that exists and for one a later call creates, until trt_shutdown.  Takes the default context's turn,
+ * as trt_set_scene_policy does. */
+int trt_set_default_specular(int on);
+
 /* Resource usage of the render kernel trt_render_variant describes (hipFuncGetAttributes / occupancy query; max_blocks_per_cu
  * counts workgroups of trt_render_variant's size, and for 256-thread workgroups is the plain rounds' figure, which sizes them). */
 int trt_kernel_info(trt_context *ctx, int *vgprs, int *sgprs, int *static_lds_bytes, int *max_blocks_per_cu,

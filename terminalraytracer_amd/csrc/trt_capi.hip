@@ -229,6 +229,12 @@ static int init_context(trt_context *ctx)
         if (sscanf(e, "%d", &mode) == 1 && mode >= -1 && mode <= 1)
             ctx->compaction = mode;
     }
+    if (const char *e = getenv("TRT_SPECULAR"))
+    {
+        int on = 0;
+        if (sscanf(e, "%d", &on) == 1 && (on == 0 || on == 1))
+            ctx->specular = on;
+    }
     if (const char *e = getenv("TRT_PATH_LEAN"))
     {
         int mode = -1;
@@ -377,6 +383,7 @@ extern "C" int trt_share_scene(trt_context *dst, trt_context *src)
     dst->sky_dim = src->sky_dim;
     dst->sky_stamp = src->sky_stamp;
     dst->ior_count = 0;
+    dst->specular = 0; // per context, like the refraction indices: dst starts with the extension off
     dst->have_scene = true;
     dst->occupancy_for_lds = (size_t)-1;
     return refresh_occupancy(dst);
@@ -434,6 +441,24 @@ extern "C" int trt_set_refraction(trt_context *ctx, const double *ior, int count
     HIP_TRY(ctx->d_ior.reserve((size_t)count));
     HIP_TRY(hipMemcpy(ctx->d_ior.ptr, ior, (size_t)count * sizeof(double), hipMemcpyHostToDevice));
     ctx->ior_count = count;
+    return TRT_OK;
+}
+
+extern "C" int trt_set_specular(trt_context *ctx, int on)
+{
+    if (!ctx)
+        return fail(TRT_ERR_ARGUMENT, "ctx is NULL");
+    if (on != 0 && on != 1)
+        return fail(TRT_ERR_ARGUMENT, "specular %d (0 or 1)", on);
+    ctx->specular = on;
+    return TRT_OK;
+}
+
+extern "C" int trt_get_specular(trt_context *ctx, int *on)
+{
+    if (!ctx || !on)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    *on = ctx->specular;
     return TRT_OK;
 }
 

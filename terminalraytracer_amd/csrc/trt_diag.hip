@@ -11,9 +11,12 @@ namespace trt_impl
 {
 void allow_large_lds_diag(const trt_context *ctx)
 {
-    (void)hipFuncSetAttribute((const void *)trt::probe_rays_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
+    (void)hipFuncSetAttribute((const void *)trt::probe_rays_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
+    (void)hipFuncSetAttribute((const void *)trt::probe_rays_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
     (void)hipFuncSetAttribute((const void *)trt::probe_rounds_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
     (void)hipFuncSetAttribute((const void *)trt::probe_rounds_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
+    (void)hipFuncSetAttribute((const void *)trt::probe_rounds_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
+    (void)hipFuncSetAttribute((const void *)trt::probe_rounds_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
 }
 } // namespace trt_impl
 
@@ -320,8 +323,8 @@ extern "C" int trt_probe_rays(trt_context *ctx, const Ray *rays, size_t n, int *
     HIP_TRY(dobj.reserve(n));
     double *dr = buf.ptr, *dp = dr + 6 * n, *dn = dp + 3 * n, *dm = dn + 3 * n, *dl = dm + 5 * n;
     HIP_TRY(hipMemcpy(dr, rays, n * sizeof(Ray), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(trt::probe_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), scene_lds_bytes(ctx->scene), ctx->stream,
-                       ctx->scene, dr, (long)n, dobj.ptr, dp, dn, dm, dl);
+    hipLaunchKernelGGL(ctx->specular ? trt::probe_rays_kernel<true> : trt::probe_rays_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256),
+                       scene_lds_bytes(ctx->scene), ctx->stream, ctx->scene, (const double *)dr, (long)n, dobj.ptr, dp, dn, dm, dl);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipMemcpy(obj, dobj.ptr, n * sizeof(int), hipMemcpyDeviceToHost));
@@ -379,14 +382,12 @@ extern "C" int trt_probe_rays_production(trt_context *ctx, const Camera *camera,
     trt::FrameView f{};
     memcpy(f.cam, camera, sizeof(Camera));
     f.jitter = ctx->d_jitter.ptr; // spp = 0: nothing is read through it
-    if (ctx->grids.path_enabled && ctx->grids.patch_m > 0)
-        hipLaunchKernelGGL(trt::probe_rounds_kernel<true>, dim3((unsigned)((n + trt::kPersistentBlock - 1) / trt::kPersistentBlock)), dim3(trt::kPersistentBlock),
-                           image_lds_bytes(ctx, 0), ctx->stream, ctx->scene, ctx->cull, f, ctx->grids, (const double *)dr,
-                           families ? (const int *)(dobj.ptr + n) : (const int *)nullptr, (long)n, dobj.ptr, dp, dn, dm, dl);
-    else
-        hipLaunchKernelGGL(trt::probe_rounds_kernel<false>, dim3((unsigned)((n + trt::kPersistentBlock - 1) / trt::kPersistentBlock)), dim3(trt::kPersistentBlock),
-                           image_lds_bytes(ctx, 0), ctx->stream, ctx->scene, ctx->cull, f, ctx->grids, (const double *)dr,
-                           families ? (const int *)(dobj.ptr + n) : (const int *)nullptr, (long)n, dobj.ptr, dp, dn, dm, dl);
+    const bool patches = ctx->grids.path_enabled && ctx->grids.patch_m > 0;
+    const auto probe = patches ? (ctx->specular ? trt::probe_rounds_kernel<true, true> : trt::probe_rounds_kernel<true>)
+                               : (ctx->specular ? trt::probe_rounds_kernel<false, true> : trt::probe_rounds_kernel<false>); // trt_set_specular
+    hipLaunchKernelGGL(probe, dim3((unsigned)((n + trt::kPersistentBlock - 1) / trt::kPersistentBlock)), dim3(trt::kPersistentBlock),
+                       image_lds_bytes(ctx, 0), ctx->stream, ctx->scene, ctx->cull, f, ctx->grids, (const double *)dr,
+                       families ? (const int *)(dobj.ptr + n) : (const int *)nullptr, (long)n, dobj.ptr, dp, dn, dm, dl);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipMemcpy(obj, dobj.ptr, n * sizeof(int), hipMemcpyDeviceToHost));

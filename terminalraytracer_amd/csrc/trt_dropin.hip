@@ -12,6 +12,8 @@ int g_default_device = 0;
 // shares one device context, so calls on the default context take turns.
 std::mutex g_default_mutex;
 
+int g_default_specular = -1; // trt_set_default_specular: 0 / 1 for the default context until trt_shutdown; -1: what a new context starts with
+
 int default_context(trt_context **out)
 {
     if (!g_default)
@@ -19,6 +21,8 @@ int default_context(trt_context **out)
         int rc = trt_create(g_default_device, &g_default);
         if (rc)
             return rc;
+        if (g_default_specular >= 0)
+            g_default->specular = g_default_specular;
     }
     *out = g_default;
     return TRT_OK;
@@ -43,6 +47,7 @@ extern "C" int trt_shutdown(void)
     std::lock_guard<std::mutex> turn(g_default_mutex);
     int rc = trt_destroy(g_default);
     g_default = nullptr;
+    g_default_specular = -1;
     return rc;
 }
 
@@ -113,6 +118,19 @@ extern "C" int trt_set_scene_policy(int moving_after, int still_after)
     // tables built for a moving scene under a scene that is not, and builds the full ones.
     if (moving_after == 0 && g_default)
         g_default->moving_scene = false;
+    return TRT_OK;
+}
+
+// The specular extension (trt_set_specular) for the default context, which the callers of the drop-in entries cannot reach: it holds
+// for the context that exists and for one that a later call creates, until trt_shutdown.
+extern "C" int trt_set_default_specular(int on)
+{
+    if (on != 0 && on != 1)
+        return fail(TRT_ERR_ARGUMENT, "specular %d (0 or 1)", on);
+    std::lock_guard<std::mutex> turn(g_default_mutex);
+    g_default_specular = on;
+    if (g_default)
+        g_default->specular = on;
     return TRT_OK;
 }
 

@@ -780,16 +780,48 @@ TRT_DEV PathHit path_stage(const LdsImage &L, const CullView &cull, const GridVi
     return r;
 }
 
+// The exponent of the specular extension from a material's specularity e: 0 unless e >= 0 (negative values, NaN), 65535 from there
+// up, otherwise e truncated.
+TRT_DEV int specular_exponent(double e)
+{
+    return !(e >= 0.0) ? 0 : (e >= 65535.0 ? 65535 : (int)e);
+}
+
+// c^n by binary exponentiation, right to left, every product ONE rounded FP64 multiplication (no contraction: there is nothing to
+// contract with), so that a CPU restatement and an exact model reach the same bits -- pow() is correctly rounded neither in glibc nor in
+// the device library.  n = 0 gives 1.0, as pow(c, 0) does.  The lanes of a wave loop to the wave's largest n; a lane whose n is
+// exhausted has left the loop's exec mask and multiplies nothing.  n = 100, the demo's, is six squarings and two products.
+TRT_DEV double specular_power(double c, int n)
+{
+    double r = 1.0, b = c;
+    while (n)
+    {
+        if (n & 1)
+            r = r * b;
+        n >>= 1;
+        if (n)
+            b = b * b;
+    }
+    return r;
+}
+
 // S(i): lighting of TRT.c:894-957 for the lanes with `lit_lanes`: one shadow ray per light from the (nudged) surface point
 // `o` with unit normal `normal`, candidates from the light's table (trt_lightgrid.h) unless some lane's origin is outside
 // its range; the lit colour is accumulated in the reference's light order, NOT yet clamped (TRT.c:960).
-template <bool COUNT>
+// SPECULAR (EXTENSION, parity unpinned; the declared rules are in include/trt_hip.h above trt_set_specular): every light that reaches
+// the point also adds its Blinn-Phong term -- the lines the reference keeps commented out (TRT.c:913-916, :921, :947-950, :955) with
+// specular_power in pow's place -- after its diffuse term and before the clamp.  `view`: minus the path ray's unit direction (TRT.c:1029).
+template <bool COUNT, bool SPECULAR = false>
 TRT_DEV d3 shadow_stage(const LdsImage &L, const CullView &cull, const GridView &grids, int n, int nd, int nl, d3 o, d3 normal, int mat,
-                        bool lit_lanes, unsigned long long lit_word, d3 gp, d3 gn, Tally &tally) // lit_word: lanes_with(lit_lanes) (trt_device.hpp)
+                        bool lit_lanes, unsigned long long lit_word, d3 gp, d3 gn, Tally &tally, // lit_word: lanes_with(lit_lanes) (trt_device.hpp)
+                        d3 view = d3{0.0, 0.0, 0.0})
 {
     d3 lit = d3{0.0, 0.0, 0.0};
     if (lit_word == 0)
         return lit;
+    int spec_n = 0; // the exponent of the hit material, formed once for all lights
+    if constexpr (SPECULAR)
+        spec_n = specular_exponent(L.mat[mat * 5 + 4]);
     for (int li = 0; li < nl; li++)
     {
         if (COUNT && lit_lanes)
@@ -797,6 +829,7 @@ TRT_DEV d3 shadow_stage(const LdsImage &L, const CullView &cull, const GridView 
         d3 sd, lcolor;
         bool is_lit;
         double factor;
+        [[maybe_unused]] double spec_scale = 0.0; // SPECULAR, point lights: light_intensity
         if (li < nd)
         { // directional light, TRT.c:900-923
             TRT_MARK_AT(24); // ISA profile: a directional light's pass starts
@@ -886,10 +919,20 @@ TRT_DEV d3 shadow_stage(const LdsImage &L, const CullView &cull, const GridView 
                 }
             }
             factor = strength * min1(dot(normal, sd));
+            if constexpr (SPECULAR)
+                spec_scale = strength;
             TRT_MARK_AT(19); // point shadow tail
         }
         if (lit_lanes && is_lit)
+        {
             lit = add(lit, mulc(scale(lcolor, factor), load3(L.mat + mat * 5)));
+            if constexpr (SPECULAR)
+            { // TRT.c:914-916 / :948-950, then :921 / :955: not multiplied by the material's colour
+                const d3 half = unit(add(sd, view));
+                const double s = specular_power(clampd(dot(normal, half), 0.0, 1.0), spec_n);
+                lit = add(lit, scale(lcolor, li < nd ? s : spec_scale * s)); // a point light: ONE product first, then the scale
+            }
+        }
     }
     return lit;
 }
@@ -1065,9 +1108,13 @@ constexpr int kBigBlock = 1024;
 // BATCH: several frames of one scene per launch (BatchView above); the launch has a fifth argument, `batch`, a BatchView, which the
 // kernel reads where it needs it (stage_lds_image_batch, load_batch_shape).  Every difference is behind `if constexpr (BATCH)` or a
 // constant that folds: the single-frame instantiations are what they were.
+// SPECULAR (EXTENSION, parity unpinned, trt_set_specular): the lights' Blinn-Phong terms (shadow_stage), on the plain rounds with or
+// without patches.  A task of the decoupled ring would have to carry the view vector, three more doubles: not built.  Its register
+// budget is four waves per SIMD: left at three the allocator took 137 VGPRs for the instantiation without patches -- three waves -- and
+// the term cost config 2 45 % of a frame instead of 24 (profiles/r25/a_specular.md); asked for four it settles at 126, nothing spilt.
 template <bool COUNT, bool REFRACT = false, bool COMPACT = false, bool PATCHES = false, bool BIG = false, bool DEVICE_IMAGE = false, bool BATCH = false,
-          class... BatchArgument>
-__global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersistentBlock, ((COMPACT && !COUNT) || BIG) ? 4 : TRT_ROUNDS_WAVES) void render_rounds_kernel(SceneView s, CullView cull, FrameView f, GridView grids, BatchArgument... batch)
+          bool SPECULAR = false, class... BatchArgument>
+__global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersistentBlock, ((COMPACT && !COUNT) || BIG || (SPECULAR && !COUNT) /* 126 / 127 VGPRs asked for four waves, 137 left at three */) ? 4 : TRT_ROUNDS_WAVES) void render_rounds_kernel(SceneView s, CullView cull, FrameView f, GridView grids, BatchArgument... batch)
 {
     static_assert(sizeof...(BatchArgument) == (BATCH ? 1 : 0), "a BATCH launch has one more argument, a BatchView; the others none");
     static_assert(!BATCH || (!COUNT && !REFRACT && !BIG && !DEVICE_IMAGE), "several frames per launch: the plain, patch and decoupled rounds");
@@ -1075,6 +1122,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
     static_assert(!(PATCHES && COMPACT), "scenes with patches run the plain rounds");
     static_assert(!BIG || (PATCHES && !COUNT && !REFRACT && !COMPACT), "1024-thread workgroups: the shipping patch instantiation only");
     static_assert(!DEVICE_IMAGE || (!REFRACT && !COMPACT && !BIG), "the device-memory image: the plain rounds only");
+    static_assert(!SPECULAR || (!COMPACT && !BIG && !DEVICE_IMAGE && !BATCH && !REFRACT), "the specular extension: the plain rounds with the image in LDS, one frame a launch");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const LdsImage L = BATCH ? stage_lds_image_batch(lds, s, cull, f, grids)
                        : DEVICE_IMAGE ? image_view(image_layout(const_cast<double *>(f.image), s.num_spheres, s.num_dir, s.num_point, cull.padded, f.spp))
@@ -1366,6 +1414,9 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
                 tally.passes++;
             {
                 TRT_FRESH_ARGS;
+                if constexpr (SPECULAR)
+                    lit = shadow_stage<COUNT, true>(L, cull, grids, n, nd, nl, o, h_normal, h_mat, path_hit, hit.hit_lanes, gp, gn, tally, scale(d, -1.0)); // TRT.c:1029
+                else
                 lit = shadow_stage<COUNT>(L, cull, grids, n, nd, nl, o, h_normal, h_mat, path_hit, hit.hit_lanes, gp, gn, tally); // !REFRACT: path_hit is hit.hit
             }
         }
@@ -1492,7 +1543,9 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
 // trt_probe_rays through the PRODUCTION stages: one lane per ray, the very path_stage / shadow_stage of the render kernel
 // (tables, fall-back sweep, exact tests, lighting).  families[i]: the family ray i is looked up in (trt_raygrid.h; < 0: none,
 // the wave sweeps); nullptr: none for every ray.  Outputs as trace_ray / apply_lighting produce them (TRT.c:793-963).
-template <bool PATCHES>
+// SPECULAR: the context's specular extension is on (trt_set_specular); lit_out then holds the clamped colour with the lights' terms,
+// the view vector being minus the ray's direction as it was given.
+template <bool PATCHES, bool SPECULAR = false>
 __global__ __launch_bounds__(kPersistentBlock) void probe_rounds_kernel(SceneView s, CullView cull, FrameView f, GridView grids, const double *rays,
                                                                         const int *families, long count, int *obj, double *point, double *normal,
                                                                         double *material, double *lit_out)
@@ -1509,7 +1562,11 @@ __global__ __launch_bounds__(kPersistentBlock) void probe_rounds_kernel(SceneVie
     Tally tally;
     const PathHit hit = path_stage<false, false, PATCHES>(L, cull, grids, n, o, d, fam, alive, lanes_with(alive), gp, gn, tally);
     const d3 surface = hit.hit ? add(hit.ph.p, scale(hit.back, 0.000001)) : o; // TRT.c:873-874 / :860
-    const d3 lit = shadow_stage<false>(L, cull, grids, n, nd, nl, surface, hit.normal, hit.mat, hit.hit, hit.hit_lanes, gp, gn, tally);
+    d3 lit;
+    if constexpr (SPECULAR)
+        lit = shadow_stage<false, true>(L, cull, grids, n, nd, nl, surface, hit.normal, hit.mat, hit.hit, hit.hit_lanes, gp, gn, tally, scale(d, -1.0));
+    else
+        lit = shadow_stage<false>(L, cull, grids, n, nd, nl, surface, hit.normal, hit.mat, hit.hit, hit.hit_lanes, gp, gn, tally);
     const uint32_t sky_t = sky_texel_wave(s.sky, s.sky_dim, hit.back, s.sky_dim_f, alive && !hit.hit, hit.sky_lanes); // the render kernels' look-up
     if (!alive)
         return;

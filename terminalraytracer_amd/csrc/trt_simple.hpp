@@ -115,8 +115,37 @@ TRT_DEV Surface closest_hit(const SceneView &s, const LdsScene &l, d3 o, d3 d)
     return best;
 }
 
-// TRT.c:894-963
-TRT_DEV d3 lit_color(const SceneView &s, const LdsScene &l, d3 at, d3 normal, d3 albedo, unsigned &shadow_count)
+// The specular extension (EXTENSION, parity unpinned; the declared rules are in include/trt_hip.h above trt_set_specular) as this
+// kernel states it: the factor of one light's Blinn-Phong term, the lines TRT.c:914-916 / :948-950 with a power by repeated
+// squaring where they call pow.  Bit i of the exponent, from the lowest up, multiplies the result by c^(2^i); the squares stop at
+// the exponent's highest bit.
+TRT_DEV double blinn_phong(d3 to_light, d3 view, d3 normal, double specularity)
+{
+    d3 half = unit(add(to_light, view));
+    const double c = clampd(dot(normal, half), 0.0, 1.0);
+    unsigned bits = 0; // the exponent: a specularity that is negative or not a number counts as 0, one of 65535 or more as 65535
+    if (specularity >= 65535.0)
+        bits = 65535u;
+    else if (specularity >= 0.0)
+        bits = (unsigned)(int)specularity; // a fraction is cut off
+    double power = 1.0, square = c;
+    for (;;)
+    {
+        if (bits % 2u)
+            power = power * square;
+        bits /= 2u;
+        if (bits == 0u)
+            break;
+        square = square * square;
+    }
+    return power;
+}
+
+// TRT.c:894-963.  SPECULAR: with the commented-out lines TRT.c:913-916, :921, :947-950, :955 (blinn_phong); `view` points back along the
+// ray (TRT.c:1029), `specularity` is the hit material's.
+template <bool SPECULAR = false>
+TRT_DEV d3 lit_color(const SceneView &s, const LdsScene &l, d3 at, d3 normal, d3 albedo, unsigned &shadow_count, d3 view = d3{0.0, 0.0, 0.0},
+                     double specularity = 0.0)
 {
     d3 out = d3{0.0, 0.0, 0.0};
     for (int i = 0; i < s.num_dir; i++)
@@ -129,6 +158,8 @@ TRT_DEV d3 lit_color(const SceneView &s, const LdsScene &l, d3 at, d3 normal, d3
         {
             d3 diffuse = scale(load3(li + 3), min1(dot(normal, to_light)));
             out = add(out, mulc(diffuse, albedo));
+            if constexpr (SPECULAR)
+                out = add(out, scale(load3(li + 3), blinn_phong(to_light, view, normal, specularity)));
         }
     }
     for (int i = 0; i < s.num_point; i++)
@@ -146,6 +177,8 @@ TRT_DEV d3 lit_color(const SceneView &s, const LdsScene &l, d3 at, d3 normal, d3
         {
             d3 diffuse = scale(load3(li + 3), strength * min1(dot(normal, to_light)));
             out = add(out, mulc(diffuse, albedo));
+            if constexpr (SPECULAR)
+                out = add(out, scale(load3(li + 3), strength * blinn_phong(to_light, view, normal, specularity)));
         }
     }
     return d3{clampd(out.x, 0.0, 1.0), clampd(out.y, 0.0, 1.0), clampd(out.z, 0.0, 1.0)};
@@ -153,7 +186,8 @@ TRT_DEV d3 lit_color(const SceneView &s, const LdsScene &l, d3 at, d3 normal, d3
 
 #ifdef TRT_UNIT_RENDER // the kernel's ONE home among the library's translation units (trt_context.hpp)
 // DEVICE_SCENE: the records are read where SceneView has them (the same layout), for scenes whose records do not fit LDS
-template <bool DEVICE_SCENE = false>
+// SPECULAR: the specular extension (trt_set_specular), see lit_color
+template <bool DEVICE_SCENE = false, bool SPECULAR = false>
 __global__ __launch_bounds__(256) void render_simple_kernel(SceneView s, FrameView f)
 {
     extern __shared__ double lds[];
@@ -182,7 +216,12 @@ __global__ __launch_bounds__(256) void render_simple_kernel(SceneView s, FrameVi
             Surface hit = closest_hit<true>(s, l, org, dir);
             d3 color = hit.color;
             if (hit.what != 0)
-                color = lit_color(s, l, hit.point, hit.normal, color, n_shadow);
+            {
+                if constexpr (SPECULAR)
+                    color = lit_color<true>(s, l, hit.point, hit.normal, color, n_shadow, scale(dir, -1.0), hit.spec); // TRT.c:1029
+                else
+                    color = lit_color(s, l, hit.point, hit.normal, color, n_shadow);
+            }
             weight_sum += weight;
             color = scale(color, weight);
             if (hit.what != 0)
@@ -216,7 +255,9 @@ __global__ __launch_bounds__(256) void render_simple_kernel(SceneView s, FrameVi
 #endif // TRT_UNIT_RENDER
 #ifdef TRT_UNIT_DIAG
 
-// trt_probe_rays: closest hit + lighting of arbitrary rays (tests)
+// trt_probe_rays: closest hit + lighting of arbitrary rays (tests).  SPECULAR: the context's specular extension is on; the view vector
+// is minus the ray's direction as it was given
+template <bool SPECULAR = false>
 __global__ __launch_bounds__(256) void probe_rays_kernel(SceneView s, const double *rays, long n, int *obj, double *point,
                                                           double *normal, double *material, double *lit)
 {
@@ -236,7 +277,10 @@ __global__ __launch_bounds__(256) void probe_rays_kernel(SceneView s, const doub
     if (h.what != 0)
     {
         unsigned dummy = 0;
-        c = lit_color(s, l, h.point, h.normal, h.color, dummy);
+        if constexpr (SPECULAR)
+            c = lit_color<true>(s, l, h.point, h.normal, h.color, dummy, scale(d, -1.0), h.spec);
+        else
+            c = lit_color(s, l, h.point, h.normal, h.color, dummy);
     }
     lit[3 * i + 0] = c.x, lit[3 * i + 1] = c.y, lit[3 * i + 2] = c.z;
 }

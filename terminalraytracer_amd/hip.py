@@ -165,6 +165,9 @@ SYMBOLS = {
     "trt_read_shading_passes": (_I, [_VP, C.POINTER(C.c_ulonglong)]),
     "trt_read_loop_diagnostics": (_I, [_VP, C.POINTER(C.c_ulonglong)]),
     "trt_set_refraction": (_I, [_VP, _VP, _I]),
+    "trt_set_specular": (_I, [_VP, _I]),
+    "trt_get_specular": (_I, [_VP, C.POINTER(_I)]),
+    "trt_set_default_specular": (_I, [_I]),
     "trt_reserve_cus": (_I, [_VP, _I]),
     "trt_get_stream": (_I, [_VP, C.POINTER(C.c_void_p)]),
     "trt_selftest_cube": (_I, [_VP, _VP, C.c_size_t, _VP, _VP]),
@@ -414,6 +417,17 @@ class Context:
         else:
             a = np.ascontiguousarray(ior, dtype=np.float64)
             _check(lib().trt_set_refraction(self._h, a.ctypes.data, a.size))
+
+    def set_specular(self, on=True):
+        """EXTENSION, parity unpinned: the lights' Blinn-Phong terms from Material.specularity; 0 / False is the reference's path
+        (trt_set_specular)"""
+        _check(lib().trt_set_specular(self._h, int(on)))
+
+    def specular(self):
+        """whether the specular extension is on (trt_get_specular)"""
+        v = _I()
+        _check(lib().trt_get_specular(self._h, C.byref(v)))
+        return bool(v.value)
 
     def read_sweep_fallbacks(self):
         v = C.c_ulonglong()
@@ -924,6 +938,12 @@ def render_frame_rgb8(scene_data, width, height, bounce_limit=10, rays_per_pixel
     out = np.zeros((height, width, 3), dtype=np.uint8)
     _check(lib().trt_render_frame_rgb8(C.byref(scene), width, height, bounce_limit, rays_per_pixel, out.ctypes.data))
     return out
+
+
+def set_default_specular(on=True):
+    """EXTENSION, parity unpinned: the specular extension for the default context behind project_scene and the trt_render_frame_*
+    entries, until trt_shutdown (trt_set_default_specular)"""
+    _check(lib().trt_set_default_specular(int(on)))
 
 
 def ansi_bytes(width, rows):
