@@ -2,8 +2,8 @@
  * host C builds the demo scene and the orbiting camera, the MI355X produces the frame through
  * the drop-in project_scene(), and the ANSI emitter stays on the host.
  *
- *   trt_demo <skybox-directory> [frames=0 (until Ctrl-C)] [width=160] [height=48] [--no-draw] [--rgb8] [--ansi] [--half] [--kitty] [--sixel] [--256] [--delta] [--step=SECONDS]
- *            [--batch=N]
+ *   trt_demo <skybox-directory> [frames=0 (until Ctrl-C)] [width=160] [height=48] [--no-draw] [--rgb8] [--ansi] [--half] [--kitty] [--sixel] [--256] [--delta] [--delta256]
+ *            [--step=SECONDS] [--batch=N]
  *
  * --rgb8: the frame crosses PCIe as the 3 bytes per pixel the emitter makes of it (trt_render_frame_rgb8: the (int)(c*255) of
  * TRT.c:1157-1163 done on the device) instead of as 24-byte doubles; what reaches the terminal is the same.
@@ -21,16 +21,20 @@
  * numColorRegisters: 256).  No terminal has shown this picture (csrc/trt_sixel.h).  It has no --delta form.
  * --256: the text route for a terminal that has only the xterm 256-colour palette (trt_render_frame_ansi256; with --half
  * trt_render_frame_ansi256_half): "48;5;N" cells, N the entry of the palette's fixed part nearest to the pixel, no dithering;
- * trt_ansi256_bytes or trt_ansi256_half_bytes(width, height) bytes, one fwrite.  No terminal was at hand to look at this picture.  It has
- * no --delta form.
+ * trt_ansi256_bytes or trt_ansi256_half_bytes(width, height) bytes, one fwrite.  No terminal was at hand to look at this picture.  --256
+ * sends whole texts and does not go with --delta: the palette's delta route has a flag of its own, --delta256.
  * --delta: the text route, but only what changed (trt_render_frame_ansi_delta): frame 0 arrives as the whole text, every later frame as the
  * records of the cells whose colour changed, each written with exactly the bytes the call reports.  Nothing else may be printed over
  * the picture, so the frames-per-second line goes to stderr once, at the end.
  * --half --delta: the same in half-block cells (trt_render_frame_ansi_delta_half): frame 0 arrives as --half's whole text, every later frame
  * as the records of the one-column cells either of whose two pixels changed.
+ * --delta256: --delta in the xterm 256-colour palette (trt_render_frame_ansi256_delta; with --half trt_render_frame_ansi256_delta_half): frame 0
+ * arrives as --256's whole text, every later frame as the records of the cells whose palette ENTRY changed -- fewer and shorter records than
+ * --delta's, for the links where bytes per frame decide the frame rate.  Each frame is one fwrite of exactly the bytes the call reported.  It
+ * goes with --half and --batch=N, and with none of --kitty, --sixel, --ansi and --rgb8.
  * --step=SECONDS: frame k is rendered at orbit time k * SECONDS instead of at the wall clock's (a replay: the same frames every run).
- * --batch=N, with --delta (or --half --delta) and --step=: the replay rendered ahead, N cameras per call, through a context of the program's
- * own (trt_render_host_batch_ansi_delta, trt_render_host_batch_ansi_delta_half): one render and three text kernels per N frames, two
+ * --batch=N, with --delta or --delta256 (with or without --half) and --step=: the replay rendered ahead, N cameras per call, through a context of
+ * the program's own (trt_render_host_batch_ansi_delta, trt_render_host_batch_ansi_delta_half and their ansi256 forms): one render and three text kernels per N frames, two
  * transfers for their N texts, which are written frame by frame.  What reaches the terminal is byte for byte what --delta alone sends.
  * --specular: EXTENSION, parity unpinned (trt_set_default_specular; with --batch also trt_set_specular on the program's own context): the
  * lights' Blinn-Phong highlights from the specularity of 100.0 that the reference's scene gives every material and never reads.  Goes with
@@ -63,12 +67,12 @@ int main(int argc, char **argv)
 {
     if (argc < 2)
     {
-        fprintf(stderr, "usage: %s <skybox-directory> [frames] [width] [height] [--no-draw] [--rgb8] [--ansi] [--half] [--kitty] [--sixel] [--256] [--delta] [--step=SECONDS] [--batch=N] [--specular]\n", argv[0]);
+        fprintf(stderr, "usage: %s <skybox-directory> [frames] [width] [height] [--no-draw] [--rgb8] [--ansi] [--half] [--kitty] [--sixel] [--256] [--delta] [--delta256] [--step=SECONDS] [--batch=N] [--specular]\n", argv[0]);
         return 2;
     }
     const long frames = argc > 2 ? atol(argv[2]) : 0;
     const int width = argc > 3 ? atoi(argv[3]) : 160, height = argc > 4 ? atoi(argv[4]) : 48;
-    int draw = 1, bytes_only = 0, text_only = 0, delta = 0, half = 0, kitty = 0, sixel = 0, palette = 0, batch = 0, specular = 0;
+    int draw = 1, bytes_only = 0, text_only = 0, ansi = 0, delta = 0, delta256 = 0, half = 0, kitty = 0, sixel = 0, palette = 0, batch = 0, specular = 0;
     double step = -1.0;
     for (int i = 5; i < argc; i++)
     {
@@ -77,7 +81,7 @@ int main(int argc, char **argv)
         else if (strcmp(argv[i], "--rgb8") == 0)
             bytes_only = 1;
         else if (strcmp(argv[i], "--ansi") == 0)
-            text_only = 1;
+            text_only = ansi = 1;
         else if (strcmp(argv[i], "--half") == 0)
             text_only = half = 1;
         else if (strcmp(argv[i], "--kitty") == 0)
@@ -88,6 +92,8 @@ int main(int argc, char **argv)
             text_only = palette = 1;
         else if (strcmp(argv[i], "--delta") == 0)
             text_only = delta = 1;
+        else if (strcmp(argv[i], "--delta256") == 0)
+            text_only = delta = delta256 = 1; /* a delta route: whatever holds of --delta below holds of it */
         else if (strncmp(argv[i], "--step=", 7) == 0)
             step = atof(argv[i] + 7);
         else if (strncmp(argv[i], "--batch=", 8) == 0)
@@ -97,7 +103,7 @@ int main(int argc, char **argv)
     }
     if (batch && (batch < 1 || batch > TRT_BATCH_MAX || !delta || step < 0.0))
     {
-        fprintf(stderr, "--batch=N renders a replay ahead: 1 <= N <= %d, with --delta and --step=SECONDS\n", TRT_BATCH_MAX);
+        fprintf(stderr, "--batch=N renders a replay ahead: 1 <= N <= %d, with --delta or --delta256 and --step=SECONDS\n", TRT_BATCH_MAX);
         return 2;
     }
     if (kitty && (delta || half || trt_kitty_bytes(width, height) == 0))
@@ -112,7 +118,12 @@ int main(int argc, char **argv)
     }
     if (palette && (delta || kitty))
     {
-        fprintf(stderr, "--256 sends whole texts in the xterm palette: it goes with --half, with neither --delta nor --kitty\n");
+        fprintf(stderr, "--256 sends whole texts in the xterm palette: it goes with --half, with neither --delta nor --kitty; the palette's delta route is --delta256\n");
+        return 2;
+    }
+    if (delta256 && (ansi || bytes_only))
+    {
+        fprintf(stderr, "--delta256 sends delta texts in the xterm palette: it goes with --half and --batch=N, with none of --kitty, --sixel, --ansi and --rgb8\n");
         return 2;
     }
     if (specular && trt_set_default_specular(1) != TRT_OK)
@@ -154,7 +165,15 @@ int main(int argc, char **argv)
 
     Screen screen = {(Vector *)malloc(sizeof(Vector) * (size_t)width * height), width, height};
     unsigned char *rgb = (unsigned char *)malloc((size_t)width * height * 3);
-    const size_t text_room = delta  ? (size_t)(batch ? batch : 1) * (half ? trt_ansi_delta_half_capacity(width, height) : trt_ansi_delta_capacity(width, height))
+    /* the delta routes by kind: [--delta256][--half] */
+    size_t (*const delta_capacity[2][2])(int, int) = {{trt_ansi_delta_capacity, trt_ansi_delta_half_capacity}, {trt_ansi256_delta_capacity, trt_ansi256_delta_half_capacity}};
+    size_t (*const whole_bytes[2][2])(int, int) = {{trt_ansi_bytes, trt_ansi_half_bytes}, {trt_ansi256_bytes, trt_ansi256_half_bytes}};
+    int (*const render_delta[2][2])(const Scene *, int, int, int, int, char *, size_t, size_t *) = {
+        {trt_render_frame_ansi_delta, trt_render_frame_ansi_delta_half}, {trt_render_frame_ansi256_delta, trt_render_frame_ansi256_delta_half}};
+    int (*const render_batch_delta[2][2])(trt_context *, const Camera *, int, const trt_rowset *, int, int, char *, size_t, size_t *) = {
+        {trt_render_host_batch_ansi_delta, trt_render_host_batch_ansi_delta_half}, {trt_render_host_batch_ansi256_delta, trt_render_host_batch_ansi256_delta_half}};
+    const char *const delta_name[2][2] = {{"ansi_delta", "ansi_delta_half"}, {"ansi256_delta", "ansi256_delta_half"}};
+    const size_t text_room = delta  ? (size_t)(batch ? batch : 1) * delta_capacity[delta256][half](width, height)
                              : palette ? (half ? trt_ansi256_half_bytes(width, height) : trt_ansi256_bytes(width, height))
                              : half  ? trt_ansi_half_bytes(width, height)
                              : kitty ? trt_kitty_bytes(width, height)
@@ -191,10 +210,9 @@ int main(int argc, char **argv)
             cameras[b] = scene.camera;
         }
         const double before = seconds_since(&start);
-        if ((half ? trt_render_host_batch_ansi_delta_half : trt_render_host_batch_ansi_delta)(ctx, cameras, n, &whole, TRT_REF_BOUNCE_LIMIT, TRT_REF_RAYS_PER_PIXEL, text,
-                                                                                           text_room, batch_bytes) != TRT_OK)
+        if (render_batch_delta[delta256][half](ctx, cameras, n, &whole, TRT_REF_BOUNCE_LIMIT, TRT_REF_RAYS_PER_PIXEL, text, text_room, batch_bytes) != TRT_OK)
         {
-            fprintf(stderr, "trt_render_host_batch_ansi_delta%s: %s\n", half ? "_half" : "", trt_last_error());
+            fprintf(stderr, "trt_render_host_batch_%s: %s\n", delta_name[delta256][half], trt_last_error());
             return 1;
         }
         if (frame == 0) /* as below: initialisation is in the first call, which here is a whole batch */
@@ -217,19 +235,11 @@ int main(int argc, char **argv)
         trt_orbit_camera(&scene.camera, step >= 0.0 ? step * (double)frame : t);
 
         const double before = seconds_since(&start);
-        if (delta && half)
+        if (delta)
         {
-            if (trt_render_frame_ansi_delta_half(&scene, width, height, TRT_REF_BOUNCE_LIMIT, TRT_REF_RAYS_PER_PIXEL, text, text_room, &text_bytes) != TRT_OK)
+            if (render_delta[delta256][half](&scene, width, height, TRT_REF_BOUNCE_LIMIT, TRT_REF_RAYS_PER_PIXEL, text, text_room, &text_bytes) != TRT_OK)
             {
-                fprintf(stderr, "trt_render_frame_ansi_delta_half: %s\n", trt_last_error());
-                return 1;
-            }
-        }
-        else if (delta)
-        {
-            if (trt_render_frame_ansi_delta(&scene, width, height, TRT_REF_BOUNCE_LIMIT, TRT_REF_RAYS_PER_PIXEL, text, text_room, &text_bytes) != TRT_OK)
-            {
-                fprintf(stderr, "trt_render_frame_ansi_delta: %s\n", trt_last_error());
+                fprintf(stderr, "trt_render_frame_%s: %s\n", delta_name[delta256][half], trt_last_error());
                 return 1;
             }
         }
@@ -309,10 +319,10 @@ int main(int argc, char **argv)
     }
     if (delta)
         fprintf(stderr, "\033[%d;1H\n%.02f fps, %zu bytes of text for %ld frames (%zu each as whole texts)\n", half ? (height + 1) / 2 : height,
-                (double)frame / seconds_since(&start), written_bytes, frame, half ? trt_ansi_half_bytes(width, height) : trt_ansi_bytes(width, height));
+                (double)frame / seconds_since(&start), written_bytes, frame, whole_bytes[delta256][half](width, height));
     fprintf(stderr, "%ld frames %dx%d, frame producer %.3f ms/frame after a first call of %.1f ms (host-in/host-out%s, 10 bounces, 10 rays per pixel)\n",
             frame, width, height, frame > first_batch ? 1e3 * producer_seconds / (frame - first_batch) : 0.0, 1e3 * first_call_seconds,
-            delta && half ? " as half-block delta text" : delta ? " as delta text" : palette && half ? " as half-block 256-colour text" : palette ? " as 256-colour text" : half ? " as half-block text" : kitty ? " as a kitty image" : sixel ? " as a sixel image" : text_only ? " as text" : bytes_only ? " as RGB8" : "");
+            delta256 && half ? " as half-block 256-colour delta text" : delta256 ? " as 256-colour delta text" : delta && half ? " as half-block delta text" : delta ? " as delta text" : palette && half ? " as half-block 256-colour text" : palette ? " as 256-colour text" : half ? " as half-block text" : kitty ? " as a kitty image" : sixel ? " as a sixel image" : text_only ? " as text" : bytes_only ? " as RGB8" : "");
 
     trt_emitter_destroy(emitter);
     free(screen.pixels);

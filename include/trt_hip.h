@@ -105,6 +105,15 @@ int trt_render_frame_ansi_delta(const Scene *scene, int width, int height, int b
 int trt_render_frame_ansi_delta_half(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text,
                                      size_t capacity_bytes, size_t *bytes);
 
+/* The two in the XTERM 256-COLOUR PALETTE (trt_render_host_ansi256_delta and trt_render_host_ansi256_delta_half below, on the default
+ * context: their formats -- a cell is changed where its palette INDEX is -- and their rules): the keyframe is trt_render_frame_ansi256's
+ * or trt_render_frame_ansi256_half's text, capacity_bytes >= trt_ansi256_delta_capacity / trt_ansi256_delta_half_capacity(width,
+ * height).  The one shown frame remembers which of the FOUR kinds it was sent as: a call of any other kind returns a keyframe. */
+extern int trt_render_frame_ansi256_delta(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text,
+                                          size_t capacity_bytes, size_t *bytes);
+extern int trt_render_frame_ansi256_delta_half(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text,
+                                               size_t capacity_bytes, size_t *bytes);
+
 /* The frame as a DEC SIXEL image (trt_render_host_sixel below, on the default context: its format and its caveat -- no terminal has shown
  * it): true pixels in the 240 fixed colours of the xterm palette, for the terminals that take sixel and not the kitty protocol.  The
  * length depends on the picture: text holds capacity_bytes >= trt_sixel_capacity(width, height) bytes, the host writes *bytes of them
@@ -323,9 +332,10 @@ int trt_kitty_from_rgb8_device(trt_context *ctx, const void *d_rgb8, int width, 
  * csrc/trt_ansi256.h and csrc/trt_ansi256_half.h are the formats in code, trt_emitter_ansi256_rgb8 and trt_emitter_ansi256_half_rgb8
  * (trt_host.h) their sequential statements on the host.  Limits: those of the 24-bit texts (fewer than 2^31 - 1 pixels).  Checks,
  * TRT_ERR_*, stream behaviour and the trt_kernel_times accounting of every entry are those of the _ansi_half entry it mirrors;
- * capacities count bytes of text, to the byte.  OUT OF SCOPE: there is no delta form -- none of these entries reads or changes the delta
- * entries' shown frame -- no refraction form, no dithering and no 16-colour text; of a trt_dist_render_rgb8 gather rank 0 formats the
- * assembled bytes with the _from_rgb8_device entries.  No terminal was at hand to look at the picture: the tests hold the texts against
+ * capacities count bytes of text, to the byte.  These are the WHOLE texts: none of these entries reads or changes the delta entries'
+ * shown frame; the delta forms of both, for the links where bytes per frame decide the frame rate, stand below the 24-bit delta texts
+ * (trt_render_device_ansi256_delta, trt_render_device_ansi256_delta_half).  OUT OF SCOPE: no refraction form, no dithering and no
+ * 16-colour text; of a trt_dist_render_rgb8 gather rank 0 formats the assembled bytes with the _from_rgb8_device entries.  No terminal was at hand to look at the picture: the tests hold the texts against
  * the sequential emitters and a structural reader. */
 
 /* Lengths of the two texts: 6 + (13 width + 5) rows and 6 + (23 width + 5) ((rows + 1) / 2); 0 unless both arguments are positive. */
@@ -371,8 +381,11 @@ int trt_xterm256_from_rgb8_device(trt_context *ctx, const void *d_rgb8, size_t n
  *   - the refraction extension has no delta form; the batch entries have one (trt_render_device_batch_ansi_delta, below the batch
  *     entries); of a trt_dist_render_rgb8 gather rank 0 formats the assembled bytes with trt_ansi_delta_from_rgb8_device, several
  *     gathered frames at once with trt_ansi_delta_chain_from_rgb8_device;
- *   - the records here are of two-column cells of the full text; the half-block text has a delta form of its own, below, and a
- *     context remembers which of the two its shown frame was sent as: changing over is a keyframe. */
+ *   - the records here are of two-column cells of the full text in 24-bit colour.  The half-block text has a delta form of its own,
+ *     below, and so have the two texts in the xterm 256-colour palette, below that: FOUR kinds.  A context keeps ONE shown frame and
+ *     remembers which of the four it was sent as: a delta call is a keyframe unless the shown frame is of exactly this rowset AND this
+ *     kind, so changing between any two kinds is a keyframe;
+ *   - the sixel and kitty images and a 16-colour text have no delta form. */
 
 /* Room for any text the delta entries write for a screen of `width` x `rows` owned rows: max(trt_ansi_bytes, rows * (21 * width + 18)),
  * the keyframe or the longest delta; 0 when either is not positive or above the limits. */
@@ -406,7 +419,7 @@ int trt_render_device_ansi_delta(trt_context *ctx, const Camera *camera, const t
  * two small transfers instead of one large one.  capacity_bytes counts the bytes at text, checked as above. */
 int trt_render_host_ansi_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
                                char *text, size_t capacity_bytes, size_t *bytes);
-/* Forget the shown frame: the next delta call, of either kind, returns a keyframe.  For a host that dropped a text, cleared its
+/* Forget the shown frame: the next delta call, of any of the four kinds, returns a keyframe.  For a host that dropped a text, cleared its
  * terminal or printed over the picture. */
 int trt_ansi_delta_reset(trt_context *ctx);
 
@@ -454,6 +467,70 @@ int trt_render_device_ansi_delta_half(trt_context *ctx, const Camera *camera, co
 /* The same into HOST memory, synchronous: the 8-byte length is read back, then exactly *bytes bytes cross PCIe. */
 int trt_render_host_ansi_delta_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
                                     char *text, size_t capacity_bytes, size_t *bytes);
+
+/* ---- the delta texts in the xterm 256-colour palette --------------------------------------------------------------------------------
+ * The delta texts of a terminal that shows the 256-COLOUR texts (trt_render_device_ansi256, trt_render_device_ansi256_half): the links
+ * that have only the palette -- ssh, an old tmux, a serial or CI console -- are those where bytes per frame decide the frame rate.  The
+ * frames are the same RGB8 bytes; a pixel's INDEX is its palette entry 16..255 (the rule above the 256-colour texts).  A cell is CHANGED
+ * when an INDEX differs, not when a byte does: a cell whose bytes move inside one palette entry has no record, so the text has at most
+ * as many records as the 24-bit delta of the same two frames, and each is shorter.  Runs, record order and the cursor are those of the
+ * 24-bit kind of the same cells; "the same as the left neighbour's" compares NEW INDICES.
+ *
+ * Full cells (two columns wide), a record:
+ *   "[RRRRR;CCCCCH"        14 bytes, where a run starts: RRRRR = owned row + 1, CCCCC = 2 * column + 1
+ *   "[48;5;NNNm"           11 bytes, where a run starts or the new index differs from the left neighbour's new index
+ *   two spaces
+ *   "[0m"                   4 bytes, where the run ends
+ * 2, 6, 13, 17, 27 or 31 bytes.  A text has at most rows * (13 * width + 13 + 5 * ((width + 1) / 2)) bytes: here a run's fixed cost (18)
+ * exceeds a cell's (13), so MORE runs cost more -- with k runs a row holds at most width - k + 1 changed cells, 18 k + 13 (width - k + 1)
+ * bytes, which grows up to k = (width + 1) / 2 -- reached by changed and unchanged cells in turn.  Limits: width <= 49999, rows <= 99999.
+ *
+ * Half-block cells (T = (rows + 1) / 2 text rows, upper pixel owned row 2 t, lower pixel owned row 2 t + 1; index 016 behind an odd
+ * frame's last row in both frames, never read from memory), a record:
+ *   "[RRRRR;CCCCCH"        14 bytes, where a run starts: RRRRR = t + 1, CCCCC = c + 1
+ *   "[38;5;UUU;48;5;LLLm"  20 bytes, where a run starts or BOTH indices differ from the left neighbour's
+ *   "[38;5;UUUm"           11 bytes, where only the upper index differs
+ *   "[48;5;LLLm"           11 bytes, where only the lower index differs; nothing where neither differs
+ *   E2 96 80                    3 bytes, the glyph U+2580
+ *   "[0m"                   4 bytes, where the run ends
+ * 3, 7, 14, 18, 23, 27, 37 or 41 bytes.  A text has at most T * (23 * width + 18) bytes (one run is worst, as in the 24-bit kind).
+ * Limits: width <= 99999, T <= 99999.
+ *
+ * csrc/trt_ansi256_delta.h and csrc/trt_ansi256_delta_half.h are the formats in code, trt_emitter_delta256_rgb8 and
+ * trt_emitter_delta256_half_rgb8 (trt_host.h) their sequential statements on the host; the measured bytes and times are in
+ * profiles/r26/a_delta256.md.  Every entry below mirrors the 24-bit delta entry of the same name without "256": semantics, errors,
+ * stream behaviour and trt_kernel_times accounting are that entry's, the capacity, the limits and the keyframe this kind's.  The rules
+ * for the host are those of the delta text above.  OUT OF SCOPE: no refraction form, no sixel, kitty or 16-colour delta.
+ * The entries of this family are declared `extern int`, which says what `int` says: the table of stream-order scenarios that
+ * tests/test_ansi256_stream_order.py holds against the `int trt_...256...` declarations of this header is that of the WHOLE 256-colour
+ * texts; this family's asynchronous entries have their scenarios, and the check that none lacks one, in
+ * tests/test_ansi256_delta_stream_order.py. */
+
+/* Room for any text the 256-colour delta entries write: the larger of the whole text (trt_ansi256_bytes, trt_ansi256_half_bytes) -- the
+ * keyframe -- and the bound above; 0 when either size is not positive or above the limits. */
+size_t trt_ansi256_delta_capacity(int width, int rows);
+size_t trt_ansi256_delta_half_capacity(int width, int rows);
+
+/* trt_ansi_delta_from_rgb8_device and trt_ansi_delta_half_from_rgb8_device in the palette: the frames are RGB8 bytes (what a
+ * trt_dist_render_rgb8 gather holds), which the kernels map to indices as they load them; no paletted copy of a frame is made.  They
+ * neither read nor change the context's shown frame.  capacity_bytes >= the kind's capacity, else TRT_ERR_CAPACITY. */
+extern int trt_ansi256_delta_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows,
+                                              void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+extern int trt_ansi256_delta_half_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows,
+                                                   void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+
+/* trt_render_device_ansi_delta and trt_render_device_ansi_delta_half in the palette, on the same ONE shown frame: a KEYFRAME unless the
+ * context has a shown frame for exactly this rowset AND this kind of the four.  The keyframe is byte for byte
+ * trt_render_device_ansi256's (or trt_render_device_ansi256_half's) text, *d_bytes its length. */
+extern int trt_render_device_ansi256_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                           void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+extern int trt_render_device_ansi256_delta_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit,
+                                                int rays_per_pixel, void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+/* The same into HOST memory, synchronous: the 8-byte length is read back, then exactly *bytes bytes cross PCIe. */
+extern int trt_render_host_ansi256_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                         char *text, size_t capacity_bytes, size_t *bytes);
+extern int trt_render_host_ansi256_delta_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
+                                              char *text, size_t capacity_bytes, size_t *bytes);
 
 /* ---- the DEC sixel image: true pixels for the terminals that take sixel and nothing else -----------------------------------------------
  * The kitty image above reaches kitty, WezTerm, Ghostty and Konsole.  xterm, foot, mlterm, Windows Terminal, VS Code's terminal, contour
@@ -653,6 +730,23 @@ int trt_render_host_batch_ansi_delta(trt_context *ctx, const Camera *cameras, in
                                      int rays_per_pixel, char *text, size_t capacity_bytes, size_t *bytes);
 int trt_render_host_batch_ansi_delta_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
                                           int rays_per_pixel, char *text, size_t capacity_bytes, size_t *bytes);
+
+/* The six entries above in the xterm 256-colour palette (the delta texts in the palette, above): each is the entry of the same name
+ * without "256" -- launches, texts back to back, lengths, trt_batch_info, errors, stream behaviour -- with this kind's cells, capacity
+ * (n * trt_ansi256_delta_capacity / trt_ansi256_delta_half_capacity) and limits, and with trt_render_device_ansi256's or
+ * trt_render_device_ansi256_half's text as the keyframe.  Two frames of a chain that map to the same indices give a text of 0 bytes. */
+extern int trt_ansi256_delta_chain_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows,
+                                                    void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+extern int trt_ansi256_delta_half_chain_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width,
+                                                         int rows, void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+extern int trt_render_device_batch_ansi256_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                                 int rays_per_pixel, void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+extern int trt_render_device_batch_ansi256_delta_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                                      int rays_per_pixel, void *d_text, size_t capacity_bytes, unsigned long long *d_bytes);
+extern int trt_render_host_batch_ansi256_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                               int rays_per_pixel, char *text, size_t capacity_bytes, size_t *bytes);
+extern int trt_render_host_batch_ansi256_delta_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit,
+                                                    int rays_per_pixel, char *text, size_t capacity_bytes, size_t *bytes);
 
 /* The most recent batch call of this context: its frames, and how many render-kernel launches served them
  * (1 = one launch over all frames; n = one launch per camera; between: the batch was split for LDS). */

@@ -227,6 +227,16 @@ int trt_ansi_delta_chain_kernel_times(trt_context *ctx, const void *d_shown_rgb8
                                       void *d_text, size_t capacity_bytes, unsigned long long *d_bytes, float *ms);
 int trt_ansi_delta_half_chain_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows,
                                            void *d_text, size_t capacity_bytes, unsigned long long *d_bytes, float *ms);
+/* The four above of the delta texts in the xterm 256-colour palette (trt_ansi256_delta_from_rgb8_device and its _half and _chain forms):
+ * the kind's measure kernel, the shared offsets kernel, the kind's write kernel (tools/ansi256_delta_bench.py). */
+int trt_ansi256_delta_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                   size_t capacity_bytes, unsigned long long *d_bytes, float *ms);
+int trt_ansi256_delta_half_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                        size_t capacity_bytes, unsigned long long *d_bytes, float *ms);
+int trt_ansi256_delta_chain_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows,
+                                         void *d_text, size_t capacity_bytes, unsigned long long *d_bytes, float *ms);
+int trt_ansi256_delta_half_chain_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows,
+                                              void *d_text, size_t capacity_bytes, unsigned long long *d_bytes, float *ms);
 
 #ifdef __cplusplus
 }

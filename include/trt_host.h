@@ -125,6 +125,24 @@ int trt_emitter_ansi256_rgb8(const unsigned char *rgb, int width, int rows, char
  * "\033[38;5;UUU;48;5;LLLm" and the glyph U+2580 in UTF-8 (E2 96 80) -- UUU the index of row 2 t, LLL that of row 2 t + 1; 016, black, behind
  * the last row of an odd frame -- then "\033[0m\n".  No NUL: *bytes = 6 + (23 * width + 5) * ((rows + 1) / 2).  Errors as above. */
 int trt_emitter_ansi256_half_rgb8(const unsigned char *rgb, int width, int rows, char *text, size_t capacity, size_t *bytes);
+/* The DELTA text in that palette (csrc/trt_ansi256_delta.h): what a terminal that shows `shown` as trt_emitter_ansi256_rgb8's text must be
+ * sent to show `next`.  A pixel's index is the SEARCH's; a cell is CHANGED when its index differs between the frames, not when a byte
+ * does.  Per changed cell, rows ascending, left to right: "\033[RRRRR;CCCCCH" (row + 1, 2 * column + 1) where a run of changed cells of one
+ * row starts, "\033[48;5;NNNm" where a run starts or the index differs from the new index of the cell to the left, two spaces, and "\033[0m"
+ * where the run ends.  No NUL; frames of equal indices give *bytes = 0.  At most rows * (13 * width + 13 + 5 * ((width + 1) / 2)) bytes
+ * -- every other cell changed: here more runs cost more --, which `capacity` must hold; rows <= 99999, width <= 49999.  The sequential
+ * statement the device kernels (trt_render_device_ansi256_delta, trt_hip.h) are tested against.  TRT_HOST_ERR_ARGUMENT: NULL, a size
+ * that is not positive or above the limits, a capacity below the bound. */
+int trt_emitter_delta256_rgb8(const unsigned char *shown, const unsigned char *next, int width, int rows, char *text, size_t capacity,
+                              size_t *bytes);
+/* The same in HALF-BLOCK cells (csrc/trt_ansi256_delta_half.h), for a terminal that shows trt_emitter_ansi256_half_rgb8's text: a cell of
+ * text row t < (rows + 1) / 2 has the indices of rows 2 t and 2 t + 1 (016 behind an odd frame's last row, in both frames, and not read)
+ * and is changed when either differs.  Per changed cell: "\033[RRRRR;CCCCCH" (text row + 1, column + 1) where a run starts; the colours
+ * that differ from the left neighbour's new ones -- "\033[38;5;UUU;48;5;LLLm" where a run starts or both do, "\033[38;5;UUUm" or
+ * "\033[48;5;LLLm" where one does, nothing where neither does --; the glyph E2 96 80; "\033[0m" where the run ends.  At most
+ * ((rows + 1) / 2) * (23 * width + 18) bytes, which `capacity` must hold; width <= 99999, (rows + 1) / 2 <= 99999.  Errors as above. */
+int trt_emitter_delta256_half_rgb8(const unsigned char *shown, const unsigned char *next, int width, int rows, char *text, size_t capacity,
+                                   size_t *bytes);
 /* The frame of such bytes (rows x width x 3) as a DEC SIXEL image, for the terminals that take sixel and not the kitty protocol (xterm,
  * foot, mlterm, Windows Terminal, VS Code's terminal, contour, tmux built with sixel).  The format is the project's own statement
  * (csrc/trt_sixel.h), written from memory of DEC's description, and NO TERMINAL HAS SHOWN IT.  "\033[0;0H"; "\033P0;1;0q";

@@ -497,6 +497,130 @@ int trt_emitter_ansi256_half_rgb8(const unsigned char *rgb, int width, int rows,
     return TRT_HOST_OK;
 }
 
+/* The delta text in the palette (csrc/trt_ansi256_delta.h holds the format): trt_emitter_delta_rgb8's walk over the INDICES the search
+ * finds -- a cell is changed where its index is, and "as the cell to the left" compares indices.  Plain loops, on purpose without that
+ * header and without the closed form -- this is what the header's arithmetic and the device kernels are held against. */
+static unsigned index256_at(const unsigned char *px) { return trt_xterm256_index_search(px[0], px[1], px[2]); }
+
+enum
+{
+    COLOUR256_LEN = 11 /* the palette cell up to and including its 'm' */
+};
+
+int trt_emitter_delta256_rgb8(const unsigned char *shown, const unsigned char *next, int width, int rows, char *text, size_t capacity, size_t *bytes)
+{
+    if (!shown || !next || !text || !bytes || width <= 0 || rows <= 0 || width > DELTA_MAX_WIDTH || rows > DELTA_MAX_ROWS)
+        return TRT_HOST_ERR_ARGUMENT;
+    if (capacity < (size_t)rows * ((size_t)13 * width + 13 + (size_t)5 * (((size_t)width + 1) / 2)))
+        return TRT_HOST_ERR_ARGUMENT;
+    char *p = text;
+    for (int row = 0; row < rows; row++)
+    {
+        const unsigned char *was = shown + (size_t)row * width * 3, *now = next + (size_t)row * width * 3;
+        int in_run = 0;
+        for (int col = 0; col < width; col++)
+        {
+            const unsigned index = index256_at(now + 3 * col);
+            if (index256_at(was + 3 * col) == index)
+                continue;
+            if (!in_run)
+            { /* the cursor to the cell's first column: rows and columns count from 1, a cell is two columns wide */
+                memcpy(p, k_goto, GOTO_LEN);
+                five_digits(p + GOTO_ROW_AT, row + 1);
+                five_digits(p + GOTO_COLUMN_AT, 2 * col + 1);
+                p += GOTO_LEN;
+            }
+            if (!in_run || index256_at(now + 3 * (col - 1)) != index)
+            { /* the background colour, unless the cell painted just before has it */
+                memcpy(p, k_cell256, COLOUR256_LEN);
+                three_digits(p + INDEX256_AT, (int)index);
+                p += COLOUR256_LEN;
+            }
+            *p++ = ' ';
+            *p++ = ' ';
+            in_run = col + 1 < width && index256_at(was + 3 * (col + 1)) != index256_at(now + 3 * (col + 1));
+            if (!in_run)
+            {
+                memcpy(p, k_reset, RESET_LEN);
+                p += RESET_LEN;
+            }
+        }
+    }
+    *bytes = (size_t)(p - text);
+    return TRT_HOST_OK;
+}
+
+/* The half-block delta text in the palette (csrc/trt_ansi256_delta_half.h holds the format): trt_emitter_delta_half_rgb8's walk over the
+ * indices the search finds; behind an odd frame's last row the lower index is black, 016, in both frames, and nothing there is read. */
+static const char k_upper256[] = "\033[38;5;000";
+static const char k_lower256[] = "48;5;000";
+enum
+{
+    UPPER256_LEN = sizeof(k_upper256) - 1, /* 10 */
+    LOWER256_LEN = sizeof(k_lower256) - 1  /* 8 */
+};
+
+int trt_emitter_delta256_half_rgb8(const unsigned char *shown, const unsigned char *next, int width, int rows, char *text, size_t capacity, size_t *bytes)
+{
+    if (!shown || !next || !text || !bytes || width <= 0 || rows <= 0 || width > DELTA_HALF_MAX_WIDTH || rows > 2 * DELTA_HALF_MAX_TEXT_ROWS)
+        return TRT_HOST_ERR_ARGUMENT;
+    const size_t text_rows = ((size_t)rows + 1) / 2;
+    if (capacity < text_rows * ((size_t)23 * width + 18))
+        return TRT_HOST_ERR_ARGUMENT;
+    char *p = text;
+    for (size_t t = 0; t < text_rows; t++)
+    {
+        const int has_lower = 2 * t + 1 < (size_t)rows;
+        const unsigned char *was_up = shown + 2 * t * width * 3, *now_up = next + 2 * t * width * 3;
+        const unsigned char *was_low = has_lower ? was_up + (size_t)width * 3 : NULL, *now_low = has_lower ? now_up + (size_t)width * 3 : NULL;
+        int in_run = 0;
+        for (int col = 0; col < width; col++)
+        {
+            const unsigned up = index256_at(now_up + 3 * col), low = has_lower ? index256_at(now_low + 3 * col) : BLACK256;
+            if (index256_at(was_up + 3 * col) == up && (!has_lower || index256_at(was_low + 3 * col) == low))
+                continue;
+            if (!in_run)
+            { /* the cursor to the cell: text rows and columns count from 1, a cell is one column wide */
+                memcpy(p, k_goto, GOTO_LEN);
+                five_digits(p + GOTO_ROW_AT, (int)t + 1);
+                five_digits(p + GOTO_COLUMN_AT, col + 1);
+                p += GOTO_LEN;
+            }
+            /* the colours, unless the cell painted just before has them */
+            const int set_upper = !in_run || index256_at(now_up + 3 * (col - 1)) != up;
+            const int set_lower = !in_run || (has_lower && index256_at(now_low + 3 * (col - 1)) != low);
+            if (set_upper)
+            {
+                memcpy(p, k_upper256, UPPER256_LEN);
+                three_digits(p + UPPER256_AT, (int)up);
+                p += UPPER256_LEN;
+            }
+            if (set_lower)
+            {
+                *p++ = set_upper ? ';' : '\033';
+                if (!set_upper)
+                    *p++ = '[';
+                memcpy(p, k_lower256, LOWER256_LEN);
+                three_digits(p + 5, (int)low);
+                p += LOWER256_LEN;
+            }
+            if (set_upper || set_lower)
+                *p++ = 'm';
+            memcpy(p, k_glyph, GLYPH_LEN);
+            p += GLYPH_LEN;
+            in_run = col + 1 < width && (index256_at(was_up + 3 * (col + 1)) != index256_at(now_up + 3 * (col + 1)) ||
+                                         (has_lower && index256_at(was_low + 3 * (col + 1)) != index256_at(now_low + 3 * (col + 1))));
+            if (!in_run)
+            {
+                memcpy(p, k_reset, RESET_LEN);
+                p += RESET_LEN;
+            }
+        }
+    }
+    *bytes = (size_t)(p - text);
+    return TRT_HOST_OK;
+}
+
 /* The DEC sixel image (csrc/trt_sixel.h holds the format): the 240 fixed palette entries as colour registers, then the picture in bands of
  * six pixel rows, a band one colour row per index that occurs in it.  Plain loops over the search, on purpose without that header -- this is
  * what the header's arithmetic and the device kernels are held against.  No terminal has shown this picture: the format is written from

@@ -3,7 +3,9 @@
 // chain of one: there is no other set of kernels.  A text has one of two KINDS of cell: the full text's, two columns wide
 // (trt_ansi_delta.h), and half-block cells, two pixel rows a cell (trt_ansi_delta_half.h).  Each header holds its format, the record
 // lengths and bytes, and the LANE'S WALK: which bytes of the two frames a lane loads for its cells.  This file holds the tile scheme,
-// once for both kinds: the prefix sum that gives every record its place.
+// once for all kinds: the prefix sum that gives every record its place.  Each of the two shapes of cell also exists in the xterm 256-colour
+// palette (trt_ansi256_delta.h, trt_ansi256_delta_half.h): the same frames of RGB8 bytes, which the walk maps to palette indices itself, a
+// cell changed where an INDEX differs; to this file two more kinds, nothing else.
 //
 //   measure   a grid of tiles x n, the pair in blockIdx.y: a workgroup per tile of TRT_DELTA_TILE cells (row-major; over the TEXT rows
 //             for half-block cells), a lane per TRT_DELTA_LANE_CELLS consecutive cells: the kind's walk reads the pair's two frames and
@@ -20,6 +22,8 @@
 // the shown frame is somebody else's memory, behind a frame of the chain the next one.  LDS: the waves' sums, nothing else.
 #pragma once
 
+#include "trt_ansi256_delta.h"
+#include "trt_ansi256_delta_half.h"
 #include "trt_ansi_delta.h"
 #include "trt_ansi_delta_chain.h"
 #include "trt_ansi_delta_half.h"
@@ -49,6 +53,26 @@ struct DeltaHalf
         return trt_delta_half_lane_cells(shown, next, width, rows, tile, thread);
     }
     static __device__ __forceinline__ unsigned byte(const Lane &c, int j, unsigned k) { return trt_delta_half_lane_byte(&c, j, k); }
+};
+
+struct Delta256Full
+{
+    using Lane = trt_delta256_lane;
+    static __device__ __forceinline__ Lane cells(const unsigned char *shown, const unsigned char *next, int width, int rows, unsigned long long tile, unsigned thread)
+    {
+        return trt_delta256_lane_cells(shown, next, width, rows, tile, thread);
+    }
+    static __device__ __forceinline__ unsigned byte(const Lane &c, int j, unsigned k) { return trt_delta256_lane_byte(&c, j, k); }
+};
+
+struct Delta256Half
+{
+    using Lane = trt_delta256_half_lane;
+    static __device__ __forceinline__ Lane cells(const unsigned char *shown, const unsigned char *next, int width, int rows, unsigned long long tile, unsigned thread)
+    {
+        return trt_delta256_half_lane_cells(shown, next, width, rows, tile, thread);
+    }
+    static __device__ __forceinline__ unsigned byte(const Lane &c, int j, unsigned k) { return trt_delta256_half_lane_byte(&c, j, k); }
 };
 
 template <class Kind>
@@ -182,6 +206,30 @@ __global__ __launch_bounds__(TRT_DELTA_BLOCK) void ansi_delta_half_chain_write_k
                                                                                      const unsigned long long *tile_at, unsigned char *out, unsigned long long capacity)
 {
     delta_chain_write<DeltaHalf>(shown, frames, width, rows, tile_at, out, capacity);
+}
+
+__global__ __launch_bounds__(TRT_DELTA_BLOCK) void ansi256_delta_chain_measure_kernel(const unsigned char *shown, const unsigned char *frames, int width, int rows,
+                                                                                     unsigned *tile_bytes)
+{
+    delta_chain_measure<Delta256Full>(shown, frames, width, rows, tile_bytes);
+}
+
+__global__ __launch_bounds__(TRT_DELTA_BLOCK) void ansi256_delta_half_chain_measure_kernel(const unsigned char *shown, const unsigned char *frames, int width, int rows,
+                                                                                          unsigned *tile_bytes)
+{
+    delta_chain_measure<Delta256Half>(shown, frames, width, rows, tile_bytes);
+}
+
+__global__ __launch_bounds__(TRT_DELTA_BLOCK) void ansi256_delta_chain_write_kernel(const unsigned char *shown, const unsigned char *frames, int width, int rows,
+                                                                                   const unsigned long long *tile_at, unsigned char *out, unsigned long long capacity)
+{
+    delta_chain_write<Delta256Full>(shown, frames, width, rows, tile_at, out, capacity);
+}
+
+__global__ __launch_bounds__(TRT_DELTA_BLOCK) void ansi256_delta_half_chain_write_kernel(const unsigned char *shown, const unsigned char *frames, int width, int rows,
+                                                                                        const unsigned long long *tile_at, unsigned char *out, unsigned long long capacity)
+{
+    delta_chain_write<Delta256Half>(shown, frames, width, rows, tile_at, out, capacity);
 }
 
 // ONE workgroup of TRT_DELTA_SCAN_BLOCK threads: the scan over all n * tiles sums from `base`, a frame's first tile anywhere in a turn,

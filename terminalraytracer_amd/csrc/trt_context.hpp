@@ -121,6 +121,10 @@ using trt_impl::kEventRing;
 // that the kernels keep reading ONE table base and ONE pool base whoever built what.
 constexpr int kEyeSlots = 8; // = the most frames a trt_dist keeps in flight
 
+// The KIND of a delta text: the shape of its cells and its colours.  The full text's cells or half-block cells, in 24-bit colour
+// (trt_ansi_delta.h, trt_ansi_delta_half.h) or in the xterm 256-colour palette (trt_ansi256_delta.h, trt_ansi256_delta_half.h).
+enum DeltaKind : int { kDeltaFull, kDeltaHalf, kDelta256, kDelta256Half, kDeltaKinds };
+
 struct SceneTables
 {
     int device = 0;
@@ -213,8 +217,7 @@ struct trt_context
     DeviceBuffer<unsigned char> d_delta_frames[2];
     int shown_at = 0, shown_frame = 0;
     bool shown_valid = false; // false: the next delta call sends a keyframe
-    bool shown_half = false;  // the text the shown frame was sent as: half-block cells (trt_ansi_delta_half.h) or the full text's;
-                              // a delta call of the other kind sends a keyframe
+    DeltaKind shown_kind = kDeltaFull; // the text the shown frame was sent as, one of four; a delta call of any other kind sends a keyframe
     trt_rowset shown_rows{};
     DeviceBuffer<unsigned> d_delta_tile_bytes;         // per tile of cells: the bytes of its records
     DeviceBuffer<unsigned long long> d_delta_tile_at;  // ... and where they start in the text

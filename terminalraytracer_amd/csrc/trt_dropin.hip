@@ -266,6 +266,20 @@ extern "C" int trt_render_frame_ansi_delta_half(const Scene *scene, int width, i
                               trt_render_host_ansi_delta_half);
 }
 
+extern "C" int trt_render_frame_ansi256_delta(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text, size_t capacity_bytes,
+                                              size_t *bytes)
+{
+    return render_frame_delta(scene, width, height, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, trt_ansi256_delta_capacity,
+                              trt_render_host_ansi256_delta);
+}
+
+extern "C" int trt_render_frame_ansi256_delta_half(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text, size_t capacity_bytes,
+                                                   size_t *bytes)
+{
+    return render_frame_delta(scene, width, height, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, trt_ansi256_delta_half_capacity,
+                              trt_render_host_ansi256_delta_half);
+}
+
 // the sixel image: a text whose length the call reports, as the delta texts', but of the frame alone -- no shown frame is read or changed
 extern "C" int trt_render_frame_sixel(const Scene *scene, int width, int height, int bounce_limit, int rays_per_pixel, char *text, size_t capacity_bytes, size_t *bytes)
 {

@@ -1408,8 +1408,9 @@ extern "C" int trt_kernel_info(trt_context *ctx, int *vgprs, int *sgprs, int *st
     return TRT_OK;
 }
 
-// ---- the delta texts (trt_ansi_delta.h: the full text's cells; trt_ansi_delta_half.h: half-block cells; trt_ansi_delta_chain.h: a chain of n
-// texts; trt_ansi_delta.hpp: the kernels).  ONE path: the text between two frames is a chain of one, a single frame a batch of one ----
+// ---- the delta texts (trt_ansi_delta.h: the full text's cells; trt_ansi_delta_half.h: half-block cells; trt_ansi256_delta.h and
+// trt_ansi256_delta_half.h: the two in the xterm 256-colour palette; trt_ansi_delta_chain.h: a chain of n texts; trt_ansi_delta.hpp: the
+// kernels).  ONE path for the four KINDS (DeltaKind): the text between two frames is a chain of one, a single frame a batch of one ----
 
 static_assert(TRT_DELTA_CHAIN_MAX == TRT_BATCH_MAX, "a chain holds a batch's frames");
 
@@ -1427,7 +1428,17 @@ extern "C" size_t trt_ansi_delta_half_capacity(int width, int rows)
     return (size_t)std::max(trt_ansi_half_text_bytes(width, rows), trt_delta_half_bound(width, rows));
 }
 
-// What a kind of MEASURED text -- one whose length depends on the picture, so that the device reports it: the two delta texts and the sixel
+extern "C" size_t trt_ansi256_delta_capacity(int width, int rows)
+{
+    return (size_t)trt_delta256_capacity(width, rows);
+}
+
+extern "C" size_t trt_ansi256_delta_half_capacity(int width, int rows)
+{
+    return (size_t)trt_delta256_half_capacity(width, rows);
+}
+
+// What a kind of MEASURED text -- one whose length depends on the picture, so that the device reports it: the four delta texts and the sixel
 // image (below) -- says of a frame size: whether it has such a text, the refusal where it has none, and the room any text of the size fits.
 struct MeasuredText
 {
@@ -1436,10 +1447,16 @@ struct MeasuredText
     int max_width, max_rows;
     size_t (*capacity)(int width, int rows);
 };
-static const MeasuredText kDeltaText[2] = { // by `half`: the full text's cells, half-block cells
+static const MeasuredText kDeltaText[kDeltaKinds] = { // by DeltaKind
     {trt_delta_size_ok, "%d x %d: a delta text has 1 to %d cells per row and 1 to %d rows", TRT_DELTA_MAX_WIDTH, TRT_DELTA_MAX_ROWS, trt_ansi_delta_capacity},
     {trt_delta_half_size_ok, "%d x %d: a half-block delta text has 1 to %d cells per row and 1 to %d text rows", TRT_DELTA_HALF_MAX_WIDTH, TRT_DELTA_HALF_MAX_TEXT_ROWS,
-     trt_ansi_delta_half_capacity}};
+     trt_ansi_delta_half_capacity},
+    {trt_delta256_size_ok, "%d x %d: a 256-colour delta text has 1 to %d cells per row and 1 to %d rows", TRT_DELTA256_MAX_WIDTH, TRT_DELTA256_MAX_ROWS,
+     trt_ansi256_delta_capacity},
+    {trt_delta256_half_size_ok, "%d x %d: a half-block 256-colour delta text has 1 to %d cells per row and 1 to %d text rows", TRT_DELTA256_HALF_MAX_WIDTH,
+     TRT_DELTA256_HALF_MAX_TEXT_ROWS, trt_ansi256_delta_half_capacity}};
+// the shape of a kind's cells: its tiles are of the text rows' cells
+static bool delta_half_cells(DeltaKind kind) { return kind == kDeltaHalf || kind == kDelta256Half; }
 static const MeasuredText kSixelText = {trt_sixel_size_ok, "%d x %d: a sixel image has 1 to %d pixels a row and 1 to %d rows", TRT_SIXEL_MAX, TRT_SIXEL_MAX,
                                         trt_sixel_capacity};
 
@@ -1501,17 +1518,21 @@ static int copy_out_measured(trt_context *ctx, int n, size_t room, char *text, s
 }
 
 // measure, offsets, write on `stream` for the pairs (d_shown, frame 0), (frame 0, frame 1) ... of the n frames at d_frames, of the full text's
-// cells or of half-block cells (the tiles are then of the text rows' cells): text b at d_text + base + the lengths before it, its length at
+// cells or of half-block cells (the tiles are then of the text rows' cells), in 24-bit colour or in the palette: text b at d_text + base + the lengths before it, its length at
 // d_bytes[b]; capacity_bytes: the bytes at d_text; marks: four events, recorded around and between the launches (the ..._kernel_times entries)
-static int launch_ansi_delta(trt_context *ctx, hipStream_t stream, bool half, const unsigned char *d_shown, const unsigned char *d_frames, int n, int width, int rows,
+static int launch_ansi_delta(trt_context *ctx, hipStream_t stream, DeltaKind kind, const unsigned char *d_shown, const unsigned char *d_frames, int n, int width, int rows,
                              void *d_text, size_t capacity_bytes, unsigned long long base, unsigned long long *d_bytes, const Event *marks = nullptr)
 {
     static const struct
     {
         void (*measure)(const unsigned char *, const unsigned char *, int, int, unsigned *);
         void (*write)(const unsigned char *, const unsigned char *, int, int, const unsigned long long *, unsigned char *, unsigned long long);
-    } kernels[2] = {{trt::ansi_delta_chain_measure_kernel, trt::ansi_delta_chain_write_kernel}, {trt::ansi_delta_half_chain_measure_kernel, trt::ansi_delta_half_chain_write_kernel}};
-    const unsigned long long cells = (unsigned long long)width * (unsigned long long)(half ? trt_ansi_half_text_rows(rows) : rows), tiles = trt_delta_tiles(cells);
+    } kernels[kDeltaKinds] = {{trt::ansi_delta_chain_measure_kernel, trt::ansi_delta_chain_write_kernel},
+                              {trt::ansi_delta_half_chain_measure_kernel, trt::ansi_delta_half_chain_write_kernel},
+                              {trt::ansi256_delta_chain_measure_kernel, trt::ansi256_delta_chain_write_kernel},
+                              {trt::ansi256_delta_half_chain_measure_kernel, trt::ansi256_delta_half_chain_write_kernel}};
+    const unsigned long long cells = (unsigned long long)width * (unsigned long long)(delta_half_cells(kind) ? trt_ansi_half_text_rows(rows) : rows),
+                             tiles = trt_delta_tiles(cells);
     const size_t all = (size_t)tiles * (size_t)n;
     if (ctx->d_delta_tile_bytes.capacity < all || ctx->d_delta_tile_at.capacity < all)
         HIP_TRY(hipStreamSynchronize(stream)); // a text in flight may still use the old sums
@@ -1520,14 +1541,14 @@ static int launch_ansi_delta(trt_context *ctx, hipStream_t stream, bool half, co
     const dim3 grid((unsigned)tiles, (unsigned)n);
     if (marks)
         HIP_TRY(hipEventRecord(marks[0], stream));
-    hipLaunchKernelGGL(kernels[half].measure, grid, dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_frames, width, rows, ctx->d_delta_tile_bytes.ptr);
+    hipLaunchKernelGGL(kernels[kind].measure, grid, dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_frames, width, rows, ctx->d_delta_tile_bytes.ptr);
     if (marks)
         HIP_TRY(hipEventRecord(marks[1], stream));
     hipLaunchKernelGGL(trt::ansi_delta_chain_offsets_kernel, dim3(1), dim3(TRT_DELTA_SCAN_BLOCK), 0, stream, (const unsigned *)ctx->d_delta_tile_bytes.ptr, tiles, (unsigned)n,
                        base, ctx->d_delta_tile_at.ptr, d_bytes);
     if (marks)
         HIP_TRY(hipEventRecord(marks[2], stream));
-    hipLaunchKernelGGL(kernels[half].write, grid, dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_frames, width, rows, (const unsigned long long *)ctx->d_delta_tile_at.ptr,
+    hipLaunchKernelGGL(kernels[kind].write, grid, dim3(TRT_DELTA_BLOCK), 0, stream, d_shown, d_frames, width, rows, (const unsigned long long *)ctx->d_delta_tile_at.ptr,
                        (unsigned char *)d_text, (unsigned long long)capacity_bytes);
     if (marks)
         HIP_TRY(hipEventRecord(marks[3], stream));
@@ -1535,19 +1556,19 @@ static int launch_ansi_delta(trt_context *ctx, hipStream_t stream, bool half, co
     return TRT_OK;
 }
 
-// The formatting alone, all eight entries: trt_ansi_delta(_half)_from_rgb8_device with d_next as a chain of one frame,
-// trt_ansi_delta(_half)_chain_from_rgb8_device, and with `ms` their ..._kernel_times forms, which are synchronous
-static int delta_from_rgb8(trt_context *ctx, bool half, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text, size_t capacity_bytes,
+// The formatting alone, all sixteen entries: trt_ansi[256]_delta(_half)_from_rgb8_device with d_next as a chain of one frame,
+// trt_ansi[256]_delta(_half)_chain_from_rgb8_device, and with `ms` their ..._kernel_times forms, which are synchronous
+static int delta_from_rgb8(trt_context *ctx, DeltaKind kind, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text, size_t capacity_bytes,
                            unsigned long long *d_bytes, float *ms = nullptr)
 {
     if (!ctx || !d_shown_rgb8 || !d_frames_rgb8 || !d_text || !d_bytes)
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
     if (n < 1 || n > TRT_BATCH_MAX)
         return fail(TRT_ERR_ARGUMENT, "a chain has 1 to %d frames, %d given", TRT_BATCH_MAX, n);
-    int rc = check_measured_size(kDeltaText[half], width, rows);
+    int rc = check_measured_size(kDeltaText[kind], width, rows);
     if (rc)
         return rc;
-    const size_t need = (size_t)n * kDeltaText[half].capacity(width, rows);
+    const size_t need = (size_t)n * kDeltaText[kind].capacity(width, rows);
     if (capacity_bytes < need)
         return fail(TRT_ERR_CAPACITY, "%d delta text(s) of %d x %d need room for %zu B, %zu given", n, width, rows, need, capacity_bytes);
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1555,7 +1576,7 @@ static int delta_from_rgb8(trt_context *ctx, bool half, const void *d_shown_rgb8
     if (ms)
         for (Event &e : marks)
             HIP_TRY(e.create());
-    rc = launch_ansi_delta(ctx, ctx->stream, half, (const unsigned char *)d_shown_rgb8, (const unsigned char *)d_frames_rgb8, n, width, rows, d_text, capacity_bytes, 0, d_bytes,
+    rc = launch_ansi_delta(ctx, ctx->stream, kind, (const unsigned char *)d_shown_rgb8, (const unsigned char *)d_frames_rgb8, n, width, rows, d_text, capacity_bytes, 0, d_bytes,
                            ms ? marks : nullptr);
     if (!ms)
         return rc;
@@ -1570,52 +1591,100 @@ static int delta_from_rgb8(trt_context *ctx, bool half, const void *d_shown_rgb8
 extern "C" int trt_ansi_delta_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
                                                size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    return delta_from_rgb8(ctx, false, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes);
+    return delta_from_rgb8(ctx, kDeltaFull, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes);
 }
 
 extern "C" int trt_ansi_delta_half_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
                                                     size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    return delta_from_rgb8(ctx, true, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes);
+    return delta_from_rgb8(ctx, kDeltaHalf, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes);
 }
 
 extern "C" int trt_ansi_delta_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
                                            size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
 {
-    return ms ? delta_from_rgb8(ctx, false, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
+    return ms ? delta_from_rgb8(ctx, kDeltaFull, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
 }
 
 extern "C" int trt_ansi_delta_half_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
                                                 size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
 {
-    return ms ? delta_from_rgb8(ctx, true, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
+    return ms ? delta_from_rgb8(ctx, kDeltaHalf, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
 }
 
 extern "C" int trt_ansi_delta_chain_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
                                                      size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    return delta_from_rgb8(ctx, false, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes);
+    return delta_from_rgb8(ctx, kDeltaFull, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes);
 }
 
 extern "C" int trt_ansi_delta_half_chain_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
                                                           size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    return delta_from_rgb8(ctx, true, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes);
+    return delta_from_rgb8(ctx, kDeltaHalf, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes);
 }
 
 extern "C" int trt_ansi_delta_chain_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
                                                  size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
 {
-    return ms ? delta_from_rgb8(ctx, false, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
+    return ms ? delta_from_rgb8(ctx, kDeltaFull, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
 }
 
 extern "C" int trt_ansi_delta_half_chain_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
                                                       size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
 {
-    return ms ? delta_from_rgb8(ctx, true, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
+    return ms ? delta_from_rgb8(ctx, kDeltaHalf, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
 }
 
-// ---- the render entries of both delta texts: one shown frame, which remembers the kind of text it was sent as ----
+extern "C" int trt_ansi256_delta_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                                size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return delta_from_rgb8(ctx, kDelta256, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes);
+}
+
+extern "C" int trt_ansi256_delta_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                            size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
+{
+    return ms ? delta_from_rgb8(ctx, kDelta256, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
+}
+
+extern "C" int trt_ansi256_delta_chain_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
+                                                      size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return delta_from_rgb8(ctx, kDelta256, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes);
+}
+
+extern "C" int trt_ansi256_delta_chain_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
+                                                  size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
+{
+    return ms ? delta_from_rgb8(ctx, kDelta256, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
+}
+
+extern "C" int trt_ansi256_delta_half_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                                     size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return delta_from_rgb8(ctx, kDelta256Half, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes);
+}
+
+extern "C" int trt_ansi256_delta_half_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_next_rgb8, int width, int rows, void *d_text,
+                                                 size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
+{
+    return ms ? delta_from_rgb8(ctx, kDelta256Half, d_shown_rgb8, d_next_rgb8, 1, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
+}
+
+extern "C" int trt_ansi256_delta_half_chain_from_rgb8_device(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
+                                                           size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return delta_from_rgb8(ctx, kDelta256Half, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes);
+}
+
+extern "C" int trt_ansi256_delta_half_chain_kernel_times(trt_context *ctx, const void *d_shown_rgb8, const void *d_frames_rgb8, int n, int width, int rows, void *d_text,
+                                                       size_t capacity_bytes, unsigned long long *d_bytes, float *ms)
+{
+    return ms ? delta_from_rgb8(ctx, kDelta256Half, d_shown_rgb8, d_frames_rgb8, n, width, rows, d_text, capacity_bytes, d_bytes, ms) : fail(TRT_ERR_ARGUMENT, "NULL argument");
+}
+
+// ---- the render entries of the four delta texts: one shown frame, which remembers the kind of text it was sent as ----
 
 extern "C" int trt_ansi_delta_reset(trt_context *ctx)
 {
@@ -1627,9 +1696,9 @@ extern "C" int trt_ansi_delta_reset(trt_context *ctx)
 
 // check_render_measured for n delta texts of the kind
 static int check_render_delta(const trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, const void *text,
-                              size_t capacity_bytes, const void *bytes, bool half)
+                              size_t capacity_bytes, const void *bytes, DeltaKind kind)
 {
-    return check_render_measured(ctx, kDeltaText[half], cameras, n, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, [&](size_t need) {
+    return check_render_measured(ctx, kDeltaText[kind], cameras, n, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, [&](size_t need) {
         return fail(TRT_ERR_CAPACITY, "%d text(s) of %d x %d owned rows need room for %zu B, %zu given", n, rows->width, trt_rowset_rows(rows), need, capacity_bytes);
     });
 }
@@ -1639,19 +1708,19 @@ static bool same_rowset(const trt_rowset &a, const trt_rowset &b)
     return a.width == b.width && a.height == b.height && a.tile_rows == b.tile_rows && a.tile_first == b.tile_first && a.tile_step == b.tile_step;
 }
 
-// trt_render_device_ansi_delta and trt_render_device_batch_ansi_delta, and their _half forms: n cameras as n texts back to back, text 0
+// trt_render_device_ansi_delta and trt_render_device_batch_ansi_delta, their _half forms and the ansi256 forms of the four: n cameras as n texts back to back, text 0
 // against the shown frame.  `batch` as in render_host_as: the batch route, which picks the render kernel's BATCH form and counts for
 // trt_batch_info; otherwise n is 1 and the frame is the single frame's launch.
 static int render_device_delta(trt_context *ctx, const Camera *cameras, int n, bool batch, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
-                               size_t capacity_bytes, unsigned long long *d_bytes, bool half)
+                               size_t capacity_bytes, unsigned long long *d_bytes, DeltaKind kind)
 {
-    int rc = check_render_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, half);
+    int rc = check_render_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, kind);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const int width = rows->width, owned = trt_rowset_rows(rows);
     const size_t frame = (size_t)owned * width * 3;
-    const bool keyframe = !(ctx->shown_valid && ctx->shown_half == half && same_rowset(ctx->shown_rows, *rows));
+    const bool keyframe = !(ctx->shown_valid && ctx->shown_kind == kind && same_rowset(ctx->shown_rows, *rows));
     const int into = ctx->shown_at ^ 1;
     if (ctx->d_delta_frames[into].capacity < frame * n)
     { // only the buffer rendered into grows, with nothing in flight that uses it: a buffer that grows loses its contents, and the other one holds the shown frame
@@ -1667,24 +1736,24 @@ static int render_device_delta(trt_context *ctx, const Camera *cameras, int n, b
     if (rc)
         return rc;
     if (keyframe)
-    { // text 0 is the whole text of frame 0, as trt_render_device_ansi or trt_render_device_ansi_half writes it; the chain of the pairs behind it starts where that text ends
-        const Output kind = half ? kHalfText : kText;
-        const unsigned long long whole = frame_bytes(kind, width, owned);
-        launch_text_from_rgb8(ctx->stream, kind, frames, width, owned, d_text);
+    { // text 0 is the whole text of frame 0, as trt_render_device_ansi[256][_half] writes it; the chain of the pairs behind it starts where that text ends
+        static const Output kWhole[kDeltaKinds] = {kText, kHalfText, kText256, kHalfText256};
+        const unsigned long long whole = frame_bytes(kWhole[kind], width, owned);
+        launch_text_from_rgb8(ctx->stream, kWhole[kind], frames, width, owned, d_text);
         hipLaunchKernelGGL(trt::ansi_delta_keyframe_bytes_kernel, dim3(1), dim3(1), 0, ctx->stream, d_bytes, whole);
         HIP_TRY(hipGetLastError());
         if (n > 1)
-            rc = launch_ansi_delta(ctx, ctx->stream, half, frames, frames + frame, n - 1, width, owned, d_text, capacity_bytes, whole, d_bytes + 1);
+            rc = launch_ansi_delta(ctx, ctx->stream, kind, frames, frames + frame, n - 1, width, owned, d_text, capacity_bytes, whole, d_bytes + 1);
     }
     else // a shown frame of this size: the other buffer holds it, untouched since the call that rendered it
-        rc = launch_ansi_delta(ctx, ctx->stream, half, ctx->d_delta_frames[ctx->shown_at].ptr + (size_t)ctx->shown_frame * frame, frames, n, width, owned, d_text, capacity_bytes,
+        rc = launch_ansi_delta(ctx, ctx->stream, kind, ctx->d_delta_frames[ctx->shown_at].ptr + (size_t)ctx->shown_frame * frame, frames, n, width, owned, d_text, capacity_bytes,
                                0, d_bytes);
     if (rc)
         return rc;
     ctx->shown_at = into; // the buffers flip: the last frame is the shown one from here on, where it was rendered
     ctx->shown_frame = n - 1;
     ctx->shown_rows = *rows;
-    ctx->shown_half = half;
+    ctx->shown_kind = kind;
     ctx->shown_valid = true;
     return TRT_OK;
 }
@@ -1692,37 +1761,61 @@ static int render_device_delta(trt_context *ctx, const Camera *cameras, int n, b
 extern "C" int trt_render_device_ansi_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
                                             size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    return render_device_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, false);
+    return render_device_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, kDeltaFull);
 }
 
 extern "C" int trt_render_device_ansi_delta_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
                                                  size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    return render_device_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, true);
+    return render_device_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, kDeltaHalf);
 }
 
 extern "C" int trt_render_device_batch_ansi_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
                                                   size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    return render_device_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, false);
+    return render_device_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, kDeltaFull);
 }
 
 extern "C" int trt_render_device_batch_ansi_delta_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel,
                                                        void *d_text, size_t capacity_bytes, unsigned long long *d_bytes)
 {
-    return render_device_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, true);
+    return render_device_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, kDeltaHalf);
 }
 
-// The copy-out of the four host entries, timed as `name` under print_host_times(): the n texts in the context's text buffer, their
+extern "C" int trt_render_device_ansi256_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                                              size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return render_device_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, kDelta256);
+}
+
+extern "C" int trt_render_device_batch_ansi256_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                                                    size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return render_device_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, kDelta256);
+}
+
+extern "C" int trt_render_device_ansi256_delta_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                                                   size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return render_device_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, kDelta256Half);
+}
+
+extern "C" int trt_render_device_batch_ansi256_delta_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, void *d_text,
+                                                         size_t capacity_bytes, unsigned long long *d_bytes)
+{
+    return render_device_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, d_text, capacity_bytes, d_bytes, kDelta256Half);
+}
+
+// The copy-out of the eight host entries, timed as `name` under print_host_times(): the n texts in the context's text buffer, their
 // lengths read back, then exactly their sum -- two transfers whatever n is.
 static int render_host_delta(trt_context *ctx, const Camera *cameras, int n, bool batch, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
-                             size_t capacity_bytes, size_t *bytes, bool half, const char *name)
+                             size_t capacity_bytes, size_t *bytes, DeltaKind kind, const char *name)
 {
-    int rc = check_render_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, half);
+    int rc = check_render_delta(ctx, cameras, n, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, kind);
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t room = (size_t)n * kDeltaText[half].capacity(rows->width, trt_rowset_rows(rows));
+    const size_t room = (size_t)n * kDeltaText[kind].capacity(rows->width, trt_rowset_rows(rows));
     if (ctx->d_text.capacity < room || ctx->d_delta_bytes.capacity < (size_t)n)
         HIP_TRY(hipStreamSynchronize(ctx->stream)); // a text in flight may still be written to the old buffers
     HIP_TRY(ctx->d_text.reserve(room));
@@ -1731,7 +1824,7 @@ static int render_host_delta(trt_context *ctx, const Camera *cameras, int n, boo
     // its texts grow.  A batch: the lengths now and the texts' sum when it is known -- n capacities are hundreds of MB at 1920x1080.
     HIP_TRY(ctx->h_staging.reserve(batch ? sizeof(unsigned long long) * TRT_BATCH_MAX : room));
     const double t_begin = host_now_ms();
-    rc = render_device_delta(ctx, cameras, n, batch, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, room, ctx->d_delta_bytes.ptr, half);
+    rc = render_device_delta(ctx, cameras, n, batch, rows, bounce_limit, rays_per_pixel, ctx->d_text.ptr, room, ctx->d_delta_bytes.ptr, kind);
     if (rc)
         return rc;
     unsigned long long sum = 0;
@@ -1750,25 +1843,49 @@ static int render_host_delta(trt_context *ctx, const Camera *cameras, int n, boo
 extern "C" int trt_render_host_ansi_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
                                           size_t capacity_bytes, size_t *bytes)
 {
-    return render_host_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, false, "trt_render_host_ansi_delta");
+    return render_host_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, kDeltaFull, "trt_render_host_ansi_delta");
 }
 
 extern "C" int trt_render_host_ansi_delta_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
                                                size_t capacity_bytes, size_t *bytes)
 {
-    return render_host_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, true, "trt_render_host_ansi_delta_half");
+    return render_host_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, kDeltaHalf, "trt_render_host_ansi_delta_half");
 }
 
 extern "C" int trt_render_host_batch_ansi_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
                                                 size_t capacity_bytes, size_t *bytes)
 {
-    return render_host_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, false, "trt_render_host_batch_ansi_delta");
+    return render_host_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, kDeltaFull, "trt_render_host_batch_ansi_delta");
 }
 
 extern "C" int trt_render_host_batch_ansi_delta_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
                                                      size_t capacity_bytes, size_t *bytes)
 {
-    return render_host_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, true, "trt_render_host_batch_ansi_delta_half");
+    return render_host_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, kDeltaHalf, "trt_render_host_batch_ansi_delta_half");
+}
+
+extern "C" int trt_render_host_ansi256_delta(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
+                                            size_t capacity_bytes, size_t *bytes)
+{
+    return render_host_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, kDelta256, "trt_render_host_ansi256_delta");
+}
+
+extern "C" int trt_render_host_batch_ansi256_delta(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
+                                                  size_t capacity_bytes, size_t *bytes)
+{
+    return render_host_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, kDelta256, "trt_render_host_batch_ansi256_delta");
+}
+
+extern "C" int trt_render_host_ansi256_delta_half(trt_context *ctx, const Camera *camera, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
+                                                 size_t capacity_bytes, size_t *bytes)
+{
+    return render_host_delta(ctx, camera, 1, false, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, kDelta256Half, "trt_render_host_ansi256_delta_half");
+}
+
+extern "C" int trt_render_host_batch_ansi256_delta_half(trt_context *ctx, const Camera *cameras, int n, const trt_rowset *rows, int bounce_limit, int rays_per_pixel, char *text,
+                                                       size_t capacity_bytes, size_t *bytes)
+{
+    return render_host_delta(ctx, cameras, n, true, rows, bounce_limit, rays_per_pixel, text, capacity_bytes, bytes, kDelta256Half, "trt_render_host_batch_ansi256_delta_half");
 }
 
 // ---- the sixel image (trt_sixel.h: the format, its position map and its lane map; trt_sixel.hpp: the kernels).  Its length depends on the

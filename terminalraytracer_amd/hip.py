@@ -131,6 +131,26 @@ SYMBOLS = {
     "trt_render_device_batch_ansi_delta_half": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ, _VP]),
     "trt_render_host_batch_ansi_delta": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
     "trt_render_host_batch_ansi_delta_half": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
+    "trt_ansi256_delta_capacity": (_SZ, [_I, _I]),
+    "trt_ansi256_delta_half_capacity": (_SZ, [_I, _I]),
+    "trt_ansi256_delta_from_rgb8_device": (_I, [_VP, _VP, _VP, _I, _I, _VP, _SZ, _VP]),
+    "trt_ansi256_delta_half_from_rgb8_device": (_I, [_VP, _VP, _VP, _I, _I, _VP, _SZ, _VP]),
+    "trt_ansi256_delta_kernel_times": (_I, [_VP, _VP, _VP, _I, _I, _VP, _SZ, _VP, C.POINTER(C.c_float)]),
+    "trt_ansi256_delta_half_kernel_times": (_I, [_VP, _VP, _VP, _I, _I, _VP, _SZ, _VP, C.POINTER(C.c_float)]),
+    "trt_render_device_ansi256_delta": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ, _VP]),
+    "trt_render_device_ansi256_delta_half": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ, _VP]),
+    "trt_render_host_ansi256_delta": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
+    "trt_render_host_ansi256_delta_half": (_I, [_VP, C.POINTER(L.Camera), C.POINTER(RowSet), _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
+    "trt_render_frame_ansi256_delta": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
+    "trt_render_frame_ansi256_delta_half": (_I, [C.POINTER(L.Scene), _I, _I, _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
+    "trt_ansi256_delta_chain_from_rgb8_device": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP]),
+    "trt_ansi256_delta_half_chain_from_rgb8_device": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP]),
+    "trt_ansi256_delta_chain_kernel_times": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP, C.POINTER(C.c_float)]),
+    "trt_ansi256_delta_half_chain_kernel_times": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _SZ, _VP, C.POINTER(C.c_float)]),
+    "trt_render_device_batch_ansi256_delta": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ, _VP]),
+    "trt_render_device_batch_ansi256_delta_half": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ, _VP]),
+    "trt_render_host_batch_ansi256_delta": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
+    "trt_render_host_batch_ansi256_delta_half": (_I, [_VP, _VP, _I, C.POINTER(RowSet), _I, _I, _VP, _SZ, C.POINTER(_SZ)]),
     "trt_synchronize": (_I, [_VP]),
     "trt_kernel_times": (_I, [_VP, C.POINTER(C.c_float), _I]),
     "trt_render_kernel_times": (_I, [_VP, C.POINTER(C.c_float), C.POINTER(C.c_float), _I]),
@@ -651,7 +671,7 @@ class Context:
         return self._render_host_delta("trt_render_host_ansi_delta", ansi_delta_capacity, camera_array, rows, bounce_limit, rays_per_pixel, out)
 
     def ansi_delta_reset(self):
-        """forget the shown frame: the next delta text, of either kind, is a keyframe (trt_ansi_delta_reset)"""
+        """forget the shown frame: the next delta text, of any of the four kinds, is a keyframe (trt_ansi_delta_reset)"""
         _check(lib().trt_ansi_delta_reset(self._h))
 
     def ansi_delta_half_from_rgb8(self, shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr):
@@ -673,6 +693,30 @@ class Context:
         """the same into host memory: the uint8 text, exactly as long as the host is to write it (trt_render_host_ansi_delta_half); `out`:
         a uint8 buffer of ansi_delta_half_capacity bytes to reuse"""
         return self._render_host_delta("trt_render_host_ansi_delta_half", ansi_delta_half_capacity, camera_array, rows, bounce_limit, rays_per_pixel, out)
+
+    # the delta entries in the xterm 256-colour palette: the 24-bit ones' helpers, `half` choosing the cells as in the ansi256 entries
+
+    def ansi256_delta_from_rgb8(self, shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr, half=False):
+        """ansi_delta_from_rgb8 (half: ansi_delta_half_from_rgb8) in the palette: a cell has a record where its palette index changed
+        (trt_ansi256_delta_from_rgb8_device, trt_ansi256_delta_half_from_rgb8_device)"""
+        self._delta_from_rgb8("trt_ansi256_delta" + _half(half) + "_from_rgb8_device", shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr)
+
+    def ansi256_delta_kernel_times(self, shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr, half=False):
+        """the same, synchronous: ms of the (measure, offsets, write) kernels by HIP events (trt_ansi256_delta_kernel_times,
+        trt_ansi256_delta_half_kernel_times)"""
+        return self._delta_kernel_times("trt_ansi256_delta" + _half(half) + "_kernel_times", shown_ptr, next_ptr, width, rows, text_ptr, capacity_bytes, bytes_ptr)
+
+    def render_device_ansi256_delta(self, camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr, half=False):
+        """the frame as the 256-colour delta text against the context's shown frame (a keyframe, the whole 256-colour text, when there is
+        none for this rowset and this kind) in device memory, its length (a uint64) at the device address bytes_ptr
+        (trt_render_device_ansi256_delta, trt_render_device_ansi256_delta_half)"""
+        self._render_device_delta("trt_render_device_ansi256_delta" + _half(half), camera_array, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr)
+
+    def render_host_ansi256_delta(self, camera_array, rows, bounce_limit, rays_per_pixel, out=None, half=False):
+        """the same into host memory: the uint8 text, exactly as long as the host is to write it (trt_render_host_ansi256_delta,
+        trt_render_host_ansi256_delta_half); `out`: a uint8 buffer of ansi256_delta_capacity bytes to reuse"""
+        return self._render_host_delta("trt_render_host_ansi256_delta" + _half(half), functools.partial(ansi256_delta_capacity, half=half), camera_array, rows,
+                                       bounce_limit, rays_per_pixel, out)
 
     # the sixel image: a text whose length depends on the picture, reported as the delta entries report theirs
 
@@ -785,6 +829,27 @@ class Context:
     def render_host_batch_ansi_delta_half(self, cameras, rows, bounce_limit, rays_per_pixel, out=None):
         """the same in half-block cells (trt_render_host_batch_ansi_delta_half); `out`: n * ansi_delta_half_capacity bytes"""
         return self._render_host_batch_delta("trt_render_host_batch_ansi_delta_half", ansi_delta_half_capacity, cameras, rows, bounce_limit, rays_per_pixel, out)
+
+    def ansi256_delta_chain_from_rgb8(self, shown_ptr, frames_ptr, n, width, rows, text_ptr, capacity_bytes, bytes_ptr, half=False):
+        """ansi_delta_chain_from_rgb8 in the palette (trt_ansi256_delta_chain_from_rgb8_device, trt_ansi256_delta_half_chain_from_rgb8_device)"""
+        self._delta_chain_from_rgb8("trt_ansi256_delta" + _half(half) + "_chain_from_rgb8_device", shown_ptr, frames_ptr, n, width, rows, text_ptr, capacity_bytes, bytes_ptr)
+
+    def ansi256_delta_chain_kernel_times(self, shown_ptr, frames_ptr, n, width, rows, text_ptr, capacity_bytes, bytes_ptr, half=False):
+        """the same, synchronous: ms of the (measure, offsets, write) kernels by HIP events (trt_ansi256_delta_chain_kernel_times,
+        trt_ansi256_delta_half_chain_kernel_times)"""
+        return self._delta_chain_kernel_times("trt_ansi256_delta" + _half(half) + "_chain_kernel_times", shown_ptr, frames_ptr, n, width, rows, text_ptr, capacity_bytes,
+                                              bytes_ptr)
+
+    def render_device_batch_ansi256_delta(self, cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes, bytes_ptr, half=False):
+        """render_device_batch_ansi_delta in the palette (trt_render_device_batch_ansi256_delta, trt_render_device_batch_ansi256_delta_half)"""
+        self._render_device_batch_delta("trt_render_device_batch_ansi256_delta" + _half(half), cameras, rows, bounce_limit, rays_per_pixel, device_ptr, capacity_bytes,
+                                        bytes_ptr)
+
+    def render_host_batch_ansi256_delta(self, cameras, rows, bounce_limit, rays_per_pixel, out=None, half=False):
+        """the same into host memory: a list of n uint8 texts (trt_render_host_batch_ansi256_delta, trt_render_host_batch_ansi256_delta_half);
+        `out`: n * ansi256_delta_capacity bytes"""
+        return self._render_host_batch_delta("trt_render_host_batch_ansi256_delta" + _half(half), functools.partial(ansi256_delta_capacity, half=half), cameras, rows,
+                                             bounce_limit, rays_per_pixel, out)
 
     def batch_info(self):
         """(frames, render-kernel launches) of this context's most recent batch call (trt_batch_info)"""
@@ -1035,6 +1100,21 @@ def render_frame_ansi_delta_half(scene_data, width, height, bounce_limit=10, ray
     """Host-in frame as the half-block delta text against the frame this entry returned before (a keyframe the first time): the uint8
     text, as long as the host is to write it (trt_render_frame_ansi_delta_half)."""
     return _render_frame_delta("trt_render_frame_ansi_delta_half", ansi_delta_half_capacity, scene_data, width, height, bounce_limit, rays_per_pixel)
+
+
+def ansi256_delta_capacity(width, rows, half=False):
+    """room for any text the 256-colour delta entries write, the whole 256-colour text or the longest delta: rows * (13 * width + 13 +
+    5 * ((width + 1) // 2)), half: ((rows + 1) // 2) * (23 * width + 18); 0 when a size is not positive or above the format's limits
+    (trt_ansi256_delta_capacity, trt_ansi256_delta_half_capacity)"""
+    return _delta_capacity("trt_ansi256_delta" + _half(half) + "_capacity", width, rows)
+
+
+def render_frame_ansi256_delta(scene_data, width, height, bounce_limit=10, rays_per_pixel=10, half=False):
+    """Host-in frame as the 256-colour delta text against the frame this entry returned before (a keyframe the first time, and after a
+    delta entry of another kind): the uint8 text, as long as the host is to write it (trt_render_frame_ansi256_delta,
+    trt_render_frame_ansi256_delta_half)."""
+    return _render_frame_delta("trt_render_frame_ansi256_delta" + _half(half), functools.partial(ansi256_delta_capacity, half=half), scene_data, width, height,
+                               bounce_limit, rays_per_pixel)
 
 
 def render_frame_ansi(scene_data, width, height, bounce_limit=10, rays_per_pixel=10):

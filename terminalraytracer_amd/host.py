@@ -36,6 +36,8 @@ HOST_SYMBOLS = {
     "trt_emitter_ansi256_half_rgb8": (_I, [_VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_sixel_rgb8": (_I, [_VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_delta_half_rgb8": (_I, [_VP, _VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "trt_emitter_delta256_rgb8": (_I, [_VP, _VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "trt_emitter_delta256_half_rgb8": (_I, [_VP, _VP, _I, _I, _VP, C.c_size_t, C.POINTER(C.c_size_t)]),
     "trt_emitter_write": (_I, [_VP, _VP]),
     "trt_draw_screen": (_I, [C.POINTER(L.Screen), _VP]),
     "trt_fnv1a64": (C.c_ulonglong, [_VP, C.c_size_t]),
@@ -206,6 +208,23 @@ def emitter_delta_half_rgb8(shown, nxt):
     rc = lib().trt_emitter_delta_half_rgb8(a.ctypes.data, b.ctypes.data, width, rows, out.ctypes.data, out.size, C.byref(n))
     if rc != 0:
         raise ValueError(f"trt_emitter_delta_half_rgb8({width}, {rows}) failed with {rc}")
+    return out[:n.value].copy()
+
+
+def emitter_delta256_rgb8(shown, nxt, half=False):
+    """the delta text in the xterm 256-colour palette between two frames of bytes [rows, width, 3], formatted on the host, the indices
+    by the search: uint8 (trt_emitter_delta256_rgb8; half: in half-block cells, trt_emitter_delta256_half_rgb8)"""
+    a, b = np.ascontiguousarray(shown, dtype=np.uint8), np.ascontiguousarray(nxt, dtype=np.uint8)
+    rows, width, _ = b.shape
+    if a.shape != b.shape:
+        raise ValueError(f"frames of {a.shape} and {b.shape}")
+    bound = ((rows + 1) // 2) * (23 * width + 18) if half else rows * (13 * width + 13 + 5 * ((width + 1) // 2))
+    out = np.empty(max(bound, 1), dtype=np.uint8)
+    n = C.c_size_t(0)
+    entry = "trt_emitter_delta256_half_rgb8" if half else "trt_emitter_delta256_rgb8"
+    rc = getattr(lib(), entry)(a.ctypes.data, b.ctypes.data, width, rows, out.ctypes.data, out.size, C.byref(n))
+    if rc != 0:
+        raise ValueError(f"{entry}({width}, {rows}) failed with {rc}")
     return out[:n.value].copy()
 
 
