@@ -55,11 +55,9 @@ TRT_DEV unsigned hi32(double x) { return (unsigned)(__builtin_bit_cast(unsigned 
 // positive, finite, biased exponent in [723, 1323): 2^-300 <= x < 2^300
 TRT_DEV bool mid_range(double x) { return hi32(x) - (723u << 20) < (600u << 20); }
 
-// the short way first, the compiler's sequence as a rare fix-up behind ONE forward branch (no diamond)
-TRT_DEV double sqrt_exact(double x) // == __builtin_sqrt(x)
+// the steps of the compiler's sqrt expansion between its scaling and its 0/inf select: __builtin_sqrt(x) for mid_range(x), garbage otherwise
+TRT_DEV double sqrt_steps(double x)
 {
-    // the steps of the compiler's expansion between its scaling and its 0/inf select, for every lane; a lane outside the window gets
-    // garbage from them and, in the rare wave that has such a lane, the compiler's full sequence instead
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y, h = y * 0.5;
     const double r = __builtin_fma(-h, g, 0.5);
@@ -68,7 +66,15 @@ TRT_DEV double sqrt_exact(double x) // == __builtin_sqrt(x)
     double d = __builtin_fma(-g, g, x);
     g = __builtin_fma(d, h, g);
     d = __builtin_fma(-g, g, x);
-    double root = __builtin_fma(d, h, g);
+    return __builtin_fma(d, h, g);
+}
+
+// the short way first, the compiler's sequence as a rare fix-up behind ONE forward branch (no diamond)
+TRT_DEV double sqrt_exact(double x) // == __builtin_sqrt(x)
+{
+    // the short steps for every lane; a lane outside the window gets garbage from them and, in the rare wave that has such a lane,
+    // the compiler's full sequence instead
+    double root = sqrt_steps(x);
     const bool outside = !mid_range(x);
     if (__builtin_expect(__any(outside), 0))
     {
@@ -78,7 +84,8 @@ TRT_DEV double sqrt_exact(double x) // == __builtin_sqrt(x)
     return root;
 }
 
-// TRT.c:439-450: sqrt of the squared length, then THREE divisions, only when length > 1e-4
+// TRT.c:439-450: sqrt of the squared length, then THREE divisions, only when length > 1e-4.  Every range guard on its own: what
+// everything outside the render rounds calls, and the fall-back of unit_round() below.
 TRT_DEV d3 unit(d3 a)
 {
     const double len = sqrt_exact(a.x * a.x + a.y * a.y + a.z * a.z);
@@ -120,6 +127,65 @@ TRT_DEV d3 unit(d3 a)
         a.z /= len;
     }
     return a;
+}
+
+// ---- ONE window on the squared length instead of the range guards above ----
+// A lane is PLAIN when 2^-26 <= s < 2^300 for its squared length s: biased exponent in [997, 1323), one unsigned compare of the
+// high word as in mid_range.  Zero, negative values, NaN and infinity are outside.  What the lower end buys, with len = sqrt(s):
+//   2^-26 -> mid_range(s):  [2^-26, 2^300) lies inside [2^-300, 2^300), so sqrt_steps(s) IS the square root;
+//   2^-26 -> `longer`:      the root is correctly rounded, hence monotone, and exact at 2^-26: len >= 2^-13 = 1.2207e-4 > 1e-4,
+//                           so the reference divides and den = len: nothing to select;
+//   2^-26 -> len < 2^300:   s < 2^300 gives len <= 2^150.
+// (2^-26 is the smallest power of two that does: the root of 2^-27 is 8.6e-5.)
+TRT_DEV bool plain_square(double s) { return hi32(s) - (997u << 20) < (326u << 20); }
+
+// unit(a), bit for bit, for the four normalisations of a render round.  The WAVE takes the short way when every active lane is
+// plain and has no component that is neither zero nor at least 2^-300 in magnitude (unit()'s component test, unchanged): two
+// compares whose lane words are ORed in SALU (lanes_with above), ONE branch, and behind it unit()'s own steps with den = len and
+// nothing selected.  Any other wave -- a camera with a basis of length 1e-5, a zero vector, a NaN -- goes through unit(), laid out
+// as rare.
+// `plain_wave` (wave-uniform: a scalar, no lane flag): the wave went the short way.  Then, in EVERY active lane, the results are
+// correctly rounded quotients q_k = (a_k / len)(1 + e_k) by len = sqrt(s)(1 + e_l) with s = (a.a)(1 + t), |e| <= u = 2^-53 and
+// |t| <= 3u (positive terms, three roundings deep); no a_k^2, q_k or q_k^2 other than an exact zero is below 2^-900, so nothing
+// underflows.  Hence sum q_k^2 = (1 +- 2u) / ((1 +- 3u)(1 +- 2u)) = 1 +- 7u, and dot(q, q) rounds three times more:
+//     |dot(q, q) - 1| <= 10u + O(u^2) < 2^-49,
+// far inside the 2^-40 of trt_rayfamily_member's unit test: where the flag is set, that test is known to pass and may be skipped.
+// Where it is not set nothing is known, and the test runs.
+TRT_DEV d3 unit_round(d3 a, bool &plain_wave)
+{
+    const double s = a.x * a.x + a.y * a.y + a.z * a.z;
+    const int ex = __builtin_amdgcn_frexp_exp(a.x), ey = __builtin_amdgcn_frexp_exp(a.y), ez = __builtin_amdgcn_frexp_exp(a.z);
+    int lo = ex < ey ? ex : ey;
+    lo = lo < ez ? lo : ez;
+    const unsigned long long odd_lanes = lanes_with(!plain_square(s)) | lanes_with(lo <= -300);
+    plain_wave = odd_lanes == 0;
+    if (TRT_LIKELY(odd_lanes == 0))
+    {
+        const double len = sqrt_steps(s);
+        double r = __builtin_amdgcn_rcp(len);
+        double e = __builtin_fma(-len, r, 1.0);
+        r = __builtin_fma(r, e, r);
+        e = __builtin_fma(-len, r, 1.0);
+        r = __builtin_fma(r, e, r);
+        double q[3] = {a.x, a.y, a.z};
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+        {
+            const double num = q[k];
+            const double q0 = num * r;
+            const double err = __builtin_fma(-len, q0, num);
+            const double quo = __builtin_fma(err, r, q0);
+            q[k] = __builtin_copysign(quo, num); // as in unit()
+        }
+        return d3{q[0], q[1], q[2]};
+    }
+    return unit(a);
+}
+
+TRT_DEV d3 unit_round(d3 a)
+{
+    bool plain_wave;
+    return unit_round(a, plain_wave);
 }
 
 // the compiler's own expansions, for trt_selftest_unit

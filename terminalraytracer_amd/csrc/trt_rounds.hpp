@@ -588,9 +588,11 @@ TRT_DEV void point_light_search(const LdsImage &L, int n, d3 o, d3 d, bool activ
 // lanes_with(active) (trt_device.hpp).
 // BATCH: the ray belongs to frame `frame` of a batch launch, whose eye families and tables it reads (0 and unused otherwise)
 // DIAG (trt_probe_path_lookups only; the render kernels never set it): *read_at = the index into G.path_lists the lane read, -1: none
+// `d_plain` (wave-uniform): `d` comes from unit_round() and the whole wave took its short way, so |d.d - 1| <= 2^-40 holds in every
+// active lane (trt_device.hpp has the bound) and the membership's unit test is not run.  false: nothing is known, the test runs.
 template <bool BATCH = false, bool DIAG = false>
 TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n, int fam, d3 o, d3 d, bool active, unsigned long long active_lanes,
-                                     unsigned long long &fallback_lanes, int frame = 0, int inside = -1, long long *read_at = nullptr)
+                                     unsigned long long &fallback_lanes, int frame = 0, int inside = -1, long long *read_at = nullptr, bool d_plain = false)
 {
     const bool in_family = fam >= 0;
     const unsigned long long family_lanes = lanes_with(in_family); // next to its compare: a vote on a compare of another block is a select and a compare again
@@ -609,14 +611,19 @@ TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n
         r_chk = E[3];
     }
     const double rg2 = of_eye ? rg2_eye : G.rg2_sph; // by value: a pointer chosen between LDS and the kernel arguments is a flat load
-    // trt_rayfamily_member, operation for operation (all four conditions evaluated: no branches between them)
+    // trt_rayfamily_member, operation for operation (no branches between the first three conditions)
     const d3 w = sub(o, apex);
     const d3 c = d3{w.y * d.z - w.z * d.y, w.z * d.x - w.x * d.z, w.x * d.y - w.y * d.x};
     const double along = dot(w, d);
     const bool near_line = dot(c, c) <= r_chk * r_chk, ahead = along >= -r_chk, in_range = dot(w, w) <= rg2;
-    const bool unit_dir = __builtin_fabs(dot(d, d) - 1.0) <= 9.094947017729282e-13;
-    const bool member = near_line & ahead & in_range & unit_dir;
-    const unsigned long long member_lanes = family_lanes & lanes_with(near_line) & lanes_with(ahead) & lanes_with(in_range) & lanes_with(unit_dir);
+    bool member = near_line & ahead & in_range;
+    unsigned long long member_lanes = family_lanes & lanes_with(near_line) & lanes_with(ahead) & lanes_with(in_range);
+    if (TRT_EXPECT_RARE(!d_plain)) // the fourth condition, where unit_round() has not already settled it for the wave
+    {
+        const bool unit_dir = __builtin_fabs(dot(d, d) - 1.0) <= 9.094947017729282e-13;
+        member &= unit_dir;
+        member_lanes &= lanes_with(unit_dir);
+    }
     const int g = of_eye ? G.g_eye : G.g_sph;
     const int at = trt_cubemap_cell((float)d.x, (float)d.y, (float)d.z, 0.5f * (float)g, (float)(g - 1), g);
     const unsigned eye_cells = 6u * (unsigned)G.g_eye * (unsigned)G.g_eye, sph_cells = 6u * (unsigned)G.g_sph * (unsigned)G.g_sph;
@@ -644,10 +651,10 @@ TRT_DEV unsigned long long path_cell(const LdsImage &L, const GridView &G, int n
 // from the ground cannot hit the ground again).  `fallback_lanes` holds the active lanes whose ray fails the family's
 // membership test (its line must pass within r_chk of the apex, its origin not more than r_chk behind it, within the table's
 // range; a unit direction) or whose cell has no list: the caller then sweeps.
-// DIAG: as in path_cell.
+// DIAG, `d_plain`: as in path_cell.
 template <bool BATCH = false, bool DIAG = false>
 TRT_DEV unsigned long long path_cell_patches(const LdsImage &L, const GridView &G, int n, int &fam, d3 o, d3 d, bool active, unsigned long long active_lanes,
-                                             unsigned long long &fallback_lanes, int frame = 0, int inside = -1, long long *read_at = nullptr)
+                                             unsigned long long &fallback_lanes, int frame = 0, int inside = -1, long long *read_at = nullptr, bool d_plain = false)
 {
     const bool in_family = fam >= 0;
     const unsigned long long family_lanes = lanes_with(in_family); // next to its compare: a vote on a compare of another block is a select and a compare again
@@ -679,13 +686,18 @@ TRT_DEV unsigned long long path_cell_patches(const LdsImage &L, const GridView &
     r_chk = mirrored ? r_chk + TRT_FAMILY_SLACK : r_chk;
     r_chk = of_eye ? rchk_eye : r_chk;
     rg2 = of_eye ? rg2_eye : rg2;
-    // trt_rayfamily_member, operation for operation (all four conditions evaluated: no branches between them)
+    // trt_rayfamily_member, operation for operation (no branches between the first three conditions)
     const d3 w = sub(o, apex);
     const d3 c = d3{w.y * d.z - w.z * d.y, w.z * d.x - w.x * d.z, w.x * d.y - w.y * d.x};
     const bool near_line = dot(c, c) <= r_chk * r_chk, ahead = dot(w, d) >= -r_chk, in_range = dot(w, w) <= rg2;
-    const bool unit_dir = __builtin_fabs(dot(d, d) - 1.0) <= 9.094947017729282e-13;
-    const bool member = near_line & ahead & in_range & unit_dir;
-    const unsigned long long member_lanes = family_lanes & lanes_with(near_line) & lanes_with(ahead) & lanes_with(in_range) & lanes_with(unit_dir);
+    bool member = near_line & ahead & in_range;
+    unsigned long long member_lanes = family_lanes & lanes_with(near_line) & lanes_with(ahead) & lanes_with(in_range);
+    if (TRT_EXPECT_RARE(!d_plain)) // the fourth condition, where unit_round() has not already settled it for the wave
+    {
+        const bool unit_dir = __builtin_fabs(dot(d, d) - 1.0) <= 9.094947017729282e-13;
+        member &= unit_dir;
+        member_lanes &= lanes_with(unit_dir);
+    }
     const int g = of_eye ? G.g_eye : G.g_sph;
     const int at = trt_cubemap_cell((float)d.x, (float)d.y, (float)d.z, 0.5f * (float)g, (float)(g - 1), g);
     const unsigned eye_cells = 6u * (unsigned)G.g_eye * (unsigned)G.g_eye, sph_cells = 6u * (unsigned)G.g_sph * (unsigned)G.g_sph;
@@ -738,7 +750,7 @@ struct PathHit
 // does, it has no family).
 template <bool COUNT, bool REFRACT = false, bool PATCHES = false, bool BATCH = false>
 TRT_DEV PathHit path_stage(const LdsImage &L, const CullView &cull, const GridView &grids, int n, d3 o, d3 d, int &fam, bool alive, unsigned long long alive_lanes,
-                           d3 gp, d3 gn, Tally &tally, int inside = -1, int frame = 0)
+                           d3 gp, d3 gn, Tally &tally, int inside = -1, int frame = 0, bool d_plain = false) // d_plain: see path_cell
 {
     bool p_list = false;
     unsigned long long p_cell = 0;
@@ -746,9 +758,9 @@ TRT_DEV PathHit path_stage(const LdsImage &L, const CullView &cull, const GridVi
     {
         unsigned long long fallback_lanes;
         if constexpr (PATCHES)
-            p_cell = path_cell_patches<BATCH>(L, grids, n, fam, o, d, alive, alive_lanes, fallback_lanes, frame, REFRACT ? inside : -1); // fam: now what a reflection by the ground belongs to
+            p_cell = path_cell_patches<BATCH>(L, grids, n, fam, o, d, alive, alive_lanes, fallback_lanes, frame, REFRACT ? inside : -1, nullptr, d_plain); // fam: now what a reflection by the ground belongs to
         else
-            p_cell = path_cell<BATCH>(L, grids, n, fam, o, d, alive, alive_lanes, fallback_lanes, frame, REFRACT ? inside : -1);
+            p_cell = path_cell<BATCH>(L, grids, n, fam, o, d, alive, alive_lanes, fallback_lanes, frame, REFRACT ? inside : -1, nullptr, d_plain);
         p_list = fallback_lanes == 0;
     }
     if (COUNT && !p_list)
@@ -762,7 +774,7 @@ TRT_DEV PathHit path_stage(const LdsImage &L, const CullView &cull, const GridVi
     if (r.hit)
         fam = r.ph.i < n ? 2 + r.ph.i : (PATCHES ? fam : (fam == 0 ? 1 : (fam >= 2 && fam < 2 + n ? fam + n : -1)));
     // one unit() for "back along the ray" (nudge, TRT.c:871-872) or the sky direction (TRT.c:702), one for the normal
-    r.back = unit(r.hit ? sub(o, r.ph.p) : d);
+    r.back = unit_round(r.hit ? sub(o, r.ph.p) : d);
     r.normal = d;
     r.mat = 0;
     if (r.hit_lanes != 0)
@@ -774,7 +786,7 @@ TRT_DEV PathHit path_stage(const LdsImage &L, const CullView &cull, const GridVi
             raw = sub(r.ph.p, load3(L.sph + 4 * r.ph.i)); // TRT.c:824
             r.mat = r.ph.i;
         }
-        r.normal = unit(raw); // TRT.c:878
+        r.normal = unit_round(raw); // TRT.c:878
     }
     TRT_MARK_AT(6); // P post: nudge direction, normal
     return r;
@@ -862,7 +874,8 @@ TRT_DEV d3 shadow_stage(const LdsImage &L, const CullView &cull, const GridView 
             const d3 to_light = sub(load3(pl), o);
             const double light_d2 = dot(to_light, to_light);
             const double strength = clampd(pl[6] / light_d2, 0.0, 1.0);
-            sd = unit(to_light);
+            bool sd_plain;
+            sd = unit_round(to_light, sd_plain);
             lcolor = load3(pl + 3);
             bool use_list = false;
             unsigned long long cell = 0;
@@ -871,7 +884,8 @@ TRT_DEV d3 shadow_stage(const LdsImage &L, const CullView &cull, const GridView 
                 const trt_pointgrid *G = L.pointgrid + (li - nd);
                 int far;
                 const int c = trt_pointgrid_cell(G, o.x, o.y, o.z, &far);
-                far |= !(__builtin_fabs(dot(sd, sd) - 1.0) <= 9.094947017729282e-13);
+                if (TRT_EXPECT_RARE(!sd_plain)) // otherwise known to hold for the wave (unit_round, trt_device.hpp)
+                    far |= !(__builtin_fabs(dot(sd, sd) - 1.0) <= 9.094947017729282e-13);
                 if (lit_lanes && !far)
                     cell = grids.point_lists[(size_t)(li - nd) * grids.point_stride + (unsigned)c];
                 use_list = (lit_word & (lanes_with(far != 0) | lanes_with((unsigned)(cell >> 56) == TRT_LIST_NONE))) == 0;
@@ -1258,7 +1272,8 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
         if (COUNT)
             tally.rounds++;
         TRT_MARK_AT(0); // units + primary rays
-        d = unit(next_dir); // TRT.c:1008 for a primary ray, TRT.c:1055 for a reflected one
+        bool d_plain; // the wave's directions are unit vectors by construction (unit_round, trt_device.hpp)
+        d = unit_round(next_dir, d_plain); // TRT.c:1008 for a primary ray, TRT.c:1055 for a reflected one
 
         // ======================================= P: the path ray =======================================
         if (COUNT && alive)
@@ -1267,7 +1282,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
         PathHit hit;
         {
             TRT_FRESH_ARGS;
-            hit = path_stage<COUNT, REFRACT, PATCHES, BATCH>(L, cull, grids, n, o, d, fam, alive, alive_lanes, gp, gn, tally, inside, BATCH ? bounces >> kBatchFrameShift : 0);
+            hit = path_stage<COUNT, REFRACT, PATCHES, BATCH>(L, cull, grids, n, o, d, fam, alive, alive_lanes, gp, gn, tally, inside, BATCH ? bounces >> kBatchFrameShift : 0, d_plain);
         }
         if constexpr (COMPACT)
         {
