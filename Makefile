@@ -38,6 +38,7 @@ $(BUILD)/trt_render$(TAG).o: $(CSRC)/trt_render.hip $(HIP_HEADERS)
 		|| (cat $(BUILD)/resource_usage$(TAG).txt; false)
 	@grep -E "error|warning:" $(BUILD)/resource_usage$(TAG).txt || true
 	@awk '/Function Name: .*render_rounds_kernelILb0/ {f=1} f && /VGPRs:/ {split($$0,a,"VGPRs: "); v=a[2]+0; print "render_rounds_kernel<false>: " v " VGPRs" (v>128 ? "  ** WARNING: more than 128 -> 3 waves/SIMD **" : " (4 waves/SIMD)"); exit}' $(BUILD)/resource_usage$(TAG).txt
+	@awk '/Function Name: .*render_rounds_kernelILb0ELb0ELb0ELb0ELb0ELb0ELb0ELb0ELb1E/ {f=1} f && /VGPRs:/ {split($$0,a,"VGPRs: "); v=a[2]+0; print "render_rounds_kernel<SKY_FILTER>: " v " VGPRs" (v>128 ? "  ** WARNING: more than 128 -> 3 waves/SIMD **" : " (4 waves/SIMD)"); exit}' $(BUILD)/resource_usage$(TAG).txt
 
 $(BUILD)/%$(TAG).o: $(CSRC)/%.hip $(HIP_HEADERS)
 	@mkdir -p $(BUILD)

@@ -39,6 +39,8 @@
  * --specular: EXTENSION, parity unpinned (trt_set_default_specular; with --batch also trt_set_specular on the program's own context): the
  * lights' Blinn-Phong highlights from the specularity of 100.0 that the reference's scene gives every material and never reads.  Goes with
  * every other flag.
+ * --sky-filter: EXTENSION, parity unpinned (trt_set_default_sky_filter; with --batch also trt_set_sky_filter): the sky blended from the
+ * four texels around each look-up where the reference takes the nearest.  Goes with every other flag but --specular.
  *
  * The scene literals are the reference's (TRT.c:1256-1288). */
 #include <signal.h>
@@ -67,12 +69,12 @@ int main(int argc, char **argv)
 {
     if (argc < 2)
     {
-        fprintf(stderr, "usage: %s <skybox-directory> [frames] [width] [height] [--no-draw] [--rgb8] [--ansi] [--half] [--kitty] [--sixel] [--256] [--delta] [--delta256] [--step=SECONDS] [--batch=N] [--specular]\n", argv[0]);
+        fprintf(stderr, "usage: %s <skybox-directory> [frames] [width] [height] [--no-draw] [--rgb8] [--ansi] [--half] [--kitty] [--sixel] [--256] [--delta] [--delta256] [--step=SECONDS] [--batch=N] [--specular] [--sky-filter]\n", argv[0]);
         return 2;
     }
     const long frames = argc > 2 ? atol(argv[2]) : 0;
     const int width = argc > 3 ? atoi(argv[3]) : 160, height = argc > 4 ? atoi(argv[4]) : 48;
-    int draw = 1, bytes_only = 0, text_only = 0, ansi = 0, delta = 0, delta256 = 0, half = 0, kitty = 0, sixel = 0, palette = 0, batch = 0, specular = 0;
+    int draw = 1, bytes_only = 0, text_only = 0, ansi = 0, delta = 0, delta256 = 0, half = 0, kitty = 0, sixel = 0, palette = 0, batch = 0, specular = 0, sky_filter = 0;
     double step = -1.0;
     for (int i = 5; i < argc; i++)
     {
@@ -100,6 +102,8 @@ int main(int argc, char **argv)
             batch = atoi(argv[i] + 8);
         else if (strcmp(argv[i], "--specular") == 0)
             specular = 1; /* EXTENSION, parity unpinned: highlights from Material.specularity; goes with every other flag */
+        else if (strcmp(argv[i], "--sky-filter") == 0)
+            sky_filter = 1; /* EXTENSION, parity unpinned: bilinear filtering of the sky */
     }
     if (batch && (batch < 1 || batch > TRT_BATCH_MAX || !delta || step < 0.0))
     {
@@ -125,6 +129,16 @@ int main(int argc, char **argv)
     {
         fprintf(stderr, "--delta256 sends delta texts in the xterm palette: it goes with --half and --batch=N, with none of --kitty, --sixel, --ansi and --rgb8\n");
         return 2;
+    }
+    if (specular && sky_filter)
+    {
+        fprintf(stderr, "--specular and --sky-filter do not combine yet\n");
+        return 2;
+    }
+    if (sky_filter && trt_set_default_sky_filter(TRT_SKY_BILINEAR) != TRT_OK)
+    {
+        fprintf(stderr, "trt_set_default_sky_filter: %s\n", trt_last_error());
+        return 1;
     }
     if (specular && trt_set_default_specular(1) != TRT_OK)
     {
@@ -190,9 +204,10 @@ int main(int argc, char **argv)
     const trt_rowset whole = {width, height, height, 0, 1};
     Camera cameras[TRT_BATCH_MAX];
     size_t batch_bytes[TRT_BATCH_MAX];
-    if (batch && (trt_create(0, &ctx) != TRT_OK || trt_set_scene(ctx, &scene) != TRT_OK || trt_set_specular(ctx, specular) != TRT_OK))
+    if (batch && (trt_create(0, &ctx) != TRT_OK || trt_set_scene(ctx, &scene) != TRT_OK || trt_set_specular(ctx, specular) != TRT_OK ||
+                  trt_set_sky_filter(ctx, sky_filter) != TRT_OK))
     {
-        fprintf(stderr, "trt_create / trt_set_scene / trt_set_specular: %s\n", trt_last_error());
+        fprintf(stderr, "trt_create / trt_set_scene / trt_set_specular / trt_set_sky_filter: %s\n", trt_last_error());
         return 1;
     }
 

@@ -892,6 +892,53 @@ int trt_get_specular(trt_context *ctx, int *on);
  * as trt_set_scene_policy does. */
 int trt_set_default_specular(int on);
 
+/* EXTENSION, PARITY UNPINNED.  Bilinear filtering of the sky.  get_skybox_color takes the nearest texel of a face, and directly under
+ * that line its author wrote `//TODO->bicubic interpolation between the surrounding pixels in the texture` (TRT.c:786).  mode =
+ * TRT_SKY_BILINEAR blends the four texels around the look-up for the frames this context renders, TRT_SKY_NEAREST (the default) is the
+ * reference's path; anything else fails with TRT_ERR_ARGUMENT.  Four taps, clamped inside the face: no bicubic filter, no filtering
+ * across the edges of the cube.
+ *
+ * THE DECLARED RULES (tests/sky_filter_model.py is written from these, not from the kernel).  Every step is one rounded binary64
+ * operation, nothing contracted; clamp(a, lo, hi) is the reference's: a < lo ? lo : (a > hi ? hi : a).  dim is skybox.dim as a double.
+ *
+ *     f, u, v                                         the face and the coordinates of TRT.c:702-779, the clamp to +-0.5 included
+ *     U = (u + 0.5) * dim;  V = (v + 0.5) * dim       TRT.c:782-783 before the truncation
+ *     x = clamp(U - 0.5, 0.0, dim - 1.0)              texel centres lie at i + 0.5; the filter never leaves the face (clamp to edge)
+ *     i0 = (int)x;  fx = x - (double)i0;  i1 = (i0 + 1 < dim) ? i0 + 1 : i0
+ *     y, j0, fy, j1                                   likewise from V
+ *     t00 = face[i0 + j0*dim]   t10 = face[i1 + j0*dim]   t01 = face[i0 + j1*dim]   t11 = face[i1 + j1*dim]
+ *     per channel, the bytes converted to double:
+ *     top = t00 + (t10 - t00) * fx;   bot = t01 + (t11 - t01) * fx;   c = (top + (bot - top) * fy) / 255.0
+ *
+ * f, u and v may be formed symbolically -- the products with the axis table's +-1 and 0 carried out on paper, as the nearest look-up
+ * of the production kernel does: only the sign of a zero can differ, which u + 0.5 cannot see.  A direction with a component that is
+ * not a number has no face in the reference and u, v that are not numbers: it gives face 0, all four taps texel 0 and fx = fy = 0, the
+ * colour the nearest look-up defines for it; so does every direction whose u or v is not a number, which leaves the zero vector
+ * (0 * inf) and vectors so short that dir * (1 / scale_by) overflows (a largest component below 2^-1024: the axis table's zeros then
+ * meet inf).  The symbolic form holds these to the same answer by counting a u or v that is not FINITE before the clamp as not a number.  The lerp form, not a*(1-f) + b*f, on purpose: (a) four equal taps give exactly byte / 255.0, the reference's value;
+ * (b) fx = fy = 0 gives exactly the texel (i0, j0) -- at a texel's centre the texel the nearest look-up returns --; (c) every channel
+ * lies within [min, max] of its four taps over 255, so it never leaves [0, 1].
+ *
+ * The result replaces the colour of TRT.c:866; reflectivity and specularity of the miss stay 0.  Rays, shadow tests, weights and
+ * bounces do not change: a frame's path-ray and shadow-ray counts are the oracle's.
+ *
+ * Like the specular extension it runs on the plain rounds (256-thread workgroups, never decoupled, with or without patches) and on the
+ * reference-order kernel: a batch of cameras is served one launch per camera; a scene whose image outgrows LDS fails at render time
+ * with TRT_ERR_CAPACITY; a render with the filter on and the refraction or the specular extension on fails with TRT_ERR_ARGUMENT -- they
+ * do not combine yet.  Every output kind works unchanged: they read the ordered mean.  trt_dist_create and trt_dist_set_scene switch
+ * it off on every frame slot's context; trt_share_scene(dst, src) switches dst's off.  Environment: TRT_SKY_FILTER=0|1 sets the
+ * default of new contexts.
+ *
+ * UNPINNED TO THE REFERENCE, which has no filter.  Frames are checked bit for bit against tests/sky_filter_restatement.c, which with
+ * the switch off equals the oracle bit for bit and whose every look-up is held to an exact model of the rules above
+ * (tests/test_sky_filter_model.py).  With the filter off other kernel instantiations run and nothing of this is on the path. */
+#define TRT_SKY_NEAREST 0
+#define TRT_SKY_BILINEAR 1
+int trt_set_sky_filter(trt_context *ctx, int mode);
+int trt_get_sky_filter(trt_context *ctx, int *mode);
+/* ... for the default context, as trt_set_default_specular is. */
+int trt_set_default_sky_filter(int mode);
+
 /* Resource usage of the render kernel trt_render_variant describes (hipFuncGetAttributes / occupancy query; max_blocks_per_cu
  * counts workgroups of trt_render_variant's size, and for 256-thread workgroups is the plain rounds' figure, which sizes them). */
 int trt_kernel_info(trt_context *ctx, int *vgprs, int *sgprs, int *static_lds_bytes, int *max_blocks_per_cu,

@@ -235,6 +235,12 @@ static int init_context(trt_context *ctx)
         if (sscanf(e, "%d", &on) == 1 && (on == 0 || on == 1))
             ctx->specular = on;
     }
+    if (const char *e = getenv("TRT_SKY_FILTER"))
+    {
+        int mode = 0;
+        if (sscanf(e, "%d", &mode) == 1 && (mode == TRT_SKY_NEAREST || mode == TRT_SKY_BILINEAR))
+            ctx->sky_filter = mode;
+    }
     if (const char *e = getenv("TRT_PATH_LEAN"))
     {
         int mode = -1;
@@ -384,6 +390,7 @@ extern "C" int trt_share_scene(trt_context *dst, trt_context *src)
     dst->sky_stamp = src->sky_stamp;
     dst->ior_count = 0;
     dst->specular = 0; // per context, like the refraction indices: dst starts with the extension off
+    dst->sky_filter = TRT_SKY_NEAREST; // the same
     dst->have_scene = true;
     dst->occupancy_for_lds = (size_t)-1;
     return refresh_occupancy(dst);
@@ -459,6 +466,24 @@ extern "C" int trt_get_specular(trt_context *ctx, int *on)
     if (!ctx || !on)
         return fail(TRT_ERR_ARGUMENT, "NULL argument");
     *on = ctx->specular;
+    return TRT_OK;
+}
+
+extern "C" int trt_set_sky_filter(trt_context *ctx, int mode)
+{
+    if (!ctx)
+        return fail(TRT_ERR_ARGUMENT, "ctx is NULL");
+    if (mode != TRT_SKY_NEAREST && mode != TRT_SKY_BILINEAR)
+        return fail(TRT_ERR_ARGUMENT, "sky filter %d (TRT_SKY_NEAREST or TRT_SKY_BILINEAR)", mode);
+    ctx->sky_filter = mode;
+    return TRT_OK;
+}
+
+extern "C" int trt_get_sky_filter(trt_context *ctx, int *mode)
+{
+    if (!ctx || !mode)
+        return fail(TRT_ERR_ARGUMENT, "NULL argument");
+    *mode = ctx->sky_filter;
     return TRT_OK;
 }
 

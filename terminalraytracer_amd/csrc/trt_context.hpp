@@ -229,6 +229,7 @@ struct trt_context
     DeviceBuffer<unsigned long long> d_sixel_band_at;
     int ior_count = 0;          // 0 = off (the reference's path)
     int specular = 0;           // trt_set_specular: 1 = the lights' Blinn-Phong terms (EXTENSION, parity unpinned); 0 = off (the reference's path)
+    int sky_filter = 0;         // trt_set_sky_filter: TRT_SKY_BILINEAR = four taps blended (EXTENSION, parity unpinned); TRT_SKY_NEAREST = the reference's path
     DeviceBuffer<unsigned long long> d_counters;
     DeviceBuffer<unsigned int> d_queue;
     PinnedBuffer h_staging; // trt_render_host, trt_render_host_rgb8, trt_render_host_ansi

@@ -542,6 +542,92 @@ TRT_DEV d3 texel_color(uint32_t t) // TRT.c:866: byte / 255.0
     return d3{(double)(t & 0xFF) / 255.0, (double)((t >> 8) & 0xFF) / 255.0, (double)((t >> 16) & 0xFF) / 255.0};
 }
 
+// ---- bilinear sky filtering (EXTENSION, parity unpinned; the declared rules are in include/trt_hip.h above trt_set_sky_filter) ----
+// What a filtered look-up carries from where its loads are issued to where the colour is needed: the four texels and the two weights.
+struct SkyTaps
+{
+    uint32_t t00, t10, t01, t11; // (i0, j0), (i1, j0), (i0, j1), (i1, j1), 0x00BBGGRR
+    double fx, fy;               // in [0, 1)
+};
+
+// The four taps of an ALREADY normalised direction, for the lanes with `active` (the others load nothing).  Always the FP64
+// coordinates, in the symbolic form of sky_index_unit: the FP32 estimate can vouch for a texel, not for a weight.  Only LOADS: the
+// blend (sky_blend) belongs where the colour is needed.  A direction whose u or v is not a number -- one with a NaN component, and the
+// zero vector, whose coordinates are 0 * inf, or a vector so short that dir / best overflows -- has face 0, four times texel 0 and both
+// weights 0.
+TRT_DEV SkyTaps sky_filtered_wave(const uint32_t *sky, int dim, d3 dir, double dim_f, bool active)
+{
+    int face = 0;
+    double best = -1.0;
+    const double t[6] = {dir.x, -dir.x, dir.y, -dir.y, dir.z, -dir.z};
+#pragma unroll
+    for (int f = 0; f < 6; f++)
+        if (t[f] > best) // strict, first wins (TRT.c:708)
+        {
+            best = t[f];
+            face = f;
+        }
+    const d3 ds = scale(dir, 1.0 / best); // TRT.c:718-719
+    const int axis = face >> 1;
+    const double sgn = (face & 1) ? -0.5 : 0.5;
+    const double cu = axis == 0 ? ds.y : (axis == 1 ? ds.z : ds.x);
+    const double cv = axis == 0 ? ds.z : (axis == 1 ? ds.x : ds.y);
+    double u = sgn * cu, v = sgn * cv;
+    if (face & 1)
+        u = -u;
+    if (face < 2)
+    {
+        const double w = u;
+        u = v;
+        v = -w;
+    }
+    else if (face < 4)
+    {
+        const double w = u;
+        u = -v;
+        v = w;
+    }
+    else if (face == 4)
+    {
+        u = -u;
+        v = -v;
+    }
+    // not a number: a NaN, and dir / best overflowed (best below 2^-1024: 1 / best is inf) -- there the axis-table form, which
+    // multiplies inf by the table's zeros, has u and v that are not numbers either, and the symbolic form must not take a corner tap
+    const bool number = __builtin_fabs(u) < __builtin_inf() && __builtin_fabs(v) < __builtin_inf();
+    u = clampd(u, -0.5, 0.5);
+    v = clampd(v, -0.5, 0.5);
+    const double last = dim_f - 1.0;
+    double x = clampd((u + 0.5) * dim_f - 0.5, 0.0, last), y = clampd((v + 0.5) * dim_f - 0.5, 0.0, last); // texel centres lie at i + 0.5
+    x = number ? x : 0.0, y = number ? y : 0.0;
+    const int i0 = (int)x, j0 = (int)y; // 0 <= x, y <= dim - 1
+    const int i1 = i0 + 1 < dim ? i0 + 1 : i0, j1 = j0 + 1 < dim ? j0 + 1 : j0; // clamp to edge: the filter never leaves the face
+    const uint32_t *const texels = sky + (number ? (long)face * dim * dim : 0l);
+    const long row0 = (long)j0 * dim, row1 = (long)j1 * dim;
+    SkyTaps k;
+    k.fx = x - (double)i0, k.fy = y - (double)j0;
+    k.t00 = k.t10 = k.t01 = k.t11 = 0u;
+    if (active)
+    {
+        k.t00 = texels[row0 + i0], k.t10 = texels[row0 + i1];
+        k.t01 = texels[row1 + i0], k.t11 = texels[row1 + i1];
+    }
+    return k;
+}
+
+// The colour of the four taps, per channel in lerp form -- top = t00 + (t10 - t00) fx, bot = t01 + (t11 - t01) fx,
+// (top + (bot - top) fy) / 255.0 --, every step one rounded FP64 operation (the build has contraction off).  Four equal taps give
+// byte / 255.0, the nearest look-up's value; fx = fy = 0 gives the texel (i0, j0); a channel never leaves the range of its taps.
+TRT_DEV double sky_blend_channel(const SkyTaps &k, int shift)
+{
+    const double a = (double)((k.t00 >> shift) & 0xFF), b = (double)((k.t10 >> shift) & 0xFF);
+    const double c = (double)((k.t01 >> shift) & 0xFF), d = (double)((k.t11 >> shift) & 0xFF);
+    const double top = a + (b - a) * k.fx, bot = c + (d - c) * k.fx;
+    return (top + (bot - top) * k.fy) / 255.0;
+}
+
+TRT_DEV d3 sky_blend(const SkyTaps &k) { return d3{sky_blend_channel(k, 0), sky_blend_channel(k, 8), sky_blend_channel(k, 16)}; }
+
 // ---- primary rays, TRT.c:981-1011 -------------------------------------------------------------------------
 TRT_DEV d3 primary_direction(const FrameView &f, int row, int column, int k)
 {

@@ -17,6 +17,9 @@ void allow_large_lds_diag(const trt_context *ctx)
     (void)hipFuncSetAttribute((const void *)trt::probe_rounds_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
     (void)hipFuncSetAttribute((const void *)trt::probe_rounds_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
     (void)hipFuncSetAttribute((const void *)trt::probe_rounds_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
+    (void)hipFuncSetAttribute((const void *)trt::probe_rays_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
+    (void)hipFuncSetAttribute((const void *)trt::probe_rounds_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
+    (void)hipFuncSetAttribute((const void *)trt::probe_rounds_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
 }
 } // namespace trt_impl
 
@@ -323,7 +326,10 @@ extern "C" int trt_probe_rays(trt_context *ctx, const Ray *rays, size_t n, int *
     HIP_TRY(dobj.reserve(n));
     double *dr = buf.ptr, *dp = dr + 6 * n, *dn = dp + 3 * n, *dm = dn + 3 * n, *dl = dm + 5 * n;
     HIP_TRY(hipMemcpy(dr, rays, n * sizeof(Ray), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(ctx->specular ? trt::probe_rays_kernel<true> : trt::probe_rays_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256),
+    // the context's switches: the specular extension, or the sky filter (trt_set_sky_filter); both together no render accepts, and the
+    // specular one goes first here
+    const auto probe = ctx->specular ? trt::probe_rays_kernel<true> : ctx->sky_filter ? trt::probe_rays_kernel<false, true> : trt::probe_rays_kernel<false>;
+    hipLaunchKernelGGL(probe, dim3((unsigned)((n + 255) / 256)), dim3(256),
                        scene_lds_bytes(ctx->scene), ctx->stream, ctx->scene, (const double *)dr, (long)n, dobj.ptr, dp, dn, dm, dl);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -383,8 +389,8 @@ extern "C" int trt_probe_rays_production(trt_context *ctx, const Camera *camera,
     memcpy(f.cam, camera, sizeof(Camera));
     f.jitter = ctx->d_jitter.ptr; // spp = 0: nothing is read through it
     const bool patches = ctx->grids.path_enabled && ctx->grids.patch_m > 0;
-    const auto probe = patches ? (ctx->specular ? trt::probe_rounds_kernel<true, true> : trt::probe_rounds_kernel<true>)
-                               : (ctx->specular ? trt::probe_rounds_kernel<false, true> : trt::probe_rounds_kernel<false>); // trt_set_specular
+    const auto probe = patches ? (ctx->specular ? trt::probe_rounds_kernel<true, true> : ctx->sky_filter ? trt::probe_rounds_kernel<true, false, true> : trt::probe_rounds_kernel<true>)
+                               : (ctx->specular ? trt::probe_rounds_kernel<false, true> : ctx->sky_filter ? trt::probe_rounds_kernel<false, false, true> : trt::probe_rounds_kernel<false>); // trt_set_specular, trt_set_sky_filter
     hipLaunchKernelGGL(probe, dim3((unsigned)((n + trt::kPersistentBlock - 1) / trt::kPersistentBlock)), dim3(trt::kPersistentBlock),
                        image_lds_bytes(ctx, 0), ctx->stream, ctx->scene, ctx->cull, f, ctx->grids, (const double *)dr,
                        families ? (const int *)(dobj.ptr + n) : (const int *)nullptr, (long)n, dobj.ptr, dp, dn, dm, dl);

@@ -302,6 +302,7 @@ static int init_dist(trt_dist *d, const Scene *scene, const void *id, int frames
         DIST_TRT(trt_create(d->device, &ctx));
         s.ctx.reset(ctx);
         DIST_TRT(trt_set_specular(ctx, 0)); // the specular extension is out of scope here (trt_hip.h): off on every slot, whatever TRT_SPECULAR gave the context
+        DIST_TRT(trt_set_sky_filter(ctx, TRT_SKY_NEAREST)); // ... and so is the sky filter, whatever TRT_SKY_FILTER gave it
         // ONE copy of the scene and of its candidate tables per device: the first slot builds them, the others render from them
         // (trt_share_scene); only the eye's tables, the scratch and the frame buffers are a slot's own
         if (&s == &d->slots[0])
@@ -395,6 +396,8 @@ extern "C" int trt_dist_set_scene(trt_dist *d, const Scene *scene)
         int rc = &s == &d->slots[0] ? trt_set_scene(s.ctx.get(), scene) : trt_share_scene(s.ctx.get(), d->slots[0].ctx.get());
         if (!rc) // ... and every slot with the specular extension off, a slot whose context a caller reached through trt_dist_context too: slots
             rc = trt_set_specular(s.ctx.get(), 0); // that differ would make frames alternate
+        if (!rc)
+            rc = trt_set_sky_filter(s.ctx.get(), TRT_SKY_NEAREST); // the same for the sky filter
         if (rc)
         { // some slots may hold the new scene and others the old one: frames would alternate between the two without an error.
           // Nothing of this trt_dist can be trusted any more -- the same state a failed collective leaves (trt_hip.h).

@@ -13,6 +13,7 @@ int g_default_device = 0;
 std::mutex g_default_mutex;
 
 int g_default_specular = -1; // trt_set_default_specular: 0 / 1 for the default context until trt_shutdown; -1: what a new context starts with
+int g_default_sky_filter = -1; // trt_set_default_sky_filter: the same for the sky filter
 
 int default_context(trt_context **out)
 {
@@ -23,6 +24,8 @@ int default_context(trt_context **out)
             return rc;
         if (g_default_specular >= 0)
             g_default->specular = g_default_specular;
+        if (g_default_sky_filter >= 0)
+            g_default->sky_filter = g_default_sky_filter;
     }
     *out = g_default;
     return TRT_OK;
@@ -48,6 +51,7 @@ extern "C" int trt_shutdown(void)
     int rc = trt_destroy(g_default);
     g_default = nullptr;
     g_default_specular = -1;
+    g_default_sky_filter = -1;
     return rc;
 }
 
@@ -131,6 +135,18 @@ extern "C" int trt_set_default_specular(int on)
     g_default_specular = on;
     if (g_default)
         g_default->specular = on;
+    return TRT_OK;
+}
+
+// ... and the sky filter (trt_set_sky_filter), in the same way.
+extern "C" int trt_set_default_sky_filter(int mode)
+{
+    if (mode != TRT_SKY_NEAREST && mode != TRT_SKY_BILINEAR)
+        return fail(TRT_ERR_ARGUMENT, "sky filter %d (TRT_SKY_NEAREST or TRT_SKY_BILINEAR)", mode);
+    std::lock_guard<std::mutex> turn(g_default_mutex);
+    g_default_sky_filter = mode;
+    if (g_default)
+        g_default->sky_filter = mode;
     return TRT_OK;
 }
 

@@ -21,7 +21,7 @@ namespace trt_impl
 {
 
 // ---- which kernel a frame runs ----
-// The production kernel's instantiations (render_rounds_kernel<COUNT, REFRACT, COMPACT, PATCHES, BIG, DEVICE_IMAGE, BATCH, SPECULAR>), each with its
+// The production kernel's instantiations (render_rounds_kernel<COUNT, REFRACT, COMPACT, PATCHES, BIG, DEVICE_IMAGE, BATCH, SPECULAR, SKY_FILTER>), each with its
 // counting form where it has one (the rays trt_read_counters reports), and the reference-order kernel (trt_set_kernel(1)).
 enum Variant : int
 {
@@ -32,6 +32,7 @@ enum Variant : int
     kRefract, kRefractCount, kRefractPatches, kRefractPatchesCount, // the refraction extension (parity unpinned)
     kPlainImage, kPlainImageCount, kPatchesImage, kPatchesImageCount, // the plain rounds with the scene image in device memory (DEVICE_IMAGE)
     kSpecular, kSpecularCount, kSpecularPatches, kSpecularPatchesCount, // the specular extension (parity unpinned)
+    kSkyFilter, kSkyFilterCount, kSkyFilterPatches, kSkyFilterPatchesCount, // bilinear sky filtering (parity unpinned)
     kReference,                  // render_simple_kernel: one thread per pixel; not in kRounds
     kReferenceImage,             // ... reading the scene's records from device memory
 };
@@ -50,12 +51,12 @@ struct RoundsVariant
     BatchKernel batch; // null: no BATCH form
 };
 static const RoundsVariant kRounds[kReference] = {
-    {trt::render_rounds_kernel<false>, trt::kPersistentBlock, false, false, trt::render_rounds_kernel<false, false, false, false, false, false, true, false, trt::BatchView>},
+    {trt::render_rounds_kernel<false>, trt::kPersistentBlock, false, false, trt::render_rounds_kernel<false, false, false, false, false, false, true, false, false, trt::BatchView>},
     {trt::render_rounds_kernel<true>, trt::kPersistentBlock, false},
-    {trt::render_rounds_kernel<false, false, false, true>, trt::kPersistentBlock, false, false, trt::render_rounds_kernel<false, false, false, true, false, false, true, false, trt::BatchView>},
+    {trt::render_rounds_kernel<false, false, false, true>, trt::kPersistentBlock, false, false, trt::render_rounds_kernel<false, false, false, true, false, false, true, false, false, trt::BatchView>},
     {trt::render_rounds_kernel<true, false, false, true>, trt::kPersistentBlock, false},
     {trt::render_rounds_kernel<false, false, false, true, true>, trt::kBigBlock, false},
-    {trt::render_rounds_kernel<false, false, true>, trt::kCompactBlock, true, false, trt::render_rounds_kernel<false, false, true, false, false, false, true, false, trt::BatchView>},
+    {trt::render_rounds_kernel<false, false, true>, trt::kCompactBlock, true, false, trt::render_rounds_kernel<false, false, true, false, false, false, true, false, false, trt::BatchView>},
     {trt::render_rounds_kernel<true, false, true>, trt::kCompactBlock, true},
     {trt::render_rounds_kernel<false, true>, trt::kPersistentBlock, false},
     {trt::render_rounds_kernel<true, true>, trt::kPersistentBlock, false},
@@ -69,6 +70,10 @@ static const RoundsVariant kRounds[kReference] = {
     {trt::render_rounds_kernel<true, false, false, false, false, false, false, true>, trt::kPersistentBlock, false},
     {trt::render_rounds_kernel<false, false, false, true, false, false, false, true>, trt::kPersistentBlock, false},
     {trt::render_rounds_kernel<true, false, false, true, false, false, false, true>, trt::kPersistentBlock, false},
+    {trt::render_rounds_kernel<false, false, false, false, false, false, false, false, true>, trt::kPersistentBlock, false},
+    {trt::render_rounds_kernel<true, false, false, false, false, false, false, false, true>, trt::kPersistentBlock, false},
+    {trt::render_rounds_kernel<false, false, false, true, false, false, false, false, true>, trt::kPersistentBlock, false},
+    {trt::render_rounds_kernel<true, false, false, true, false, false, false, false, true>, trt::kPersistentBlock, false},
 };
 static_assert(TRT_BATCH_MAX == kEyeSlots && TRT_BATCH_MAX == trt::kBatchMax, "a frame of a batch has an eye slot of the scene's tables and a place in BatchView");
 
@@ -132,6 +137,8 @@ static Variant choose_variant(const trt_context *ctx, long units, int spp, int f
         return patches ? (count ? kRefractPatchesCount : kRefractPatches) : (count ? kRefractCount : kRefract);
     if (ctx->specular) // the same: the plain rounds with the image in LDS, one launch per camera, never decoupled
         return patches ? (count ? kSpecularPatchesCount : kSpecularPatches) : (count ? kSpecularCount : kSpecular);
+    if (ctx->sky_filter) // the same again
+        return patches ? (count ? kSkyFilterPatchesCount : kSkyFilterPatches) : (count ? kSkyFilterCount : kSkyFilter);
     if (device_image)
         return patches ? (count ? kPatchesImageCount : kPatchesImage) : (count ? kPlainImageCount : kPlainImage);
     // scenes whose spheres have patches (dense ones) run the plain rounds; the rings must fit beside the image (the occupancy
@@ -315,6 +322,7 @@ void allow_large_lds_render(const trt_context *ctx)
 {
     (void)hipFuncSetAttribute((const void *)trt::render_simple_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
     (void)hipFuncSetAttribute((const void *)trt::render_simple_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
+    (void)hipFuncSetAttribute((const void *)trt::render_simple_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
     for (const RoundsVariant &k : kRounds)
     {
         if (!k.image)
@@ -598,7 +606,8 @@ static int launch_reference(trt_context *ctx, const RenderPlan &plan, trt::Frame
         HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
     const bool device_scene = plan.variant != kReference;
     const auto kernel = ctx->specular ? (device_scene ? trt::render_simple_kernel<true, true> : trt::render_simple_kernel<false, true>) // trt_set_specular
-                                      : (device_scene ? trt::render_simple_kernel<true> : trt::render_simple_kernel<false>);
+                      : ctx->sky_filter ? (device_scene ? trt::render_simple_kernel<true, false, true> : trt::render_simple_kernel<false, false, true>) // trt_set_sky_filter
+                                        : (device_scene ? trt::render_simple_kernel<true> : trt::render_simple_kernel<false>);
     hipLaunchKernelGGL(kernel, dim3(plan.grid), dim3(plan.block), device_scene ? 0 : plan.lds, stream, ctx->scene, f);
     if (entry & kEntryCloses)
         HIP_TRY(hipEventRecord(ctx->ev_mid[slot], stream));
@@ -713,11 +722,17 @@ static int launch_render(trt_context *ctx, const RenderPlan &plan, const trt::Fr
     const bool reference = plan.variant == kReference || plan.variant == kReferenceImage;
     if (ctx->ior_count && ctx->specular) // whichever kernel: nothing of the launch has been recorded yet, the context renders again once one is off
         return fail(TRT_ERR_ARGUMENT, "the refraction extension (trt_set_refraction) and the specular extension (trt_set_specular) do not combine yet");
+    if (ctx->sky_filter && (ctx->ior_count || ctx->specular)) // the same
+        return fail(TRT_ERR_ARGUMENT, "bilinear sky filtering (trt_set_sky_filter) and the %s do not combine yet",
+                    ctx->ior_count ? "refraction extension (trt_set_refraction)" : "specular extension (trt_set_specular)");
+    if (ctx->sky_filter && ctx->scene_image == 1 && !reference) // the caller asks for the device image, which the filter's instantiations do not have
+        return fail(TRT_ERR_CAPACITY, "bilinear sky filtering stages the scene image in LDS only: trt_set_scene_image(ctx, 1) cannot be served");
     if (plan.lds > (size_t)ctx->lds_limit) // LDS only (trt_set_scene_image(ctx, 0)), or an extension, neither of which has a device-image form
         return fail(TRT_ERR_CAPACITY, "%s and %d rays per pixel need %zu B of LDS staging, device offers %d%s", plan.variant == kReference ? "scene" : "scene image",
                     f.spp, plan.lds, ctx->lds_limit,
                     plan.variant == kReference ? "" : ctx->ior_count ? " (the refraction extension stages it in LDS only)"
-                    : ctx->specular            ? " (the specular extension stages it in LDS only)" : "");
+                    : ctx->specular            ? " (the specular extension stages it in LDS only)"
+                    : ctx->sky_filter          ? " (bilinear sky filtering stages it in LDS only)" : "");
 #if defined(TRT_MARKS) && TRT_MARKS == 2
     HIP_TRY(hipMemsetAsync(ctx->d_counters.ptr, 0, kCounterSlots * sizeof(unsigned long long), stream));
 #endif

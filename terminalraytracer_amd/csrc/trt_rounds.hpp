@@ -1126,8 +1126,16 @@ constexpr int kBigBlock = 1024;
 // without patches.  A task of the decoupled ring would have to carry the view vector, three more doubles: not built.  Its register
 // budget is four waves per SIMD: left at three the allocator took 137 VGPRs for the instantiation without patches -- three waves -- and
 // the term cost config 2 45 % of a frame instead of 24 (profiles/r25/a_specular.md); asked for four it settles at 126, nothing spilt.
+// SKY_FILTER (EXTENSION, parity unpinned, trt_set_sky_filter): a sample that ends on the sky takes the bilinear blend of four texels
+// (sky_filtered_wave / sky_blend, trt_device.hpp) where the others take the nearest one, on the plain rounds with or without patches.
+// The round carries the four words and the two weights from the loads to the END of the bounce, seven registers more than the one
+// word; the FP64 coordinates are always formed, there is no FP32 estimate of a weight.  Its register budget is the plain rounds' -- the
+// launch bound is left at TRT_ROUNDS_WAVES, and the allocator settles at 124 / 125 VGPRs, four waves a SIMD like its twins (118 / 119).
+// NOTHING IN THE LAUNCH BOUND HOLDS IT THERE: a change that takes the instantiations without counters above 128 drops them to three
+// waves, as the specular term did at 137 before it asked for four.  The Makefile prints their VGPRs beside render_rounds_kernel<false>'s
+// and warns above 128; asking for four waves outright has not been measured against this.
 template <bool COUNT, bool REFRACT = false, bool COMPACT = false, bool PATCHES = false, bool BIG = false, bool DEVICE_IMAGE = false, bool BATCH = false,
-          bool SPECULAR = false, class... BatchArgument>
+          bool SPECULAR = false, bool SKY_FILTER = false, class... BatchArgument>
 __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersistentBlock, ((COMPACT && !COUNT) || BIG || (SPECULAR && !COUNT) /* 126 / 127 VGPRs asked for four waves, 137 left at three */) ? 4 : TRT_ROUNDS_WAVES) void render_rounds_kernel(SceneView s, CullView cull, FrameView f, GridView grids, BatchArgument... batch)
 {
     static_assert(sizeof...(BatchArgument) == (BATCH ? 1 : 0), "a BATCH launch has one more argument, a BatchView; the others none");
@@ -1137,6 +1145,7 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
     static_assert(!BIG || (PATCHES && !COUNT && !REFRACT && !COMPACT), "1024-thread workgroups: the shipping patch instantiation only");
     static_assert(!DEVICE_IMAGE || (!REFRACT && !COMPACT && !BIG), "the device-memory image: the plain rounds only");
     static_assert(!SPECULAR || (!COMPACT && !BIG && !DEVICE_IMAGE && !BATCH && !REFRACT), "the specular extension: the plain rounds with the image in LDS, one frame a launch");
+    static_assert(!SKY_FILTER || (!COMPACT && !BIG && !DEVICE_IMAGE && !BATCH && !REFRACT && !SPECULAR), "bilinear sky filtering: the plain rounds with the image in LDS, one frame a launch, no other extension");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const LdsImage L = BATCH ? stage_lds_image_batch(lds, s, cull, f, grids)
                        : DEVICE_IMAGE ? image_view(image_layout(const_cast<double *>(f.image), s.num_spheres, s.num_dir, s.num_point, cull.padded, f.spp))
@@ -1407,11 +1416,15 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
         bool end_sample = false;
         double weight_sum_new = weight_sum + weight; // TRT.c:1034
         uint32_t sky_t = 0;
+        [[maybe_unused]] SkyTaps sky_taps{}; // SKY_FILTER: the four texels and the two weights in sky_t's place
         if (hit.sky_lanes != 0)
         { // TRT.c:858-867, :1044-1048: colour = texel, the sample ends here.  The texel is only LOADED here: it is a dependent read
           // from global memory, and what uses it (the sample's colour) is not needed before the END of the round, behind the other
           // lanes' shadow stages
             TRT_FRESH_ARGS;
+            if constexpr (SKY_FILTER)
+                sky_taps = sky_filtered_wave(s.sky, s.sky_dim, hit.back, s.sky_dim_f, path_sky); // four loads, blended at the END of the round
+            else
             sky_t = sky_texel_wave(s.sky, s.sky_dim, hit.back, s.sky_dim_f, path_sky, hit.sky_lanes);
             end_sample = path_sky;
         }
@@ -1498,7 +1511,11 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
         }
         if (path_sky)
         { // TRT.c:866, :1035-1051: colour = texel / 255, scaled by the sample's weight
-            const d3 color = d3{L.b255[sky_t & 0xFF], L.b255[(sky_t >> 8) & 0xFF], L.b255[(sky_t >> 16) & 0xFF]};
+            d3 color;
+            if constexpr (SKY_FILTER)
+                color = sky_blend(sky_taps);
+            else
+                color = d3{L.b255[sky_t & 0xFF], L.b255[(sky_t >> 8) & 0xFF], L.b255[(sky_t >> 16) & 0xFF]};
             sample = add(sample, scale(color, weight));
         }
         if (__any(end_sample))
@@ -1560,7 +1577,8 @@ __global__ __launch_bounds__(BIG ? kBigBlock : COMPACT ? kCompactBlock : kPersis
 // the wave sweeps); nullptr: none for every ray.  Outputs as trace_ray / apply_lighting produce them (TRT.c:793-963).
 // SPECULAR: the context's specular extension is on (trt_set_specular); lit_out then holds the clamped colour with the lights' terms,
 // the view vector being minus the ray's direction as it was given.
-template <bool PATCHES, bool SPECULAR = false>
+// SKY_FILTER: the context's sky filter is bilinear (trt_set_sky_filter); a miss's material colour is then the blend of the four taps.
+template <bool PATCHES, bool SPECULAR = false, bool SKY_FILTER = false>
 __global__ __launch_bounds__(kPersistentBlock) void probe_rounds_kernel(SceneView s, CullView cull, FrameView f, GridView grids, const double *rays,
                                                                         const int *families, long count, int *obj, double *point, double *normal,
                                                                         double *material, double *lit_out)
@@ -1582,7 +1600,12 @@ __global__ __launch_bounds__(kPersistentBlock) void probe_rounds_kernel(SceneVie
         lit = shadow_stage<false, true>(L, cull, grids, n, nd, nl, surface, hit.normal, hit.mat, hit.hit, hit.hit_lanes, gp, gn, tally, scale(d, -1.0));
     else
         lit = shadow_stage<false>(L, cull, grids, n, nd, nl, surface, hit.normal, hit.mat, hit.hit, hit.hit_lanes, gp, gn, tally);
-    const uint32_t sky_t = sky_texel_wave(s.sky, s.sky_dim, hit.back, s.sky_dim_f, alive && !hit.hit, hit.sky_lanes); // the render kernels' look-up
+    uint32_t sky_t = 0;
+    [[maybe_unused]] SkyTaps sky_taps{};
+    if constexpr (SKY_FILTER)
+        sky_taps = sky_filtered_wave(s.sky, s.sky_dim, hit.back, s.sky_dim_f, alive && !hit.hit);
+    else
+        sky_t = sky_texel_wave(s.sky, s.sky_dim, hit.back, s.sky_dim_f, alive && !hit.hit, hit.sky_lanes); // the render kernels' look-up
     if (!alive)
         return;
     d3 color = d3{0.0, 0.0, 0.0};
@@ -1598,7 +1621,10 @@ __global__ __launch_bounds__(kPersistentBlock) void probe_rounds_kernel(SceneVie
     else
     {
         const uint32_t t = sky_t;
-        color = d3{L.b255[t & 0xFF], L.b255[(t >> 8) & 0xFF], L.b255[(t >> 16) & 0xFF]};
+        if constexpr (SKY_FILTER)
+            color = sky_blend(sky_taps);
+        else
+            color = d3{L.b255[t & 0xFF], L.b255[(t >> 8) & 0xFF], L.b255[(t >> 16) & 0xFF]};
     }
     obj[i] = hit.hit ? (hit.ph.i < n ? 1 : 2) : 0;
     point[3 * i + 0] = surface.x, point[3 * i + 1] = surface.y, point[3 * i + 2] = surface.z;

@@ -42,7 +42,8 @@ TRT_DEV LdsScene stage_scene(const SceneView &s, double *lds)
 }
 
 // TRT.c:793-889.  WANT_SURFACE=false is the shadow-ray form (normal/material NULL in the reference).
-template <bool WANT_SURFACE>
+// SKY_FILTER (EXTENSION, parity unpinned, trt_set_sky_filter): a miss's colour is the bilinear blend of four texels (trt_device.hpp).
+template <bool WANT_SURFACE, bool SKY_FILTER = false>
 TRT_DEV Surface closest_hit(const SceneView &s, const LdsScene &l, d3 o, d3 d)
 {
     Surface best;
@@ -105,7 +106,9 @@ TRT_DEV Surface closest_hit(const SceneView &s, const LdsScene &l, d3 o, d3 d)
     }
     if (best.what == 0)
     {
-        if (WANT_SURFACE)
+        if constexpr (WANT_SURFACE && SKY_FILTER)
+            best.color = sky_blend(sky_filtered_wave(s.sky, s.sky_dim, unit(d), s.sky_dim_f, true)); // TRT.c:702, then the declared rules
+        else if (WANT_SURFACE)
             best.color = texel_color(sky_texel(s.sky, s.sky_dim, d));
     }
     else
@@ -187,7 +190,8 @@ TRT_DEV d3 lit_color(const SceneView &s, const LdsScene &l, d3 at, d3 normal, d3
 #ifdef TRT_UNIT_RENDER // the kernel's ONE home among the library's translation units (trt_context.hpp)
 // DEVICE_SCENE: the records are read where SceneView has them (the same layout), for scenes whose records do not fit LDS
 // SPECULAR: the specular extension (trt_set_specular), see lit_color
-template <bool DEVICE_SCENE = false, bool SPECULAR = false>
+// SKY_FILTER: bilinear sky filtering (trt_set_sky_filter), see closest_hit
+template <bool DEVICE_SCENE = false, bool SPECULAR = false, bool SKY_FILTER = false>
 __global__ __launch_bounds__(256) void render_simple_kernel(SceneView s, FrameView f)
 {
     extern __shared__ double lds[];
@@ -213,7 +217,7 @@ __global__ __launch_bounds__(256) void render_simple_kernel(SceneView s, FrameVi
         while (going && bounces < f.bounce_limit && weight > 0.00001) // TRT.c:1018
         {
             n_path++;
-            Surface hit = closest_hit<true>(s, l, org, dir);
+            Surface hit = closest_hit<true, SKY_FILTER>(s, l, org, dir);
             d3 color = hit.color;
             if (hit.what != 0)
             {
@@ -256,8 +260,8 @@ __global__ __launch_bounds__(256) void render_simple_kernel(SceneView s, FrameVi
 #ifdef TRT_UNIT_DIAG
 
 // trt_probe_rays: closest hit + lighting of arbitrary rays (tests).  SPECULAR: the context's specular extension is on; the view vector
-// is minus the ray's direction as it was given
-template <bool SPECULAR = false>
+// is minus the ray's direction as it was given.  SKY_FILTER: the context's sky filter is bilinear (trt_set_sky_filter)
+template <bool SPECULAR = false, bool SKY_FILTER = false>
 __global__ __launch_bounds__(256) void probe_rays_kernel(SceneView s, const double *rays, long n, int *obj, double *point,
                                                           double *normal, double *material, double *lit)
 {
@@ -267,7 +271,7 @@ __global__ __launch_bounds__(256) void probe_rays_kernel(SceneView s, const doub
     if (i >= n)
         return;
     d3 o = load3(rays + 6 * i), d = load3(rays + 6 * i + 3);
-    Surface h = closest_hit<true>(s, l, o, d);
+    Surface h = closest_hit<true, SKY_FILTER>(s, l, o, d);
     obj[i] = h.what;
     point[3 * i + 0] = h.point.x, point[3 * i + 1] = h.point.y, point[3 * i + 2] = h.point.z;
     normal[3 * i + 0] = h.normal.x, normal[3 * i + 1] = h.normal.y, normal[3 * i + 2] = h.normal.z;

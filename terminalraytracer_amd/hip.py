@@ -188,6 +188,9 @@ SYMBOLS = {
     "trt_set_specular": (_I, [_VP, _I]),
     "trt_get_specular": (_I, [_VP, C.POINTER(_I)]),
     "trt_set_default_specular": (_I, [_I]),
+    "trt_set_sky_filter": (_I, [_VP, _I]),
+    "trt_get_sky_filter": (_I, [_VP, C.POINTER(_I)]),
+    "trt_set_default_sky_filter": (_I, [_I]),
     "trt_reserve_cus": (_I, [_VP, _I]),
     "trt_get_stream": (_I, [_VP, C.POINTER(C.c_void_p)]),
     "trt_selftest_cube": (_I, [_VP, _VP, C.c_size_t, _VP, _VP]),
@@ -448,6 +451,17 @@ class Context:
         v = _I()
         _check(lib().trt_get_specular(self._h, C.byref(v)))
         return bool(v.value)
+
+    def set_sky_filter(self, mode=1):
+        """EXTENSION, parity unpinned: SKY_BILINEAR (1) blends the four sky texels around a look-up; SKY_NEAREST (0) is the reference's
+        path (trt_set_sky_filter)"""
+        _check(lib().trt_set_sky_filter(self._h, int(mode)))
+
+    def sky_filter(self):
+        """the context's sky filter, SKY_NEAREST or SKY_BILINEAR (trt_get_sky_filter)"""
+        v = _I()
+        _check(lib().trt_get_sky_filter(self._h, C.byref(v)))
+        return int(v.value)
 
     def read_sweep_fallbacks(self):
         v = C.c_ulonglong()
@@ -1009,6 +1023,15 @@ def set_default_specular(on=True):
     """EXTENSION, parity unpinned: the specular extension for the default context behind project_scene and the trt_render_frame_*
     entries, until trt_shutdown (trt_set_default_specular)"""
     _check(lib().trt_set_default_specular(int(on)))
+
+
+SKY_NEAREST, SKY_BILINEAR = 0, 1
+
+
+def set_default_sky_filter(mode=SKY_BILINEAR):
+    """EXTENSION, parity unpinned: the sky filter of the default context behind project_scene and the trt_render_frame_* entries, until
+    trt_shutdown (trt_set_default_sky_filter)"""
+    _check(lib().trt_set_default_sky_filter(int(mode)))
 
 
 def ansi_bytes(width, rows):
